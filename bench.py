@@ -10,9 +10,15 @@ batch = 4 episodes per GPU.  N>1: one process per GPU (torchrun), each rank runs
 step (weak scaling), no data-path collective; the single RCCL sum-all-reduce of the [2, nclass]
 inter/union buffers happens once after the timed steps (end of the evaluation stream).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel =
-the MFMA implicit-GEMM conv3x3, measured live with events on the launch stream in an instrumented
-eager pass) and `cpu_baseline` (the fp32 CPU oracle timed on a bounded sample on this box's host cores).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps steps, writes --dump-outputs if given, and prints the line with `roofline`, `cpu_baseline` and
+`secondary` null.  `--full` adds, as before: the eager (no graph) step time, `roofline` (dominant kernel =
+the MFMA implicit-GEMM conv3x3, measured live with events on the launch stream in an instrumented eager
+pass), `cpu_baseline` (the fp32 CPU oracle timed on a bounded sample on this box's host cores) and, at the
+BASELINE configs[1] shape on one GPU, `secondary` (the other BASELINE.json GPU configurations).
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned, as DIR/<name>.npy (float32;
+integer counts as float64).  Inputs and weights are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -31,6 +37,22 @@ MFMA_PEAK_TFLOPS = 2500.0  # dense bf16/fp16 MFMA, /opt/skills/guides/MI355X_MIC
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per tensor, float32 (int64 / float64 as float64, exact for the counts)."""
+    import numpy as np
+    conv = {k: (v.double() if v.dtype in (torch.int64, torch.float64) else v.float()).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte cap")
+    os.makedirs(path, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"[bench] --dump-outputs: {', '.join(f'{k}{list(a.shape)}' for k, a in conv.items())} ({total / 2**20:.1f} MiB) -> {path}")
 
 
 def build_pipeline(dtype, tiny=False, blobs=None, residual_dtype=None):
@@ -513,8 +535,13 @@ def train_main(args):
     log(f"[bench] rank {rank}: {elapsed / args.steps * 1e3:.2f} ms/step, loss {loss:.5f}")
     if not (loss == loss and abs(loss) < 1e6):
         raise SystemExit("non-finite loss: invalid run")
+    if rank == 0 and args.dump_outputs:
+        # the step's loss and a fixed, seeded sample of 2^20 updated fp32 master parameters (all of them are GBs)
+        idx = torch.randint(0, tr.P.numel, (1 << 20,), generator=torch.Generator().manual_seed(0))
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([loss], dtype=torch.float64),
+                                         "master_sample": tr.P.master[idx.cuda()]})
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # heaviest kernel pair of the step: the KV-fusion attention backward (dQ + dK/dV), live event timing on the launch
         # stream in one instrumented step; algorithmic FLOPs = 10 * 64 * heads * n_q * keys per image (5 GEMMs)
         saved = red
@@ -553,7 +580,7 @@ def train_main(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4, help="episodes per GPU per step")
     ap.add_argument("--nshot", type=int, default=None,
@@ -564,8 +591,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline value does not need: the eager step time, the roofline pass, the "
+                         "cpu_baseline and (N=1, configs[1] shape) the secondary configurations; off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the fp32-stream / configs[2] / configs[4] measurements that follow the headline one (N=1 only)")
+                    help="--full: skip the fp32-stream / configs[2] / configs[4] measurements that follow the headline one (N=1 only)")
     ap.add_argument("--cfg", action="append", default=[], metavar="FIELD=INT",
                     help="dfw_config field for this run (A/B of kernel plans, e.g. --cfg k8=0); not a default-changing flag")
     ap.add_argument("--vae-flash", default="auto", choices=["auto", "on", "off"],
@@ -588,6 +620,8 @@ def main():
                     help="BASELINE configs[4] instead of the headline metric: training step (VAE-encode with sampling, UNet "
                          "fwd+bwd over a 7-shot episode per GPU, gradient all-reduce over the ranks, clip + AdamW)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.secondary_child:
         return secondary_child_main(args)
@@ -595,7 +629,7 @@ def main():
         return spawn_ranks(args.gpus)            # before ANY torch.cuda / HIP call in this process
     if args.train:
         return train_main(args)
-    want_secondary = (args.gpus == 1 and "RANK" not in os.environ and not args.no_secondary and not args.tiny
+    want_secondary = (args.full and args.gpus == 1 and "RANK" not in os.environ and not args.no_secondary and not args.tiny
                       and (args.res, args.nshot or 1, args.batch) == (512, 1, 4) and args.residual_dtype == "storage")
     worker = bool(os.environ.get("DFW_BENCH_WORKER"))
     if want_secondary and not args.inline and not worker:
@@ -686,6 +720,12 @@ def main():
         tmax = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's result (the graph's output buffers: copied out before any later pass reuses them) and the
+        # meter's int64 buffers, which hold the sums over the timed steps
+        rr = out["r"]
+        dump_outputs(args.dump_outputs, {**{k: rr[k] for k in ("z0", "dec", "seg_u8", "counts") if rr.get(k) is not None},
+                                         "meter_intersection": meter.intersection_buf, "meter_union": meter.union_buf})
 
     # end-of-stream metric reduction: the one collective of the evaluation path
     meter.all_reduce()
@@ -703,7 +743,7 @@ def main():
             "inter", meter.intersection_buf[:, [0, 4, 8, 12]].tolist(), "union", meter.union_buf[:, [0, 4, 8, 12]].tolist())
 
     eager_ms = None
-    if rank == 0 and use_graph:                  # the same step launched kernel by kernel (host-bound): recorded, not `value`
+    if rank == 0 and args.full and use_graph:    # the same step launched kernel by kernel (host-bound): recorded, not `value`
         step(captured=False)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -713,7 +753,7 @@ def main():
         eager_ms = (time.perf_counter() - t1) / 3 * 1e3
         log(f"[bench] eager (no graph) {eager_ms:.2f} ms/step vs graph {elapsed / args.steps * 1e3:.2f} ms/step")
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         agg = roofline_pass(lambda: step(captured=False))
         tot_t = sum(v[2] for v in agg.values())
         for name, (n, fl, t) in sorted(agg.items(), key=lambda kv: -kv[1][2]):
@@ -751,7 +791,7 @@ def main():
     cpu = None
     ref_path = os.environ.get("DFW_BENCH_REF_OUT") or (os.path.join(tempfile.mkdtemp(prefix="dfw_bench_"), "oracle_z0.pt")
                                                        if want_secondary and args.inline else None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(blobs, res, s, ref_out=ref_path)
         except Exception as e:  # the baseline is reported, never required for `value`
