@@ -172,6 +172,7 @@ SYMBOLS = {
     "dfw_meter_update": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "dfw_gemm_tn": (_i32, [C.POINTER(GemmTnArgs), _vp]),
     "dfw_gemm_tn_workspace_bytes": (_sz, [C.POINTER(GemmTnArgs)]),
+    "dfw_gemm_tn_kernel_name": (_i32, [C.POINTER(GemmTnArgs), C.c_char_p, _sz]),
     "dfw_colsum": (_i32, [_vp, _vp, _vp, _sz, _i64, _i32, _i32, _i32, _i64, _f32, _i32, _i32, _vp]),
     "dfw_colsum_plan": (_i32, [_i64, C.POINTER(_i32), C.POINTER(_i32)]),
     "dfw_table_write": (_i32, [_vp, _i64, _vp, _i32, _vp]),

@@ -7,6 +7,7 @@
 // Deterministic throughout: split reductions go through fp32 slabs folded in a fixed order, no float atomics.
 #include "common.h"
 #include "attention_common.h"
+#include <stdio.h>
 
 #ifndef DFW_TN_PRIO_ON
 #define DFW_TN_PRIO_ON 1
@@ -1173,6 +1174,18 @@ extern "C" size_t dfw_gemm_tn_workspace_bytes(const dfw_gemm_tn_args* a) {
   TnPlan pl;
   if (tn_plan(a, pl)) return 0;
   return (size_t)pl.splits * pl.Z * a->N * a->Kc * sizeof(float);
+}
+
+extern "C" int dfw_gemm_tn_kernel_name(const dfw_gemm_tn_args* a, char* buf, size_t n) {
+  TnPlan pl;
+  int rc = tn_plan(a, pl);
+  if (rc) return rc;
+  if (!buf || n == 0) return DFW_EINVAL;
+  const char* t = a->dtype == DFW_BF16 ? "bf16" : "f16";
+  const int len = pl.ring ? snprintf(buf, n, "gemm_tn_ring_kernel<%s,%d,%d,%s>", t, pl.nsa, pl.nsb, pl.conv ? "conv" : "lin")
+                          : snprintf(buf, n, "gemm_tn_kernel<%s>", t);
+  if (pl.splits > 1 && len > 0 && (size_t)len < n) snprintf(buf + len, n - len, "+split%d", pl.splits);
+  return 0;
 }
 
 template <typename T, int NSA, int NSB, bool CONV>

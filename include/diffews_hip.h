@@ -375,6 +375,10 @@ typedef struct {
 
 int dfw_gemm_tn(const dfw_gemm_tn_args* a, dfw_stream_t stream);
 size_t dfw_gemm_tn_workspace_bytes(const dfw_gemm_tn_args* a);
+/* Which kernel dfw_gemm_tn would launch for these arguments (host-only plan query, like dfw_gemm_kernel_name), e.g.
+ * "gemm_tn_ring_kernel<bf16,2,1,conv>+split6" or "gemm_tn_kernel<f16>+split2" (+splitS: S split-M slabs folded by
+ * tn_reduce_kernel; no suffix: one split, written directly). */
+int dfw_gemm_tn_kernel_name(const dfw_gemm_tn_args* a, char* buf, size_t n);
 
 /* Column sums: out[seg * ldo + n] (+)= scale * sum_{r < rows_per_seg} x[(seg * rows_per_seg + r) * ldx + n].
  * Bias gradients (segs = 1) and the gradient of the per-image time-embedding projection added in
