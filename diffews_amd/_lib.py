@@ -152,6 +152,7 @@ SYMBOLS = {
     "dfw_gemm_gn_chunks": (_i32, [C.POINTER(GemmArgs)]),
     "dfw_fsa_attention": (_i32, [C.POINTER(FsaArgs), _vp]),
     "dfw_fsa_workspace_bytes": (_sz, [C.POINTER(FsaArgs)]),
+    "dfw_fsa_kernel_name": (_i32, [C.POINTER(FsaArgs), C.c_char_p, _sz]),
     "dfw_cross_attention": (_i32, [C.POINTER(XattnArgs), _vp]),
     "dfw_vae_attention": (_i32, [C.POINTER(VattnArgs), _vp]),
     "dfw_groupnorm": (_i32, [C.POINTER(GroupNormArgs), _vp]),

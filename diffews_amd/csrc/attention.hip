@@ -536,7 +536,7 @@ extern "C" size_t dfw_fsa_workspace_bytes(const dfw_fsa_args* a) {
   return (size_t)(a->batch - a->n_plain) * ns * a->heads * a->n_q * 68 * sizeof(float);
 }
 
-extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
+static int fsa_check_args(const dfw_fsa_args* a) {
   if (!a || !a->q || !a->k || !a->v || !a->out) return DFW_EINVAL;
   if (a->batch <= 0 || a->heads <= 0 || a->n_q <= 0 || a->n_kv <= 0 || a->nshot < 0) return DFW_EINVAL;
   if (a->nshot > 0 && (!a->k_bank || !a->v_bank || a->n_bank <= 0)) return DFW_EINVAL;
@@ -545,6 +545,41 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8 != 0) return DFW_ESHAPE;
   if (a->nshot > 0 && (a->ldkb | a->ldvb) % 8 != 0) return DFW_ESHAPE;
   if ((a->q_bs | a->k_bs | a->v_bs | a->o_bs) % 8 != 0) return DFW_ESHAPE;
+  return 0;
+}
+
+// The launch dfw_fsa_attention makes: waves per workgroup, key splits taken (only with a caller-provided workspace of
+// dfw_fsa_workspace_bytes(); without one the launch is unsplit) and grid.z.
+struct FsaPlan { int nw, nsplit, grid_z; };
+static FsaPlan fsa_plan(const dfw_fsa_args* a) {
+  FsaPlan pl;
+  pl.nw = a->n_q <= 1024 ? 4 : 8;   // 8 waves x 32 query rows per workgroup; short rows: 128-query workgroups balance better
+  pl.nsplit = 1;
+  const int ns = fsa_split_count(a);
+  if (ns > 1 && a->workspace && a->workspace_bytes >= dfw_fsa_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0)
+    pl.nsplit = ns;
+  pl.grid_z = a->n_plain + (a->batch - a->n_plain) * pl.nsplit;
+  return pl;
+}
+
+// Host-only plan query, e.g. "fsa_ring_kernel<bf16,8,1,pre>+xcd+split3": +xcd when the kernel re-maps its grid onto the
+// XCDs (heads * grid.z % 8 == 0), +splitS when S key splits are merged by fsa_combine_kernel.
+extern "C" int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n) {
+  const int rc = fsa_check_args(a);
+  if (rc) return rc;
+  if (!buf || n == 0) return DFW_EINVAL;
+  const FsaPlan pl = fsa_plan(a);
+  const int len = snprintf(buf, n, "fsa_ring_kernel<%s,%d,1,%s>%s", a->dtype == DFW_BF16 ? "bf16" : "f16", pl.nw,
+                           a->q_prescaled ? "pre" : "scale", (a->heads * pl.grid_z) % 8 == 0 ? "+xcd" : "");
+  if (pl.nsplit > 1 && len > 0 && (size_t)len < n) snprintf(buf + len, n - len, "+split%d", pl.nsplit);
+  return 0;
+}
+
+extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
+  {
+    const int rc = fsa_check_args(a);
+    if (rc) return rc;
+  }
   FsaP p;
   p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v;
   p.kb = (const char*)a->k_bank; p.vb = (const char*)a->v_bank; p.out = (char*)a->out;
@@ -572,20 +607,14 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   p.pre = a->q_prescaled ? 1 : 0;
   p.lse = a->lse;
   // key split: only with a caller-provided workspace of dfw_fsa_workspace_bytes(); without one the launch is unsplit
-  p.nsplit = 1; p.part = nullptr;
-  {
-    const int ns = fsa_split_count(a);
-    if (ns > 1 && a->workspace && a->workspace_bytes >= dfw_fsa_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0) {
-      p.nsplit = ns;
-      p.part = (float*)a->workspace;
-    }
-  }
-  const int grid_z = a->n_plain + (a->batch - a->n_plain) * p.nsplit;
+  const FsaPlan pl = fsa_plan(a);
+  p.nsplit = pl.nsplit;
+  p.part = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
+  const int grid_z = pl.grid_z;
   hipStream_t st = (hipStream_t)stream;
   const bool bf = a->dtype == DFW_BF16;
   {
-    // 8 waves x 32 query rows per workgroup; short rows (n_q <= 1024): 128-query workgroups balance the grid better
-    const int nw = a->n_q <= 1024 ? 4 : 8;
+    const int nw = pl.nw;
     dim3 grid((a->n_q + nw * 32 - 1) / (nw * 32), a->heads, grid_z);
     const bool pre = a->q_prescaled != 0;
     if (nw == 8) {

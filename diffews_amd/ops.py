@@ -233,12 +233,16 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
         keys = n_plain * k.shape[1] + (B - n_plain) * (k.shape[1] + (nshot * k_bank.shape[1] if nshot else 0))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        L.check(L.lib().dfw_fsa_attention(C.byref(a), _stream()), "dfw_fsa_attention")
+        _fsa_call(a)
         e1.record()
         gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
         return out
-    L.check(L.lib().dfw_fsa_attention(C.byref(a), _stream()), "dfw_fsa_attention")
+    _fsa_call(a)
     return out
+
+
+def _fsa_call(a):
+    L.check(L.lib().dfw_fsa_attention(C.byref(a), _stream()), "dfw_fsa_attention")
 
 
 def zeros(shape, dtype, device="cuda"):

@@ -169,6 +169,10 @@ typedef struct {
 
 int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream);
 size_t dfw_fsa_workspace_bytes(const dfw_fsa_args* a);
+/* Which kernel dfw_fsa_attention would launch for these arguments (host-only plan query, like dfw_gemm_tn_kernel_name),
+ * e.g. "fsa_ring_kernel<bf16,8,1,pre>+xcd+split3" ("scale": q not pre-scaled; +xcd: the grid is re-mapped onto the XCDs;
+ * +splitS: S key splits of the bank-reading images merged by fsa_combine_kernel, only with the workspace passed). */
+int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n);
 
 /*
  * Cross-attention over a short context (attn2 of BasicTransformerBlock; L = 2 prompt tokens at
