@@ -943,6 +943,16 @@ __global__ __launch_bounds__(256) void ew_kernel(const char* a, const char* b, c
   }
 }
 
+// (T)(v * s) that keeps the sign of a zero product.  For _Float16 clang folds the conversion of a product into
+// v_fma_mixlo_f16 dst, v, s, 0, and fma(-0, s, +0) is +0 where the IEEE product is -0 (found by
+// tests/test_glue_exact_gpu.py).  The empty asm keeps the product a value of its own: v_mul_f32 + v_cvt_f16_f32.
+template <typename T>
+__device__ __forceinline__ T scale_round(float v, float s) {
+  float p = v * s;
+  asm volatile("" : "+v"(p));
+  return (T)p;
+}
+
 // NCHW fp32 [B][C][H][W] -> NHWC storage dtype [B][H][W][Cp] (Cp >= C, zero padded), times `scale`
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* x, T* y, int B, int C, int HW, int Cp, float scale) {
@@ -952,7 +962,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* x, T* y,
     const long long pix = e / Cp;
     const long long b = pix / HW;
     const int p = (int)(pix - b * HW);
-    y[e] = c < C ? (T)(x[((size_t)b * C + c) * HW + p] * scale) : (T)0.f;
+    y[e] = c < C ? scale_round<T>(x[((size_t)b * C + c) * HW + p], scale) : (T)0.f;
   }
 }
 
@@ -973,7 +983,7 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float
     const int p = (int)(e - bc * HW);
     const long long b = bc / C;
     const int c = (int)(bc - b * C);
-    const T g = (T)(d * gscale);
+    const T g = scale_round<T>(d, gscale);
     dpred[((size_t)b * HW + p) * 8 + c] = g;
     if (dnchw) dnchw[e] = (float)g;       // the same (rounded) values, NCHW fp32, for the direct data-gradient conv
   }
@@ -993,7 +1003,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* g, T* dpred
     const int p = (int)(e - bc * HW);
     const long long b = bc / C;
     const int c = (int)(bc - b * C);
-    const T r = (T)(g[e] * scale);
+    const T r = scale_round<T>(g[e], scale);
     dpred[((size_t)b * HW + p) * 8 + c] = r;
     if (dnchw) dnchw[e] = (float)r;
   }

@@ -1,6 +1,7 @@
 // Small HBM-bound kernels around the MFMA path: boundary convs with tiny channel counts, row
 // softmax, transpose, channel concat, timestep embedding, segmentation post-processing + metric.
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace dfw {
@@ -611,13 +612,49 @@ extern "C" int32_t dfw_conv_small_gn_chunks(const dfw_conv_small_args* a) {
   return (int32_t)(per_img / per_blk);
 }
 
-extern "C" int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream) {
-  if (!a || !a->x || !a->W || !a->y) return DFW_EINVAL;
+// Which kernel, grid and pixel groups per thread dfw_conv_small launches: the one rule behind the launch and
+// dfw_conv_small_kernel_name (only the alignment of a->x is read, never the memory behind it).
+enum { CS_SCALAR = 0, CS_W4 = 1, CS_W8 = 2 };
+struct CsPlan { int kernel, iters; unsigned gx, gy; };
+
+static int cs_plan(const dfw_conv_small_args* a, CsPlan& pl) {
   if (a->B <= 0 || a->H <= 0 || a->Wd <= 0 || a->Cout <= 0) return DFW_EINVAL;
   if (a->Cin <= 0 || a->Cin > 8 || (a->taps != 1 && a->taps != 9)) return DFW_ESHAPE;
   if (a->out_mode != DFW_OUT_NCHW_F32 && (a->Cout % 8 != 0 || a->ldy % 8 != 0)) return DFW_ESHAPE;
   if (a->out_mode != DFW_OUT_T && a->out_mode != DFW_OUT_F32 && a->out_mode != DFW_OUT_NCHW_F32) return DFW_ESHAPE;
   if (a->dtype != DFW_BF16 && a->dtype != DFW_F16) return DFW_EINVAL;
+  const long long pix = (long long)a->B * a->H * a->Wd;
+  pl.iters = 1;
+  if (cs8w_ok(a)) {
+    const long long cblocks = (a->Cout + 127) / 128, groups16 = (pix / 8 + 15) / 16;
+    const long long iters = cs8w_iters(a);
+    pl.kernel = CS_W8; pl.iters = (int)iters;
+    pl.gx = (unsigned)((groups16 + iters - 1) / iters); pl.gy = (unsigned)cblocks;
+  } else if (a->Wd % 4 == 0 && ((uintptr_t)a->x % 16) == 0) {
+    pl.kernel = CS_W4;
+    pl.gx = (unsigned)((pix / 4 + 255) / 256); pl.gy = (unsigned)((a->Cout + 7) / 8);
+  } else {
+    pl.kernel = CS_SCALAR;
+    pl.gx = (unsigned)((pix + 255) / 256); pl.gy = (unsigned)((a->Cout + 7) / 8);
+  }
+  return 0;
+}
+
+extern "C" int dfw_conv_small_kernel_name(const dfw_conv_small_args* a, char* buf, size_t n) {
+  if (!a || !buf || n == 0) return DFW_EINVAL;
+  CsPlan pl;
+  const int rc = cs_plan(a, pl);
+  if (rc) return rc;
+  if (pl.kernel == CS_W8) snprintf(buf, n, "conv_small8w_kernel<%d> iters=%d grid=%ux%u", a->taps, pl.iters, pl.gx, pl.gy);
+  else snprintf(buf, n, "%s grid=%ux%u", pl.kernel == CS_W4 ? "conv_small4_kernel" : "conv_small_kernel", pl.gx, pl.gy);
+  return 0;
+}
+
+extern "C" int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream) {
+  if (!a || !a->x || !a->W || !a->y) return DFW_EINVAL;
+  CsPlan pl;
+  const int rc = cs_plan(a, pl);
+  if (rc) return rc;
   CsP p;
   p.x = a->x; p.W = a->W; p.bias = a->bias; p.y = (char*)a->y;
   p.B = a->B; p.Cin = a->Cin; p.H = a->H; p.Wd = a->Wd; p.Cout = a->Cout; p.taps = a->taps;
@@ -630,7 +667,6 @@ extern "C" int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream)
   p.ybs = a->y_bstride > 0 ? a->y_bstride : (long long)a->Cout * a->H * a->Wd;
   if (a->out_mode == DFW_OUT_NCHW_F32 && (p.ybs < (long long)a->Cout * a->H * a->Wd || (p.ybs & 3) || ((uintptr_t)a->y & 15)))
     return DFW_ESHAPE;
-  const long long pix = (long long)a->B * a->H * a->Wd;
   hipStream_t st = (hipStream_t)stream;
   p.gn_partial = nullptr; p.gn_groups = 0; p.gn_chunks = 0;
   if (a->gn_partial) {
@@ -638,12 +674,10 @@ extern "C" int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream)
     if (p.gn_chunks <= 0) return DFW_ESHAPE;     // ask dfw_conv_small_gn_chunks() first
     p.gn_partial = a->gn_partial; p.gn_groups = a->gn_groups;
   }
-  if (cs8w_ok(a)) {
+  p.iters = pl.iters;
+  const dim3 grid(pl.gx, pl.gy);
+  if (pl.kernel == CS_W8) {
     const size_t lds = ((size_t)a->taps * a->Cin + 1) * 128 * sizeof(float) + (p.gn_partial ? 16 * 128 * 2 * sizeof(float) : 0);
-    const long long cblocks = (a->Cout + 127) / 128, groups16 = (pix / 8 + 15) / 16;
-    const long long iters = cs8w_iters(a);
-    p.iters = (int)iters;
-    dim3 grid((unsigned)((groups16 + iters - 1) / iters), (unsigned)cblocks);
     const bool bf = a->dtype == DFW_BF16;
     if (a->taps == 9) {
       if (bf) hipLaunchKernelGGL((conv_small8w_kernel<__bf16, 9>), grid, dim3(256), lds, st, p);
@@ -655,14 +689,12 @@ extern "C" int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream)
     DFW_CHECK_LAUNCH();
     return 0;
   }
-  if (a->Wd % 4 == 0 && ((uintptr_t)a->x % 16) == 0) {
-    dim3 grid((unsigned)((pix / 4 + 255) / 256), (a->Cout + 7) / 8);
+  if (pl.kernel == CS_W4) {
     if (a->dtype == DFW_BF16) hipLaunchKernelGGL((conv_small4_kernel<__bf16>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv_small4_kernel<_Float16>), grid, dim3(256), 0, st, p);
     DFW_CHECK_LAUNCH();
     return 0;
   }
-  dim3 grid((unsigned)((pix + 255) / 256), (a->Cout + 7) / 8);
   if (a->dtype == DFW_BF16) hipLaunchKernelGGL((conv_small_kernel<__bf16>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((conv_small_kernel<_Float16>), grid, dim3(256), 0, st, p);
   DFW_CHECK_LAUNCH();

@@ -254,6 +254,10 @@ typedef struct {
 
 int dfw_conv_small(const dfw_conv_small_args* a, dfw_stream_t stream);
 int32_t dfw_conv_small_gn_chunks(const dfw_conv_small_args* a);
+/* Which kernel dfw_conv_small would launch for these arguments (host-only plan query, like dfw_gemm_kernel_name; of x
+ * only the alignment is read), with its grid: "conv_small8w_kernel<9> iters=4 grid=512x1" (8 pixels x 8 channels per
+ * thread, iters pixel groups per thread), "conv_small4_kernel grid=3x40" or "conv_small_kernel grid=2x1". */
+int dfw_conv_small_kernel_name(const dfw_conv_small_args* a, char* buf, size_t n);
 
 /* Row softmax of fp32 scores -> storage dtype probabilities (VAE mid-block attention, 1 head of
  * dim 512: diffusers Attention.get_attention_scores with upcast_softmax).  y = softmax(x*scale). */

@@ -11,6 +11,9 @@ u_T is the unit roundoff of the output (2^-8 bf16, 2^-11 fp16, 2^-24 fp32), floo
 fixed before any GPU run and is not fitted to measurements.  SiLU / GEGLU propagate the pre-activation term through their
 slope bound and add their own approximation error (rcp / exp, the Abramowitz-Stegun erf of csrc/common.h).
 
+The boundary convs (ops.conv_small) have their own reference and chunk-sum checker below (conv_small_ref, cs_chunk_check):
+fp32 operands, K = taps * Cin, the same bound without splits.
+
 Unlike a global relative L2, this flags an error that stays inside one tile, one K-chunk or one image: one tile with one
 64-deep K-chunk missing passes `rel(y, ref) < TOL` and fails here (tests/test_gemm_plans_cpu.py).
 """
@@ -185,5 +188,65 @@ def gn_chunk_check(y, part, groups, bm, bn, label=""):
         b, c, g = [int(t) for t in torch.nonzero(ratio == ratio.max())[0]]
         raise AssertionError(f"{label}: fused GroupNorm sums off (worst ratio {worst:.3g}) at image {b}, chunk {c} "
                              f"(patch {c // wgm}, wave row {c % wgm}), group {g}: got {got[b, c, g].tolist()}, "
+                             f"fp64 {[float(s[b, c, g]), float(q[b, c, g])]}")
+    return worst
+
+
+def conv_small_ref(x, w, bias, taps, in_scale=1.0, out_scale=1.0):
+    """Boundary conv (ops.conv_small): NCHW fp32 x [B, Cin, H, W], fp32 w [Cout, taps, Cin], fp32 bias or None ->
+    fp64 (r, e) [B*H*W, Cout] in NHWC order, as `taps` shifted products over the zero-padded input (pad 1 for 9 taps,
+    none for 1), in_scale applied to the input, bias added, out_scale last;
+    e = C_ACC 2^-24 (sqrt(K) |x in_scale|.|w| + |bias|) |out_scale|, K = taps * Cin."""
+    B, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    w = w.reshape(Cout, taps, Cin).to(F64)
+    pad = 1 if taps == 9 else 0
+    assert taps in (1, 9)
+    xs = x.to(F64) * float(in_scale)
+    xp = xs.new_zeros(B, Cin, H + 2 * pad, W + 2 * pad)
+    xp[:, :, pad:pad + H, pad:pad + W] = xs
+    xp = xp.permute(0, 2, 3, 1)                                  # [B, Hp, Wp, Cin]
+    s = a = None
+    k = 3 if taps == 9 else 1
+    for ky in range(k):
+        for kx in range(k):
+            col = xp[:, ky:ky + H, kx:kx + W].reshape(B * H * W, Cin)
+            wt = w[:, ky * k + kx]
+            ds, da = col @ wt.t(), col.abs() @ wt.abs().t()
+            s, a = (ds, da) if s is None else (s + ds, a + da)
+    add = aadd = 0.0
+    if bias is not None:
+        add = bias.to(x.device, F64)[None, :]
+        aadd = add.abs()
+    r = (s + add) * float(out_scale)
+    e = C_ACC * 2.0 ** -24 * (math.sqrt(taps * Cin) * a + aadd) * abs(float(out_scale))
+    return r, e
+
+
+def cs_chunk_check(y, part, groups, iters, label=""):
+    """Fused GroupNorm partial sums part [B, chunks, groups, 2] of conv_small8w's NHWC output y [B, H, W, N] against
+    fp64 sums of the STORED y per (image, chunk, group).  Chunk c of an image is the c-th run of 16 * iters consecutive
+    8-pixel groups in row-major order (one workgroup's pixels).  Tolerance as in gn_chunk_check: recursive fp32 summation
+    of n terms in any order, n 2^-24 sum |y| (n + 1 for the squares).  Returns the worst err / tolerance ratio."""
+    B, H, W, N = y.shape
+    per_img, per_blk = H * (W // 8), 16 * iters
+    assert W % 8 == 0 and per_img % per_blk == 0 and N % groups == 0, (H, W, iters, N, groups)
+    chunks, cpg = per_img // per_blk, N // groups
+    assert tuple(part.shape) == (B, chunks, groups, 2), (tuple(part.shape), B, chunks, groups)
+    # [B, chunks, per_blk * 8 pixels, groups, cpg] -> [B, chunks, groups, pixels x cpg]
+    v = y.to(F64).reshape(B, chunks, per_blk * 8, groups, cpg).permute(0, 1, 3, 2, 4).reshape(B, chunks, groups, -1)
+    n = v.shape[-1]
+    s, q = v.sum(-1), (v * v).sum(-1)
+    got = part.to(v.device, F64)
+    tol_s = n * 2.0 ** -24 * v.abs().sum(-1) + 1e-30
+    tol_q = (n + 1) * 2.0 ** -24 * q + 1e-30
+    ratio = torch.maximum((got[..., 0] - s).abs() / tol_s, (got[..., 1] - q).abs() / tol_q)
+    ratio = torch.where(torch.isfinite(got).all(-1), ratio, torch.full_like(ratio, math.inf))
+    worst = float(ratio.max())
+    if not worst <= 1.0:
+        b, c, g = [int(t) for t in torch.nonzero(ratio == ratio.max())[0]]
+        g0 = c * per_blk
+        raise AssertionError(f"{label}: fused GroupNorm sums off (worst ratio {worst:.3g}) at image {b}, chunk {c} "
+                             f"(pixel groups {g0}..{g0 + per_blk - 1}), group {g}: got {got[b, c, g].tolist()}, "
                              f"fp64 {[float(s[b, c, g]), float(q[b, c, g])]}")
     return worst
