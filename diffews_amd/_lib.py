@@ -34,7 +34,7 @@ class FsaArgs(C.Structure):
                 ("ldq", _i32), ("ldk", _i32), ("ldv", _i32), ("ldkb", _i32), ("ldvb", _i32), ("ldo", _i32),
                 ("q_bs", _i64), ("k_bs", _i64), ("v_bs", _i64), ("kb_bs", _i64), ("vb_bs", _i64), ("o_bs", _i64),
                 ("scale", _f32), ("dtype", _i32), ("n_plain", _i32), ("q_prescaled", _i32), ("lse", _vp),
-                ("workspace", _vp), ("workspace_bytes", _sz)]
+                ("workspace", _vp), ("workspace_bytes", _sz), ("bank_shared", _i32)]
 
 
 class XattnArgs(C.Structure):

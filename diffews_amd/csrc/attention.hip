@@ -3,6 +3,8 @@
 // Keys come from two base pointers (the query pass' own K/V and the per-layer bank written by the
 // support pass); the reference's torch.cat (attention_processor.py:258,267) is never materialised.
 // Key order is the reference's: [own ; shot 0 ; shot 1 ; ...] with bank image = episode*nshot+shot.
+// Shared bank (dfw_fsa_args.bank_shared): the bank holds ONE support set of nshot images and every bank-reading
+// batch entry walks it -- bank image = episode*0 + shot (FsaP::bank_stride).
 //
 // Workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 query rows.
 // Per 64-key tile (K and V tiles double-buffered in LDS, register-staged issue-early/write-late):
@@ -40,6 +42,7 @@ struct FsaP {
   // accumulator, running maximum and sum in `part`; fsa_combine_kernel merges them.  nsplit = 1: nothing of this.
   int nsplit;
   float* part;   // [(batch - n_plain) * nsplit][heads][n_q][68]: o[64] (un-normalised), m (log2 units), l, 2 pad
+  int bank_stride;   // bank images between two episodes: nshot, or 0 when every episode reads the same nshot images
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
     const int key0 = ld_tt * KT;
     const bool own = ld_seg == 0;
     const int nseg = own ? p.n_kv : p.n_bank;
-    const size_t img = own ? (size_t)b : (size_t)bank_b * p.nshot + (ld_seg - 1);
+    const size_t img = own ? (size_t)b : (size_t)bank_b * p.bank_stride + (ld_seg - 1);
     const size_t kbase = img * (own ? p.k_bs : p.kb_bs) + head * 64;
     const size_t vbase = img * (own ? p.v_bs : p.vb_bs) + head * 64;
     const int ldk = own ? p.ldk : p.ldkb, ldv = own ? p.ldv : p.ldvb;
@@ -541,6 +544,8 @@ static int fsa_check_args(const dfw_fsa_args* a) {
   if (a->batch <= 0 || a->heads <= 0 || a->n_q <= 0 || a->n_kv <= 0 || a->nshot < 0) return DFW_EINVAL;
   if (a->nshot > 0 && (!a->k_bank || !a->v_bank || a->n_bank <= 0)) return DFW_EINVAL;
   if (a->n_plain < 0 || a->n_plain > a->batch || (a->n_plain > 0 && a->nshot == 0)) return DFW_EINVAL;
+  // shared bank: one support set read by every batch entry (a query-only launch, so no plain entries)
+  if (a->bank_shared != 0 && (a->bank_shared != 1 || a->nshot == 0 || a->n_plain != 0)) return DFW_EINVAL;
   if (a->dtype != DFW_BF16 && a->dtype != DFW_F16) return DFW_EINVAL;
   if ((a->ldq | a->ldk | a->ldv | a->ldo) % 8 != 0) return DFW_ESHAPE;
   if (a->nshot > 0 && (a->ldkb | a->ldvb) % 8 != 0) return DFW_ESHAPE;
@@ -563,7 +568,8 @@ static FsaPlan fsa_plan(const dfw_fsa_args* a) {
 }
 
 // Host-only plan query, e.g. "fsa_ring_kernel<bf16,8,1,pre>+xcd+split3": +xcd when the kernel re-maps its grid onto the
-// XCDs (heads * grid.z % 8 == 0), +splitS when S key splits are merged by fsa_combine_kernel.
+// XCDs (heads * grid.z % 8 == 0), +splitS when S key splits are merged by fsa_combine_kernel, +shared (last) when every
+// bank reader walks the same nshot bank images.
 extern "C" int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n) {
   const int rc = fsa_check_args(a);
   if (rc) return rc;
@@ -571,7 +577,9 @@ extern "C" int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n) {
   const FsaPlan pl = fsa_plan(a);
   const int len = snprintf(buf, n, "fsa_ring_kernel<%s,%d,1,%s>%s", a->dtype == DFW_BF16 ? "bf16" : "f16", pl.nw,
                            a->q_prescaled ? "pre" : "scale", (a->heads * pl.grid_z) % 8 == 0 ? "+xcd" : "");
-  if (pl.nsplit > 1 && len > 0 && (size_t)len < n) snprintf(buf + len, n - len, "+split%d", pl.nsplit);
+  int at = len;
+  if (pl.nsplit > 1 && at > 0 && (size_t)at < n) at += snprintf(buf + at, n - at, "+split%d", pl.nsplit);
+  if (a->bank_shared && at > 0 && (size_t)at < n) snprintf(buf + at, n - at, "+shared");
   return 0;
 }
 
@@ -588,7 +596,8 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   const int64_t ve = extent(a->batch, a->v_bs, a->n_kv, a->ldv, a->heads);
   int64_t kbe = 0, vbe = 0;
   if (a->nshot > 0) {
-    const int nb = (a->batch - a->n_plain) * a->nshot;   // bank images
+    // bank images; a shared bank holds nshot of them however many entries read it (the descriptor must not claim more)
+    const int nb = a->bank_shared ? a->nshot : (a->batch - a->n_plain) * a->nshot;
     if (nb > 0) {
       kbe = extent(nb, a->kb_bs, a->n_bank, a->ldkb, a->heads);
       vbe = extent(nb, a->vb_bs, a->n_bank, a->ldvb, a->heads);
@@ -610,6 +619,7 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   const FsaPlan pl = fsa_plan(a);
   p.nsplit = pl.nsplit;
   p.part = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
+  p.bank_stride = a->bank_shared ? 0 : a->nshot;
   const int grid_z = pl.grid_z;
   hipStream_t st = (hipStream_t)stream;
   const bool bf = a->dtype == DFW_BF16;

@@ -58,3 +58,23 @@ def test_diffusion(pipe, n_episodes, nshot=1, res=512, batch=1, benchmark="coco"
     meter.all_reduce()
     miou, fb_iou, _ = meter.compute_iou()
     return float(miou), float(fb_iou), meter
+
+
+@torch.no_grad()
+def evaluate_support_set(pipe, support_imgs, support_masks, query_batches, class_id, benchmark="coco", fold=0, r_threshold=0.25,
+                     threshold=0.0, batch_max=False, captured=True, device=None):
+    """One fixed support set against a stream of queries: the bank is prepared ONCE (pipe.prepare_support), then every
+    item of `query_batches` -- (query_img [b, 3, H, W], query_mask uint8 [b, H, W]) device tensors, b may vary -- goes
+    through pipe.segment_queries and its counts into the AverageMeter under `class_id` (the support set's class).
+    Returns (miou, fb_iou, meter) like test_diffusion; single process, no sharding (shard `query_batches` outside)."""
+    device = device or pipe.device
+    meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
+    bank = pipe.prepare_support(support_imgs, support_masks)
+    for query_img, query_mask in query_batches:
+        r = pipe.segment_queries(bank, query_img, query_mask, r_threshold=r_threshold, threshold=threshold,
+                                 batch_max=batch_max, captured=captured)
+        cls = torch.full((query_img.shape[0],), int(class_id), dtype=torch.int64, device=device)
+        meter.update_from_counts(r["counts"], cls)
+    meter.all_reduce()
+    miou, fb_iou, _ = meter.compute_iou()
+    return float(miou), float(fb_iou), meter

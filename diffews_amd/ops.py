@@ -197,13 +197,16 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
 
 
 def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None, out=None, n_plain=0,
-                  q_prescaled=False, lse=None, key_split=True):
+                  q_prescaled=False, lse=None, key_split=True, bank_shared=False):
     """KV-fusion self-attention.  q/k/v: [B, N, heads*64] views (token stride = stride(1));
     k_bank/v_bank: [(B-n_plain)*nshot, Nb, heads*64] views written by the support pass.
     n_plain: the first n_plain batch entries ignore the bank (lock-step [support ; query] launch).
     q_prescaled: q already carries scale * log2(e) (linear(..., colscale=(C, FSA_QSCALE))).
     key_split: let the library split the bank readers' key range over several workgroups when that balances the launch
-    (many shots; needs a scratch buffer, allocated here)."""
+    (many shots; needs a scratch buffer, allocated here).
+    bank_shared: k_bank/v_bank hold ONE support set, [nshot, Nb, heads*64], and every batch entry attends over
+    [own ; that set] (a prepared SupportBank read by a batch of queries) -- same kernel, same key order as the bank
+    repeated B times."""
     B, N, Cq = q.shape
     assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
     if out is None:
@@ -215,11 +218,17 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
     a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     if nshot:
-        assert k_bank.shape[0] == (B - n_plain) * nshot and k_bank.stride(2) == 1 and v_bank.stride(2) == 1
+        if bank_shared:
+            assert n_plain == 0 and k_bank.shape[0] == nshot
+        else:
+            assert k_bank.shape[0] == (B - n_plain) * nshot
+        assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1
         assert k_bank.dtype == q.dtype and v_bank.shape == k_bank.shape
         a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
-        a.n_bank, a.nshot = k_bank.shape[1], nshot
+        a.n_bank, a.nshot, a.bank_shared = k_bank.shape[1], nshot, int(bool(bank_shared))
         a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
+    elif bank_shared:
+        raise ValueError("bank_shared needs a bank (nshot > 0)")
     a.scale = scale if scale is not None else 64 ** -0.5
     a.dtype, a.n_plain, a.q_prescaled = _dt(q), n_plain, int(bool(q_prescaled))
     if lse is not None:   # training: per-row log2-sum-exp2 for the backward

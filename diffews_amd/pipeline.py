@@ -320,6 +320,94 @@ class MarigoldPipelineRGBLatentNoise:
         seg_u8, counts = ops.seg_postprocess(dec, query_gt, *flags)
         return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
 
+    # ------------------------------------------------------------------ shared support bank
+    MAX_QUERY_GRAPHS = 4    # captured segment_queries steps kept per pipeline (least recently used goes first)
+
+    def _single_step_timestep(self):
+        sched = self.scheduler
+        sched.set_timesteps(1, device=self.device)
+        t = sched.timesteps[0]
+        return t, t * self.test_timestep
+
+    @torch.no_grad()
+    def prepare_support(self, support_imgs, support_masks):
+        """Prepare ONE support set for any number of segment_queries() calls: support_imgs / support_masks [s, 3, H, W] in
+        [-1, 1] -> SupportBank (diffews_amd.unet), the K/V of the s support images in every self-attention layer.
+        One VAE-encoder launch train over the 2s images, quant_conv straight into cat([z_ref, z_mask_ref]) (P:674) as in
+        run_episodes, then one support pass of the UNet (unet.prepare_bank).  The bank is valid for this pipeline's
+        current test_timestep, prompt, residual-stream mode and weights, and for queries of the same H x W."""
+        t, tt = self._single_step_timestep()
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        sup = support_imgs.to(dev, torch.float32).contiguous()
+        msk = support_masks.to(dev, torch.float32).contiguous()
+        if sup.shape != msk.shape or sup.dim() != 4:
+            raise ValueError(f"support_imgs {tuple(sup.shape)} and support_masks {tuple(msk.shape)} must both be [s, 3, H, W]")
+        s = sup.shape[0]
+        lc = self.vae.config["latent_channels"]
+        mom = self.vae.encoder([sup, msk])                                        # [2s, 2 lc, h, w] fp32
+        h, w = mom.shape[-2:]
+        cond_ref = torch.empty(s, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
+        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
+        qc(mom[:s], out_scale=sf, out=cond_ref[:, :lc], channels=lc)              # z_ref      (P:649)
+        qc(mom[s:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)              # z_mask_ref (P:651)
+        return self.unet.prepare_bank(cond_ref, tt, None if folded else self.encode_clip_feature())
+
+    @torch.no_grad()
+    def segment_queries(self, bank, query_img, query_gt=None, r_threshold=0.25, threshold=0.0, batch_max=False,
+                        captured=None):
+        """One denoising step for b query images against a prepared support set (prepare_support): query_img
+        [b, 3, H, W] in [-1, 1], any b >= 1; query_gt optional uint8 [b, H, W].  Returns run_episodes' dict (z0, dec,
+        seg_u8, counts) -- per image what run_episodes computes with the supports replicated b times, without encoding
+        the supports or running them through the UNet again: only the queries are encoded, every attn1 reads the bank
+        (unet.forward_queries, z0 = -v folded into conv_out), decode, seg_postprocess.
+
+        Needs the reference's degenerate one-step scheduler (z0 = -v); any other scheduler raises NotImplementedError
+        (use run_episodes, which falls back to single_infer).  A bank prepared under another test_timestep, prompt,
+        residual-stream mode, resolution or set of weights raises ValueError.
+
+        captured (default: self.use_graph): as in run_episodes, one HIP graph per (bank, query shape, flags, ...); the
+        bank's identity is part of the key and its tensors are read in place, so two banks of equal shape never share a
+        graph.  At most MAX_QUERY_GRAPHS captured query steps are kept per pipeline: capturing one more drops the least
+        recently used (its buffers with it; outputs returned from it must have been consumed)."""
+        t, tt = self._single_step_timestep()
+        if not self.scheduler.z0_is_neg_v(t):
+            raise NotImplementedError("segment_queries needs the one-step scheduler with z0 = -v (the reference's setting); "
+                                      "with this scheduler use run_episodes(), which runs the generic single_infer path")
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        prompt = None if folded else self.encode_clip_feature()
+        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
+                   query_gt=None if query_gt is None else query_gt.to(dev).contiguous())
+        # the whole validity check on the host, before anything is launched or replayed
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)     # the encoder halves (floor) once per level but the last
+        H, W = ins["query_img"].shape[-2:]
+        bank.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
+                   fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        flags = (float(r_threshold), float(threshold), bool(batch_max))
+
+        def step(query_img, query_gt=None):
+            lc = self.vae.config["latent_channels"]
+            mom = self.vae.encoder(query_img)
+            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
+            z0 = self.unet.forward_queries(z_tag, tt, bank, prompt, out_scale=-1.0)
+            dec = self.decode_seg(z0)
+            seg_u8, counts = ops.seg_postprocess(dec, query_gt, *flags)
+            return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
+        if captured is None:
+            captured = self.use_graph
+        if not captured:
+            return step(**ins)
+        key = ("queries", bank.uid, tuple(ins["query_img"].shape), query_gt is not None, flags, float(tt), folded,
+               getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
+        if key in self._graphs:
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        else:
+            mine = [k for k in self._graphs if k[0] == "queries"]
+            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
+                del self._graphs[k]
+        return self._replay(key, step, ins)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

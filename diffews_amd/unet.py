@@ -19,7 +19,7 @@ import os
 import torch
 
 from . import _lib as L
-from . import ops, packing, weights
+from . import ops, ops_bwd, packing, weights
 
 
 @dataclass
@@ -45,6 +45,14 @@ def _needs_rebuild(self, device, dtype):
     if dtype is not None and dtype != self.dtype:
         return True
     return device is not None and _resolve_device(device) != _resolve_device(self.device)
+
+
+_WEIGHTS_IDS = [0]
+
+
+def _next_weights_id():
+    _WEIGHTS_IDS[0] += 1
+    return _WEIGHTS_IDS[0]
 
 
 class _Resnet:
@@ -83,6 +91,97 @@ class _Resnet:
         return ops.conv3x3(h, self.w2, self.cout, bias=self.cb2, residual=sc, gn_groups=self.groups, out_f32=f32s)
 
 
+def bank_layout(config, h, w):
+    """(tokens, channels) of every self-attention layer's K (= V) for an h x w latent, in `_transformers()` order
+    (down blocks, up blocks, mid block): what a SupportBank holds per support image."""
+    boc = list(config["block_out_channels"])
+    lpb = config["layers_per_block"]
+    sizes = [(h, w)]
+    for _ in boc[1:]:
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))      # stride-2, pad-1 downsampler
+    out = []
+    for i, typ in enumerate(config["down_block_types"]):
+        if typ == "CrossAttnDownBlock2D":
+            out += [(sizes[i][0] * sizes[i][1], boc[i])] * lpb
+    for i, typ in enumerate(config["up_block_types"]):
+        if typ == "CrossAttnUpBlock2D":
+            j = len(boc) - 1 - i
+            out += [(sizes[j][0] * sizes[j][1], boc[j])] * (lpb + 1)
+    out.append((sizes[-1][0] * sizes[-1][1], boc[-1]))
+    return out
+
+
+class SupportBank:
+    """Immutable handle on ONE prepared support set: every self-attention layer's K and V of its `nshot` support images
+    (`prepare_bank`), read by any number of query passes (`forward_queries`).  It is not module state: the UNet's own
+    k_bank / v_bank, `clear_attn_bank()` and `forward_pair` neither see nor change it.
+
+    k[i] / v[i]: [nshot, tokens_i, channels_i] storage-dtype views, layers in `_transformers()` order (`bank_layout`).
+    Only K and V are kept (not the support pass' Q): at SD-2.1 / 512 x 512 that is sum_i tokens_i * channels_i =
+    11.55 M elements per image, x 2 (K and V) x 2 bytes = 46.2 MB per support image.  The handle owns these tensors, so
+    their storage cannot be recycled while it (or a captured query step that reads it) lives.
+
+    What makes it valid travels with it -- nshot, the latent (h, w), the storage dtype, the residual-stream mode, the
+    fold key (timestep and prompt embedding it was prepared under) and the identity of the weights; `check()` raises
+    ValueError naming the first mismatch."""
+    _next_uid = [0]
+
+    def __init__(self, k, v, nshot, hw, dtype, residual_dtype, fold_key, weights_id, layout):
+        k, v = tuple(k), tuple(v)
+        hw = (int(hw[0]), int(hw[1]))
+        if len(k) != len(layout) or len(v) != len(layout):
+            raise ValueError(f"support bank: {len(k)} K / {len(v)} V layers, the UNet has {len(layout)} self-attention layers")
+        for i, ((n, c), kk, vv) in enumerate(zip(layout, k, v)):
+            for name, t in (("K", kk), ("V", vv)):
+                if t.dtype != dtype:
+                    raise ValueError(f"support bank: layer {i} {name} is {t.dtype}, the storage dtype is {dtype}")
+                if t.dim() != 3 or t.shape[0] != nshot:
+                    raise ValueError(f"support bank: layer {i} {name} holds {tuple(t.shape)[:1]} images, nshot is {nshot}")
+                if tuple(t.shape[1:]) != (n, c):
+                    raise ValueError(f"support bank: layer {i} {name} is {tuple(t.shape[1:])} (tokens, channels); a latent "
+                                     f"(h, w) = {hw} needs {(n, c)}")
+        if nshot < 1:
+            raise ValueError("support bank: nshot must be >= 1")
+        object.__setattr__(self, "_f", dict(k=k, v=v, nshot=int(nshot), hw=hw, dtype=dtype, residual_dtype=residual_dtype,
+                                            fold_key=fold_key, weights_id=weights_id, uid=SupportBank._next_uid[0]))
+        SupportBank._next_uid[0] += 1
+
+    def __getattr__(self, name):
+        f = object.__getattribute__(self, "_f")
+        if name in f:
+            return f[name]
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SupportBank is immutable")
+
+    def tensors(self):
+        return list(self.k) + list(self.v)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def check(self, hw=None, dtype=None, residual_dtype=None, fold_key=None, weights_id=None):
+        """ValueError unless the bank was prepared for these (any argument left None is not compared)."""
+        for name, got, have in (("latent (h, w)", hw and (int(hw[0]), int(hw[1])), self.hw),
+                                ("storage dtype", dtype, self.dtype),
+                                ("residual-stream dtype", residual_dtype, self.residual_dtype),
+                                ("fold key (timestep, prompt)", fold_key, self.fold_key),
+                                ("weights", weights_id, self.weights_id)):
+            if got is not None and got != have:
+                raise ValueError(f"support bank mismatch: {name} is {got} now, the bank was prepared with {have}")
+
+
+class _BankIO:
+    """One trunk pass' access to a SupportBank under construction (fill) or in use (read), per transformer index."""
+
+    def __init__(self, n, bank=None):
+        self.fill = bank is None
+        self.k = [None] * n if bank is None else bank.k
+        self.v = [None] * n if bank is None else bank.v
+        self.nshot = 0 if bank is None else bank.nshot
+
+
 class _Transformer:
     """Transformer2DModel(use_linear_projection) with one BasicTransformerBlock; owns the bank."""
 
@@ -109,6 +208,7 @@ class _Transformer:
         self.v_bank = None
         self.kv_slice = (0, 2 * self.w_q2.shape[0])   # column range in the fused prompt-K/V buffer
         self.fold2 = None   # (G [64, C], U^T [C, 64], L): attn2 folded on a constant prompt (fold_attn2)
+        self.index = 0      # position in MyUNet2DConditionModel._transformers(): this layer's slot of a SupportBank
 
     def fold_attn2(self, kv, L_ctx):
         """attn2 on a CONSTANT prompt: with keys/values fixed, per head h and prompt token l
@@ -139,10 +239,12 @@ class _Transformer:
         self.k_bank = None
         self.v_bank = None
 
-    def __call__(self, x, ehs2d, L_ctx, n_ref=0):
+    def __call__(self, x, ehs2d, L_ctx, n_ref=0, bank_io=None):
         """n_ref == 0: reference bank semantics (fill on the first pass after clear, read on the next).
         n_ref > 0: lock-step pair -- the batch is [n_ref support images ; query images]; the support
-        rows run plain self-attention and are the bank of the query rows within the same call."""
+        rows run plain self-attention and are the bank of the query rows within the same call.
+        bank_io (a _BankIO): the module's own bank is left alone -- a fill pass runs plain self-attention and copies
+        its K/V out, a read pass attends over [own ; the shared support set] for every image of the batch."""
         B, H, W, C = x.shape
         N = H * W
         heads = self.heads
@@ -157,7 +259,15 @@ class _Transformer:
         # attention kernel then exponentiates q.k - m directly; k and v (the bank, A:251-267) are untouched
         qkv = ops.linear(ln, self.w_qkv, colscale=(C, ops.FSA_QSCALE)).view(B, N, 3 * C)
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        if n_ref:
+        if bank_io is not None and bank_io.fill:
+            # K | V columns of the QKV buffer -> one contiguous [B, N, 2C] buffer (library copy kernel; Q is not kept)
+            kv = ops_bwd.slice_channels(qkv, C, 2 * C)
+            bank_io.k[self.index], bank_io.v[self.index] = kv[..., :C], kv[..., C:]
+            att = ops.fsa_attention(q, k, v, heads, q_prescaled=True)
+        elif bank_io is not None:
+            att = ops.fsa_attention(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], nshot=bank_io.nshot,
+                                    q_prescaled=True, bank_shared=True)
+        elif n_ref:
             bq = B - n_ref
             if bq <= 0 or n_ref % bq != 0:
                 raise ValueError(f"{n_ref} support images is not a multiple of the {bq} query images")
@@ -307,13 +417,15 @@ class MyUNet2DConditionModel:
         self.tp_b = torch.cat(bs, 0).float().to(dev)
         # prompt K/V projections (attn2.to_k / to_v) of every transformer layer fused into one GEMM
         kvw, off = [], 0
-        for t in self._transformers():
+        for i, t in enumerate(self._transformers()):
+            t.index = i
             kvw.append(t.w_kv2)
             t.kv_slice = (off, t.w_kv2.shape[0])
             off += t.w_kv2.shape[0]
         self.kv_w_all = torch.cat(kvw, 0).contiguous()
         # fold_conditioning() also folds attn2 on the constant prompt (set False before folding for an A/B run)
         self.fold_attn2 = True
+        self._weights_id = _next_weights_id()   # changes whenever the packed weights are rebuilt (SupportBank validity)
 
     def _resnets_with_prefix(self):
         for i, blk in enumerate(self.down):
@@ -430,7 +542,7 @@ class MyUNet2DConditionModel:
         pe = pe.reshape(-1, pe.shape[-1]).contiguous()
         t = float(timestep)
         self._folded = {"t": t, "L": pe.shape[0], "prompt": pe, "tproj": self._time_proj(1, t),
-                        "kv": ops.linear(pe, self.kv_w_all), "rows": {}}
+                        "kv": ops.linear(pe, self.kv_w_all), "rows": {}, "serial": _next_weights_id()}
         for tr in self._transformers():
             tr.fold2 = None
             if self.fold_attn2:
@@ -487,7 +599,75 @@ class MyUNet2DConditionModel:
         out = self._trunk(x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all)
         return out[n_ref:]
 
-    def _trunk(self, x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all=None):
+    # ------------------------------------------------------------------ shared support bank
+    def _fold_key(self, timestep, encoder_hidden_states):
+        """What the conditioning of a pass depends on: the timestep value and the prompt -- the folded constant (identified
+        by a serial number that every fold_conditioning() call renews) or the tensor passed (by object and version)."""
+        if torch.is_tensor(timestep):
+            if timestep.numel() != 1:
+                raise ValueError("a support bank is prepared for ONE timestep (python number or 1-element tensor)")
+            timestep = float(timestep)
+        if encoder_hidden_states is None:
+            f = getattr(self, "_folded", None)
+            if f is None:
+                raise ValueError("encoder_hidden_states=None needs fold_conditioning() first")
+            return (float(timestep), "folded", f["serial"])
+        pe = encoder_hidden_states
+        return (float(timestep), "prompt", id(pe), pe._version)
+
+    def _conditioning(self, B, timestep, encoder_hidden_states):
+        """(tproj, ehs2d, kv_all, L_ctx) of a B-image pass; encoder_hidden_states [1, L, D] (or [L, D]) is the one prompt
+        every image shares, None = the folded constant."""
+        if encoder_hidden_states is None:
+            return self._folded_rows(B, timestep)
+        ehs = encoder_hidden_states.to(device=self.device, dtype=self.dtype)
+        ehs = ehs.reshape(-1, ehs.shape[-2], ehs.shape[-1])
+        if ehs.shape[0] != 1:
+            raise ValueError("the shared-bank passes take ONE prompt embedding ([1, L, D]) for all images")
+        L_ctx = ehs.shape[1]
+        return self._time_proj(B, timestep), ehs.expand(B, -1, -1).reshape(B * L_ctx, ehs.shape[2]).contiguous(), None, L_ctx
+
+    @torch.no_grad()
+    def prepare_bank(self, cond_ref, timestep, encoder_hidden_states=None):
+        """ONE support pass over cond_ref [s, in_channels_ref, h, w] -- the arithmetic of forward(..., is_target=False) --
+        whose self-attention K/V go into a new SupportBank instead of the module's k_bank / v_bank (left untouched).
+        encoder_hidden_states: the prompt embedding [1, L, D] shared by all images, or None for the folded constant."""
+        cfg, dt, dev = self.config, self.dtype, self.device
+        x_in = cond_ref.to(device=dev, dtype=torch.float32).contiguous()
+        s, Cin, h, w = x_in.shape
+        if Cin != cfg["in_channels_ref"]:
+            raise ValueError(f"support pass expects {cfg['in_channels_ref']} channels, got {Cin}")
+        key = self._fold_key(timestep, encoder_hidden_states)
+        tproj, ehs2d, kv_all, L_ctx = self._conditioning(s, timestep, encoder_hidden_states)
+        c0 = cfg["block_out_channels"][0]
+        x = ops.conv_small(x_in, self.w_in_ref, self.b_in_ref, c0, 9, dt, out_f32=self._f32s)
+        io = _BankIO(len(list(self._transformers())))
+        self._trunk(x, tproj, ehs2d, L_ctx, 0, 1.0, kv_all, bank_io=io)     # the support pass' output is discarded (P:719)
+        return SupportBank(io.k, io.v, s, (h, w), dt, self.residual_dtype, key, self._weights_id, bank_layout(cfg, h, w))
+
+    @torch.no_grad()
+    def forward_queries(self, z_tag, timestep, bank, encoder_hidden_states=None, out_scale=1.0):
+        """Query pass over z_tag [b, in_channels, h, w], any b >= 1: every attn1 attends over [own ; the bank's support
+        set] (fsa_attention(..., bank_shared=True)).  Per image the arithmetic of forward(query) after a support pass
+        that filled the module bank with the same support set; the bank is only read.  Returns the sample (fp32 NCHW).
+        ValueError if `bank` was prepared for another latent size, dtype, residual-stream mode, timestep / prompt or
+        other weights."""
+        cfg, dt, dev = self.config, self.dtype, self.device
+        if not isinstance(bank, SupportBank):
+            raise TypeError("bank must be a SupportBank (prepare_bank)")
+        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
+        B, Cin, h, w = x_in.shape
+        if Cin != cfg["in_channels"]:
+            raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
+        bank.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
+                   fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
+        tproj, ehs2d, kv_all, L_ctx = self._conditioning(B, timestep, encoder_hidden_states)
+        c0 = cfg["block_out_channels"][0]
+        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
+        io = _BankIO(len(bank.k), bank)
+        return self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
+
+    def _trunk(self, x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all=None, bank_io=None):
         # all layers' prompt K/V in one launch: [B*L, sum(2C)]; layers take column slices; the third
         # entry says the prompt is the folded constant (layers may then use their folded attn2)
         ehs2d = (ehs2d, kv_all if kv_all is not None else ops.linear(ehs2d, self.kv_w_all), kv_all is not None)
@@ -497,7 +677,7 @@ class MyUNet2DConditionModel:
             for j, r in enumerate(blk["res"]):
                 x = r(x, tproj)
                 if blk["attn"] is not None:
-                    x = blk["attn"][j](x, ehs2d, L_ctx, n_ref)
+                    x = blk["attn"][j](x, ehs2d, L_ctx, n_ref, bank_io)
                 skips.append(x)
             if blk["down"] is not None:
                 d = blk["down"]
@@ -505,7 +685,7 @@ class MyUNet2DConditionModel:
                 skips.append(x)
         # ---- 4. mid (U:1189-1198)
         x = self.mid["res"][0](x, tproj)
-        x = self.mid["attn"](x, ehs2d, L_ctx, n_ref)
+        x = self.mid["attn"](x, ehs2d, L_ctx, n_ref, bank_io)
         x = self.mid["res"][1](x, tproj)
         # ---- 5. up (U:1214-1243)
         for blk in self.up:
@@ -513,7 +693,7 @@ class MyUNet2DConditionModel:
                 x = ops.concat_channels(x, skips.pop())
                 x = r(x, tproj)
                 if blk["attn"] is not None:
-                    x = blk["attn"][j](x, ehs2d, L_ctx, n_ref)
+                    x = blk["attn"][j](x, ehs2d, L_ctx, n_ref, bank_io)
             if blk["up"] is not None:
                 u = blk["up"]
                 x = ops.conv3x3_stream(x, u.w, u.cout, bias=u.b, ups=True)

@@ -141,6 +141,8 @@ int32_t dfw_gemm_gn_chunks(const dfw_gemm_args* a);
  * evaluation_util/main_oss.py:103), each with n_bank tokens; keys are visited in the reference
  * order [own ; shot0 ; shot1 ; ...] without materialising the concat.  nshot == 0: plain
  * self-attention (bank-fill pass, A:251-252).  head_dim must be 64.
+ * bank_shared: one support set for the whole batch -- the bank holds exactly nshot images and every
+ * entry walks [own ; bank image 0 ; ... ; bank image nshot-1] (ref image index = shot).
  */
 typedef struct {
   const void* q; const void* k; const void* v;
@@ -165,13 +167,18 @@ typedef struct {
    * walk many more keys than the plain ones (nshot >= 2) splits those images' key range over several workgroups and merges
    * the partial softmax results (same mathematics, fp32 partials, fixed order); without it the launch is unsplit. */
   void* workspace; size_t workspace_bytes;
+  /* 0: the bank holds (batch - n_plain) * nshot images, entry b reads its own nshot of them (above).
+   * 1: the bank holds nshot images and EVERY entry reads them (one prepared support set, many queries); the bank's
+   *    extent is then nshot images.  Needs nshot > 0 and n_plain == 0; any other value is DFW_EINVAL. */
+  int32_t bank_shared;
 } dfw_fsa_args;
 
 int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream);
 size_t dfw_fsa_workspace_bytes(const dfw_fsa_args* a);
 /* Which kernel dfw_fsa_attention would launch for these arguments (host-only plan query, like dfw_gemm_tn_kernel_name),
  * e.g. "fsa_ring_kernel<bf16,8,1,pre>+xcd+split3" ("scale": q not pre-scaled; +xcd: the grid is re-mapped onto the XCDs;
- * +splitS: S key splits of the bank-reading images merged by fsa_combine_kernel, only with the workspace passed). */
+ * +splitS: S key splits of the bank-reading images merged by fsa_combine_kernel, only with the workspace passed;
+ * +shared, always last: bank_shared launch). */
 int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n);
 
 /*
