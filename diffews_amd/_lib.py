@@ -153,6 +153,8 @@ SYMBOLS = {
     "dfw_fsa_attention": (_i32, [C.POINTER(FsaArgs), _vp]),
     "dfw_fsa_workspace_bytes": (_sz, [C.POINTER(FsaArgs)]),
     "dfw_fsa_kernel_name": (_i32, [C.POINTER(FsaArgs), C.c_char_p, _sz]),
+    "dfw_fsa_attention_sets": (_i32, [C.POINTER(FsaArgs), _i32, _vp]),
+    "dfw_fsa_sets_kernel_name": (_i32, [C.POINTER(FsaArgs), _i32, C.c_char_p, _sz]),
     "dfw_cross_attention": (_i32, [C.POINTER(XattnArgs), _vp]),
     "dfw_vae_attention": (_i32, [C.POINTER(VattnArgs), _vp]),
     "dfw_groupnorm": (_i32, [C.POINTER(GroupNormArgs), _vp]),
@@ -171,6 +173,7 @@ SYMBOLS = {
     "dfw_timestep_embedding": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp]),
     "dfw_seg_postprocess": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "dfw_seg_postprocess_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
+    "dfw_seg_labels": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
     "dfw_meter_update": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "dfw_gemm_tn": (_i32, [C.POINTER(GemmTnArgs), _vp]),
     "dfw_gemm_tn_workspace_bytes": (_sz, [C.POINTER(GemmTnArgs)]),

@@ -5,6 +5,8 @@
 // Key order is the reference's: [own ; shot 0 ; shot 1 ; ...] with bank image = episode*nshot+shot.
 // Shared bank (dfw_fsa_args.bank_shared): the bank holds ONE support set of nshot images and every bank-reading
 // batch entry walks it -- bank image = episode*0 + shot (FsaP::bank_stride).
+// Bank sets (dfw_fsa_attention_sets): the bank holds batch/group support sets and `group` consecutive entries share one
+// -- bank image = (entry/group)*nshot + shot (FsaP::bank_div); the class-major batch of an N-way query pass.
 //
 // Workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 query rows.
 // Per 64-key tile (K and V tiles double-buffered in LDS, register-staged issue-early/write-late):
@@ -21,6 +23,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 
 // Measured and removed: exponentiating half a tile inside the P.V MFMA gaps of the SAME tile (-17 %),
 // an anti-phase two-barrier schedule of the two wave groups (-4.5 %), a first kernel with register-staged K/V tiles.
@@ -43,6 +46,7 @@ struct FsaP {
   int nsplit;
   float* part;   // [(batch - n_plain) * nsplit][heads][n_q][68]: o[64] (un-normalised), m (log2 units), l, 2 pad
   int bank_stride;   // bank images between two episodes: nshot, or 0 when every episode reads the same nshot images
+  int bank_div;      // consecutive entries that read the same bank images: 1, or `group` of dfw_fsa_attention_sets
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -102,6 +106,8 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
     b = p.n_plain + v / p.nsplit;
   }
   const int bank_b = b - p.n_plain;          // episode index into the bank (< 0: own keys only)
+  // first bank image of this entry (uniform, once per workgroup); only a sets launch (n_plain == 0) has a divisor > 1
+  const int bank_img0 = (p.bank_div > 1 ? bank_b / p.bank_div : bank_b) * p.bank_stride;
   const int q0 = qblk * (NW * 32 * QB) + wave * (32 * QB);
   const uint32_t lds0 = lds_addr(smem);
 
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
     const int key0 = ld_tt * KT;
     const bool own = ld_seg == 0;
     const int nseg = own ? p.n_kv : p.n_bank;
-    const size_t img = own ? (size_t)b : (size_t)bank_b * p.bank_stride + (ld_seg - 1);
+    const size_t img = own ? (size_t)b : (size_t)(bank_img0 + (ld_seg - 1));
     const size_t kbase = img * (own ? p.k_bs : p.kb_bs) + head * 64;
     const size_t vbase = img * (own ? p.v_bs : p.vb_bs) + head * 64;
     const int ldk = own ? p.ldk : p.ldkb, ldv = own ? p.ldv : p.ldvb;
@@ -583,11 +589,41 @@ extern "C" int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n) {
   return 0;
 }
 
+// Bank sets: `group` consecutive entries read one support set of a bank of batch / group sets (the two-pass read launch
+// with another bank index, so its plan); everything that is not such a launch is rejected here, before any launch.
+static int fsa_check_sets(const dfw_fsa_args* a, int32_t group) {
+  const int rc = fsa_check_args(a);
+  if (rc) return rc;
+  if (a->nshot <= 0 || a->n_plain != 0 || a->bank_shared != 0 || group < 1 || a->batch % group != 0) return DFW_EINVAL;
+  return 0;
+}
+
+extern "C" int dfw_fsa_sets_kernel_name(const dfw_fsa_args* a, int32_t group, char* buf, size_t n) {
+  int rc = fsa_check_sets(a, group);
+  if (rc) return rc;
+  rc = dfw_fsa_kernel_name(a, buf, n);
+  if (rc) return rc;
+  const size_t at = strlen(buf);
+  if (at < n) snprintf(buf + at, n - at, "+sets");
+  return 0;
+}
+
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream);
+
 extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
-  {
-    const int rc = fsa_check_args(a);
-    if (rc) return rc;
-  }
+  const int rc = fsa_check_args(a);
+  if (rc) return rc;
+  return fsa_launch(a, 1, stream);
+}
+
+extern "C" int dfw_fsa_attention_sets(const dfw_fsa_args* a, int32_t group, dfw_stream_t stream) {
+  const int rc = fsa_check_sets(a, group);
+  if (rc) return rc;
+  return fsa_launch(a, group, stream);
+}
+
+// `a` has passed fsa_check_args, and fsa_check_sets unless group == 1
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream) {
   FsaP p;
   p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v;
   p.kb = (const char*)a->k_bank; p.vb = (const char*)a->v_bank; p.out = (char*)a->out;
@@ -597,7 +633,8 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   int64_t kbe = 0, vbe = 0;
   if (a->nshot > 0) {
     // bank images; a shared bank holds nshot of them however many entries read it (the descriptor must not claim more)
-    const int nb = a->bank_shared ? a->nshot : (a->batch - a->n_plain) * a->nshot;
+    // and `group` entries share a set of a sets launch (n_plain == 0 there)
+    const int nb = a->bank_shared ? a->nshot : (a->batch - a->n_plain) / group * a->nshot;
     if (nb > 0) {
       kbe = extent(nb, a->kb_bs, a->n_bank, a->ldkb, a->heads);
       vbe = extent(nb, a->vb_bs, a->n_bank, a->ldvb, a->heads);
@@ -620,6 +657,7 @@ extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   p.nsplit = pl.nsplit;
   p.part = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
   p.bank_stride = a->bank_shared ? 0 : a->nshot;
+  p.bank_div = group;
   const int grid_z = pl.grid_z;
   hipStream_t st = (hipStream_t)stream;
   const bool bf = a->dtype == DFW_BF16;

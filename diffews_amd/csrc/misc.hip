@@ -576,6 +576,96 @@ __global__ void seg_zero_kernel(uint32_t* mx, int B, unsigned long long* counts)
   if (counts && e < 4 * B) counts[e] = 0ull;
 }
 
+// N-way label fusion: one pass over the quantised masks of all N classes (seg_u8 [N][B][3][H][W], the maxima mx [N][B]
+// that seg_u8_kernel left).  Per pixel and class the score is seg_count_kernel's mean (same fp32 expressions, same
+// table) and the class is foreground when score > its threshold; label = 0 with no foreground class, else 1 + c of the
+// foreground class with the largest score (classes are visited in ascending order and only a strictly larger score
+// takes over, so the lowest c wins a tie).  With gt (0..N, anything above N dropped like the ignore index 255) the
+// workgroup keeps pred / gt / intersection histograms of N + 1 bins in LDS and issues one 64-bit atomic per non-zero
+// cell: counts [B][2][N+1] = intersections, unions (pred + gt - inter).  4 pixels per thread through 32-bit words when
+// HW % 4 == 0 and every pointer is word-aligned; a scalar path otherwise.
+__global__ __launch_bounds__(256) void seg_labels_kernel(const uint8_t* u8, const uint32_t* mx, const uint8_t* gt,
+                                                         uint8_t* labels, unsigned long long* counts, int N, int HW,
+                                                         float r_thr, float fixed_thr, int batch_max) {
+  __shared__ float lut[256];
+  __shared__ float thr[256];
+  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][N + 1]
+  const int b = blockIdx.y, B = gridDim.y, NL = N + 1;
+  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  if ((int)threadIdx.x < N) {
+    float t = fixed_thr;
+    if (r_thr > 0.f) {
+      const uint32_t* mc = mx + (size_t)threadIdx.x * B;
+      uint32_t m = mc[b];
+      if (batch_max)
+        for (int i = 0; i < B; ++i) m = max(m, mc[i]);
+      t = ((float)m / 255.0f) * r_thr;
+    }
+    thr[threadIdx.x] = t;
+  }
+  for (int i = threadIdx.x; i < 3 * NL; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const size_t cls = (size_t)B * 3 * HW;                  // bytes between two classes
+  const uint8_t* ub = u8 + (size_t)b * 3 * HW;            // class 0 of this image
+  const uint8_t* gb = gt ? gt + (size_t)b * HW : nullptr;
+  uint8_t* lb = labels + (size_t)b * HW;
+  auto count = [&](uint32_t l, uint32_t g) {
+    if (g > (uint32_t)N) return;   // 255 = ignore; N < g < 255 has no bin: dropped from every histogram too
+    atomicAdd(&hist[NL + l], 1u);
+    atomicAdd(&hist[2 * NL + g], 1u);
+    if (l == g) atomicAdd(&hist[l], 1u);
+  };
+  if ((HW & 3) == 0 && (((uintptr_t)ub | (uintptr_t)gb | (uintptr_t)lb) & 3) == 0) {
+    const int n4 = HW >> 2;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
+      float best[4] = {-1.f, -1.f, -1.f, -1.f};
+      uint32_t lab[4] = {0u, 0u, 0u, 0u};
+      const uint8_t* uc = ub + 4 * (size_t)e;
+      for (int c = 0; c < N; ++c, uc += cls) {
+        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
+        const float t = thr[c];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
+          if (sc > t && sc > best[k]) { best[k] = sc; lab[k] = (uint32_t)(c + 1); }
+        }
+      }
+      *(uint32_t*)(lb + 4 * (size_t)e) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+      if (gb) {
+        const uint32_t wg = *(const uint32_t*)(gb + 4 * (size_t)e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) count(lab[k], (wg >> (8 * k)) & 255u);
+      }
+    }
+  } else {
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
+      float best = -1.f;
+      uint32_t lab = 0u;
+      const uint8_t* uc = ub + e;
+      for (int c = 0; c < N; ++c, uc += cls) {
+        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
+        if (sc > thr[c] && sc > best) { best = sc; lab = (uint32_t)(c + 1); }
+      }
+      lb[e] = (uint8_t)lab;
+      if (gb) count(lab, gb[e]);
+    }
+  }
+  if (!gb) return;
+  __syncthreads();
+  unsigned long long* cb = counts + (size_t)b * 2 * NL;
+  for (int l = threadIdx.x; l < NL; l += 256) {
+    const unsigned in = hist[l], un = hist[NL + l] + hist[2 * NL + l] - in;
+    if (in) atomicAdd(cb + l, (unsigned long long)in);
+    if (un) atomicAdd(cb + NL + l, (unsigned long long)un);
+  }
+}
+
+// counts of dfw_seg_labels: a library kernel for the reason seg_zero_kernel gives
+__global__ void seg_labels_zero_kernel(unsigned long long* counts, int n) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) counts[e] = 0ull;
+}
+
 __global__ void meter_update_kernel(const long long* counts, const long long* cls, unsigned long long* ib,
                                     unsigned long long* ub, int B, int nclass) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -839,6 +929,28 @@ extern "C" int dfw_seg_postprocess_ex(const float* x, uint8_t* seg_u8, const uin
   return 0;
 }
 
+extern "C" int dfw_seg_labels(const uint8_t* seg_u8, const uint32_t* mx, const uint8_t* gt, uint8_t* labels, int64_t* counts,
+                              int32_t N, int32_t B, int32_t H, int32_t Wd, float r_threshold, float threshold,
+                              int32_t batch_max, dfw_stream_t stream) {
+  if (!seg_u8 || !labels || N < 1 || N > 254 || B <= 0 || H <= 0 || Wd <= 0) return DFW_EINVAL;
+  if ((r_threshold > 0.f && !mx) || (gt && !counts)) return DFW_EINVAL;
+  if (B > 65535 || (long long)H * Wd > (1ll << 30)) return DFW_ERANGE;
+  hipStream_t st = (hipStream_t)stream;
+  const int HW = H * Wd;
+  if (gt) {
+    const int n = B * 2 * (N + 1);
+    hipLaunchKernelGGL(seg_labels_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (unsigned long long*)counts, n);
+    DFW_CHECK_LAUNCH();
+  }
+  int cx = (HW / 4 + 255) / 256;
+  if (cx > 64) cx = 64;
+  if (cx < 1) cx = 1;
+  hipLaunchKernelGGL(seg_labels_kernel, dim3(cx, B), dim3(256), 0, st, seg_u8, mx, gt, labels,
+                     (unsigned long long*)counts, N, HW, r_threshold, threshold, batch_max ? 1 : 0);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int dfw_meter_update(const int64_t* counts, const int64_t* class_id, int64_t* inter_buf, int64_t* union_buf,
                                 int32_t B, int32_t nclass, dfw_stream_t stream) {
   if (!counts || !class_id || !inter_buf || !union_buf || B <= 0 || nclass <= 0) return DFW_EINVAL;
@@ -900,7 +1012,7 @@ extern "C" void dfw_get_config(dfw_config* out) {
   if (out) *out = g_cfg;
 }
 
-extern "C" int dfw_version(void) { return 103; }
+extern "C" int dfw_version(void) { return 104; }
 
 extern "C" const char* dfw_error_string(int code) {
   switch (code) {

@@ -114,3 +114,22 @@ class AverageMeter:
         fb_iou = (inter.index_select(1, self.class_ids_interest).sum(dim=1)
                   / union.index_select(1, self.class_ids_interest).sum(dim=1)).mean() * 100
         return miou, fb_iou, iou[1][:min(len(iou[1]), 20)]
+
+
+def nway_iou(counts):
+    """counts int64 [B, 2, N+1] (ops.seg_labels / segment_classes: per image and label, row 0 intersections, row 1 unions;
+    label 0 = background) or their running sum [2, N+1] -> (iou [N+1] float64, miou): the counts are summed over the
+    images (exact, int64), iou_l = 100 * inter_l / union_l (0 where the union is empty), and miou is the mean over the
+    class labels 1..N whose union is non-zero (a class neither predicted nor present anywhere says nothing; 0.0 when
+    there is none).  Percent, like AverageMeter.compute_iou."""
+    c = counts.to(torch.int64)
+    if c.dim() == 3:
+        c = c.sum(0)
+    if c.dim() != 2 or c.shape[0] != 2 or c.shape[1] < 2:
+        raise ValueError(f"counts must be [B, 2, N+1] or [2, N+1] with N >= 1, got {tuple(counts.shape)}")
+    inter, union = c[0].double(), c[1].double()
+    seen = union > 0
+    iou = torch.where(seen, 100.0 * inter / union.clamp(min=1.0), torch.zeros_like(union))
+    fg = seen[1:]
+    miou = float(iou[1:][fg].mean()) if bool(fg.any()) else 0.0
+    return iou, miou

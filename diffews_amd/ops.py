@@ -197,7 +197,7 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
 
 
 def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None, out=None, n_plain=0,
-                  q_prescaled=False, lse=None, key_split=True, bank_shared=False):
+                  q_prescaled=False, lse=None, key_split=True, bank_shared=False, _group=0):
     """KV-fusion self-attention.  q/k/v: [B, N, heads*64] views (token stride = stride(1));
     k_bank/v_bank: [(B-n_plain)*nshot, Nb, heads*64] views written by the support pass.
     n_plain: the first n_plain batch entries ignore the bank (lock-step [support ; query] launch).
@@ -218,7 +218,9 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
     a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     if nshot:
-        if bank_shared:
+        if _group:      # fsa_attention_sets
+            assert n_plain == 0 and not bank_shared and B % _group == 0 and k_bank.shape[0] == (B // _group) * nshot
+        elif bank_shared:
             assert n_plain == 0 and k_bank.shape[0] == nshot
         else:
             assert k_bank.shape[0] == (B - n_plain) * nshot
@@ -242,16 +244,32 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
         keys = n_plain * k.shape[1] + (B - n_plain) * (k.shape[1] + (nshot * k_bank.shape[1] if nshot else 0))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _fsa_call(a)
+        _fsa_sets_call(a, _group) if _group else _fsa_call(a)
         e1.record()
         gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
         return out
-    _fsa_call(a)
+    _fsa_sets_call(a, _group) if _group else _fsa_call(a)
     return out
 
 
 def _fsa_call(a):
     L.check(L.lib().dfw_fsa_attention(C.byref(a), _stream()), "dfw_fsa_attention")
+
+
+def _fsa_sets_call(a, group):
+    L.check(L.lib().dfw_fsa_attention_sets(C.byref(a), group, _stream()), "dfw_fsa_attention_sets")
+
+
+def fsa_attention_sets(q, k, v, heads, k_bank, v_bank, nshot, group, scale=None, out=None, q_prescaled=False,
+                       lse=None, key_split=True):
+    """KV-fusion self-attention of a class-major batch against a STACK of support sets: q/k/v [B, N, heads*64],
+    k_bank/v_bank [(B // group) * nshot, Nb, heads*64]; entries [j*group, (j+1)*group) attend over [own ; set j]
+    (bank image = (entry // group) * nshot + shot).  Same kernel, plan and workspace as fsa_attention on the bank
+    materialised per entry; group == 1 is that launch, group == B with one set reads like bank_shared."""
+    if not nshot or nshot < 1 or group < 1:
+        raise ValueError("fsa_attention_sets needs a bank (nshot >= 1) and group >= 1")
+    return fsa_attention(q, k, v, heads, k_bank, v_bank, nshot=nshot, scale=scale, out=out, q_prescaled=q_prescaled,
+                         lse=lse, key_split=key_split, _group=int(group))
 
 
 def zeros(shape, dtype, device="cuda"):
@@ -538,3 +556,29 @@ def seg_postprocess(x, gt=None, r_threshold=0.25, threshold=0.0, batch_max=False
                                            B, H, W, float(r_threshold), float(threshold), int(bool(batch_max)),
                                            _stream()), "dfw_seg_postprocess")
     return u8, counts
+
+
+def seg_labels(seg_u8, mx, gt=None, r_threshold=0.25, threshold=0.0, batch_max=False, labels_out=None, counts_out=None):
+    """N-way label fusion.  seg_u8: uint8 [N, B, 3, H, W], the quantised masks of N classes (seg_postprocess per class,
+    or per chunk of classes, into slices of one buffer); mx: int32 [N, B] (or [N*B]), the maxima those calls left in
+    their `scratch` (may be None with the fixed threshold).  Returns (labels uint8 [B, H, W], counts int64 [B, 2, N+1] or
+    None): label 0 = no class above its threshold (seg_postprocess' rule per class), else 1 + the foreground class of
+    the largest score, lowest class on a tie; with gt (uint8 [B, H, W]: 0..N, 255 and anything above N ignored) the
+    per-label intersections (row 0) and unions (row 1)."""
+    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 5 and seg_u8.shape[2] == 3
+    N, B, _, H, W = seg_u8.shape
+    if mx is not None:
+        assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == N * B
+    elif r_threshold > 0:
+        raise ValueError("the dynamic threshold needs the per-image maxima (mx)")
+    labels = labels_out if labels_out is not None else torch.empty(B, H, W, dtype=torch.uint8, device=seg_u8.device)
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.shape == (B, H, W)
+    counts = None
+    if gt is not None:
+        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, H, W)
+        counts = counts_out if counts_out is not None else torch.empty(B, 2, N + 1, dtype=torch.int64, device=seg_u8.device)
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == (B, 2, N + 1)
+    L.check(L.lib().dfw_seg_labels(seg_u8.data_ptr(), _p(mx), _p(gt), labels.data_ptr(), _p(counts), N, B, H, W,
+                                   float(r_threshold), float(threshold), int(bool(batch_max)), _stream()),
+            "dfw_seg_labels")
+    return labels, counts

@@ -408,6 +408,101 @@ class MarigoldPipelineRGBLatentNoise:
                 del self._graphs[k]
         return self._replay(key, step, ins)
 
+    # ------------------------------------------------------------------ N-way: a stack of class banks
+    @torch.no_grad()
+    def prepare_support_classes(self, support_imgs, support_masks):
+        """Prepare the support sets of N classes for segment_classes(): support_imgs / support_masks [N, s, 3, H, W] in
+        [-1, 1] (s annotated examples of each class) -> SupportBankSet (diffews_amd.unet).  prepare_support's launches over
+        all N * s images at once: one VAE-encoder launch train, quant_conv into cat([z_ref, z_mask_ref]), one support pass
+        of the UNet (unet.prepare_bank_sets).  Valid for what a SupportBank is valid for."""
+        t, tt = self._single_step_timestep()
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        sup = support_imgs.to(dev, torch.float32).contiguous()
+        msk = support_masks.to(dev, torch.float32).contiguous()
+        if sup.shape != msk.shape or sup.dim() != 5:
+            raise ValueError(f"support_imgs {tuple(sup.shape)} and support_masks {tuple(msk.shape)} must both be "
+                             "[N, s, 3, H, W]")
+        N, s = sup.shape[:2]
+        sup, msk = sup.view(N * s, *sup.shape[2:]), msk.view(N * s, *msk.shape[2:])
+        lc = self.vae.config["latent_channels"]
+        mom = self.vae.encoder([sup, msk])                                        # [2 N s, 2 lc, h, w] fp32
+        h, w = mom.shape[-2:]
+        cond_ref = torch.empty(N * s, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
+        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
+        qc(mom[:N * s], out_scale=sf, out=cond_ref[:, :lc], channels=lc)          # z_ref      (P:649)
+        qc(mom[N * s:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)          # z_mask_ref (P:651)
+        return self.unet.prepare_bank_sets(cond_ref, N, tt, None if folded else self.encode_clip_feature())
+
+    @torch.no_grad()
+    def segment_classes(self, bankset, query_img, query_labels=None, r_threshold=0.25, threshold=0.0, batch_max=False,
+                        max_batch=16, captured=None):
+        """N-way segmentation of b query images against the N prepared classes of `bankset` (prepare_support_classes):
+        query_img [b, 3, H, W] in [-1, 1]; query_labels optional uint8 [b, H, W] with 0 = background, 1 + c = class c,
+        255 (or anything above N) = ignore.  The queries are encoded ONCE; the classes go through the UNet and the decoder
+        in chunks of max(1, max_batch // b) sets, each chunk one class-major batch whose attn1 reads its sets of the stack
+        in place (unet.forward_query_sets); seg_postprocess writes every chunk into its slice of one uint8 buffer and of
+        the maxima, and one ops.seg_labels launch fuses the N masks into labels and counts.
+
+        Returns dict(z0 [N, b, 4, h, w], dec [N, b, 3, H, W], seg_u8 [N, b, 3, H, W], labels uint8 [b, H, W], counts int64
+        [b, 2, N+1] or None) -- z0[c] / dec[c] / seg_u8[c] are what segment_queries(bankset.bank(c), query_img) returns;
+        a class is foreground where segment_queries' prediction is (batch_max: the maximum over that class' b masks) and
+        the label is 0 where none is, else 1 + the foreground class of the largest mean mask value, lowest class on a
+        tie; counts rows are per-label intersections and unions (metrics.nway_iou).
+
+        Scheduler restriction, stale-handle ValueErrors and `captured` as in segment_queries; the graph key holds the
+        set's uid, the shapes, max_batch and the flags, and the graphs share segment_queries' MAX_QUERY_GRAPHS."""
+        from .unet import SupportBankSet
+        if not isinstance(bankset, SupportBankSet):
+            raise TypeError("bankset must be a SupportBankSet (prepare_support_classes)")
+        t, tt = self._single_step_timestep()
+        if not self.scheduler.z0_is_neg_v(t):
+            raise NotImplementedError("segment_classes needs the one-step scheduler with z0 = -v (the reference's setting)")
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        prompt = None if folded else self.encode_clip_feature()
+        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
+                   query_labels=None if query_labels is None else query_labels.to(dev).contiguous())
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        b, _, H, W = ins["query_img"].shape
+        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
+                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        flags = (float(r_threshold), float(threshold), bool(batch_max))
+        N, per = bankset.nsets, max(1, int(max_batch) // b)
+
+        def step(query_img, query_labels=None):
+            lc = self.vae.config["latent_channels"]
+            mom = self.vae.encoder(query_img)
+            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
+            seg_u8 = torch.empty(N, b, 3, H, W, dtype=torch.uint8, device=query_img.device)
+            mx = torch.empty(N * b, dtype=torch.int32, device=query_img.device)
+            z0s, decs = [], []
+            for c0 in range(0, N, per):
+                c1 = min(N, c0 + per)
+                z0 = self.unet.forward_query_sets(z_tag, tt, bankset, prompt, out_scale=-1.0, sets=range(c0, c1))
+                dec = self.decode_seg(z0.view(-1, *z0.shape[2:]))
+                # gt-less call: zeroes this chunk's maxima, quantises, takes the per-image maxima
+                ops.seg_postprocess(dec, None, *flags, u8_out=seg_u8[c0:c1].view(-1, 3, H, W), scratch=mx[c0 * b:c1 * b])
+                z0s.append(z0)
+                decs.append(dec.view(c1 - c0, b, *dec.shape[1:]))
+            labels, counts = ops.seg_labels(seg_u8, mx, query_labels, *flags)
+            z0 = z0s[0] if len(z0s) == 1 else torch.cat(z0s)
+            dec = decs[0] if len(decs) == 1 else torch.cat(decs)
+            return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=labels, counts=counts)
+        if captured is None:
+            captured = self.use_graph
+        if not captured:
+            return step(**ins)
+        key = ("queries", "classes", bankset.uid, tuple(ins["query_img"].shape), query_labels is not None, flags, int(max_batch),
+               float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
+        if key in self._graphs:
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        else:
+            mine = [k for k in self._graphs if k[0] == "queries"]
+            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
+                del self._graphs[k]
+        return self._replay(key, step, ins)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

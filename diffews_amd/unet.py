@@ -172,14 +172,95 @@ class SupportBank:
                 raise ValueError(f"support bank mismatch: {name} is {got} now, the bank was prepared with {have}")
 
 
-class _BankIO:
-    """One trunk pass' access to a SupportBank under construction (fill) or in use (read), per transformer index."""
+class SupportBankSet:
+    """Immutable handle on a STACK of prepared support sets -- `nsets` classes of `nshot` support images each, set-major in
+    one tensor per layer -- for N-way segmentation: one query pass over a class-major batch reads all of them
+    (`forward_query_sets`, ops.fsa_attention_sets), without a copy of any bank per query.
 
-    def __init__(self, n, bank=None):
+    k[i] / v[i]: [nsets * nshot, tokens_i, channels_i], image = set * nshot + shot, layers as in SupportBank; the validity
+    fields (hw, dtype, residual_dtype, fold_key, weights_id) and `check()` are SupportBank's.  `.bank(c)` is set c as a
+    SupportBank of zero-copy slices, so everything that takes a SupportBank takes one class of the stack."""
+
+    def __init__(self, k, v, nsets, nshot, hw, dtype, residual_dtype, fold_key, weights_id, layout):
+        k, v = tuple(k), tuple(v)
+        if nsets < 1 or nshot < 1:
+            raise ValueError("support bank set: nsets and nshot must be >= 1")
+        # per-layer validation is SupportBank's, on the whole stack as one nsets * nshot-image bank
+        whole = SupportBank(k, v, int(nsets) * int(nshot), hw, dtype, residual_dtype, fold_key, weights_id, layout)
+        object.__setattr__(self, "_f", dict(k=k, v=v, nsets=int(nsets), nshot=int(nshot), hw=whole.hw, dtype=dtype,
+                                            residual_dtype=residual_dtype, fold_key=fold_key, weights_id=weights_id,
+                                            layout=tuple(layout), uid=SupportBank._next_uid[0], banks={}))
+        SupportBank._next_uid[0] += 1      # one counter: a set and a bank never share a uid (captured-graph keys)
+
+    def __getattr__(self, name):
+        f = object.__getattribute__(self, "_f")
+        if name in f and name != "banks":
+            return f[name]
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SupportBankSet is immutable")
+
+    tensors = SupportBank.tensors
+    nbytes = SupportBank.nbytes
+
+    def check(self, hw=None, dtype=None, residual_dtype=None, fold_key=None, weights_id=None):
+        """ValueError unless the sets were prepared for these (any argument left None is not compared)."""
+        for name, got, have in (("latent (h, w)", hw and (int(hw[0]), int(hw[1])), self.hw),
+                                ("storage dtype", dtype, self.dtype),
+                                ("residual-stream dtype", residual_dtype, self.residual_dtype),
+                                ("fold key (timestep, prompt)", fold_key, self.fold_key),
+                                ("weights", weights_id, self.weights_id)):
+            if got is not None and got != have:
+                raise ValueError(f"support bank set mismatch: {name} is {got} now, the sets were prepared with {have}")
+
+    def bank(self, c):
+        """Set c as a SupportBank whose K / V are slices of this stack (no copy; the same handle on every call, so a
+        captured segment_queries step keyed on it is found again)."""
+        c = int(c)
+        if not 0 <= c < self.nsets:
+            raise IndexError(f"set {c} of a support bank set of {self.nsets}")
+        banks = object.__getattribute__(self, "_f")["banks"]
+        if c not in banks:
+            s = self.nshot
+            banks[c] = SupportBank([t[c * s:(c + 1) * s] for t in self.k], [t[c * s:(c + 1) * s] for t in self.v], s, self.hw,
+                                   self.dtype, self.residual_dtype, self.fold_key, self.weights_id, self.layout)
+        return banks[c]
+
+    @staticmethod
+    def stack(banks):
+        """A set from existing SupportBanks (one per class, in order), by copying their K / V into one tensor per layer.
+        ValueError naming the first of nshot, (h, w), dtype, residual mode, fold key, weights in which a bank differs from
+        the first."""
+        banks = list(banks)
+        if not banks:
+            raise ValueError("support bank set: stack() of no banks")
+        b0 = banks[0]
+        for i, b in enumerate(banks[1:], 1):
+            for name, attr in (("nshot", "nshot"), ("latent (h, w)", "hw"), ("storage dtype", "dtype"),
+                               ("residual-stream dtype", "residual_dtype"), ("fold key (timestep, prompt)", "fold_key"),
+                               ("weights", "weights_id")):
+                if getattr(b, attr) != getattr(b0, attr):
+                    raise ValueError(f"support bank set: bank {i} differs from bank 0 in {name}: {getattr(b, attr)} "
+                                     f"against {getattr(b0, attr)}")
+        n = len(b0.k)
+        k = [torch.cat([b.k[i] for b in banks], 0) for i in range(n)]
+        v = [torch.cat([b.v[i] for b in banks], 0) for i in range(n)]
+        layout = [tuple(t.shape[1:]) for t in b0.k]
+        return SupportBankSet(k, v, len(banks), b0.nshot, b0.hw, b0.dtype, b0.residual_dtype, b0.fold_key, b0.weights_id,
+                              layout)
+
+
+class _BankIO:
+    """One trunk pass' access to a SupportBank under construction (fill) or in use (read), per transformer index.
+    group > 0: the K / V are a stack of support sets and `group` consecutive batch entries read one of them."""
+
+    def __init__(self, n, bank=None, k=None, v=None, group=0):
         self.fill = bank is None
-        self.k = [None] * n if bank is None else bank.k
-        self.v = [None] * n if bank is None else bank.v
+        self.k = [None] * n if bank is None else (bank.k if k is None else k)
+        self.v = [None] * n if bank is None else (bank.v if v is None else v)
         self.nshot = 0 if bank is None else bank.nshot
+        self.group = group
 
 
 class _Transformer:
@@ -264,6 +345,9 @@ class _Transformer:
             kv = ops_bwd.slice_channels(qkv, C, 2 * C)
             bank_io.k[self.index], bank_io.v[self.index] = kv[..., :C], kv[..., C:]
             att = ops.fsa_attention(q, k, v, heads, q_prescaled=True)
+        elif bank_io is not None and bank_io.group:
+            att = ops.fsa_attention_sets(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], bank_io.nshot,
+                                         bank_io.group, q_prescaled=True)
         elif bank_io is not None:
             att = ops.fsa_attention(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], nshot=bank_io.nshot,
                                     q_prescaled=True, bank_shared=True)
@@ -632,6 +716,19 @@ class MyUNet2DConditionModel:
         """ONE support pass over cond_ref [s, in_channels_ref, h, w] -- the arithmetic of forward(..., is_target=False) --
         whose self-attention K/V go into a new SupportBank instead of the module's k_bank / v_bank (left untouched).
         encoder_hidden_states: the prompt embedding [1, L, D] shared by all images, or None for the folded constant."""
+        return self._prepare(cond_ref, timestep, encoder_hidden_states, None)
+
+    @torch.no_grad()
+    def prepare_bank_sets(self, cond_ref, nsets, timestep, encoder_hidden_states=None):
+        """ONE support pass over the nsets * s support images of nsets classes, cond_ref [nsets * s, in_channels_ref, h, w]
+        set-major -> SupportBankSet.  The support pass is per-image self-attention, so this is prepare_bank's pass over a
+        larger batch with another handle around the same K/V."""
+        nsets = int(nsets)
+        if nsets < 1 or cond_ref.shape[0] % nsets != 0:
+            raise ValueError(f"{cond_ref.shape[0]} support images do not divide into {nsets} sets")
+        return self._prepare(cond_ref, timestep, encoder_hidden_states, nsets)
+
+    def _prepare(self, cond_ref, timestep, encoder_hidden_states, nsets):
         cfg, dt, dev = self.config, self.dtype, self.device
         x_in = cond_ref.to(device=dev, dtype=torch.float32).contiguous()
         s, Cin, h, w = x_in.shape
@@ -643,6 +740,9 @@ class MyUNet2DConditionModel:
         x = ops.conv_small(x_in, self.w_in_ref, self.b_in_ref, c0, 9, dt, out_f32=self._f32s)
         io = _BankIO(len(list(self._transformers())))
         self._trunk(x, tproj, ehs2d, L_ctx, 0, 1.0, kv_all, bank_io=io)     # the support pass' output is discarded (P:719)
+        if nsets is not None:
+            return SupportBankSet(io.k, io.v, nsets, s // nsets, (h, w), dt, self.residual_dtype, key, self._weights_id,
+                                  bank_layout(cfg, h, w))
         return SupportBank(io.k, io.v, s, (h, w), dt, self.residual_dtype, key, self._weights_id, bank_layout(cfg, h, w))
 
     @torch.no_grad()
@@ -666,6 +766,34 @@ class MyUNet2DConditionModel:
         x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
         io = _BankIO(len(bank.k), bank)
         return self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
+
+    @torch.no_grad()
+    def forward_query_sets(self, z_tag, timestep, bankset, encoder_hidden_states=None, out_scale=1.0, sets=None):
+        """N-way query pass: the b latents z_tag [b, in_channels, h, w] against the support sets `sets` (a range, default
+        all) of `bankset`, in ONE trunk pass of batch n * b -- the latents repeated once per set, class-major, every attn1
+        through ops.fsa_attention_sets(group=b) on the stack's K/V sliced to those sets (views, no copy).  Entry (c, i) is
+        per image the arithmetic of forward_queries(z_tag[i:i+1], bankset.bank(sets[c])).  Returns [n, b, C, h, w] fp32."""
+        cfg, dt, dev = self.config, self.dtype, self.device
+        if not isinstance(bankset, SupportBankSet):
+            raise TypeError("bankset must be a SupportBankSet (prepare_bank_sets)")
+        sets = range(bankset.nsets) if sets is None else sets
+        if not isinstance(sets, range) or sets.step != 1 or len(sets) < 1 or sets.start < 0 or sets.stop > bankset.nsets:
+            raise ValueError(f"sets must be a non-empty contiguous range within [0, {bankset.nsets}), got {sets}")
+        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
+        b, Cin, h, w = x_in.shape
+        if Cin != cfg["in_channels"]:
+            raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
+        bankset.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
+                      fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
+        n, s = len(sets), bankset.nshot
+        tproj, ehs2d, kv_all, L_ctx = self._conditioning(n * b, timestep, encoder_hidden_states)
+        c0 = cfg["block_out_channels"][0]
+        x_in = x_in.unsqueeze(0).expand(n, *x_in.shape).reshape(n * b, *x_in.shape[1:])     # class-major: entry c * b + i
+        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
+        lo, hi = sets.start * s, sets.stop * s
+        io = _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b)
+        out = self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
+        return out.view(n, b, *out.shape[1:])
 
     def _trunk(self, x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all=None, bank_io=None):
         # all layers' prompt K/V in one launch: [B*L, sum(2C)]; layers take column slices; the third

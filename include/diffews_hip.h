@@ -180,6 +180,14 @@ size_t dfw_fsa_workspace_bytes(const dfw_fsa_args* a);
  * +splitS: S key splits of the bank-reading images merged by fsa_combine_kernel, only with the workspace passed;
  * +shared, always last: bank_shared launch). */
 int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n);
+/* Bank SETS: entries [j*group, (j+1)*group) read bank images j*nshot .. j*nshot+nshot-1 (key order [own ; shot 0 ; ...] as
+ * ever) -- a class-major batch of N-way queries, `group` queries per class, against N prepared support sets stacked in one
+ * bank.  Needs nshot > 0, n_plain == 0, bank_shared == 0, group >= 1, batch % group == 0 (else DFW_EINVAL, from both
+ * functions, before any launch); the bank holds (batch/group)*nshot images and its descriptor extent is exactly that.
+ * Same kernels, key-split plan and workspace as dfw_fsa_attention with the same fields; group == 1 is that launch.
+ * The name is the unshared name + "+sets". */
+int dfw_fsa_attention_sets(const dfw_fsa_args* a, int32_t group, dfw_stream_t stream);
+int dfw_fsa_sets_kernel_name(const dfw_fsa_args* a, int32_t group, char* buf, size_t n);
 
 /*
  * Cross-attention over a short context (attn2 of BasicTransformerBlock; L = 2 prompt tokens at
@@ -324,6 +332,20 @@ int dfw_seg_postprocess(const float* x, uint8_t* seg_u8, const uint8_t* gt, int6
 int dfw_seg_postprocess_ex(const float* x, uint8_t* seg_u8, const uint8_t* gt, int64_t* counts,
                            uint32_t* scratch, int32_t B, int32_t H, int32_t Wd, float r_threshold,
                            float threshold, int32_t batch_max, dfw_stream_t stream);
+
+/* N-way label fusion: seg_u8 [N][B][3][H][W] (N calls' worth of dfw_seg_postprocess_ex output, class-major) and the
+ * per-image maxima mx [N][B] those calls left in their scratch -> labels uint8 [B][H][W].  Per pixel and class c,
+ * score_c = ((u0/255.0f + u1/255.0f) + u2/255.0f) / 3.0f (the fp32 expressions of the binary prediction) and c is
+ * foreground when score_c > thr_c, thr_c = (m/255.0f) * r_threshold when r_threshold > 0 (m: the maximum of class c,
+ * image b, or over the B images of class c when batch_max), else the fixed `threshold`.  label = 0 when no class is
+ * foreground, else 1 + c of the foreground class with the largest score (lowest c on a tie).
+ * gt (optional; then counts is required): uint8 [B][H][W], 0..N, 255 = ignore, values in (N, 255) dropped as well ->
+ * counts int64 [B][2][N+1], zeroed by this call: row 0 intersections (label == gt == l), row 1 unions
+ * (pred_l + gt_l - inter_l).  With N == 1, counts[b] is dfw_seg_postprocess_ex's {inter0, inter1, union0, union1}.
+ * 1 <= N <= 254, else DFW_EINVAL; mx may be NULL with the fixed threshold. */
+int dfw_seg_labels(const uint8_t* seg_u8, const uint32_t* mx, const uint8_t* gt, uint8_t* labels, int64_t* counts,
+                   int32_t N, int32_t B, int32_t H, int32_t Wd, float r_threshold, float threshold,
+                   int32_t batch_max, dfw_stream_t stream);
 
 /* AverageMeter.update on device (evaluation_util/common/logger.py:35-37): for every episode b,
  * inter_buf[k][class_id[b]] += counts[b][k], union_buf[k][class_id[b]] += counts[b][2+k], k = 0, 1.
