@@ -409,14 +409,14 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(const GemmP p) {
 }
 
 template <typename T, int BM, int BN, bool F32O = false>
-static int launch_patch(const GemmP& p, hipStream_t st, int gn_chunks) {
+static int launch_patch(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   GemmP q = p;
   q.ntm = p.M / BM;
   q.ntn = p.N / BN;
   q.tw = 16; q.tw_log2 = 4;
   q.tpr = p.Wo / 16;
   q.tpi = q.tpr * (p.Ho / (BM / 16));
-  q.gn_chunks = p.gn_partial ? gn_chunks : 0;
+  q.gn_chunks = p.gn_partial ? pl.gn_chunks : 0;
   if (q.gn_chunks == 0) q.gn_partial = nullptr;
   constexpr int PPIX = (BM / 16 + 2) * 18, PPW = ((PPIX + 15) / 16 + 7) / 8;
   const size_t lds = 4 * (size_t)BN * 64 + 2 * (size_t)PPW * 8 * 1024 + 32 * 1024;
@@ -454,25 +454,18 @@ bool conv_patch_eligible(const GemmP& p, int& bm, int& bn) {
   return (long long)(p.M / bm) * (p.N / bn) >= 192;
 }
 
-int conv_patch_gn_chunks(const GemmP& p) {
-  int bm = 0, bn = 0;
-  if (p.gn_groups <= 0 || (p.out_mode != DFW_OUT_T && p.out_mode != DFW_OUT_F32) || !conv_patch_eligible(p, bm, bn) || p.N % p.gn_groups) return 0;
+int conv_patch_gn_chunks(const GemmP& p, int bm, int bn) {
+  if (p.gn_groups <= 0 || p.N % p.gn_groups) return 0;
   const int cpg = p.N / p.gn_groups;
   if (cpg < 4 || cpg > 64 || (cpg & (cpg - 1))) return 0;
   return (p.Wo / 16) * (p.Ho / (bm / 16)) * (8 / (bn / 64));
 }
 
-int launch_conv_patch(const GemmP& p, hipStream_t st) {
-  int bm = 0, bn = 0;
-  if (!conv_patch_eligible(p, bm, bn)) return DFW_ESHAPE;
-  const int chunks = conv_patch_gn_chunks(p);
-  const bool bf = p.dtype_bf16 != 0;
-  if (p.out_mode == DFW_OUT_F32) {
-    if (bm == 512) return bf ? launch_patch<__bf16, 512, 128, true>(p, st, chunks) : launch_patch<_Float16, 512, 128, true>(p, st, chunks);
-    return bf ? launch_patch<__bf16, 256, 256, true>(p, st, chunks) : launch_patch<_Float16, 256, 256, true>(p, st, chunks);
-  }
-  if (bm == 512) return bf ? launch_patch<__bf16, 512, 128>(p, st, chunks) : launch_patch<_Float16, 512, 128>(p, st, chunks);
-  return bf ? launch_patch<__bf16, 256, 256>(p, st, chunks) : launch_patch<_Float16, 256, 256>(p, st, chunks);
+int launch_conv_patch(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+  if (pl.f32o && pl.bm == 512) return DFW_BY_DTYPE(p, launch_patch<T, 512, 128, true>(p, pl, st));
+  if (pl.f32o) return DFW_BY_DTYPE(p, launch_patch<T, 256, 256, true>(p, pl, st));
+  if (pl.bm == 512) return DFW_BY_DTYPE(p, launch_patch<T, 512, 128>(p, pl, st));
+  return DFW_BY_DTYPE(p, launch_patch<T, 256, 256>(p, pl, st));
 }
 
 }  // namespace dfw

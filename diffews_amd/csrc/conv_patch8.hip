@@ -432,14 +432,14 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
 }
 
 template <typename T, int BN>
-static int launch_patch8(const GemmP& p, hipStream_t st, int gn_chunks) {
+static int launch_patch8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   GemmP q = p;
   q.ntm = p.M / 256;
   q.ntn = (p.N + BN - 1) / BN;
   q.tw = 16; q.tw_log2 = 4;
   q.tpr = p.Wo / 16;
   q.tpi = q.tpr * (p.Ho / 16);
-  q.gn_chunks = p.gn_partial ? gn_chunks : 0;
+  q.gn_chunks = p.gn_partial ? pl.gn_chunks : 0;
   if (q.gn_chunks == 0) q.gn_partial = nullptr;
   constexpr size_t lds = BN == 160 ? (size_t)0x26000 : 2 * 49152 + (size_t)(BN / 128) * 32768;
   int nwg = q.ntm * q.ntn;
@@ -479,22 +479,17 @@ bool conv_patch8_eligible(const GemmP& p, int& bn) {
   return mt * ((p.N + bn - 1) / bn) >= cfg().big_min_tiles;
 }
 
-int conv_patch8_gn_chunks(const GemmP& p) {
-  int bn = 0;
-  if (p.gn_groups <= 0 || !conv_patch8_eligible(p, bn) || bn == 160 || p.N % p.gn_groups) return 0;
+int conv_patch8_gn_chunks(const GemmP& p, int bn) {
+  if (p.gn_groups <= 0 || bn == 160 || p.N % p.gn_groups) return 0;
   const int cpg = p.N / p.gn_groups;
   if (cpg < 4 || cpg > 64 || (cpg & (cpg - 1))) return 0;
   return (p.Wo / 16) * (p.Ho / 16) * (8 / (bn / 64));
 }
 
-int launch_conv_patch8(const GemmP& p, hipStream_t st) {
-  int bn = 0;
-  if (!conv_patch8_eligible(p, bn)) return DFW_ESHAPE;
-  const int chunks = conv_patch8_gn_chunks(p);
-  const bool bf = p.dtype_bf16 != 0;
-  if (bn == 160) return bf ? launch_patch8<__bf16, 160>(p, st, chunks) : launch_patch8<_Float16, 160>(p, st, chunks);
-  if (bn == 256) return bf ? launch_patch8<__bf16, 256>(p, st, chunks) : launch_patch8<_Float16, 256>(p, st, chunks);
-  return bf ? launch_patch8<__bf16, 128>(p, st, chunks) : launch_patch8<_Float16, 128>(p, st, chunks);
+int launch_conv_patch8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+  if (pl.bn == 160) return DFW_BY_DTYPE(p, launch_patch8<T, 160>(p, pl, st));
+  if (pl.bn == 256) return DFW_BY_DTYPE(p, launch_patch8<T, 256>(p, pl, st));
+  return DFW_BY_DTYPE(p, launch_patch8<T, 128>(p, pl, st));
 }
 
 }  // namespace dfw

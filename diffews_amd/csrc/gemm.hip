@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmP p) {
 }
 
 template <typename T, int BM, int BN>
-static int launch_tile(const GemmP& p, hipStream_t st) {
+static int launch_tile(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   GemmP q = p;
   q.ntm = (p.M + BM - 1) / BM;
   q.ntn = (p.N + BN - 1) / BN;
@@ -342,12 +342,11 @@ static int launch_tile(const GemmP& p, hipStream_t st) {
   if (nwg > cap) nwg = cap;
   nwg = (nwg + 7) & ~7;
   dim3 grid(nwg, zdim);
-  const bool rf32 = p.res_f32 && p.splitk <= 1 && (p.N & 3) == 0 && !p.geglu;   // (split-K: the reduce pass adds the residual)
   if (p.taps == 1) {
-    if (rf32) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, true>), grid, dim3(256), lds, st, q);
+    if (pl.rf32) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, true>), grid, dim3(256), lds, st, q);
     else hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false>), grid, dim3(256), lds, st, q);
   } else {
-    if (rf32) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, true, true>), grid, dim3(256), lds, st, q);
+    if (pl.rf32) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, true, true>), grid, dim3(256), lds, st, q);
     else hipLaunchKernelGGL((gemm_kernel<T, BM, BN, true>), grid, dim3(256), lds, st, q);
   }
   DFW_CHECK_LAUNCH();
@@ -418,22 +417,64 @@ static void plan_gemm(GemmP& p, int& bm, int& bn) {
 }
 
 template <typename T>
-static int launch_gemm(const GemmP& p, hipStream_t st) {
-  int bm = p.plan_bm, bn = p.plan_bn;
-  if (bm == 128 && bn == 128) return launch_tile<T, 128, 128>(p, st);
-  if (bm == 128) return launch_tile<T, 128, 64>(p, st);
-  return launch_tile<T, 64, 64>(p, st);
+static int launch_gemm(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+  if (pl.bm == 128 && pl.bn == 128) return launch_tile<T, 128, 128>(p, pl, st);
+  if (pl.bm == 128) return launch_tile<T, 128, 64>(p, pl, st);
+  return launch_tile<T, 64, 64>(p, pl, st);
+}
+
+// What the planner asks of the other kernel files: which shapes a file's own tiles accept (and the tile), the GroupNorm chunk count
+// of a tile, and the launcher, which reads the plan.  Declared here and nowhere else: no kernel file sees another's predicate.
+bool gemm8_n160_eligible(const GemmP& p);          // gemm8.hip: the 256 x 160 Linear tile (N = 320 at the UNet's 64^2 level)
+bool gemm8_eligible(const GemmP& p, int bn);       // 256 x 256 / 256 x 128, in place of gemm_big's tile of that size
+int launch_gemm8(const GemmP& p, const GemmPlan& pl, hipStream_t st);
+bool conv_patch8_eligible(const GemmP& p, int& bn);   // conv_patch8.hip
+int conv_patch8_gn_chunks(const GemmP& p, int bn);
+int launch_conv_patch8(const GemmP& p, const GemmPlan& pl, hipStream_t st);
+bool conv_patch_eligible(const GemmP& p, int& bm, int& bn);   // conv_patch.hip
+int conv_patch_gn_chunks(const GemmP& p, int bm, int bn);
+int launch_conv_patch(const GemmP& p, const GemmPlan& pl, hipStream_t st);
+bool gemm_big_eligible(const GemmP& p, bool prefer_256x128, int& bm, int& bn, int& bk);   // gemm_big.hip
+int gemm_big_gn_chunks(const GemmP& p, int bm, int bn, int bk);
+int launch_gemm_big(const GemmP& p, const GemmPlan& pl, hipStream_t st);
+
+// THE preference ladder of dfw_gemm, for a GemmP that fill_params() filled: gemm8 256 x 160, conv_patch8, conv_patch, gemm_big
+// (with gemm8 in place of its 256 x 256 / 256 x 128 tiles where dfw_config.k8 allows), then the cost model's gemm_kernel tile:
+// plan_gemm has already run (fill_params), because its split-K choice gates the rungs above, none of which splits K.  The
+// plan depends on dfw_config and on no pointer but the alignment of C: the queries run before workspace and gn_partial exist.
+static GemmPlan gemm_plan(const GemmP& p) {
+  GemmPlan pl = {GemmKernel::Tile, p.plan_bm, p.plan_bn, 64, p.splitk, 0, false, false};
+  if (gemm8_n160_eligible(p)) {
+    pl.kernel = GemmKernel::K8; pl.bm = 256; pl.bn = 160;
+  } else if (conv_patch8_eligible(p, pl.bn)) {
+    pl.kernel = GemmKernel::Patch8; pl.bm = 256;
+    pl.gn_chunks = conv_patch8_gn_chunks(p, pl.bn);
+  } else if (conv_patch_eligible(p, pl.bm, pl.bn)) {
+    pl.kernel = GemmKernel::Patch; pl.bk = 32;
+    pl.gn_chunks = conv_patch_gn_chunks(p, pl.bm, pl.bn);
+    pl.f32o = p.out_mode == DFW_OUT_F32;
+  } else if (gemm_big_eligible(p, cfg().k8 >= 3 && gemm8_eligible(p, 128), pl.bm, pl.bn, pl.bk)) {
+    pl.kernel = GemmKernel::Big;
+    pl.gn_chunks = gemm_big_gn_chunks(p, pl.bm, pl.bn, pl.bk);
+    pl.f32o = p.out_mode == DFW_OUT_F32;
+    // gemm8 takes over gemm_big's 256-row tiles on 64-deep K-tiles: same bm x bn and chunk layout; it keeps that tile's count
+    if (pl.bm == 256 && gemm8_eligible(p, pl.bn)) { pl.kernel = GemmKernel::K8; pl.bk = 64; }
+  } else {
+    pl.bm = p.plan_bm; pl.bn = p.plan_bn;      // (a predicate that declined may have written its candidate tile)
+    pl.rf32 = p.res_f32 && p.splitk <= 1 && (p.N & 3) == 0 && !p.geglu;   // (split-K: the reduce pass adds the residual)
+  }
+  return pl;
 }
 
 }  // namespace dfw
 
 using namespace dfw;
 
-static int fill_params(const dfw_gemm_args* a, GemmP& p, int& esz) {
+static int fill_params(const dfw_gemm_args* a, GemmP& p) {
   if (!a || !a->A || !a->W || !a->C) return DFW_EINVAL;
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return DFW_EINVAL;
   if (a->dtype != DFW_BF16 && a->dtype != DFW_F16) return DFW_EINVAL;
-  esz = 2;
+  const int esz = 2;
   if (a->taps != 1 && a->taps != 9) return DFW_ESHAPE;
   if (a->Cin <= 0 || a->Cin % 64 != 0 || a->K != a->taps * a->Cin) return DFW_ESHAPE;
   if (a->lda % 8 != 0) return DFW_ESHAPE;
@@ -488,75 +529,54 @@ static int fill_params(const dfw_gemm_args* a, GemmP& p, int& esz) {
   return 0;
 }
 
+static int plan_call(const dfw_gemm_args* a, GemmP& p, GemmPlan& pl) {   // what all four entry points start with
+  const int rc = fill_params(a, p);
+  if (rc == 0) pl = gemm_plan(p);
+  return rc;
+}
+
 extern "C" int dfw_gemm_kernel_name(const dfw_gemm_args* a, char* buf, size_t n) {
   GemmP p;
-  int esz;
-  int rc = fill_params(a, p, esz);
+  GemmPlan pl;
+  const int rc = plan_call(a, p, pl);
   if (rc) return rc;
   if (!buf || n == 0) return DFW_EINVAL;
-  int big_bm = 0, big_bn = 0, big_bk = 0;
-  if (gemm8_n160_eligible(p)) {
-    snprintf(buf, n, "gemm8_kernel<%s,256,160,64,lin>", a->dtype == DFW_BF16 ? "bf16" : "f16");
-    return 0;
+  const char *t = p.dtype_bf16 ? "bf16" : "f16", *k = p.taps == 9 ? "conv" : "lin";
+  switch (pl.kernel) {
+    case GemmKernel::K8: snprintf(buf, n, "gemm8_kernel<%s,256,%d,64,%s>", t, pl.bn, k); break;
+    case GemmKernel::Patch8: snprintf(buf, n, "conv_patch8_kernel<%s,256,%d>", t, pl.bn); break;
+    case GemmKernel::Patch: snprintf(buf, n, "conv_patch_kernel<%s,%d,%d>", t, pl.bm, pl.bn); break;
+    case GemmKernel::Big: snprintf(buf, n, "gemm_big_kernel<%s,%d,%d,%d,%s>", t, pl.bm, pl.bn, pl.bk, k); break;
+    case GemmKernel::Tile: snprintf(buf, n, "gemm_kernel<%s,%d,%d,%s>%s", t, pl.bm, pl.bn, k, pl.splitk > 1 ? "+splitk" : ""); break;
   }
-  {
-    int pbm = 0, pbn = 0;
-    if (conv_patch8_eligible(p, pbn)) {
-      snprintf(buf, n, "conv_patch8_kernel<%s,256,%d>", a->dtype == DFW_BF16 ? "bf16" : "f16", pbn);
-      return 0;
-    }
-    if (conv_patch_eligible(p, pbm, pbn)) {
-      snprintf(buf, n, "conv_patch_kernel<%s,%d,%d>", a->dtype == DFW_BF16 ? "bf16" : "f16", pbm, pbn);
-      return 0;
-    }
-  }
-  if (gemm_big_eligible(p, big_bm, big_bn, big_bk)) {
-    if (big_bm == 256 && (big_bn == 256 || big_bn == 128) && gemm8_eligible(p, big_bn)) {
-      snprintf(buf, n, "gemm8_kernel<%s,256,%d,64,%s>", a->dtype == DFW_BF16 ? "bf16" : "f16", big_bn, a->taps == 9 ? "conv" : "lin");
-      return 0;
-    }
-    snprintf(buf, n, "gemm_big_kernel<%s,%d,%d,%d,%s>", a->dtype == DFW_BF16 ? "bf16" : "f16", big_bm, big_bn,
-             big_bk, a->taps == 9 ? "conv" : "lin");
-    return 0;
-  }
-  snprintf(buf, n, "gemm_kernel<%s,%d,%d,%s>%s", a->dtype == DFW_BF16 ? "bf16" : "f16", p.plan_bm, p.plan_bn,
-           a->taps == 9 ? "conv" : "lin", p.splitk > 1 ? "+splitk" : "");
   return 0;
 }
 
 extern "C" int32_t dfw_gemm_gn_chunks(const dfw_gemm_args* a) {
   GemmP p;
-  int esz;
-  if (fill_params(a, p, esz)) return 0;
-  int pbm = 0, pbn = 0;
-  if (conv_patch8_eligible(p, pbn)) return conv_patch8_gn_chunks(p);
-  if (conv_patch_eligible(p, pbm, pbn)) return conv_patch_gn_chunks(p);
-  return gemm_big_gn_chunks(p);
+  GemmPlan pl;
+  return plan_call(a, p, pl) ? 0 : pl.gn_chunks;
 }
 
 extern "C" size_t dfw_gemm_workspace_bytes(const dfw_gemm_args* a) {
   GemmP p;
-  int esz;
-  if (fill_params(a, p, esz) || p.splitk <= 1) return 0;
-  return (size_t)p.splitk * (size_t)p.M * (size_t)p.N * sizeof(float);
+  GemmPlan pl;
+  if (plan_call(a, p, pl) || pl.splitk <= 1) return 0;
+  return (size_t)pl.splitk * (size_t)p.M * (size_t)p.N * sizeof(float);
 }
 
 extern "C" int dfw_gemm(const dfw_gemm_args* a, dfw_stream_t stream) {
   GemmP p;
-  int esz;
-  int rc = fill_params(a, p, esz);
+  GemmPlan pl;
+  const int rc = plan_call(a, p, pl);
   if (rc) return rc;
-  if (p.splitk > 1) {
-    if (!a->workspace || a->workspace_bytes < (size_t)p.splitk * p.M * p.N * sizeof(float)) return DFW_EWORKSPACE;
-  }
+  if (pl.splitk > 1 && (!a->workspace || a->workspace_bytes < (size_t)pl.splitk * p.M * p.N * sizeof(float))) return DFW_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int big_bm = 0, big_bn = 0, big_bk = 0;
-  if (gemm8_n160_eligible(p)) return launch_gemm8(p, st, 160);
-  {
-    int pbm = 0, pbn = 0;
-    if (conv_patch8_eligible(p, pbn)) return launch_conv_patch8(p, st);
-    if (conv_patch_eligible(p, pbm, pbn)) return launch_conv_patch(p, st);
+  switch (pl.kernel) {
+    case GemmKernel::K8: return launch_gemm8(p, pl, st);
+    case GemmKernel::Patch8: return launch_conv_patch8(p, pl, st);
+    case GemmKernel::Patch: return launch_conv_patch(p, pl, st);
+    case GemmKernel::Big: return launch_gemm_big(p, pl, st);
+    default: return DFW_BY_DTYPE(p, launch_gemm<T>(p, pl, st));
   }
-  if (gemm_big_eligible(p, big_bm, big_bn, big_bk)) return launch_gemm_big(p, st);
-  return a->dtype == DFW_BF16 ? launch_gemm<__bf16>(p, st) : launch_gemm<_Float16>(p, st);
 }

@@ -481,11 +481,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
 }
 
 template <typename T, int BN>
-static int launch8(const GemmP& p, hipStream_t st) {
+static int launch8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   GemmP q = p;
   q.ntm = (p.M + 255) / 256;
   q.ntn = (p.N + BN - 1) / BN;
-  q.gn_chunks = p.gn_partial ? gemm_big_gn_chunks(p) : 0;
+  q.gn_chunks = p.gn_partial ? pl.gn_chunks : 0;
   if (q.gn_chunks == 0) q.gn_partial = nullptr;
   q.tw = 0; q.tw_log2 = 0; q.tpr = 0; q.tpi = 0;
   if (p.taps == 9) {
@@ -533,10 +533,10 @@ bool gemm8_n160_eligible(const GemmP& p) {
   return (long long)((p.M + 255) / 256) * (p.N / 160) >= cfg().big_min_tiles;
 }
 
-int launch_gemm8(const GemmP& p, hipStream_t st, int bn) {
-  if (bn == 160) return p.dtype_bf16 ? launch8<__bf16, 160>(p, st) : launch8<_Float16, 160>(p, st);
-  if (bn == 256) return p.dtype_bf16 ? launch8<__bf16, 256>(p, st) : launch8<_Float16, 256>(p, st);
-  return p.dtype_bf16 ? launch8<__bf16, 128>(p, st) : launch8<_Float16, 128>(p, st);
+int launch_gemm8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+  if (pl.bn == 160) return DFW_BY_DTYPE(p, launch8<T, 160>(p, pl, st));
+  if (pl.bn == 256) return DFW_BY_DTYPE(p, launch8<T, 256>(p, pl, st));
+  return DFW_BY_DTYPE(p, launch8<T, 128>(p, pl, st));
 }
 
 }  // namespace dfw

@@ -646,11 +646,11 @@ __global__ __launch_bounds__(512, 2 * OCC) void gemm_big_kernel(const GemmP p) {
 }
 
 template <typename T, int BM, int BN, int BK, int S, int OCC, bool PP = false, bool M16 = false, bool F32O = false>
-static int launch_big(const GemmP& p, hipStream_t st) {
+static int launch_big(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   GemmP q = p;
   q.ntm = (p.M + BM - 1) / BM;
   q.ntn = (p.N + BN - 1) / BN;
-  q.gn_chunks = p.gn_partial ? gemm_big_gn_chunks(p) : 0;
+  q.gn_chunks = p.gn_partial ? pl.gn_chunks : 0;
   if (q.gn_chunks == 0) q.gn_partial = nullptr;
   q.tw = 0; q.tw_log2 = 0; q.tpr = 0; q.tpi = 0;
   if (p.taps == 9) {
@@ -694,7 +694,8 @@ static bool big_cfg_ok(const GemmP& p, const BigCfg& c) {
   return (long long)((p.M + c.bm - 1) / c.bm) * ((p.N + c.bn - 1) / c.bn) * z >= (c.occ == 2 ? 256 : cfg().big_min_tiles);
 }
 
-bool gemm_big_eligible(const GemmP& p, int& bm, int& bn, int& bk) {
+// prefer_256x128: the caller runs a 256 x 128 tile on gemm8_kernel and wants it ahead of 512 x 128 (dfw_config.k8 >= 3).
+bool gemm_big_eligible(const GemmP& p, bool prefer_256x128, int& bm, int& bn, int& bk) {
   if (!cfg().big_kernels) return false;
   if (p.splitk > 1 || (p.N % 8) != 0) return false;
   const bool f32o = p.out_mode == DFW_OUT_F32;      // fp32 residual stream: the two ping-pong configurations only
@@ -736,7 +737,7 @@ bool gemm_big_eligible(const GemmP& p, int& bm, int& bn, int& bk) {
         return true;
       }
     }
-    if (list == narrow && cfg().k8 >= 3 && big_cfg_ok(p, narrow[1]) && gemm8_eligible(p, 128)) {
+    if (list == narrow && prefer_256x128 && big_cfg_ok(p, narrow[1])) {
       bm = narrow[1].bm; bn = narrow[1].bn; bk = narrow[1].bk;
       return true;
     }
@@ -749,10 +750,9 @@ bool gemm_big_eligible(const GemmP& p, int& bm, int& bn, int& bk) {
   return false;
 }
 
-int gemm_big_gn_chunks(const GemmP& p) {
-  int bm = 0, bn = 0, bk = 0;
-  if (p.gn_groups <= 0 || p.taps != 9 || p.geglu || (p.out_mode != DFW_OUT_T && p.out_mode != DFW_OUT_F32) ||
-      !gemm_big_eligible(p, bm, bn, bk)) return 0;
+// > 0: the bm x bn x bk configuration can emit GroupNorm partials for this shape
+int gemm_big_gn_chunks(const GemmP& p, int bm, int bn, int bk) {
+  if (p.gn_groups <= 0 || p.taps != 9 || p.geglu || (p.out_mode != DFW_OUT_T && p.out_mode != DFW_OUT_F32)) return 0;
   if ((size_t)(bm + bn) * bk * 2 < 8 * 4096) return 0;            // staged epilogue needs a 32 KiB slot
   if (p.N % p.gn_groups) return 0;
   const int cpg = p.N / p.gn_groups;
@@ -761,25 +761,15 @@ int gemm_big_gn_chunks(const GemmP& p) {
   return (p.Wo / 16) * (p.Ho / (bm / 16)) * wgm;
 }
 
-int launch_gemm_big(const GemmP& p, hipStream_t st) {
-  int bm = 0, bn = 0, bk = 0;
-  if (!gemm_big_eligible(p, bm, bn, bk)) return DFW_ESHAPE;
-  const bool bf = p.dtype_bf16 != 0;
+int launch_gemm_big(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   // 256 x 256 and 512 x 128: ping-pong schedule with v_mfma_f32_16x16x32 (A/B history in DESIGN.md section 3: +2 % each
   // against the in-phase schedule and against 32x32x16 in the same schedule; those instantiations are gone)
-  if (p.out_mode == DFW_OUT_F32) {
-    if (bm == 256) return bf ? launch_big<__bf16, 256, 256, 32, 4, 1, true, true, true>(p, st) : launch_big<_Float16, 256, 256, 32, 4, 1, true, true, true>(p, st);
-    return bf ? launch_big<__bf16, 512, 128, 32, 4, 1, true, true, true>(p, st) : launch_big<_Float16, 512, 128, 32, 4, 1, true, true, true>(p, st);
-  }
-  if (bm == 256 && bn == 256) {
-    if (gemm8_eligible(p, 256)) return launch_gemm8(p, st, 256);      // round 4: the 64-deep K-tile kernel (gemm8.hip)
-    return bf ? launch_big<__bf16, 256, 256, 32, 4, 1, true, true>(p, st) : launch_big<_Float16, 256, 256, 32, 4, 1, true, true>(p, st);
-  }
-  if (bm == 512)
-    return bf ? launch_big<__bf16, 512, 128, 32, 4, 1, true, true>(p, st) : launch_big<_Float16, 512, 128, 32, 4, 1, true, true>(p, st);
-  if (bm == 256 && bn == 128 && gemm8_eligible(p, 128)) return launch_gemm8(p, st, 128);   // dfw_config.k8 >= 2
-  if (bk == 64) return bf ? launch_big<__bf16, 256, 128, 64, 3, 1>(p, st) : launch_big<_Float16, 256, 128, 64, 3, 1>(p, st);
-  return bf ? launch_big<__bf16, 256, 128, 32, 4, 1>(p, st) : launch_big<_Float16, 256, 128, 32, 4, 1>(p, st);
+  if (pl.f32o && pl.bm == 256) return DFW_BY_DTYPE(p, launch_big<T, 256, 256, 32, 4, 1, true, true, true>(p, pl, st));
+  if (pl.f32o) return DFW_BY_DTYPE(p, launch_big<T, 512, 128, 32, 4, 1, true, true, true>(p, pl, st));
+  if (pl.bn == 256) return DFW_BY_DTYPE(p, launch_big<T, 256, 256, 32, 4, 1, true, true>(p, pl, st));
+  if (pl.bm == 512) return DFW_BY_DTYPE(p, launch_big<T, 512, 128, 32, 4, 1, true, true>(p, pl, st));
+  if (pl.bk == 64) return DFW_BY_DTYPE(p, launch_big<T, 256, 128, 64, 3, 1>(p, pl, st));
+  return DFW_BY_DTYPE(p, launch_big<T, 256, 128, 32, 4, 1>(p, pl, st));
 }
 
 }  // namespace dfw

@@ -239,17 +239,18 @@ struct TileC {
   int img, oy0, ox0;          // 2-D conv tiles: image and top-left output pixel
 };
 
-int launch_gemm_big(const GemmP& p, hipStream_t st);  // gemm_big.hip
-bool gemm_big_eligible(const GemmP& p, int& bm, int& bn, int& bk);
-int gemm_big_gn_chunks(const GemmP& p);   // > 0: the planned big kernel can emit GroupNorm partials
-int launch_gemm8(const GemmP& p, hipStream_t st, int bn);   // gemm8.hip
-bool gemm8_eligible(const GemmP& p, int bn);
-bool gemm8_n160_eligible(const GemmP& p);   // the 256 x 160 Linear tile (N = 320 at the UNet's 64^2 level)
-int launch_conv_patch(const GemmP& p, hipStream_t st);  // conv_patch.hip
-bool conv_patch_eligible(const GemmP& p, int& bm, int& bn);
-int conv_patch_gn_chunks(const GemmP& p);
-int launch_conv_patch8(const GemmP& p, hipStream_t st);  // conv_patch8.hip
-bool conv_patch8_eligible(const GemmP& p, int& bn);
-int conv_patch8_gn_chunks(const GemmP& p);
+// Launch plan of one dfw_gemm call: host side only, never a kernel argument.  gemm_plan() (gemm.hip) decides it once per
+// call; the plan queries format it and the launch_* functions of the kernel files take tile and chunk count from it.
+enum class GemmKernel { Tile, Big, K8, Patch, Patch8 };   // gemm_kernel, gemm_big_kernel, gemm8_kernel, conv_patch_kernel, conv_patch8_kernel
+struct GemmPlan {
+  GemmKernel kernel;
+  int bm, bn, bk, splitk;
+  int gn_chunks;        // 0: the planned kernel cannot emit the GroupNorm partial sums for this shape
+  bool f32o, rf32;      // the fp32-output form (Big, Patch) / the fp32-residual form (Tile) is taken
+};
+
+// Storage-dtype dispatch of the launchers: the expression with T = the storage type, e.g. DFW_BY_DTYPE(p, launch8<T, 256>(p, pl, st)).
+#define DFW_BY_DTYPE(p, ...) \
+  ((p).dtype_bf16 ? [&] { using T = __bf16; return __VA_ARGS__; }() : [&] { using T = _Float16; return __VA_ARGS__; }())
 
 }  // namespace dfw

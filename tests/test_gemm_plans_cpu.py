@@ -118,38 +118,39 @@ def test_gn_chunk_check_maps_chunks_to_their_pixels():
 
 # ---- plan coverage
 
-# Every instantiation dfw_gemm launches per storage dtype T, with the dispatch line that launches it.  RF32 / F32O: the
+# Every instantiation dfw_gemm launches per storage dtype T, with the dispatch line that launches it: gemm.hip's gemm_plan
+# picks the kernel family and the tile (GemmPlan pl), the family's launch_* function switches on the plan.  RF32 / F32O: the
 # fp32-residual / fp32-output forms (planned name + residual / output dtype).
 FORWARD_INSTANTIATIONS = {
-    **{f"gemm_kernel<T,{t},{k}>": f"gemm.hip launch_tile: gemm_kernel<T, BM, BN, {c}> ({t})"
+    **{f"gemm_kernel<T,{t},{k}>": f"gemm.hip launch_gemm -> launch_tile: gemm_kernel<T, BM, BN, {c}> ({t})"
        for t in ("128,128", "128,64", "64,64") for k, c in (("lin", "false"), ("conv", "true"))},
-    **{f"gemm_kernel<T,{t},{k},RF32>": f"gemm.hip launch_tile: if (rf32) gemm_kernel<T, BM, BN, {c}, true> ({t})"
+    **{f"gemm_kernel<T,{t},{k},RF32>": f"gemm.hip launch_gemm -> launch_tile: if (pl.rf32) gemm_kernel<T, BM, BN, {c}, true> ({t})"
        for t in ("128,128", "128,64", "64,64") for k, c in (("lin", "false"), ("conv", "true"))},
     "splitk_reduce_kernel<T>": "gemm.hip launch_tile: if (p.splitk > 1) splitk_reduce_kernel<T>",
-    **{f"gemm_big_kernel<T,256,256,32,{k}>": "gemm_big.hip launch_gemm_big: launch_big<T, 256, 256, 32, 4, 1, true, true>"
+    **{f"gemm_big_kernel<T,256,256,32,{k}>": "gemm_big.hip launch_gemm_big: if (pl.bn == 256) launch_big<T, 256, 256, 32, 4, 1, true, true>"
        for k in ("lin", "conv")},
-    **{f"gemm_big_kernel<T,512,128,32,{k}>": "gemm_big.hip launch_gemm_big: launch_big<T, 512, 128, 32, 4, 1, true, true>"
+    **{f"gemm_big_kernel<T,512,128,32,{k}>": "gemm_big.hip launch_gemm_big: if (pl.bm == 512) launch_big<T, 512, 128, 32, 4, 1, true, true>"
        for k in ("lin", "conv")},
-    **{f"gemm_big_kernel<T,256,128,64,{k}>": "gemm_big.hip launch_gemm_big: if (bk == 64) launch_big<T, 256, 128, 64, 3, 1>"
+    **{f"gemm_big_kernel<T,256,128,64,{k}>": "gemm_big.hip launch_gemm_big: if (pl.bk == 64) launch_big<T, 256, 128, 64, 3, 1>"
        for k in ("lin", "conv")},
     **{f"gemm_big_kernel<T,256,128,32,{k}>": "gemm_big.hip launch_gemm_big: launch_big<T, 256, 128, 32, 4, 1>"
        for k in ("lin", "conv")},
     **{f"gemm_big_kernel<T,256,256,32,{k},F32O>":
-       "gemm_big.hip launch_gemm_big: DFW_OUT_F32, launch_big<T, 256, 256, 32, 4, 1, true, true, true>" for k in ("lin", "conv")},
+       "gemm_big.hip launch_gemm_big: if (pl.f32o && pl.bm == 256) launch_big<T, 256, 256, 32, 4, 1, true, true, true>" for k in ("lin", "conv")},
     **{f"gemm_big_kernel<T,512,128,32,{k},F32O>":
-       "gemm_big.hip launch_gemm_big: DFW_OUT_F32, launch_big<T, 512, 128, 32, 4, 1, true, true, true>" for k in ("lin", "conv")},
-    "gemm8_kernel<T,256,256,64,lin>": "gemm_big.hip launch_gemm_big: if (gemm8_eligible(p, 256)) launch_gemm8(p, st, 256)",
-    "gemm8_kernel<T,256,256,64,conv>": "gemm_big.hip launch_gemm_big: if (gemm8_eligible(p, 256)) launch_gemm8(p, st, 256)",
-    "gemm8_kernel<T,256,128,64,lin>": "gemm_big.hip launch_gemm_big: if (... gemm8_eligible(p, 128)) launch_gemm8(p, st, 128)",
-    "gemm8_kernel<T,256,128,64,conv>": "gemm_big.hip launch_gemm_big: if (... gemm8_eligible(p, 128)) launch_gemm8(p, st, 128)",
-    "gemm8_kernel<T,256,160,64,lin>": "gemm.hip dfw_gemm: if (gemm8_n160_eligible(p)) launch_gemm8(p, st, 160)",
-    "conv_patch_kernel<T,512,128>": "conv_patch.hip launch_conv_patch: launch_patch<T, 512, 128>",
+       "gemm_big.hip launch_gemm_big: if (pl.f32o) launch_big<T, 512, 128, 32, 4, 1, true, true, true>" for k in ("lin", "conv")},
+    "gemm8_kernel<T,256,256,64,lin>": "gemm.hip gemm_plan: gemm_big rung, if (pl.bm == 256 && gemm8_eligible(p, pl.bn)); gemm8.hip launch_gemm8: launch8<T, 256>",
+    "gemm8_kernel<T,256,256,64,conv>": "gemm.hip gemm_plan: gemm_big rung, if (pl.bm == 256 && gemm8_eligible(p, pl.bn)); gemm8.hip launch_gemm8: launch8<T, 256>",
+    "gemm8_kernel<T,256,128,64,lin>": "gemm.hip gemm_plan: gemm_big rung, if (pl.bm == 256 && gemm8_eligible(p, pl.bn)); gemm8.hip launch_gemm8: launch8<T, 128>",
+    "gemm8_kernel<T,256,128,64,conv>": "gemm.hip gemm_plan: gemm_big rung, if (pl.bm == 256 && gemm8_eligible(p, pl.bn)); gemm8.hip launch_gemm8: launch8<T, 128>",
+    "gemm8_kernel<T,256,160,64,lin>": "gemm.hip gemm_plan: if (gemm8_n160_eligible(p)); gemm8.hip launch_gemm8: launch8<T, 160>",
+    "conv_patch_kernel<T,512,128>": "conv_patch.hip launch_conv_patch: if (pl.bm == 512) launch_patch<T, 512, 128>",
     "conv_patch_kernel<T,256,256>": "conv_patch.hip launch_conv_patch: launch_patch<T, 256, 256>",
-    "conv_patch_kernel<T,512,128,F32O>": "conv_patch.hip launch_conv_patch: DFW_OUT_F32, launch_patch<T, 512, 128, true>",
-    "conv_patch_kernel<T,256,256,F32O>": "conv_patch.hip launch_conv_patch: DFW_OUT_F32, launch_patch<T, 256, 256, true>",
-    "conv_patch8_kernel<T,256,256>": "conv_patch8.hip launch_conv_patch8: launch_patch8<T, 256>",
+    "conv_patch_kernel<T,512,128,F32O>": "conv_patch.hip launch_conv_patch: if (pl.f32o && pl.bm == 512) launch_patch<T, 512, 128, true>",
+    "conv_patch_kernel<T,256,256,F32O>": "conv_patch.hip launch_conv_patch: if (pl.f32o) launch_patch<T, 256, 256, true>",
+    "conv_patch8_kernel<T,256,256>": "conv_patch8.hip launch_conv_patch8: if (pl.bn == 256) launch_patch8<T, 256>",
     "conv_patch8_kernel<T,256,128>": "conv_patch8.hip launch_conv_patch8: launch_patch8<T, 128>",
-    "conv_patch8_kernel<T,256,160>": "conv_patch8.hip launch_conv_patch8: launch_patch8<T, 160>",
+    "conv_patch8_kernel<T,256,160>": "conv_patch8.hip launch_conv_patch8: if (pl.bn == 160) launch_patch8<T, 160>",
 }
 
 # Every kernel dfw_gemm_tn launches per storage dtype T (tn_reduce_kernel is fp32-only: one for both).
