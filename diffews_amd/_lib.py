@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DFW_LIB") or os.path.join(_HERE, "libdiffews_hip.so")   # DFW_LIB: A/B another build
 
 BF16, F16 = 0, 1
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1
 OUT_T, OUT_F32, OUT_NCHW_F32 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_CLAMP1 = 0, 1, 2
 
@@ -70,6 +71,20 @@ class ImageArgs(C.Structure):
     _fields_ = [("src", _vp), ("H", _i32), ("W", _i32), ("out_h", _i32), ("out_w", _i32),
                 ("xbounds", _vp), ("xcoef", _vp), ("xk", _i32), ("ybounds", _vp), ("ycoef", _vp), ("yk", _i32),
                 ("tmp", _vp), ("dst", _vp), ("lut", _vp)]
+
+
+class NativeItem(C.Structure):
+    _fields_ = [("h", _i32), ("w", _i32), ("xk", _i32), ("yk", _i32),
+                ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64),
+                ("tmp_off", _i64), ("u8_off", _i64), ("pred_off", _i64), ("gt_off", _i64),
+                ("gt_elem", _i32), ("class_value", _i32), ("ignore_value", _i32), ("reserved", _i32)]
+
+
+class SegNativeArgs(C.Structure):
+    _fields_ = [("seg_u8", _vp), ("B", _i32), ("Hs", _i32), ("Ws", _i32), ("items", _vp), ("items_host", _vp),
+                ("weights", _vp), ("weights_bytes", _sz), ("gt", _vp), ("gt_bytes", _sz), ("tmp", _vp), ("tmp_bytes", _sz),
+                ("tmp_res_off", _sz), ("out_u8", _vp), ("out_u8_bytes", _sz), ("pred", _vp), ("pred_bytes", _sz),
+                ("mx", _vp), ("counts", _vp), ("r_threshold", _f32), ("threshold", _f32), ("batch_max", _i32)]
 
 
 class GemmTnArgs(C.Structure):
@@ -208,6 +223,9 @@ SYMBOLS = {
     "dfw_resample_coeffs": (_i32, [_i32, _i32, _vp, _vp]),
     "dfw_image_to_tensor": (_i32, [C.POINTER(ImageArgs), _vp]),
     "dfw_mask_to_tensor": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dfw_resample_ksize_ex": (_i32, [_i32, _i32, _i32]),
+    "dfw_resample_coeffs_ex": (_i32, [_i32, _i32, _i32, _vp, _vp]),
+    "dfw_seg_native": (_i32, [C.POINTER(SegNativeArgs), _vp]),
 }
 
 _lib = None

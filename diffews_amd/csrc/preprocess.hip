@@ -11,6 +11,7 @@
 // byte is a 256-entry table supplied by the caller (computed by torch itself -> same bits).
 // HBM-bound integer/byte work: a 640x480 JPEG is 0.9 MB in, 3 MB out.
 #include "common.h"
+#include "resample_host.h"
 #include <math.h>
 
 namespace dfw {
@@ -87,49 +88,13 @@ __global__ __launch_bounds__(256) void mask_nearest_kernel(const M* __restrict__
 using namespace dfw;
 
 // ---- host: Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter, whole-image box
+// (the weight loop itself is resample_host.h's, shared with the output side's bicubic weights)
 extern "C" int32_t dfw_resample_ksize(int32_t in_size, int32_t out_size) {
-  if (in_size <= 0 || out_size <= 0) return 0;
-  double filterscale = (double)in_size / (double)out_size;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 1.0 * filterscale;
-  return (int32_t)ceil(support) * 2 + 1;
+  return resample_ksize_host(in_size, out_size, 1.0);
 }
 
 extern "C" int dfw_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs) {
-  if (in_size <= 0 || out_size <= 0 || !bounds || !coeffs) return DFW_EINVAL;
-  const double scale = (double)in_size / (double)out_size;
-  double filterscale = scale;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 1.0 * filterscale;
-  const int ksize = (int)ceil(support) * 2 + 1;
-  const double ss = 1.0 / filterscale;
-  double* w = (double*)malloc(sizeof(double) * ksize);
-  if (!w) return DFW_EINVAL;
-  for (int xx = 0; xx < out_size; ++xx) {
-    const double center = (xx + 0.5) * scale;
-    double ww = 0.0;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    for (int x = 0; x < xmax; ++x) {
-      double a = (x + xmin - center + 0.5) * ss;
-      if (a < 0.0) a = -a;
-      w[x] = a < 1.0 ? 1.0 - a : 0.0;
-      ww += w[x];
-    }
-    for (int x = 0; x < xmax; ++x)
-      if (ww != 0.0) w[x] /= ww;
-    for (int x = xmax; x < ksize; ++x) w[x] = 0.0;
-    int32_t* k = coeffs + (size_t)xx * ksize;
-    for (int x = 0; x < ksize; ++x)
-      k[x] = w[x] < 0 ? (int32_t)(-0.5 + w[x] * (1 << kPrecisionBits)) : (int32_t)(0.5 + w[x] * (1 << kPrecisionBits));
-    bounds[2 * xx] = xmin;
-    bounds[2 * xx + 1] = xmax;
-  }
-  free(w);
-  return 0;
+  return resample_coeffs_host(in_size, out_size, resample_bilinear, 1.0, bounds, coeffs);
 }
 
 extern "C" int dfw_image_to_tensor(const dfw_image_args* a, dfw_stream_t stream) {

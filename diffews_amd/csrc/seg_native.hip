@@ -1,0 +1,319 @@
+// Native-size masks and scores (the launcher's --use_original_imgsize, main_oss.py:128-155): the output-side counterpart
+// of preprocess.hip.  The reference resizes the uint8 prediction back to the query's own size with
+// `Image.fromarray(hwc).resize((W, H))` (marigold_pipeline_rgb_latent_noise.py:539 -- Pillow's default filter, BICUBIC)
+// and then thresholds and scores it on the host.  Here that is four launches for a whole RAGGED batch, however many
+// images it holds: zero, horizontal pass, vertical pass + per-image maximum, threshold + count.  Grid z runs over the
+// images, x / y are sized for the largest one and blocks beyond an image's extent exit; everything per image (size,
+// where its weights, scratch, outputs and ground truth lie) comes from one device-resident table, dfw_native_item[B].
+//
+// Arithmetic: resample_h_kernel's (Pillow's ImagingResample, 8 bits per channel): 2^21 + sum tap * weight, arithmetic
+// shift by 22, clamp to 0..255, uint8 intermediate between the passes; planar, since a 3-channel resize is three
+// single-channel ones.  Bicubic overshoots (a 0/200 block image reaches 225), so the dynamic threshold uses the maximum
+// of the RESIZED image, taken in the vertical pass.  Threshold and counts are seg_count_kernel's expressions.
+//
+// Byte work bound by HBM / L2: a thread produces 4 adjacent bytes of one channel row, one 32-bit store where the
+// address is 4-byte aligned (row starts are when w % 4 == 0: every offset of the table is 16-byte aligned), byte stores
+// otherwise.
+#include "common.h"
+#include "resample_host.h"
+
+namespace dfw {
+
+constexpr int kNativeBits = kResamplePrecisionBits;
+
+__device__ __forceinline__ uint32_t native_clip8(int acc) { return (uint32_t)min(max(acc >> kNativeBits, 0), 255); }
+
+__device__ __forceinline__ void native_store4(uint8_t* dst, uint32_t word, int nx) {
+  if (nx == 4 && ((uintptr_t)dst & 3) == 0) {
+    *(uint32_t*)dst = word;
+  } else {
+    for (int j = 0; j < nx; ++j) dst[j] = (uint8_t)(word >> (8 * j));
+  }
+}
+
+// Same job as misc.hip's seg_zero_kernel (a library kernel, not a memset node: see the comment there).
+__global__ void native_zero_kernel(uint32_t* mx, int B, unsigned long long* counts) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mx && e < B) mx[e] = 0u;
+  if (counts && e < 4 * B) counts[e] = 0ull;
+}
+
+// horizontal: seg_u8 [B][3][Hs][Ws] -> tmp[i] = [3][Hs][w_i].  Block (64, 4): x -> 4 adjacent output columns,
+// y -> row of the flat 3 * Hs rows of the image's planes.
+__global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict__ seg_u8,
+                                                       const dfw_native_item* __restrict__ items,
+                                                       const uint8_t* __restrict__ weights, uint8_t* __restrict__ tmp,
+                                                       int Hs, int Ws) {
+  const dfw_native_item it = items[blockIdx.z];
+  const int w = it.w;
+  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
+  const int row = blockIdx.y * 4 + threadIdx.y;
+  if (x4 >= w || row >= 3 * Hs) return;
+  const int32_t* bounds = (const int32_t*)(weights + it.xb_off);
+  const int32_t* coef = (const int32_t*)(weights + it.xc_off);
+  const uint8_t* src = seg_u8 + ((size_t)blockIdx.z * 3 * Hs + row) * Ws;
+  const int nx = min(4, w - x4);
+  uint32_t word = 0;
+  for (int j = 0; j < nx; ++j) {
+    const int xo = x4 + j;
+    const int x0 = bounds[2 * xo], n = bounds[2 * xo + 1];
+    const int32_t* k = coef + (size_t)xo * it.xk;
+    int acc = 1 << (kNativeBits - 1);
+    for (int x = 0; x < n; ++x) acc += (int)src[x0 + x] * k[x];
+    word |= native_clip8(acc) << (8 * j);
+  }
+  native_store4(tmp + it.tmp_off + (size_t)row * w + x4, word, nx);
+}
+
+// vertical + maximum: tmp[i] -> res + u8_off = [3][h_i][w_i] (res may be null: maximum only).  Block (64, 4) over
+// (4 adjacent columns, row of the flat 3 * h_i output rows).  One atomicMax per workgroup, as seg_u8_kernel does.
+__global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __restrict__ items,
+                                                       const uint8_t* __restrict__ weights,
+                                                       const uint8_t* __restrict__ tmp, uint8_t* __restrict__ res,
+                                                       uint32_t* mx, int Hs) {
+  const dfw_native_item it = items[blockIdx.z];
+  const int w = it.w, h = it.h;
+  if ((int)blockIdx.x * 256 >= w || (int)blockIdx.y * 4 >= 3 * h) return;   // whole block beyond this image
+  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
+  const int row = blockIdx.y * 4 + threadIdx.y;
+  uint32_t m = 0;
+  if (x4 < w && row < 3 * h) {
+    const int c = row / h, yo = row - c * h;
+    const int32_t* bounds = (const int32_t*)(weights + it.yb_off);
+    const int32_t* k = (const int32_t*)(weights + it.yc_off) + (size_t)yo * it.yk;
+    const int y0 = bounds[2 * yo], n = bounds[2 * yo + 1];
+    const uint8_t* col = tmp + it.tmp_off + ((size_t)c * Hs + y0) * w + x4;
+    const int nx = min(4, w - x4);
+    int acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = 1 << (kNativeBits - 1);
+    if (nx == 4 && (w & 3) == 0 && ((uintptr_t)col & 3) == 0) {
+      for (int y = 0; y < n; ++y) {
+        const uint32_t v = *(const uint32_t*)(col + (size_t)y * w);
+        const int kv = k[y];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += (int)((v >> (8 * j)) & 255u) * kv;
+      }
+    } else {
+      for (int y = 0; y < n; ++y) {
+        const uint8_t* px = col + (size_t)y * w;
+        const int kv = k[y];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < nx) acc[j] += (int)px[j] * kv;
+      }
+    }
+    uint32_t word = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nx) {
+        const uint32_t q = native_clip8(acc[j]);
+        word |= q << (8 * j);
+        m = max(m, q);
+      }
+    if (res) native_store4(res + it.u8_off + (size_t)row * w + x4, word, nx);
+  }
+  if (!mx) return;   // kernel argument: uniform
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+  __shared__ uint32_t wmax[4];
+  const int tid = threadIdx.y * 64 + threadIdx.x;
+  if ((tid & 63) == 0) wmax[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) atomicMax(mx + blockIdx.z, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+}
+
+// threshold + counts per image over h_i * w_i: seg_count_kernel's expressions and reduction, the ground truth read in
+// place at native size (uint8 or int32 class ids, per image).
+__global__ __launch_bounds__(256) void native_count_kernel(const dfw_native_item* __restrict__ items,
+                                                           const uint8_t* __restrict__ res, const uint8_t* gt,
+                                                           const uint32_t* mx, uint8_t* pred, long long* counts,
+                                                           float r_thr, float fixed_thr, int batch_max) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  __syncthreads();
+  const int b = blockIdx.y;
+  const dfw_native_item it = items[b];
+  const int HW = it.h * it.w;
+  uint32_t m = 0;
+  if (r_thr > 0.f) {
+    m = mx[b];
+    if (batch_max)
+      for (int i = 0; i < (int)gridDim.y; ++i) m = max(m, mx[i]);
+  }
+  const float thr = r_thr > 0.f ? ((float)m / 255.0f) * r_thr : fixed_thr;
+  // kept pixels, pred1, gt1, inter0, inter1 (scalars: a histogram indexed by pr would be spilled to LDS per thread);
+  // pred0 = kept - pred1, gt0 = kept - gt1
+  unsigned n_kept = 0, n_p1 = 0, n_g1 = 0, n_i0 = 0, n_i1 = 0;
+  const uint8_t* ub = res + it.u8_off;
+  uint8_t* pb = pred ? pred + it.pred_off : nullptr;
+  const uint8_t* g8 = counts ? gt + it.gt_off : nullptr;
+  const int32_t* g32 = (const int32_t*)g8;
+  const bool wide = it.gt_elem == 4;
+  const int cls = it.class_value, ign = it.ignore_value;
+  auto predict = [&](uint32_t u0, uint32_t u1, uint32_t u2) {
+    const float mean = ((lut[u0] + lut[u1]) + lut[u2]) / 3.0f;
+    return mean > thr ? 1 : 0;
+  };
+  auto tally = [&](int pr, int id) {
+    if (ign >= 0 && id == ign) return;  // ignore value: dropped from every histogram
+    const int g = id == cls ? 1 : 0;
+    n_kept++;
+    n_p1 += pr;
+    n_g1 += g;
+    n_i1 += pr & g;
+    n_i0 += (pr | g) ^ 1;
+  };
+  if ((HW & 3) == 0 && (((uintptr_t)ub | (uintptr_t)pb | (uintptr_t)g8) & 3) == 0) {
+    const int n4 = HW >> 2;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
+      const size_t o = 4 * (size_t)e;
+      const uint32_t w0 = *(const uint32_t*)(ub + o), w1 = *(const uint32_t*)(ub + HW + o);
+      const uint32_t w2 = *(const uint32_t*)(ub + 2 * (size_t)HW + o);
+      uint32_t pw = 0;
+      int pr[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        pr[k] = predict((w0 >> (8 * k)) & 255u, (w1 >> (8 * k)) & 255u, (w2 >> (8 * k)) & 255u);
+        pw |= (uint32_t)pr[k] << (8 * k);
+      }
+      if (pb) *(uint32_t*)(pb + o) = pw;
+      if (g8) {
+        if (wide) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) tally(pr[k], g32[o + k]);
+        } else {
+          const uint32_t wg = *(const uint32_t*)(g8 + o);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) tally(pr[k], (int)((wg >> (8 * k)) & 255u));
+        }
+      }
+    }
+  } else {
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
+      const int pr = predict(ub[e], ub[HW + e], ub[2 * (size_t)HW + e]);
+      if (pb) pb[e] = (uint8_t)pr;
+      if (g8) tally(pr, wide ? g32[e] : (int)g8[e]);
+    }
+  }
+  if (!counts) return;   // kernel argument: uniform
+  // inter0, inter1, pred0, pred1, gt0, gt1
+  unsigned c[6] = {n_i0, n_i1, n_kept - n_p1, n_p1, n_kept - n_g1, n_g1};
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    unsigned v = c[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+    c[k] = v;
+  }
+  // one set of integer atomics per workgroup
+  __shared__ unsigned wc[4][6];
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wc[threadIdx.x >> 6][k] = c[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned t[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t[k] = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
+    // counts[b] = {inter0, inter1, union0, union1}; union = pred + gt - inter
+    atomicAdd((unsigned long long*)(counts + b * 4 + 0), (unsigned long long)t[0]);
+    atomicAdd((unsigned long long*)(counts + b * 4 + 1), (unsigned long long)t[1]);
+    atomicAdd((unsigned long long*)(counts + b * 4 + 2), (unsigned long long)(t[2] + t[4] - t[0]));
+    atomicAdd((unsigned long long*)(counts + b * 4 + 3), (unsigned long long)(t[3] + t[5] - t[1]));
+  }
+}
+
+}  // namespace dfw
+
+using namespace dfw;
+
+extern "C" int32_t dfw_resample_ksize_ex(int32_t in_size, int32_t out_size, int32_t filter) {
+  resample_filter_fn fn;
+  double support;
+  if (!resample_filter(filter, &fn, &support)) return 0;
+  return resample_ksize_host(in_size, out_size, support);
+}
+
+extern "C" int dfw_resample_coeffs_ex(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds,
+                                      int32_t* coeffs) {
+  resample_filter_fn fn;
+  double support;
+  if (!resample_filter(filter, &fn, &support)) return DFW_EINVAL;
+  return resample_coeffs_host(in_size, out_size, fn, support, bounds, coeffs);
+}
+
+// [off, off + bytes) inside a buffer of `cap` bytes
+static bool native_fits(int64_t off, uint64_t bytes, size_t cap) {
+  return off >= 0 && (uint64_t)off <= (uint64_t)cap && bytes <= (uint64_t)cap - (uint64_t)off;
+}
+
+extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream) {
+  if (!a || !a->seg_u8 || !a->items || !a->items_host || !a->weights || !a->tmp) return DFW_EINVAL;
+  if (a->B <= 0 || a->Hs <= 0 || a->Ws <= 0) return DFW_EINVAL;
+  const bool count_stage = a->pred || a->counts;
+  if (!a->out_u8 && !a->mx && !count_stage) return DFW_EINVAL;   // nothing to produce
+  if (a->counts && !a->gt) return DFW_EINVAL;
+  if (count_stage && a->r_threshold > 0.f && !a->mx) return DFW_EINVAL;
+  // as dfw_seg_postprocess_ex: with neither flag > 0 the reference leaves the mask un-thresholded
+  if (count_stage && !(a->r_threshold > 0.f) && !(a->threshold > 0.f)) return DFW_EINVAL;
+  if (a->B > 65535 || a->Hs > 65535 || a->Ws > 65535) return DFW_ERANGE;
+  const bool need_res = a->out_u8 || count_stage;
+  uint8_t* res = a->out_u8 ? a->out_u8 : (need_res ? a->tmp + a->tmp_res_off : nullptr);
+  if (!a->out_u8 && need_res && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
+  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - (need_res ? a->tmp_res_off : 0);
+  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
+  int max_h = 0, max_w = 0;
+  long long max_hw = 0;
+  for (int i = 0; i < a->B; ++i) {
+    const dfw_native_item& t = it[i];
+    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
+    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
+    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
+    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
+        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
+      return DFW_ESHAPE;
+    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
+    const uint64_t hw = (uint64_t)t.h * t.w;
+    if (!native_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !native_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
+        !native_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !native_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
+      return DFW_EWORKSPACE;
+    const size_t tmp_cap = (!a->out_u8 && need_res) ? a->tmp_res_off : a->tmp_bytes;   // the horizontal intermediates' part
+    if (!native_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
+    if (need_res && !native_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
+    if (a->pred && !native_fits(t.pred_off, hw, a->pred_bytes)) return DFW_EWORKSPACE;
+    if (a->counts) {
+      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
+      if (!native_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
+    }
+    max_h = t.h > max_h ? t.h : max_h;
+    max_w = t.w > max_w ? t.w : max_w;
+    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dfw_native_item* items = (const dfw_native_item*)a->items;
+  const int B = a->B;
+  if (a->mx || a->counts) {
+    hipLaunchKernelGGL(native_zero_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, st, a->mx, B,
+                       (unsigned long long*)a->counts);
+    DFW_CHECK_LAUNCH();
+  }
+  const dim3 blk(64, 4);
+  hipLaunchKernelGGL(native_h_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, B), blk, 0, st, a->seg_u8, items,
+                     a->weights, a->tmp, a->Hs, a->Ws);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(native_v_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, B), blk, 0, st, items, a->weights,
+                     (const uint8_t*)a->tmp, res, a->mx, a->Hs);
+  DFW_CHECK_LAUNCH();
+  if (count_stage) {
+    int cx = (int)((max_hw / 4 + 255) / 256);
+    if (cx > 64) cx = 64;
+    if (cx < 1) cx = 1;
+    hipLaunchKernelGGL(native_count_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->gt,
+                       (const uint32_t*)a->mx, a->pred, (long long*)a->counts, a->r_threshold, a->threshold,
+                       a->batch_max ? 1 : 0);
+    DFW_CHECK_LAUNCH();
+  }
+  return 0;
+}

@@ -20,7 +20,7 @@ def episode_batches(indices, batch):
 @torch.no_grad()
 def test_diffusion(pipe, n_episodes, nshot=1, res=512, batch=1, benchmark="coco", fold=0, r_threshold=0.25,
                    rank=0, world_size=1, make_batch=None, device=None, episodes=None, threshold=0.0,
-                   batch_max=False, captured=True):
+                   batch_max=False, captured=True, use_original_imgsize=False, ignore_value=-1):
     """Run `n_episodes` episodes sharded over `world_size` ranks; returns (miou, fb_iou, meter).
     Sources, first match wins:
       episodes   -- indexable of HOST episodes (decoded PIL images / uint8 arrays + class-id masks, the
@@ -31,17 +31,25 @@ def test_diffusion(pipe, n_episodes, nshot=1, res=512, batch=1, benchmark="coco"
       otherwise  -- synthetic episodes (episodes.make_episode_batch).
     captured: every step is one replay of the pipeline-owned HIP graph (pipeline.run_episodes(captured=True));
     the per-step results are consumed (meter update on the same stream) before the next replay overwrites them.
-    r_threshold / threshold / batch_max: the launcher's thresholding flags (main_oss.py:128-135)."""
+    r_threshold / threshold / batch_max: the launcher's thresholding flags (main_oss.py:128-135).
+    use_original_imgsize (the launcher's flag of that name, main_oss.py:188): score every query at its own size -- the
+    prediction resized back as the reference's pipeline does, thresholded on the resized image and counted against the
+    query's class-id map at native size, pixels equal to `ignore_value` dropped (-1: none; 255: PASCAL's boundary) -- all
+    on the device (ops.seg_native); the meter is fed from r["native"]["counts"].  Host episodes only: the other two
+    sources have no native size, make_batch may return its own `native` (input_pipeline.NativeTargets)."""
     device = device or pipe.device
     meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
     mine = ep.shard(n_episodes, rank, world_size)
     if episodes is not None:
         from .input_pipeline import EpisodeLoader
-        loader = EpisodeLoader((episodes[i] for i in mine), res, batch, nshot, device=device)
+        loader = EpisodeLoader((episodes[i] for i in mine), res, batch, nshot, device=device,
+                               native=use_original_imgsize, ignore_value=ignore_value)
         for bt in loader:
             r = pipe.run_episodes(bt["support_imgs"], bt["query_img"], bt["support_masks"], bt["query_mask"],
-                                  r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
-            meter.update_from_counts(r["counts"], bt["class_id"].to(device))
+                                  r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured,
+                                  native=bt.get("native"))
+            counts = r["native"]["counts"] if use_original_imgsize else r["counts"]
+            meter.update_from_counts(counts, bt["class_id"].to(device))
         meter.all_reduce()
         miou, fb_iou, _ = meter.compute_iou()
         return float(miou), float(fb_iou), meter
@@ -52,9 +60,14 @@ def test_diffusion(pipe, n_episodes, nshot=1, res=512, batch=1, benchmark="coco"
         else:
             bt = ep.make_episode_batch(len(idx), nshot, res, seed=1000 + idx[0], device=device)
             cls = ep.episode_class_ids(idx, benchmark, fold)
+        native = bt.get("native") if use_original_imgsize else None
+        if use_original_imgsize and native is None:
+            raise ValueError("use_original_imgsize needs native sizes: pass host `episodes`, or a make_batch whose "
+                             "batches carry `native` (input_pipeline.NativeTargets)")
         r = pipe.run_episodes(bt["support_imgs"], bt["query_img"], bt["support_masks"], bt["query_mask"],
-                              r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
-        meter.update_from_counts(r["counts"], cls.to(device))
+                              r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured,
+                              native=native)
+        meter.update_from_counts(r["native"]["counts"] if native is not None else r["counts"], cls.to(device))
     meter.all_reduce()
     miou, fb_iou, _ = meter.compute_iou()
     return float(miou), float(fb_iou), meter
@@ -62,19 +75,28 @@ def test_diffusion(pipe, n_episodes, nshot=1, res=512, batch=1, benchmark="coco"
 
 @torch.no_grad()
 def evaluate_support_set(pipe, support_imgs, support_masks, query_batches, class_id, benchmark="coco", fold=0, r_threshold=0.25,
-                     threshold=0.0, batch_max=False, captured=True, device=None):
+                     threshold=0.0, batch_max=False, captured=True, device=None, use_original_imgsize=False, ignore_value=-1):
     """One fixed support set against a stream of queries: the bank is prepared ONCE (pipe.prepare_support), then every
     item of `query_batches` -- (query_img [b, 3, H, W], query_mask uint8 [b, H, W]) device tensors, b may vary -- goes
     through pipe.segment_queries and its counts into the AverageMeter under `class_id` (the support set's class).
-    Returns (miou, fb_iou, meter) like test_diffusion; single process, no sharding (shard `query_batches` outside)."""
+    Returns (miou, fb_iou, meter) like test_diffusion; single process, no sharding (shard `query_batches` outside).
+    use_original_imgsize: every item is (query_img, query_mask, native_gt) with native_gt the b queries' HOST class-id
+    maps (or 0/1/255 masks with class_value 1) at their own sizes; they are staged (input_pipeline.NativeTargets with
+    foreground value class_id + 1 and `ignore_value`) and the meter is fed from r["native"]["counts"]."""
     device = device or pipe.device
     meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
     bank = pipe.prepare_support(support_imgs, support_masks)
-    for query_img, query_mask in query_batches:
+    for item in query_batches:
+        query_img, query_mask = item[0], item[1]
+        native = None
+        if use_original_imgsize:
+            from .input_pipeline import NativeTargets
+            native = NativeTargets(query_img.shape[-2:], [g.shape for g in item[2]], gt=item[2],
+                                   class_value=int(class_id) + 1, ignore_value=ignore_value, device=device)
         r = pipe.segment_queries(bank, query_img, query_mask, r_threshold=r_threshold, threshold=threshold,
-                                 batch_max=batch_max, captured=captured)
+                                 batch_max=batch_max, captured=captured, native=native)
         cls = torch.full((query_img.shape[0],), int(class_id), dtype=torch.int64, device=device)
-        meter.update_from_counts(r["counts"], cls)
+        meter.update_from_counts(r["native"]["counts"] if native is not None else r["counts"], cls)
     meter.all_reduce()
     miou, fb_iou, _ = meter.compute_iou()
     return float(miou), float(fb_iou), meter

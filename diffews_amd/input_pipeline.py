@@ -30,6 +30,29 @@ def _align(n, a=16):
     return (n + a - 1) // a * a
 
 
+_COEF_CACHE = {}
+
+
+def resample_coeffs(in_size, out_size, filt=L.FILTER_BILINEAR):
+    """Pillow's fixed-point weights of one axis, in_size -> out_size, for filter `filt` (L.FILTER_BILINEAR: the input
+    side's Resize; L.FILTER_BICUBIC: `Image.resize`'s default, the output side) -> (bounds int32 [out, 2], weights int32
+    [out, ksize], ksize).  Cached per (in, out, filter); the arrays are shared, do not write to them."""
+    key = (int(in_size), int(out_size), int(filt))
+    c = _COEF_CACHE.get(key)
+    if c is None:
+        lib = L.lib()
+        k = lib.dfw_resample_ksize_ex(*key)
+        if k <= 0:
+            raise ValueError(f"no resample weights for in={in_size} out={out_size} filter={filt}")
+        b = np.zeros((key[1], 2), np.int32)
+        w = np.zeros((key[1], k), np.int32)
+        L.check(lib.dfw_resample_coeffs_ex(*key, b.ctypes.data, w.ctypes.data), "dfw_resample_coeffs_ex")
+        c = (b, w, k)
+        if len(_COEF_CACHE) < 4096:
+            _COEF_CACHE[key] = c
+    return c
+
+
 class DeviceImageTransform:
     """FSSDataset.transform + mask handling for one target size, on `device`."""
 
@@ -42,21 +65,11 @@ class DeviceImageTransform:
         # ToTensor + Normalize([0.5],[0.5]) of every byte value, computed by torch (same bits as the reference)
         lut = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
         self.lut = ((lut - 0.5) / 0.5).to(self.device)
-        self._coef = {}
 
     # ---- host side -----------------------------------------------------------------------------
     def coeffs(self, in_size):
-        """Pillow's fixed-point bilinear weights for in_size -> self.size (cached per input size)."""
-        c = self._coef.get(in_size)
-        if c is None:
-            k = self.lib.dfw_resample_ksize(in_size, self.size)
-            b = np.zeros((self.size, 2), np.int32)
-            w = np.zeros((self.size, k), np.int32)
-            L.check(self.lib.dfw_resample_coeffs(in_size, self.size, b.ctypes.data, w.ctypes.data), "dfw_resample_coeffs")
-            c = (b, w, k)
-            if len(self._coef) < 4096:
-                self._coef[in_size] = c
-        return c
+        """Pillow's fixed-point bilinear weights for in_size -> self.size (cached, see resample_coeffs)."""
+        return resample_coeffs(in_size, self.size, L.FILTER_BILINEAR)
 
     @staticmethod
     def as_rgb_bytes(img):
@@ -153,6 +166,106 @@ def fill_staging(host, items):
             hv[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
 
 
+class NativeTargets:
+    """Per-query native sizes (and ground truth) of one ragged batch, staged for ops.seg_native: the dfw_native_item
+    table, Pillow's bicubic weights of every axis and -- when given as host arrays -- the ground truth, laid out in ONE
+    pinned buffer and copied to `device` in one H2D copy on the current stream.
+
+    src_hw       (Hs, Ws) of the seg_u8 the batch will be resized from
+    sizes        [(h, w)] per query
+    gt           optional list of host arrays [h, w], uint8 or integer (staged as int32): 0/1 masks with 255 = ignore, or
+                 class-id maps
+    gt_device    instead of gt: (uint8 device tensor, [byte offset per query], [element size 1 | 4 per query]) -- ground
+                 truth already on the device (the EpisodeLoader's staged class-id maps); the tensor is kept alive here
+    class_value  int or one per query: foreground where id == class_value (1 for a 0/1 mask; coco.py:74-75)
+    ignore_value pixels with this id are dropped from the counts; -1 = none, 255 = PASCAL's boundary (pascal.py)
+    guard        bytes left free after every image in tmp and the packed outputs (tests put sentinels there)
+    device=None  builds the host layout only (`host` is then a numpy buffer): no GPU needed.
+
+    All offsets are 16-byte aligned.  tmp / out_u8 / pred are not allocated here: ops.seg_native sizes them from
+    tmp_bytes / u8_bytes / pred_bytes."""
+
+    def __init__(self, src_hw, sizes, gt=None, gt_device=None, class_value=1, ignore_value=-1, device="cuda", guard=0):
+        Hs, Ws = (int(v) for v in src_hw)
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        b = len(sizes)
+        if b < 1 or Hs < 1 or Ws < 1:
+            raise ValueError("NativeTargets needs at least one query and a positive source size")
+        if any(h < 1 or w < 1 for h, w in sizes):
+            raise ValueError(f"native sizes must be >= 1 x 1, got {sizes}")
+        if gt is not None and gt_device is not None:
+            raise ValueError("give the ground truth either as host arrays (gt) or as staged device bytes (gt_device)")
+        cls = [int(class_value)] * b if np.isscalar(class_value) else [int(c) for c in class_value]
+        if len(cls) != b:
+            raise ValueError("class_value must be one int or one per query")
+        if gt is not None:
+            if len(gt) != b:
+                raise ValueError("gt must hold one array per query")
+            gt = [DeviceImageTransform.as_mask(g) for g in gt]
+            for g, hw in zip(gt, sizes):
+                if g.shape != hw:
+                    raise ValueError(f"ground truth of shape {g.shape} for a query of native size {hw}")
+        self.src_hw, self.sizes, self.b, self.guard = (Hs, Ws), sizes, b, int(guard)
+        self.items = (L.NativeItem * b)()          # host mirror: what dfw_seg_native validates
+        off, parts = _align(C.sizeof(self.items)), []
+        tmp = u8 = pr = 0
+        for i, (h, w) in enumerate(sizes):
+            it = self.items[i]
+            xb, xw, it.xk = resample_coeffs(Ws, w, L.FILTER_BICUBIC)
+            yb, yw, it.yk = resample_coeffs(Hs, h, L.FILTER_BICUBIC)
+            it.h, it.w = h, w
+            offs = []
+            for arr in (xb, xw, yb, yw):
+                offs.append(off)
+                parts.append((off, arr))
+                off = _align(off + arr.nbytes)
+            it.xb_off, it.xc_off, it.yb_off, it.yc_off = offs
+            it.tmp_off, it.u8_off, it.pred_off = tmp, u8, pr
+            tmp = _align(tmp + 3 * Hs * w + self.guard)
+            u8 = _align(u8 + 3 * h * w + self.guard)
+            pr = _align(pr + h * w + self.guard)
+            it.gt_elem, it.class_value, it.ignore_value = 1, cls[i], int(ignore_value)
+        self.tmp_bytes, self.u8_bytes, self.pred_bytes = tmp, u8, pr
+        self.has_gt = gt is not None or gt_device is not None
+        self._gt_keep = None
+        if gt is not None:
+            for it, g in zip(self.items, gt):
+                it.gt_off, it.gt_elem = off, g.dtype.itemsize
+                parts.append((off, g))
+                off = _align(off + g.nbytes)
+        self.total = off
+        if gt_device is not None:
+            buf, offs, elems = gt_device
+            if buf.dtype != torch.uint8 or not buf.is_contiguous() or len(offs) != b or len(elems) != b:
+                raise ValueError("gt_device = (contiguous uint8 device tensor, b byte offsets, b element sizes)")
+            for it, o, e in zip(self.items, offs, elems):
+                if e not in (1, 4) or o < 0 or o + it.h * it.w * e > buf.numel():
+                    raise ValueError("staged ground truth leaves its buffer or has an element size other than 1 / 4")
+                it.gt_off, it.gt_elem = int(o), int(e)
+            self._gt_keep = buf
+        if device is None:
+            self.device, self.dev = None, None
+            self.host = np.zeros(self.total, np.uint8)
+            hv = self.host
+        else:
+            self.device = torch.device(device)
+            self.host = torch.empty(self.total, dtype=torch.uint8, pin_memory=True)
+            hv = self.host.numpy()
+        hv[:C.sizeof(self.items)] = np.frombuffer(self.items, dtype=np.uint8)
+        for o, arr in parts:
+            hv[o:o + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+        if device is not None:
+            self.dev = self.host.to(self.device, non_blocking=True)     # the one H2D copy
+
+    @property
+    def gt_base(self):
+        """(device tensor the gt offsets refer to, its bytes) or (None, 0)."""
+        if not self.has_gt:
+            return None, 0
+        buf = self._gt_keep if self._gt_keep is not None else self.dev
+        return buf, buf.numel()
+
+
 class EpisodeLoader:
     """Host episodes -> device batches, prefetched on a side stream.
 
@@ -164,10 +277,16 @@ class EpisodeLoader:
     recycled: they stay valid for the work enqueued on the consumer's stream before the NEXT batch is
     drawn (the producer's side stream waits on an event recorded at that point before overwriting).
     depth + 2 buffer sets: one with the consumer, `depth` queued, one being staged.
+
+    native=True: every batch also carries `native`, a NativeTargets for pipeline.run_episodes(native=...) /
+    ops.seg_native: each query's own h x w, its class id + 1 as the foreground value, `ignore_value` (-1: none, 255:
+    PASCAL's boundary) and, as ground truth, the query's raw class-id map where it already sits in this batch's staged
+    bytes -- no second copy, so `native` is valid exactly as long as the batch's tensors are.
     """
 
-    def __init__(self, episodes, size, batch, nshot, device="cuda", depth=2):
+    def __init__(self, episodes, size, batch, nshot, device="cuda", depth=2, native=False, ignore_value=-1):
         self.src, self.b, self.s, self.depth = episodes, int(batch), int(nshot), int(depth)
+        self.native, self.ignore_value = bool(native), int(ignore_value)
         self.tf = DeviceImageTransform(size, device)
         self.device = self.tf.device
         self.stream = torch.cuda.Stream(device=self.device)
@@ -229,10 +348,22 @@ class EpisodeLoader:
             sl["copied"].record(self.stream)
             sl["staged"] = True
             tf.launch(items, sl["dev"].data_ptr(), img_out, sl["tmp"], pm1, bins, mclass, self.stream.cuda_stream)
+            native = None
+            if self.native:
+                qm = items[-nb:]                     # the queries' class-id maps, last in the staging plan
+                for im, it in zip(images[-nb:], qm):
+                    if im.shape[:2] != (it[1], it[2]):
+                        raise ValueError(f"query image {im.shape[:2]} and query mask {(it[1], it[2])} differ in size")
+                native = NativeTargets((tf.size, tf.size), [(it[1], it[2]) for it in qm],
+                                       gt_device=(sl["dev"], [it[5][0][0] for it in qm], [it[3] for it in qm]),
+                                       class_value=mclass[-nb:], ignore_value=self.ignore_value, device=self.device)
             sl["event"].record(self.stream)
         cid = torch.tensor([int(e["class_id"]) for e in eps], dtype=torch.long)
-        return dict(support_imgs=sl["sup"], query_img=sl["qry"], support_masks=sl["smask"], query_mask=sl["qmask"],
-                    class_id=cid, _slot=sl)
+        out = dict(support_imgs=sl["sup"], query_img=sl["qry"], support_masks=sl["smask"], query_mask=sl["qmask"],
+                   class_id=cid, _slot=sl)
+        if native is not None:
+            out["native"] = native
+        return out
 
     def __iter__(self):
         q = queue.Queue(maxsize=self.depth)

@@ -582,3 +582,60 @@ def seg_labels(seg_u8, mx, gt=None, r_threshold=0.25, threshold=0.0, batch_max=F
                                    float(r_threshold), float(threshold), int(bool(batch_max)), _stream()),
             "dfw_seg_labels")
     return labels, counts
+
+
+def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False, want_u8=True, want_pred=True,
+               u8_out=None, pred_out=None, tmp=None):
+    """Native-size masks and scores: seg_u8 uint8 [b, 3, Hs, Ws] (seg_postprocess' output) resized back to every query's
+    own h x w exactly as `Image.fromarray(hwc).resize((w, h))` does (Pillow's default filter, BICUBIC), thresholded with
+    the launcher's expressions on the RESIZED image -- r_threshold > 0: max * r_threshold with the resized image's own
+    maximum (bicubic overshoots), or the batch's with batch_max; else the fixed `threshold` -- and, when `targets`
+    carries a ground truth, counted against it at native size (main_oss.py:128-155 under --use_original_imgsize).
+
+    targets: input_pipeline.NativeTargets for this batch and this (Hs, Ws).  Four launches whatever b.  Returns
+    dict(seg_u8=[uint8 views [3, h_i, w_i]] or None, pred=[uint8 0/1 views [h_i, w_i]] or None, counts=int64 [b, 4]
+    (inter0, inter1, union0, union1) or None, mx=int32 [b] resized maxima, sizes=[(h_i, w_i)]); the views of each list
+    are backed by one packed buffer.  u8_out / pred_out / tmp: caller-owned uint8 buffers of at least targets.u8_bytes /
+    pred_bytes / tmp_bytes (tmp_bytes + u8_bytes without want_u8) instead of fresh ones."""
+    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    b, _, Hs, Ws = seg_u8.shape
+    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
+        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, seg_u8 is {tuple(seg_u8.shape)}")
+    dev = seg_u8.device
+    if not torch.cuda.is_current_stream_capturing():
+        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
+
+    def buf(given, n):
+        if given is None:
+            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+        return given
+    a = L.SegNativeArgs()
+    u8 = buf(u8_out, targets.u8_bytes) if want_u8 else None
+    tmp = buf(tmp, targets.tmp_bytes + (0 if want_u8 else targets.u8_bytes))
+    pred = buf(pred_out, targets.pred_bytes) if want_pred else None
+    gt, gt_bytes = targets.gt_base
+    counts = torch.empty(b, 4, dtype=torch.int64, device=dev) if gt is not None else None
+    mx = torch.empty(b, dtype=torch.int32, device=dev)
+    a.seg_u8, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), b, Hs, Ws
+    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
+    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
+    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
+    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), targets.tmp_bytes
+    if u8 is not None:
+        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
+    if pred is not None:
+        a.pred, a.pred_bytes = pred.data_ptr(), pred.numel()
+    a.mx, a.counts = mx.data_ptr(), _p(counts)
+    a.r_threshold, a.threshold, a.batch_max = float(r_threshold), float(threshold), int(bool(batch_max))
+    L.check(L.lib().dfw_seg_native(C.byref(a), _stream()), "dfw_seg_native")
+
+    def views(t, chans):
+        out = []
+        for it in targets.items:
+            o = it.u8_off if chans == 3 else it.pred_off
+            v = t[o:o + chans * it.h * it.w]
+            out.append(v.view(3, it.h, it.w) if chans == 3 else v.view(it.h, it.w))
+        return out
+    return dict(seg_u8=views(u8, 3) if u8 is not None else None, pred=views(pred, 1) if pred is not None else None,
+                counts=counts, mx=mx, sizes=list(targets.sizes))

@@ -247,7 +247,7 @@ class MarigoldPipelineRGBLatentNoise:
     # ------------------------------------------------------------------ fused fast path
     @torch.no_grad()
     def run_episodes(self, support_imgs, query_img, support_masks, query_gt=None, r_threshold=0.25, threshold=0.0,
-                     batch_max=False, captured=None):
+                     batch_max=False, captured=None, native=None):
         """One denoising step for a batch of episodes, everything on device.
 
         support_imgs / support_masks [b*s, 3, H, W], query_img [b, 3, H, W] in [-1, 1];
@@ -258,6 +258,11 @@ class MarigoldPipelineRGBLatentNoise:
         degenerate DDIM (z0 = -v); falls back to it otherwise.
         r_threshold / threshold / batch_max: the launcher's thresholding flags (main_oss.py:128-135; see
         ops.seg_postprocess).
+
+        native (input_pipeline.NativeTargets for these b queries): the dict gains `native` = ops.seg_native on seg_u8 with
+        the same flags -- masks and counts at every query's own size (the launcher's --use_original_imgsize).  Launched
+        on the same stream after the step; sizes vary per batch, so after a captured replay it runs eagerly and is
+        neither part of the graph nor of its key.  Every other entry is what the call without `native` returns.
 
         captured (default: self.use_graph): replay the whole step (~750 kernel launches) as ONE HIP graph,
         captured on first use per (b, s, H, W, flags) into static buffers.  The inputs are copied into the
@@ -271,7 +276,8 @@ class MarigoldPipelineRGBLatentNoise:
             seg, lat = self.single_infer(support_imgs, query_img, support_masks, return_latents=True)
             dec = (seg / 255.0 * 2.0 - 1.0).contiguous()
             seg_u8, counts = ops.seg_postprocess(dec, query_gt, r_threshold, threshold, batch_max)
-            return dict(z0=lat["z0"], dec=dec, seg_u8=seg_u8, counts=counts)
+            return self._with_native(dict(z0=lat["z0"], dec=dec, seg_u8=seg_u8, counts=counts), native,
+                                     (r_threshold, threshold, batch_max))
         tt = t * self.test_timestep
         folded = self._fold_conditioning(tt)      # host + load-time work: never inside a capture
         dev = self.device
@@ -286,10 +292,20 @@ class MarigoldPipelineRGBLatentNoise:
         if captured is None:
             captured = self.use_graph
         if not captured:
-            return step(**ins)
+            return self._with_native(step(**ins), native, flags)
         key = (tuple(ins["support_imgs"].shape), tuple(ins["query_img"].shape), query_gt is not None, flags,
                float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
-        return self._replay(key, step, ins)
+        return self._with_native(self._replay(key, step, ins), native, flags)
+
+    @staticmethod
+    def _with_native(r, native, flags):
+        """r plus r["native"] = ops.seg_native(r["seg_u8"], native, *flags), eagerly on the current stream (r itself may be
+        a captured step's cached output dict: it is copied, not written)."""
+        if native is None:
+            return r
+        r = dict(r)
+        r["native"] = ops.seg_native(r["seg_u8"], native, *flags)
+        return r
 
     def _episodes_step(self, support_imgs, query_img, support_masks, query_gt, tt, folded, flags):
         """The kernels of one step; every buffer it touches is written by a library kernel (no torch.cat /
@@ -355,7 +371,7 @@ class MarigoldPipelineRGBLatentNoise:
 
     @torch.no_grad()
     def segment_queries(self, bank, query_img, query_gt=None, r_threshold=0.25, threshold=0.0, batch_max=False,
-                        captured=None):
+                        captured=None, native=None):
         """One denoising step for b query images against a prepared support set (prepare_support): query_img
         [b, 3, H, W] in [-1, 1], any b >= 1; query_gt optional uint8 [b, H, W].  Returns run_episodes' dict (z0, dec,
         seg_u8, counts) -- per image what run_episodes computes with the supports replicated b times, without encoding
@@ -369,7 +385,9 @@ class MarigoldPipelineRGBLatentNoise:
         captured (default: self.use_graph): as in run_episodes, one HIP graph per (bank, query shape, flags, ...); the
         bank's identity is part of the key and its tensors are read in place, so two banks of equal shape never share a
         graph.  At most MAX_QUERY_GRAPHS captured query steps are kept per pipeline: capturing one more drops the least
-        recently used (its buffers with it; outputs returned from it must have been consumed)."""
+        recently used (its buffers with it; outputs returned from it must have been consumed).
+
+        native: as in run_episodes -- the dict gains `native`, ops.seg_native on seg_u8, run eagerly after the step."""
         t, tt = self._single_step_timestep()
         if not self.scheduler.z0_is_neg_v(t):
             raise NotImplementedError("segment_queries needs the one-step scheduler with z0 = -v (the reference's setting); "
@@ -397,7 +415,7 @@ class MarigoldPipelineRGBLatentNoise:
         if captured is None:
             captured = self.use_graph
         if not captured:
-            return step(**ins)
+            return self._with_native(step(**ins), native, flags)
         key = ("queries", bank.uid, tuple(ins["query_img"].shape), query_gt is not None, flags, float(tt), folded,
                getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
         if key in self._graphs:
@@ -406,7 +424,7 @@ class MarigoldPipelineRGBLatentNoise:
             mine = [k for k in self._graphs if k[0] == "queries"]
             for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
                 del self._graphs[k]
-        return self._replay(key, step, ins)
+        return self._with_native(self._replay(key, step, ins), native, flags)
 
     # ------------------------------------------------------------------ N-way: a stack of class banks
     @torch.no_grad()

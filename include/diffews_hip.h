@@ -383,6 +383,63 @@ int dfw_image_to_tensor(const dfw_image_args* a, dfw_stream_t stream);
 int dfw_mask_to_tensor(const void* mask, int32_t elem_bytes, int32_t H, int32_t W, int32_t class_value,
                        int32_t out_h, int32_t out_w, float* dst_pm1, uint8_t* dst_bin, dfw_stream_t stream);
 
+/*
+ * Native-size masks and scores (the launcher's --use_original_imgsize, main_oss.py:128-155): the output-side counterpart
+ * of the input transform.  The quantised prediction seg_u8 [B][3][Hs][Ws] is resized back to every query's own h x w as
+ * `Image.fromarray(hwc).resize((w, h))` does (marigold_pipeline_rgb_latent_noise.py:539: Pillow's default filter,
+ * BICUBIC, a = -0.5, support 2; bit-exact, planar = three single-channel resizes), thresholded with the maximum of the
+ * RESIZED image (bicubic overshoots) and counted against a ground truth read in place at native size.
+ *
+ * dfw_resample_ksize_ex / dfw_resample_coeffs_ex: the HOST functions above for either filter; with DFW_FILTER_BILINEAR
+ * they return exactly what dfw_resample_ksize / dfw_resample_coeffs return.  Unknown filter: 0 / DFW_EINVAL.
+ */
+enum { DFW_FILTER_BILINEAR = 0, DFW_FILTER_BICUBIC = 1 };
+int32_t dfw_resample_ksize_ex(int32_t in_size, int32_t out_size, int32_t filter);
+int dfw_resample_coeffs_ex(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* coeffs);
+
+/* One image of a ragged batch.  Every offset is in BYTES from the base pointer named; bounds / coefficients need 4-byte
+ * alignment, an int32 ground truth too. */
+typedef struct {
+  int32_t h, w;                        /* native size */
+  int32_t xk, yk;                      /* dfw_resample_ksize_ex(Ws, w, BICUBIC), (Hs, h, BICUBIC) */
+  int64_t xb_off, xc_off;              /* from `weights`: x bounds [w][2], x coefficients [w][xk] (int32) */
+  int64_t yb_off, yc_off;              /* from `weights`: y bounds [h][2], y coefficients [h][yk] (int32) */
+  int64_t tmp_off;                     /* from `tmp`: horizontal intermediate [3][Hs][w] bytes */
+  int64_t u8_off;                      /* from `out_u8` (or tmp + tmp_res_off without it): resized [3][h][w] bytes */
+  int64_t pred_off;                    /* from `pred`: [h][w] bytes */
+  int64_t gt_off;                      /* from `gt`: [h][w] elements of gt_elem bytes */
+  int32_t gt_elem;                     /* 1 (uint8) or 4 (int32) */
+  int32_t class_value;                 /* foreground where id == class_value (1 for a 0/1 mask) */
+  int32_t ignore_value;                /* pixel dropped where id == ignore_value; -1: none (255: PASCAL's boundary) */
+  int32_t reserved;
+} dfw_native_item;
+
+typedef struct {
+  const uint8_t* seg_u8;               /* device, planar [B][3][Hs][Ws] */
+  int32_t B, Hs, Ws;
+  const void* items;                   /* device, dfw_native_item [B]: what the kernels read */
+  const void* items_host;              /* host mirror of the same table: what this call validates */
+  const uint8_t* weights; size_t weights_bytes;   /* device base of the bounds / coefficient offsets */
+  const uint8_t* gt; size_t gt_bytes;             /* device base of the ground-truth offsets; required with counts */
+  uint8_t* tmp; size_t tmp_bytes;                 /* device scratch */
+  size_t tmp_res_off;                  /* without out_u8 the resized bytes are staged at tmp + tmp_res_off + u8_off */
+  uint8_t* out_u8; size_t out_u8_bytes;           /* optional: packed planar [3][h_i][w_i] per image */
+  uint8_t* pred; size_t pred_bytes;               /* optional: packed [h_i][w_i] bytes 0/1 */
+  uint32_t* mx;                        /* optional, [B]: maximum of each resized image; required with pred / counts and
+                                          r_threshold > 0.  Zeroed by this call. */
+  int64_t* counts;                     /* optional, [B][4] = inter0, inter1, union0, union1 as dfw_seg_postprocess;
+                                          zeroed by this call */
+  float r_threshold, threshold;        /* as dfw_seg_postprocess_ex; m is the RESIZED image's maximum */
+  int32_t batch_max;
+} dfw_seg_native_args;
+
+/* Launches, whatever B: zero (mx / counts, a library kernel), horizontal pass, vertical pass + maximum, and -- with pred
+ * or counts -- threshold + count.  Grid z runs over images, x / y are sized for the largest image of the batch.
+ * Validated on the host mirror before the first launch: null pointers / non-positive sizes / nothing to produce /
+ * gt_elem not 1 or 4 -> DFW_EINVAL; a ksize that disagrees with dfw_resample_ksize_ex or a misaligned offset ->
+ * DFW_ESHAPE; h, w, Hs, Ws or B above 65535 -> DFW_ERANGE; an offset whose extent leaves its buffer -> DFW_EWORKSPACE. */
+int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
