@@ -87,6 +87,14 @@ class SegNativeArgs(C.Structure):
                 ("mx", _vp), ("counts", _vp), ("r_threshold", _f32), ("threshold", _f32), ("batch_max", _i32)]
 
 
+class SegLabelsNativeArgs(C.Structure):
+    _fields_ = [("seg_u8", _vp), ("N", _i32), ("B", _i32), ("Hs", _i32), ("Ws", _i32), ("items", _vp), ("items_host", _vp),
+                ("weights", _vp), ("weights_bytes", _sz), ("gt", _vp), ("gt_bytes", _sz), ("tmp", _vp), ("tmp_bytes", _sz),
+                ("tmp_res_off", _sz), ("tmp_cls_stride", _sz), ("u8_cls_stride", _sz), ("out_u8", _vp), ("out_u8_bytes", _sz),
+                ("labels", _vp), ("labels_bytes", _sz), ("mx", _vp), ("counts", _vp), ("class_ids", _vp),
+                ("r_threshold", _f32), ("threshold", _f32), ("batch_max", _i32)]
+
+
 class GemmTnArgs(C.Structure):
     _fields_ = [("A", _vp), ("B", _vp), ("out", _vp), ("workspace", _vp), ("workspace_bytes", _sz),
                 ("a_elems", _i64), ("b_elems", _i64),
@@ -226,6 +234,7 @@ SYMBOLS = {
     "dfw_resample_ksize_ex": (_i32, [_i32, _i32, _i32]),
     "dfw_resample_coeffs_ex": (_i32, [_i32, _i32, _i32, _vp, _vp]),
     "dfw_seg_native": (_i32, [C.POINTER(SegNativeArgs), _vp]),
+    "dfw_seg_labels_native": (_i32, [C.POINTER(SegLabelsNativeArgs), _vp]),
 }
 
 _lib = None

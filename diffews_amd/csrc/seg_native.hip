@@ -11,6 +11,10 @@
 // single-channel ones.  Bicubic overshoots (a 0/200 block image reaches 225), so the dynamic threshold uses the maximum
 // of the RESIZED image, taken in the vertical pass.  Threshold and counts are seg_count_kernel's expressions.
 //
+// dfw_seg_labels_native is the same for N classes (seg_u8 [N][B][3][Hs][Ws], pipeline.segment_classes): the two resize
+// kernels run over N * B planes-of-3 (grid z = c * B + i, one item per image, a byte stride per class), the fourth launch
+// is seg_labels_kernel's label rule and LDS histograms at native size.
+//
 // Byte work bound by HBM / L2: a thread produces 4 adjacent bytes of one channel row, one 32-bit store where the
 // address is 4-byte aligned (row starts are when w % 4 == 0: every offset of the table is 16-byte aligned), byte stores
 // otherwise.
@@ -32,19 +36,22 @@ __device__ __forceinline__ void native_store4(uint8_t* dst, uint32_t word, int n
 }
 
 // Same job as misc.hip's seg_zero_kernel (a library kernel, not a memset node: see the comment there).
-__global__ void native_zero_kernel(uint32_t* mx, int B, unsigned long long* counts) {
+__global__ void native_zero_kernel(uint32_t* mx, int n_mx, unsigned long long* counts, int n_counts) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mx && e < B) mx[e] = 0u;
-  if (counts && e < 4 * B) counts[e] = 0ull;
+  if (mx && e < n_mx) mx[e] = 0u;
+  if (counts && e < n_counts) counts[e] = 0ull;
 }
 
 // horizontal: seg_u8 [B][3][Hs][Ws] -> tmp[i] = [3][Hs][w_i].  Block (64, 4): x -> 4 adjacent output columns,
-// y -> row of the flat 3 * Hs rows of the image's planes.
+// y -> row of the flat 3 * Hs rows of the image's planes.  With classes (dfw_seg_labels_native) seg_u8 is [N][B][3][Hs][Ws]
+// and grid z = c * B + i: class c of image i uses item i, its intermediates lie tmp_cls bytes after class c - 1's.  The
+// binary path launches B planes with tmp_cls = 0.
 __global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict__ seg_u8,
                                                        const dfw_native_item* __restrict__ items,
                                                        const uint8_t* __restrict__ weights, uint8_t* __restrict__ tmp,
-                                                       int Hs, int Ws) {
-  const dfw_native_item it = items[blockIdx.z];
+                                                       int Hs, int Ws, int B, size_t tmp_cls) {
+  const int cls = blockIdx.z / B;
+  const dfw_native_item it = items[blockIdx.z - cls * B];
   const int w = it.w;
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
   const int row = blockIdx.y * 4 + threadIdx.y;
@@ -62,16 +69,18 @@ __global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict
     for (int x = 0; x < n; ++x) acc += (int)src[x0 + x] * k[x];
     word |= native_clip8(acc) << (8 * j);
   }
-  native_store4(tmp + it.tmp_off + (size_t)row * w + x4, word, nx);
+  native_store4(tmp + cls * tmp_cls + it.tmp_off + (size_t)row * w + x4, word, nx);
 }
 
 // vertical + maximum: tmp[i] -> res + u8_off = [3][h_i][w_i] (res may be null: maximum only).  Block (64, 4) over
 // (4 adjacent columns, row of the flat 3 * h_i output rows).  One atomicMax per workgroup, as seg_u8_kernel does.
+// Grid z = c * B + i as in native_h_kernel: mx is [N][B], class c's resized bytes lie res_cls bytes after class c - 1's.
 __global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __restrict__ items,
                                                        const uint8_t* __restrict__ weights,
                                                        const uint8_t* __restrict__ tmp, uint8_t* __restrict__ res,
-                                                       uint32_t* mx, int Hs) {
-  const dfw_native_item it = items[blockIdx.z];
+                                                       uint32_t* mx, int Hs, int B, size_t tmp_cls, size_t res_cls) {
+  const int cls = blockIdx.z / B;
+  const dfw_native_item it = items[blockIdx.z - cls * B];
   const int w = it.w, h = it.h;
   if ((int)blockIdx.x * 256 >= w || (int)blockIdx.y * 4 >= 3 * h) return;   // whole block beyond this image
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
@@ -82,7 +91,7 @@ __global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __
     const int32_t* bounds = (const int32_t*)(weights + it.yb_off);
     const int32_t* k = (const int32_t*)(weights + it.yc_off) + (size_t)yo * it.yk;
     const int y0 = bounds[2 * yo], n = bounds[2 * yo + 1];
-    const uint8_t* col = tmp + it.tmp_off + ((size_t)c * Hs + y0) * w + x4;
+    const uint8_t* col = tmp + cls * tmp_cls + it.tmp_off + ((size_t)c * Hs + y0) * w + x4;
     const int nx = min(4, w - x4);
     int acc[4];
 #pragma unroll
@@ -111,7 +120,7 @@ __global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __
         word |= q << (8 * j);
         m = max(m, q);
       }
-    if (res) native_store4(res + it.u8_off + (size_t)row * w + x4, word, nx);
+    if (res) native_store4(res + cls * res_cls + it.u8_off + (size_t)row * w + x4, word, nx);
   }
   if (!mx) return;   // kernel argument: uniform
 #pragma unroll
@@ -225,6 +234,119 @@ __global__ __launch_bounds__(256) void native_count_kernel(const dfw_native_item
   }
 }
 
+// label + counts per image over h_i * w_i, N classes: seg_labels_kernel's rule (misc.hip) on the RESIZED bytes -- class c of
+// image b at res + c * res_cls + u8_off -- with the thresholds from mx [N][B], the maxima of the resized planes.  The ground
+// truth is read in place at native size (uint8 or int32 per image): a pixel whose id is the item's ignore_value is dropped;
+// without class_ids the id is the label and ids outside 0..N are dropped; with class_ids the label is 1 + the lowest c
+// with class_ids[c] == id and every other id is background (ids 0..255 through an LDS table built once per workgroup).
+// Histograms of N + 1 bins in LDS, one 64-bit atomic per non-zero cell: counts [B][2][N+1].
+__global__ __launch_bounds__(256) void native_labels_kernel(const dfw_native_item* __restrict__ items,
+                                                            const uint8_t* __restrict__ res, size_t res_cls,
+                                                            const uint8_t* gt, const uint32_t* mx,
+                                                            const int32_t* class_ids, uint8_t* labels,
+                                                            unsigned long long* counts, int N, float r_thr,
+                                                            float fixed_thr, int batch_max) {
+  __shared__ float lut[256];
+  __shared__ float thr[256];
+  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][N + 1]
+  __shared__ int idmap[256];            // class_ids: ground-truth id 0..255 -> label
+  const int b = blockIdx.y, B = gridDim.y, NL = N + 1;
+  const dfw_native_item it = items[b];
+  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  if ((int)threadIdx.x < N) {
+    float t = fixed_thr;
+    if (r_thr > 0.f) {
+      const uint32_t* mc = mx + (size_t)threadIdx.x * B;
+      uint32_t m = mc[b];
+      if (batch_max)
+        for (int i = 0; i < B; ++i) m = max(m, mc[i]);
+      t = ((float)m / 255.0f) * r_thr;
+    }
+    thr[threadIdx.x] = t;
+  }
+  if (class_ids) {
+    int l = 0;
+    for (int c = N - 1; c >= 0; --c)
+      if (class_ids[c] == (int)threadIdx.x) l = c + 1;   // descending: the lowest c stays
+    idmap[threadIdx.x] = l;
+  }
+  for (int i = threadIdx.x; i < 3 * NL; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const int HW = it.h * it.w;
+  const uint8_t* ub = res + it.u8_off;            // class 0 of this image
+  uint8_t* lb = labels + it.pred_off;
+  const uint8_t* g8 = counts ? gt + it.gt_off : nullptr;
+  const int32_t* g32 = (const int32_t*)g8;
+  const bool wide = it.gt_elem == 4;
+  const int ign = it.ignore_value;
+  auto count = [&](uint32_t l, int id) {
+    if (ign >= 0 && id == ign) return;            // ignore value: dropped from every histogram
+    int g;
+    if (!class_ids) {
+      if (id < 0 || id > N) return;               // no bin: dropped as well (dfw_seg_labels' rule)
+      g = id;
+    } else if ((unsigned)id < 256u) {
+      g = idmap[id];
+    } else {
+      g = 0;
+      for (int c = N - 1; c >= 0; --c)
+        if (class_ids[c] == id) g = c + 1;
+    }
+    atomicAdd(&hist[NL + l], 1u);
+    atomicAdd(&hist[2 * NL + g], 1u);
+    if ((int)l == g) atomicAdd(&hist[l], 1u);
+  };
+  if ((HW & 3) == 0 && (res_cls & 3) == 0 && (((uintptr_t)ub | (uintptr_t)lb | (uintptr_t)g8) & 3) == 0) {
+    const int n4 = HW >> 2;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
+      const size_t o = 4 * (size_t)e;
+      float best[4] = {-1.f, -1.f, -1.f, -1.f};
+      uint32_t lab[4] = {0u, 0u, 0u, 0u};
+      const uint8_t* uc = ub + o;
+      for (int c = 0; c < N; ++c, uc += res_cls) {
+        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
+        const float t = thr[c];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
+          if (sc > t && sc > best[k]) { best[k] = sc; lab[k] = (uint32_t)(c + 1); }
+        }
+      }
+      *(uint32_t*)(lb + o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+      if (g8) {
+        if (wide) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) count(lab[k], g32[o + k]);
+        } else {
+          const uint32_t wg = *(const uint32_t*)(g8 + o);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) count(lab[k], (int)((wg >> (8 * k)) & 255u));
+        }
+      }
+    }
+  } else {
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
+      float best = -1.f;
+      uint32_t lab = 0u;
+      const uint8_t* uc = ub + e;
+      for (int c = 0; c < N; ++c, uc += res_cls) {
+        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
+        if (sc > thr[c] && sc > best) { best = sc; lab = (uint32_t)(c + 1); }
+      }
+      lb[e] = (uint8_t)lab;
+      if (g8) count(lab, wide ? g32[e] : (int)g8[e]);
+    }
+  }
+  if (!counts) return;   // kernel argument: uniform
+  __syncthreads();
+  unsigned long long* cb = counts + (size_t)b * 2 * NL;
+  for (int l = threadIdx.x; l < NL; l += 256) {
+    const unsigned in = hist[l], un = hist[NL + l] + hist[2 * NL + l] - in;
+    if (in) atomicAdd(cb + l, (unsigned long long)in);
+    if (un) atomicAdd(cb + NL + l, (unsigned long long)un);
+  }
+}
+
 }  // namespace dfw
 
 using namespace dfw;
@@ -296,15 +418,15 @@ extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream)
   const int B = a->B;
   if (a->mx || a->counts) {
     hipLaunchKernelGGL(native_zero_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, st, a->mx, B,
-                       (unsigned long long*)a->counts);
+                       (unsigned long long*)a->counts, 4 * B);
     DFW_CHECK_LAUNCH();
   }
   const dim3 blk(64, 4);
   hipLaunchKernelGGL(native_h_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, B), blk, 0, st, a->seg_u8, items,
-                     a->weights, a->tmp, a->Hs, a->Ws);
+                     a->weights, a->tmp, a->Hs, a->Ws, B, (size_t)0);
   DFW_CHECK_LAUNCH();
   hipLaunchKernelGGL(native_v_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, B), blk, 0, st, items, a->weights,
-                     (const uint8_t*)a->tmp, res, a->mx, a->Hs);
+                     (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, (size_t)0, (size_t)0);
   DFW_CHECK_LAUNCH();
   if (count_stage) {
     int cx = (int)((max_hw / 4 + 255) / 256);
@@ -315,5 +437,81 @@ extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream)
                        a->batch_max ? 1 : 0);
     DFW_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_stream_t stream) {
+  if (!a || !a->seg_u8 || !a->items || !a->items_host || !a->weights || !a->tmp || !a->labels) return DFW_EINVAL;
+  if (a->N < 1 || a->N > 254 || a->B <= 0 || a->Hs <= 0 || a->Ws <= 0) return DFW_EINVAL;
+  if (a->counts && !a->gt) return DFW_EINVAL;
+  if (a->r_threshold > 0.f && !a->mx) return DFW_EINVAL;
+  if (!(a->r_threshold > 0.f) && !(a->threshold > 0.f)) return DFW_EINVAL;   // as dfw_seg_native
+  if (a->B > 65535 || a->Hs > 65535 || a->Ws > 65535) return DFW_ERANGE;
+  if ((long long)a->N * a->B > 65535) return DFW_ERANGE;                    // grid z = N * B
+  // the resized bytes of every class are materialised (the thresholds need each plane's maximum first): in out_u8, or
+  // behind the horizontal intermediates at tmp + tmp_res_off
+  if (!a->out_u8 && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
+  uint8_t* res = a->out_u8 ? a->out_u8 : a->tmp + a->tmp_res_off;
+  const size_t tmp_cap = a->out_u8 ? a->tmp_bytes : a->tmp_res_off;
+  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off;
+  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
+  int max_h = 0, max_w = 0;
+  long long max_hw = 0;
+  uint64_t tmp_ext = 0, res_ext = 0;    // extent of one class plane in tmp / in the resized bytes
+  for (int i = 0; i < a->B; ++i) {
+    const dfw_native_item& t = it[i];
+    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
+    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
+    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
+    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
+        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
+      return DFW_ESHAPE;
+    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
+    const uint64_t hw = (uint64_t)t.h * t.w;
+    if (!native_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !native_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
+        !native_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !native_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
+      return DFW_EWORKSPACE;
+    if (!native_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
+    if (!native_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
+    if (!native_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
+    if (a->counts) {
+      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
+      if (!native_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
+    }
+    const uint64_t te = (uint64_t)t.tmp_off + 3ull * a->Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
+    tmp_ext = te > tmp_ext ? te : tmp_ext;
+    res_ext = re > res_ext ? re : res_ext;
+    max_h = t.h > max_h ? t.h : max_h;
+    max_w = t.w > max_w ? t.w : max_w;
+    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
+  }
+  // class c lies c strides after class 0: a stride holds one plane, and the last class ends inside its buffer
+  const uint64_t more = (uint64_t)(a->N - 1);
+  if (a->tmp_cls_stride < tmp_ext || a->u8_cls_stride < res_ext) return DFW_EWORKSPACE;
+  if (more && (a->tmp_cls_stride > (tmp_cap - tmp_ext) / more || a->u8_cls_stride > (res_cap - res_ext) / more))
+    return DFW_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const dfw_native_item* items = (const dfw_native_item*)a->items;
+  const int N = a->N, B = a->B, n_mx = N * B, n_counts = a->counts ? B * 2 * (N + 1) : 0;
+  if (a->mx || a->counts) {
+    const int n = n_mx > n_counts ? n_mx : n_counts;
+    hipLaunchKernelGGL(native_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a->mx, n_mx,
+                       (unsigned long long*)a->counts, n_counts);
+    DFW_CHECK_LAUNCH();
+  }
+  const dim3 blk(64, 4);
+  hipLaunchKernelGGL(native_h_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, N * B), blk, 0, st, a->seg_u8, items,
+                     a->weights, a->tmp, a->Hs, a->Ws, B, a->tmp_cls_stride);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(native_v_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, N * B), blk, 0, st, items, a->weights,
+                     (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, a->tmp_cls_stride, a->u8_cls_stride);
+  DFW_CHECK_LAUNCH();
+  int cx = (int)((max_hw / 4 + 255) / 256);
+  if (cx > 64) cx = 64;
+  if (cx < 1) cx = 1;
+  hipLaunchKernelGGL(native_labels_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->u8_cls_stride,
+                     a->gt, (const uint32_t*)a->mx, a->class_ids, a->labels, (unsigned long long*)a->counts, N,
+                     a->r_threshold, a->threshold, a->batch_max ? 1 : 0);
+  DFW_CHECK_LAUNCH();
   return 0;
 }

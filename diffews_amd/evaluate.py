@@ -104,17 +104,28 @@ def evaluate_support_set(pipe, support_imgs, support_masks, query_batches, class
 
 @torch.no_grad()
 def evaluate_class_set(pipe, support_imgs, support_masks, query_batches, r_threshold=0.25, threshold=0.0, batch_max=False,
-                       max_batch=16, captured=True):
+                       max_batch=16, captured=True, use_original_imgsize=False, class_ids=None):
     """N fixed classes against a stream of queries: the N support sets (support_imgs / support_masks [N, s, 3, H, W]) are
     prepared ONCE (pipe.prepare_support_classes), then every item of `query_batches` -- (query_img [b, 3, H, W],
     query_labels uint8 [b, H, W] with 0 = background, 1 + c = class c, 255 = ignore) device tensors, b may vary -- goes
     through pipe.segment_classes and its per-label counts into one int64 [2, N+1] running sum on the device.
-    Returns (miou, iou [N+1], counts [2, N+1]) as metrics.nway_iou defines them; single process, no sharding."""
+    Returns (miou, iou [N+1], counts [2, N+1]) as metrics.nway_iou defines them; single process, no sharding.
+    use_original_imgsize: every item is (query_img, input_pipeline.NativeTargets) -- the b queries' own sizes and their
+    ground truth at those sizes, label maps or, with class_ids (the ground-truth id of each class), class-id maps -- and the
+    running sum is fed from r["native"]["counts"] (ops.seg_labels_native): labels scored at every image's own h x w."""
     from .metrics import nway_iou
     bankset = pipe.prepare_support_classes(support_imgs, support_masks)
     total = torch.zeros(2, bankset.nsets + 1, dtype=torch.int64, device=pipe.device)
-    for query_img, query_labels in query_batches:
-        r = pipe.segment_classes(bankset, query_img, query_labels, r_threshold=r_threshold, threshold=threshold,
+    for query_img, target in query_batches:
+        if use_original_imgsize:
+            r = pipe.segment_classes(bankset, query_img, None, r_threshold=r_threshold, threshold=threshold,
+                                     batch_max=batch_max, max_batch=max_batch, captured=captured, native=target,
+                                     class_ids=class_ids)
+            if r["native"]["counts"] is None:
+                raise ValueError("use_original_imgsize needs NativeTargets that carry a ground truth")
+            total += r["native"]["counts"].sum(0)
+            continue
+        r = pipe.segment_classes(bankset, query_img, target, r_threshold=r_threshold, threshold=threshold,
                                  batch_max=batch_max, max_batch=max_batch, captured=captured)
         total += r["counts"].sum(0)
     iou, miou = nway_iou(total)

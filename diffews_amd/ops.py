@@ -639,3 +639,63 @@ def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False
         return out
     return dict(seg_u8=views(u8, 3) if u8 is not None else None, pred=views(pred, 1) if pred is not None else None,
                 counts=counts, mx=mx, sizes=list(targets.sizes))
+
+
+def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False, class_ids=None, want_u8=False,
+                      labels_out=None, u8_out=None, tmp=None):
+    """N-way labels and counts at every query's own size: seg_u8 uint8 [N, b, 3, Hs, Ws] (segment_classes' class-major
+    masks) resized per class and image as seg_native does (Pillow's default BICUBIC, exact), then seg_labels' rule on the
+    RESIZED bytes -- thresholds from the maxima of the resized planes (bicubic overshoots), label 0 or 1 + the foreground
+    class of the largest score, lowest class on a tie -- and, when `targets` carries a ground truth, per-label counts
+    against it at native size.
+
+    targets: input_pipeline.NativeTargets for these b queries and this (Hs, Ws); its ground truth is label maps (0 =
+    background, 1 + c = class c, ids above N dropped) or, with class_ids (N ints or an int32 tensor: the ground-truth id of
+    class c), class-id maps: 1 + the lowest c with class_ids[c] == id, every other id background.  Pixels equal to the
+    targets' ignore_value are dropped; their class_value is not read.  Four launches whatever N and b.  Returns
+    dict(labels=[uint8 views [h_i, w_i]], counts=int64 [b, 2, N+1] or None, mx=int32 [N, b] resized maxima,
+    seg_u8=[uint8 views [N, 3, h_i, w_i]] or None (want_u8), sizes=[(h_i, w_i)]); the views of each list are backed by one
+    packed buffer, classes targets.u8_bytes apart.  labels_out / u8_out / tmp: caller-owned uint8 buffers of at least
+    targets.pred_bytes / N * u8_bytes / N * tmp_bytes (N * (tmp_bytes + u8_bytes) without want_u8) instead of fresh ones."""
+    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 5 and seg_u8.shape[2] == 3
+    N, b, _, Hs, Ws = seg_u8.shape
+    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
+        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, seg_u8 is {tuple(seg_u8.shape)}")
+    dev = seg_u8.device
+    if not torch.cuda.is_current_stream_capturing():
+        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
+
+    def buf(given, n):
+        if given is None:
+            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+        return given
+    if class_ids is not None:
+        class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(dev).contiguous()
+        if class_ids.shape != (N,):
+            raise ValueError(f"class_ids must hold one id per class ({N}), got {tuple(class_ids.shape)}")
+    a = L.SegLabelsNativeArgs()
+    u8 = buf(u8_out, N * targets.u8_bytes) if want_u8 else None
+    tmp = buf(tmp, N * targets.tmp_bytes + (0 if want_u8 else N * targets.u8_bytes))
+    labels = buf(labels_out, targets.pred_bytes)
+    gt, gt_bytes = targets.gt_base
+    counts = torch.empty(b, 2, N + 1, dtype=torch.int64, device=dev) if gt is not None else None
+    mx = torch.empty(N, b, dtype=torch.int32, device=dev)
+    a.seg_u8, a.N, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), N, b, Hs, Ws
+    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
+    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
+    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
+    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), N * targets.tmp_bytes
+    a.tmp_cls_stride, a.u8_cls_stride = targets.tmp_bytes, targets.u8_bytes
+    if u8 is not None:
+        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
+    a.labels, a.labels_bytes = labels.data_ptr(), labels.numel()
+    a.mx, a.counts, a.class_ids = mx.data_ptr(), _p(counts), _p(class_ids)
+    a.r_threshold, a.threshold, a.batch_max = float(r_threshold), float(threshold), int(bool(batch_max))
+    L.check(L.lib().dfw_seg_labels_native(C.byref(a), _stream()), "dfw_seg_labels_native")
+    lab = [labels[it.pred_off:it.pred_off + it.h * it.w].view(it.h, it.w) for it in targets.items]
+    planes = None
+    if u8 is not None:
+        per = u8[:N * targets.u8_bytes].view(N, targets.u8_bytes)
+        planes = [per[:, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w)) for it in targets.items]
+    return dict(labels=lab, counts=counts, mx=mx, seg_u8=planes, sizes=list(targets.sizes))

@@ -454,7 +454,7 @@ class MarigoldPipelineRGBLatentNoise:
 
     @torch.no_grad()
     def segment_classes(self, bankset, query_img, query_labels=None, r_threshold=0.25, threshold=0.0, batch_max=False,
-                        max_batch=16, captured=None):
+                        max_batch=16, captured=None, native=None, class_ids=None):
         """N-way segmentation of b query images against the N prepared classes of `bankset` (prepare_support_classes):
         query_img [b, 3, H, W] in [-1, 1]; query_labels optional uint8 [b, H, W] with 0 = background, 1 + c = class c,
         255 (or anything above N) = ignore.  The queries are encoded ONCE; the classes go through the UNet and the decoder
@@ -469,7 +469,12 @@ class MarigoldPipelineRGBLatentNoise:
         tie; counts rows are per-label intersections and unions (metrics.nway_iou).
 
         Scheduler restriction, stale-handle ValueErrors and `captured` as in segment_queries; the graph key holds the
-        set's uid, the shapes, max_batch and the flags, and the graphs share segment_queries' MAX_QUERY_GRAPHS."""
+        set's uid, the shapes, max_batch and the flags, and the graphs share segment_queries' MAX_QUERY_GRAPHS.
+
+        native (input_pipeline.NativeTargets for these b queries): the dict gains `native` = ops.seg_labels_native on seg_u8
+        with this call's flags and `class_ids` -- labels, and per-label counts against the targets' ground truth, at every
+        query's own h x w.  As in run_episodes it runs eagerly on the same stream after the step, captured or not, and is
+        neither part of the graph nor of its key; every other entry is what the call without `native` returns."""
         from .unet import SupportBankSet
         if not isinstance(bankset, SupportBankSet):
             raise TypeError("bankset must be a SupportBankSet (prepare_support_classes)")
@@ -510,7 +515,7 @@ class MarigoldPipelineRGBLatentNoise:
         if captured is None:
             captured = self.use_graph
         if not captured:
-            return step(**ins)
+            return self._with_native_labels(step(**ins), native, flags, class_ids)
         key = ("queries", "classes", bankset.uid, tuple(ins["query_img"].shape), query_labels is not None, flags, int(max_batch),
                float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
         if key in self._graphs:
@@ -519,7 +524,16 @@ class MarigoldPipelineRGBLatentNoise:
             mine = [k for k in self._graphs if k[0] == "queries"]
             for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
                 del self._graphs[k]
-        return self._replay(key, step, ins)
+        return self._with_native_labels(self._replay(key, step, ins), native, flags, class_ids)
+
+    @staticmethod
+    def _with_native_labels(r, native, flags, class_ids):
+        """_with_native for segment_classes: r plus r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags)."""
+        if native is None:
+            return r
+        r = dict(r)
+        r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags, class_ids=class_ids)
+        return r
 
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one

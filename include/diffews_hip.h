@@ -440,6 +440,55 @@ typedef struct {
  * DFW_ESHAPE; h, w, Hs, Ws or B above 65535 -> DFW_ERANGE; an offset whose extent leaves its buffer -> DFW_EWORKSPACE. */
 int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream);
 
+/* N-way labels and counts at native size (version >= 106): dfw_seg_native's resize for the N classes of
+ * pipeline.segment_classes, then dfw_seg_labels' rule on the RESIZED bytes.  The ragged batch is the same
+ * dfw_native_item [B] table and weights; class c of image i uses item i, its horizontal intermediates at
+ * tmp + c * tmp_cls_stride + tmp_off and its resized bytes at out_u8 (or tmp + tmp_res_off) + c * u8_cls_stride + u8_off.
+ * The item's class_value is not read.
+ *   score_c = ((u0/255.0f + u1/255.0f) + u2/255.0f) / 3.0f from the resized bytes; c is foreground when score_c > thr_c,
+ *   thr_c = (m/255.0f) * r_threshold with m = mx[c][i] (batch_max: the maximum over class c's B images) when
+ *   r_threshold > 0, else the fixed `threshold`; label = 0 when no class is foreground, else 1 + c of the foreground
+ *   class with the largest score, lowest c on a tie.
+ * Ground truth (with counts): read in place at native size from the item's gt_off, gt_elem 1 or 4.  A pixel whose id
+ * equals the item's ignore_value (when >= 0) is dropped.  Without class_ids the id is the label and ids outside 0..N are
+ * dropped (dfw_seg_labels' rule); with class_ids the label is 1 + the lowest c with class_ids[c] == id and every other id
+ * is background 0.  counts [B][2][N+1]: row 0 label == gt == l, row 1 pred_l + gt_l - inter_l.
+ *
+ * Workspace: tmp_cls_stride >= max_i(tmp_off_i + 3 * Hs * w_i), u8_cls_stride >= max_i(u8_off_i + 3 * h_i * w_i);
+ * with out_u8:    tmp_bytes >= (N - 1) * tmp_cls_stride + max_i(tmp_off_i + 3 * Hs * w_i),
+ *                 out_u8_bytes >= (N - 1) * u8_cls_stride + max_i(u8_off_i + 3 * h_i * w_i);
+ * without out_u8: the same with tmp_res_off in place of tmp_bytes and tmp_bytes - tmp_res_off in place of out_u8_bytes,
+ *                 i.e. tmp_bytes = N * tmp_cls_stride + N * u8_cls_stride with tmp_res_off = N * tmp_cls_stride always fits.
+ * The resized bytes of all classes are materialised either way: a plane's maximum is known only once it is complete. */
+typedef struct {
+  const uint8_t* seg_u8;               /* device, planar [N][B][3][Hs][Ws], class-major */
+  int32_t N, B, Hs, Ws;
+  const void* items;                   /* device, dfw_native_item [B]: what the kernels read */
+  const void* items_host;              /* host mirror of the same table: what this call validates */
+  const uint8_t* weights; size_t weights_bytes;   /* device base of the bounds / coefficient offsets */
+  const uint8_t* gt; size_t gt_bytes;             /* device base of the ground-truth offsets; required with counts */
+  uint8_t* tmp; size_t tmp_bytes;                 /* device scratch */
+  size_t tmp_res_off;                  /* without out_u8 the resized bytes are staged from tmp + tmp_res_off */
+  size_t tmp_cls_stride;               /* bytes between two classes' horizontal intermediates */
+  size_t u8_cls_stride;                /* bytes between two classes' resized bytes */
+  uint8_t* out_u8; size_t out_u8_bytes;           /* optional: per class, packed planar [3][h_i][w_i] per image */
+  uint8_t* labels; size_t labels_bytes;           /* packed [h_i][w_i] bytes 0..N, at the items' pred_off */
+  uint32_t* mx;                        /* optional, [N][B]: maximum of each resized (class, image); required with
+                                          r_threshold > 0.  Zeroed by this call. */
+  int64_t* counts;                     /* optional, [B][2][N+1]; zeroed by this call */
+  const int32_t* class_ids;            /* optional, device int32 [N]: ground-truth id of class c */
+  float r_threshold, threshold;        /* as dfw_seg_labels; m is the RESIZED plane's maximum */
+  int32_t batch_max;
+} dfw_seg_labels_native_args;
+
+/* Four launches whatever N and B: zero (mx / counts, a library kernel), horizontal pass and vertical pass + maximum over
+ * N * B planes-of-3 (grid z), label + count over B images.  Validated on the host mirror before the first launch, as
+ * dfw_seg_native: null pointers / non-positive sizes / N outside 1..254 / counts without gt / r_threshold > 0 without mx /
+ * neither threshold > 0 / gt_elem not 1 or 4 -> DFW_EINVAL; ksize mismatch or a misaligned offset -> DFW_ESHAPE; h, w,
+ * Hs, Ws, B or N * B above 65535 -> DFW_ERANGE; an extent that leaves its buffer, or a class stride smaller than one
+ * class plane's extent -> DFW_EWORKSPACE. */
+int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
