@@ -95,6 +95,23 @@ class SegLabelsNativeArgs(C.Structure):
                 ("r_threshold", _f32), ("threshold", _f32), ("batch_max", _i32)]
 
 
+class InputImageItem(C.Structure):
+    _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
+                ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
+
+
+class InputMaskItem(C.Structure):
+    _fields_ = [("H", _i32), ("W", _i32), ("elem", _i32), ("class_value", _i32),
+                ("src_off", _i64), ("pm1_off", _i64), ("bin_off", _i64)]
+
+
+class InputsArgs(C.Structure):
+    _fields_ = [("image_items", _vp), ("image_items_host", _vp), ("n_img", _i32),
+                ("mask_items", _vp), ("mask_items_host", _vp), ("n_mask", _i32), ("out_h", _i32), ("out_w", _i32),
+                ("staged", _vp), ("staged_bytes", _sz), ("tmp", _vp), ("tmp_bytes", _sz), ("dst", _vp), ("dst_bytes", _sz),
+                ("pm1", _vp), ("pm1_bytes", _sz), ("bin", _vp), ("bin_bytes", _sz), ("lut", _vp)]
+
+
 class GemmTnArgs(C.Structure):
     _fields_ = [("A", _vp), ("B", _vp), ("out", _vp), ("workspace", _vp), ("workspace_bytes", _sz),
                 ("a_elems", _i64), ("b_elems", _i64),
@@ -235,6 +252,7 @@ SYMBOLS = {
     "dfw_resample_coeffs_ex": (_i32, [_i32, _i32, _i32, _vp, _vp]),
     "dfw_seg_native": (_i32, [C.POINTER(SegNativeArgs), _vp]),
     "dfw_seg_labels_native": (_i32, [C.POINTER(SegLabelsNativeArgs), _vp]),
+    "dfw_inputs_to_tensor": (_i32, [C.POINTER(InputsArgs), _vp]),
 }
 
 _lib = None

@@ -130,3 +130,56 @@ def evaluate_class_set(pipe, support_imgs, support_masks, query_batches, r_thres
         total += r["counts"].sum(0)
     iou, miou = nway_iou(total)
     return miou, iou, total
+
+
+@torch.no_grad()
+def evaluate_stream(pipe, support_images, support_class_maps, class_id=None, queries=(), class_ids=None, size=512, batch=4,
+                    depth=2, benchmark="coco", fold=0, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16,
+                    captured=True, ignore_value=-1):
+    """Decoded images in, scores out: annotated examples and a stream of queries, both as the dataset hands them over
+    (PIL / uint8 [H, W, 3] images of any sizes, [H, W] class-id maps), scored at every query's own size.
+
+    Binary (class_id, the benchmark's class index; the maps hold class_id + 1 as coco.py:74-75 stores it):
+      support_images / support_class_maps hold the s examples; returns (miou, fb_iou, meter) as evaluate_support_set does
+      under use_original_imgsize.
+    N-way (class_ids, the ground-truth id of each of the N classes): support_images / support_class_maps are N lists of s
+      examples each, class c's maps hold class_ids[c]; returns (miou, iou [N+1], counts [2, N+1]) as evaluate_class_set does
+      under use_original_imgsize with class_ids.
+    The supports become tensors through input_pipeline.support_tensors (one copy, three launches) and are prepared ONCE;
+    `queries` yields dicts with `query_img` and `gt` and runs through pipe.segment_stream (`size`: processing size; `batch`, `depth`); the meter (binary) or the int64 [2, N+1] running sum
+    (N-way) is fed from r["native"]["counts"].  Single process, no sharding (shard `queries` outside)."""
+    from .input_pipeline import support_tensors
+    if (class_id is None) == (class_ids is None):
+        raise ValueError("give class_id (one support set, binary scores) or class_ids (N support sets, N-way scores)")
+    device = pipe.device
+    stream = dict(batch=batch, size=size, depth=depth, ignore_value=ignore_value, r_threshold=r_threshold,
+                  threshold=threshold, batch_max=batch_max, captured=captured)
+    if class_ids is None:
+        meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
+        sup, msk = support_tensors(support_images, support_class_maps, int(class_id) + 1, size, device)
+        bank = pipe.prepare_support(sup, msk)
+        for index, r in pipe.segment_stream(bank, queries, class_value=int(class_id) + 1, **stream):
+            if r["native"]["counts"] is None:
+                raise ValueError("evaluate_stream needs queries that carry `gt`")
+            cls = torch.full((len(index),), int(class_id), dtype=torch.int64, device=device)
+            meter.update_from_counts(r["native"]["counts"], cls)
+        meter.all_reduce()
+        miou, fb_iou, _ = meter.compute_iou()
+        return float(miou), float(fb_iou), meter
+    from .metrics import nway_iou
+    ids = [int(c) for c in class_ids]
+    sets = [list(x) for x in support_images]
+    maps = [list(x) for x in support_class_maps]
+    N, s = len(ids), len(sets[0]) if sets else 0
+    if len(sets) != N or len(maps) != N or s < 1 or any(len(x) != s for x in sets + maps):
+        raise ValueError("N-way: support_images / support_class_maps must be N lists of the same number of examples")
+    sup, msk = support_tensors([im for x in sets for im in x], [m for x in maps for m in x],
+                               [c for c in ids for _ in range(s)], size, device)
+    bankset = pipe.prepare_support_classes(sup.view(N, s, *sup.shape[1:]), msk.view(N, s, *msk.shape[1:]))
+    total = torch.zeros(2, N + 1, dtype=torch.int64, device=device)
+    for index, r in pipe.segment_stream(bankset, queries, class_ids=ids, max_batch=max_batch, **stream):
+        if r["native"]["counts"] is None:
+            raise ValueError("evaluate_stream needs queries that carry `gt`")
+        total += r["native"]["counts"].sum(0)
+    iou, miou = nway_iou(total)
+    return miou, iou, total

@@ -15,6 +15,12 @@ result has exactly the tensor contract of `episodes.make_episode_batch`:
 
 Values are bit-identical to the reference's host transform (tests/test_preprocess_gpu.py checks them
 against PIL / torch themselves).  No CPU fallback: the kernels come from libdiffews_hip.so.
+
+A stream of queries against one prepared support has its own route: `InputBatch` /
+`DeviceImageTransform.batch` turn a whole ragged batch into tensors with one staging buffer and one dfw_inputs_to_tensor
+call (csrc/inputs_batch.hip: three launches whatever the batch), `support_tensors` builds a support set that way and
+`QueryLoader` yields what pipeline.segment_queries / segment_classes consume, `NativeTargets` included.  `EpisodeLoader`
+keeps the per-image launches.
 """
 import ctypes as C
 import queue
@@ -54,22 +60,34 @@ def resample_coeffs(in_size, out_size, filt=L.FILTER_BILINEAR):
 
 
 class DeviceImageTransform:
-    """FSSDataset.transform + mask handling for one target size, on `device`."""
+    """FSSDataset.transform + mask handling for one target size, on `device`.  `size` is the square S of the reference's
+    Resize((S, S)) or (out_h, out_w); `self.size` stays the int for a square target and is the pair otherwise.
+    device=None: host-only, for `batch`'s layout mode (no GPU needed)."""
 
     def __init__(self, size, device="cuda"):
-        self.size = int(size)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        if np.isscalar(size):
+            self.out_h = self.out_w = int(size)
+        else:
+            self.out_h, self.out_w = (int(v) for v in size)
+        if self.out_h < 1 or self.out_w < 1:
+            raise ValueError(f"target size must be >= 1 x 1, got {size}")
+        self.size = self.out_h if self.out_h == self.out_w else (self.out_h, self.out_w)
         self.lib = L.lib()
         # ToTensor + Normalize([0.5],[0.5]) of every byte value, computed by torch (same bits as the reference)
         lut = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
-        self.lut = ((lut - 0.5) / 0.5).to(self.device)
+        self.lut = (lut - 0.5) / 0.5
+        self.device = None
+        if device is not None:
+            self.device = torch.device(device)
+            if self.device.type == "cuda" and self.device.index is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            self.lut = self.lut.to(self.device)
 
     # ---- host side -----------------------------------------------------------------------------
-    def coeffs(self, in_size):
-        """Pillow's fixed-point bilinear weights for in_size -> self.size (cached, see resample_coeffs)."""
-        return resample_coeffs(in_size, self.size, L.FILTER_BILINEAR)
+    def coeffs(self, in_size, out_size=None):
+        """Pillow's fixed-point bilinear weights for in_size -> out_size (default: the square self.size; cached, see
+        resample_coeffs)."""
+        return resample_coeffs(in_size, self.out_w if out_size is None else out_size, L.FILTER_BILINEAR)
 
     @staticmethod
     def as_rgb_bytes(img):
@@ -95,8 +113,8 @@ class DeviceImageTransform:
         off, items = 0, []
         for im in images:
             H, W = im.shape[:2]
-            xb, xw, xk = self.coeffs(W)
-            yb, yw, yk = self.coeffs(H)
+            xb, xw, xk = self.coeffs(W, self.out_w)
+            yb, yw, yk = self.coeffs(H, self.out_h)
             parts = []
             for arr in (im, xb, xw, yb, yw):
                 parts.append((off, arr))
@@ -111,12 +129,12 @@ class DeviceImageTransform:
     def launch(self, items, dev_base, img_out, tmp, mask_pm1, mask_bin, mask_class, stream):
         """Kernels for a staged batch: image i -> img_out[i]; mask j -> mask_pm1[j] / mask_bin[j] (either
         may be None per entry)."""
-        S, ii, mi = self.size, 0, 0
+        oh, ow, ii, mi = self.out_h, self.out_w, 0, 0
         for kind, H, W, a, b, parts in items:
             if kind == "image":
                 args = L.ImageArgs()
                 p = [dev_base + o for o, _ in parts]
-                args.src, args.H, args.W, args.out_h, args.out_w = p[0], H, W, S, S
+                args.src, args.H, args.W, args.out_h, args.out_w = p[0], H, W, oh, ow
                 args.xbounds, args.xcoef, args.xk = p[1], p[2], a
                 args.ybounds, args.ycoef, args.yk = p[3], p[4], b
                 args.tmp, args.dst, args.lut = tmp.data_ptr(), img_out[ii].data_ptr(), self.lut.data_ptr()
@@ -124,7 +142,7 @@ class DeviceImageTransform:
                 ii += 1
             else:
                 pm1, bn = mask_pm1[mi], mask_bin[mi]
-                L.check(self.lib.dfw_mask_to_tensor(dev_base + parts[0][0], a, H, W, int(mask_class[mi]), S, S,
+                L.check(self.lib.dfw_mask_to_tensor(dev_base + parts[0][0], a, H, W, int(mask_class[mi]), oh, ow,
                                                     pm1.data_ptr() if pm1 is not None else None,
                                                     bn.data_ptr() if bn is not None else None, stream),
                         "dfw_mask_to_tensor")
@@ -134,7 +152,7 @@ class DeviceImageTransform:
     @torch.no_grad()
     def image(self, img):
         im = self.as_rgb_bytes(img)
-        out = torch.empty(1, 3, self.size, self.size, dtype=torch.float32, device=self.device)
+        out = torch.empty(1, 3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         self._run([im], [], out, [], [], [])
         return out[0]
 
@@ -143,8 +161,8 @@ class DeviceImageTransform:
         """-> (+-1 fp32 [3,S,S], uint8 {0,1} [S,S]) for class id `class_sample` (coco.py:74-75: the
         PNG stores class_sample + 1)."""
         m = self.as_mask(mask_ids)
-        pm1 = torch.empty(3, self.size, self.size, dtype=torch.float32, device=self.device)
-        bn = torch.empty(self.size, self.size, dtype=torch.uint8, device=self.device)
+        pm1 = torch.empty(3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
+        bn = torch.empty(self.out_h, self.out_w, dtype=torch.uint8, device=self.device)
         self._run([], [m], None, [pm1], [bn], [class_sample + 1])
         return pm1, bn
 
@@ -154,9 +172,34 @@ class DeviceImageTransform:
         fill_staging(host, items)
         dev = host.to(self.device, non_blocking=True)
         hmax = max([im.shape[0] for im in images], default=1)
-        tmp = torch.empty(hmax * self.size * 3, dtype=torch.uint8, device=self.device)
+        tmp = torch.empty(hmax * self.out_w * 3, dtype=torch.uint8, device=self.device)
         self.launch(items, dev.data_ptr(), img_out, tmp, mask_pm1, mask_bin, mask_class,
                     torch.cuda.current_stream().cuda_stream)
+
+    # ---- a whole ragged batch: one staging buffer, one H2D copy, one library call (three launches) ----------------
+    @torch.no_grad()
+    def batch(self, images, masks=(), mask_class=(), want_pm1=True, want_bin=True, guard=0, buffers=None):
+        """`images` (PIL / uint8 [H, W, 3], any sizes) and class-id maps `masks` (mask j is on where id == mask_class[j])
+        -> dict(images fp32 [n, 3, out_h, out_w] or None, pm1 fp32 [m1, 3, out_h, out_w] in +-1 or None, bin uint8
+        [m2, out_h, out_w] in 0/1 or None, layout = the InputBatch, staged = the device copy of its bytes): what image() /
+        mask() give per item, bit for bit.  want_pm1 / want_bin: one bool or one per mask; pm1 / bin hold the masks that
+        asked for them, in order.  Tables, image bytes, weights and mask ids travel in ONE pinned buffer and one H2D copy
+        on the current stream; one dfw_inputs_to_tensor call: three launches whatever the batch.
+        guard / buffers: see InputBatch (tests put sentinels around every item).
+        On a host-only transform (device=None) nothing is launched: returns the InputBatch, its bytes staged in the
+        numpy buffer `.host`."""
+        lay = InputBatch((self.out_h, self.out_w), [self.as_rgb_bytes(x) for x in images], [self.as_mask(m) for m in masks],
+                         mask_class, want_pm1, want_bin, guard=guard)
+        if self.device is None:
+            lay.host = np.zeros(max(lay.total, 16), np.uint8)
+            lay.fill(lay.host)
+            return lay
+        host = torch.empty(max(lay.total, 16), dtype=torch.uint8, pin_memory=True)
+        lay.fill(host.numpy())
+        dev = host.to(self.device, non_blocking=True)                       # the one H2D copy
+        out = lay.run(dev, self.lut, torch.cuda.current_stream(self.device).cuda_stream, **(buffers or {}))
+        out.update(layout=lay, staged=dev)
+        return out
 
 
 def fill_staging(host, items):
@@ -164,6 +207,149 @@ def fill_staging(host, items):
     for _, _, _, _, _, parts in items:
         for off, arr in parts:
             hv[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+
+
+class InputBatch:
+    """Byte layout of one ragged batch for dfw_inputs_to_tensor: the two item tables (ctypes arrays `img_items` /
+    `mask_items`: the host mirrors the library validates) and ONE staging buffer of `total` bytes holding
+    [image table][mask table][per image: RGB bytes, x bounds, x weights, y bounds, y weights][per mask: ids].
+
+    out_hw      (out_h, out_w) every item goes to
+    images      uint8 [H, W, 3] arrays; masks: 2-D uint8 / int32 class-id maps (DeviceImageTransform.as_rgb_bytes / as_mask)
+    mask_class  one int or one per mask: on where id == value
+    want_pm1 / want_bin   one bool or one per mask.  A mask that wants neither is staged only (no table item, no
+                launch): its bytes travel with the batch for a later reader (QueryLoader's native ground truth).
+    guard       bytes left free after every item in tmp / dst / pm1 / bin (tests put sentinels there)
+
+    `mask_src` holds every mask's (byte offset in the staging buffer, element size).  Every staging and tmp offset is
+    16-byte aligned.  The outputs are dense tensors: item i of dst lies at i * dst_stride with dst_stride = 12 * out_h *
+    out_w (+ guard, rounded up to 16, when guard > 0), pm1 alike, bin with out_h * out_w; they are 16-byte aligned
+    whenever out_h * out_w is a multiple of 16."""
+
+    def __init__(self, out_hw, images, masks=(), mask_class=(), want_pm1=True, want_bin=True, guard=0):
+        oh, ow = (int(v) for v in out_hw)
+        images, masks = list(images), list(masks)
+        m = len(masks)
+        per = lambda v, what: [v] * m if np.isscalar(v) else _n(list(v), m, what)
+        cls = [int(c) for c in per(mask_class if m else 0, "mask_class")]
+        pm1 = [bool(v) for v in per(want_pm1, "want_pm1")]
+        bn = [bool(v) for v in per(want_bin, "want_bin")]
+        self.out_hw, self.guard, self.n_img = (oh, ow), int(guard), len(images)
+        used = [j for j in range(m) if pm1[j] or bn[j]]
+        self.n_mask = len(used)
+        self.img_items = (L.InputImageItem * max(self.n_img, 1))()
+        self.mask_items = (L.InputMaskItem * max(self.n_mask, 1))()
+        self.img_table_off = 0
+        self.mask_table_off = _align(C.sizeof(L.InputImageItem) * self.n_img)
+        off = self.mask_table_off + _align(C.sizeof(L.InputMaskItem) * self.n_mask)
+        pad = (lambda n: _align(n + self.guard)) if self.guard else (lambda n: n)
+        self.dst_stride, self.pm1_stride, self.bin_stride = pad(12 * oh * ow), pad(12 * oh * ow), pad(oh * ow)
+        self.parts, tmp = [], 0
+        for i, im in enumerate(images):
+            H, W = im.shape[:2]
+            it = self.img_items[i]
+            xb, xw, it.xk = resample_coeffs(W, ow, L.FILTER_BILINEAR)
+            yb, yw, it.yk = resample_coeffs(H, oh, L.FILTER_BILINEAR)
+            it.H, it.W = H, W
+            offs = []
+            for arr in (im, xb, xw, yb, yw):
+                offs.append(off)
+                self.parts.append((off, arr))
+                off = _align(off + arr.nbytes)
+            it.src_off, it.xb_off, it.xc_off, it.yb_off, it.yc_off = offs
+            it.tmp_off, it.dst_off = tmp, i * self.dst_stride
+            tmp = _align(tmp + 3 * H * ow + self.guard)
+        self.mask_src, self.pm1_index, self.bin_index = [], [], []
+        for j, mk in enumerate(masks):
+            self.mask_src.append((off, mk.dtype.itemsize))
+            self.parts.append((off, mk))
+            if pm1[j] or bn[j]:
+                it = self.mask_items[used.index(j)]
+                it.H, it.W, it.elem, it.class_value, it.src_off = mk.shape[0], mk.shape[1], mk.dtype.itemsize, cls[j], off
+                it.pm1_off = len(self.pm1_index) * self.pm1_stride if pm1[j] else -1
+                it.bin_off = len(self.bin_index) * self.bin_stride if bn[j] else -1
+                if pm1[j]:
+                    self.pm1_index.append(j)
+                if bn[j]:
+                    self.bin_index.append(j)
+            off = _align(off + mk.nbytes)
+        self.total, self.tmp_bytes = off, tmp
+        self.dst_bytes = self.n_img * self.dst_stride
+        self.pm1_bytes = len(self.pm1_index) * self.pm1_stride
+        self.bin_bytes = len(self.bin_index) * self.bin_stride
+        self.host = None
+
+    def fill(self, hv):
+        """Write the tables and every staged array into the numpy uint8 view `hv` (>= total bytes)."""
+        if self.n_img:
+            n = C.sizeof(L.InputImageItem) * self.n_img
+            hv[:n] = np.frombuffer(self.img_items, dtype=np.uint8)[:n]
+        if self.n_mask:
+            n = C.sizeof(L.InputMaskItem) * self.n_mask
+            hv[self.mask_table_off:self.mask_table_off + n] = np.frombuffer(self.mask_items, dtype=np.uint8)[:n]
+        for off, arr in self.parts:
+            hv[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
+
+    def args(self, staged, staged_bytes, lut, tmp=(None, 0), dst=(None, 0), pm1=(None, 0), bin=(None, 0)):
+        """The dfw_inputs_args of this batch for base addresses given as (address, bytes) pairs."""
+        a = L.InputsArgs()
+        a.image_items, a.image_items_host, a.n_img = staged + self.img_table_off, C.addressof(self.img_items), self.n_img
+        a.mask_items, a.mask_items_host, a.n_mask = staged + self.mask_table_off, C.addressof(self.mask_items), self.n_mask
+        a.out_h, a.out_w = self.out_hw
+        a.staged, a.staged_bytes, a.lut = staged, staged_bytes, lut
+        (a.tmp, a.tmp_bytes), (a.dst, a.dst_bytes), (a.pm1, a.pm1_bytes), (a.bin, a.bin_bytes) = tmp, dst, pm1, bin
+        return a
+
+    def run(self, staged, lut, stream, tmp=None, dst=None, pm1=None, bin=None):
+        """One dfw_inputs_to_tensor call on `stream` over `staged` (uint8 device tensor holding fill()'s bytes from its
+        start).  tmp / dst / pm1 / bin: caller-owned contiguous uint8 device buffers of at least tmp_bytes / dst_bytes /
+        pm1_bytes / bin_bytes (fresh ones otherwise).  Returns dict(images, pm1, bin): strided views of those buffers,
+        None where the batch has nothing of the kind."""
+        dev, (oh, ow) = staged.device, self.out_hw
+        if self.n_img + self.n_mask == 0:
+            return dict(images=None, pm1=None, bin=None)
+
+        def buf(given, n):
+            if n == 0:
+                return None
+            if given is None:
+                return torch.empty(n, dtype=torch.uint8, device=dev)
+            assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+            return given
+        tmp, dst, pm1, bin = buf(tmp, self.tmp_bytes), buf(dst, self.dst_bytes), buf(pm1, self.pm1_bytes), buf(bin, self.bin_bytes)
+        pair = lambda t: (None, 0) if t is None else (t.data_ptr(), t.numel())
+        a = self.args(staged.data_ptr(), staged.numel(), lut.data_ptr(), pair(tmp), pair(dst), pair(pm1), pair(bin))
+        L.check(L.lib().dfw_inputs_to_tensor(C.byref(a), stream), "dfw_inputs_to_tensor")
+
+        def planes(t, n, stride):
+            if t is None:
+                return None
+            f = t[:n * stride].view(torch.float32)
+            return f.as_strided((n, 3, oh, ow), (stride // 4, oh * ow, ow, 1))
+        bins = None
+        if bin is not None:
+            bins = bin.as_strided((len(self.bin_index), oh, ow), (self.bin_stride, ow, 1))
+        return dict(images=planes(dst, self.n_img, self.dst_stride),
+                    pm1=planes(pm1, len(self.pm1_index), self.pm1_stride), bin=bins)
+
+
+def _n(v, n, what):
+    if len(v) != n:
+        raise ValueError(f"{what} must be one value or one per mask ({n}), got {len(v)}")
+    return v
+
+
+@torch.no_grad()
+def support_tensors(images, class_maps, class_values, size, device="cuda"):
+    """n annotated examples -- decoded images of any sizes, their class-id maps and the id (one int, or one per example)
+    that marks the object -- -> (support_imgs fp32 [n, 3, S, S] in [-1, 1], support_masks fp32 [n, 3, S, S] in +-1)
+    through DeviceImageTransform.batch: one H2D copy and three launches for the whole set.  Feed them to
+    pipeline.prepare_support, or to prepare_support_classes after a view to [N, s, 3, S, S]."""
+    images, class_maps = list(images), list(class_maps)
+    if not images or len(images) != len(class_maps):
+        raise ValueError("support_tensors needs as many class-id maps as images, and at least one")
+    r = DeviceImageTransform(size, device).batch(images, class_maps, class_values, want_pm1=True, want_bin=False)
+    return r["images"], r["pm1"]
 
 
 class NativeTargets:
@@ -391,6 +577,170 @@ class EpisodeLoader:
                 q.put(None)
             except BaseException as ex:  # surfaced in the consumer
                 q.put(ex)
+
+        th = threading.Thread(target=produce, daemon=True)
+        th.start()
+        try:
+            while True:
+                item = q.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                sl = item.pop("_slot")
+                torch.cuda.current_stream(self.device).wait_event(sl["event"])
+                yield item
+                sl["release"].record(torch.cuda.current_stream(self.device))
+                sl["released"] = True
+        finally:
+            stop.set()
+
+
+class QueryLoader:
+    """Host queries -> device batches for pipeline.segment_queries / segment_classes, prefetched on a side stream: the
+    input half of "segment a stream of images against the same few annotated examples".
+
+    `queries` yields dicts with
+        query_img: PIL image or uint8 [H, W, 3] array, any size
+        gt (optional): class-id map or label map [H, W] (uint8 / int) of the same size; all queries of a batch carry
+                       one, or none does
+    Iterating yields dicts with
+        query_img  fp32 [b, 3, out_h, out_w] in [-1, 1] (DeviceImageTransform.batch: one pinned buffer, one H2D copy and
+                   three launches per batch, whatever b)
+        native     NativeTargets for the b queries' own sizes; with `gt` its ground truth is read IN PLACE from the
+                   batch's staged bytes (gt_device: no second copy), with `ignore_value` (-1: none, 255: PASCAL's
+                   boundary) and the query's class value as foreground (1 without class_value); without `gt` it carries
+                   sizes only and the native counts are None
+        query_mask (only with class_value and gt) uint8 [b, out_h, out_w]: gt == class value, nearest-resized, so
+                   r["counts"] at the processing size works too
+        index      positions of the batch's queries in the stream (list of int)
+    class_value: one int, or a callable on the query dict.  The last batch may be short.
+
+    Producer thread, side stream, slot recycling and the copied / release / event protocol are EpisodeLoader's: a
+    batch's tensors (and its `native`) stay valid for the work enqueued on the consumer's stream before the NEXT batch
+    is drawn.  depth + 2 buffer sets: one with the consumer, `depth` queued, one being staged.
+    """
+
+    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1):
+        self.src, self.b, self.depth = queries, int(batch), int(depth)
+        if self.b < 1 or self.depth < 1:
+            raise ValueError("QueryLoader needs batch >= 1 and depth >= 1")
+        self.class_value, self.ignore_value = class_value, int(ignore_value)
+        self.tf = DeviceImageTransform(size, device)
+        self.device = self.tf.device
+        self.stream = None if self.device is None else torch.cuda.Stream(device=self.device)
+        self._slots = [None] * (self.depth + 2)
+
+    def layout(self, qs):
+        """(InputBatch, per-query class values, has_gt) of one batch of query dicts: the images, then the ground-truth
+        maps -- with class_value each also a mask item with a 0/1 destination, without it staged only."""
+        tf = self.tf
+        images = [tf.as_rgb_bytes(q["query_img"]) for q in qs]
+        with_gt = [q.get("gt") is not None for q in qs]
+        if any(with_gt) and not all(with_gt):
+            raise ValueError("either every query of a batch carries `gt` or none does")
+        gts, cls = [], [1] * len(qs)
+        if all(with_gt):
+            gts = [tf.as_mask(q["gt"]) for q in qs]
+            for im, g in zip(images, gts):
+                if im.shape[:2] != g.shape:
+                    raise ValueError(f"query image {im.shape[:2]} and its gt {g.shape} differ in size")
+            if self.class_value is not None:
+                cls = [int(self.class_value(q)) if callable(self.class_value) else int(self.class_value) for q in qs]
+        want_bin = self.class_value is not None
+        lay = InputBatch((tf.out_h, tf.out_w), images, gts, cls if gts else (), want_pm1=False, want_bin=want_bin)
+        return lay, cls, bool(gts)
+
+    def _native(self, lay, cls, has_gt, staged, device):
+        gt_device = None
+        if has_gt:
+            gt_device = (staged, [o for o, _ in lay.mask_src], [e for _, e in lay.mask_src])
+        return NativeTargets(lay.out_hw, [(it.H, it.W) for it in lay.img_items[:lay.n_img]], gt_device=gt_device,
+                             class_value=cls, ignore_value=self.ignore_value, device=device)
+
+    def host_batch(self, qs):
+        """Host-only layout of one batch of query dicts (a loader built with device=None; no GPU needed): (InputBatch with
+        its bytes in the numpy buffer `.host`, NativeTargets(device=None) whose gt offsets refer to that buffer)."""
+        lay, cls, has_gt = self.layout(qs)
+        lay.host = np.zeros(max(lay.total, 16), np.uint8)
+        lay.fill(lay.host)
+        return lay, self._native(lay, cls, has_gt, torch.from_numpy(lay.host), None)
+
+    def _slot(self, i, lay):
+        tf, dev, s = self.tf, self.device, self._slots[i]
+        if s is None:
+            s = dict(host=None, dev=None, tmp=None,
+                     qry=torch.empty(self.b * lay.dst_stride, dtype=torch.uint8, device=dev),
+                     qmask=torch.empty(self.b * lay.bin_stride, dtype=torch.uint8, device=dev)
+                     if self.class_value is not None else None,
+                     event=torch.cuda.Event(), release=torch.cuda.Event(), released=False,
+                     copied=torch.cuda.Event(), staged=False)
+            self._slots[i] = s
+        if s["host"] is None or s["host"].numel() < lay.total:
+            if s["dev"] is not None:
+                s["dev"].record_stream(self.stream)   # still read by kernels queued on the side stream
+            s["host"] = torch.empty(int(lay.total * 1.25) + 64, dtype=torch.uint8, pin_memory=True)
+            s["dev"] = torch.empty(s["host"].numel(), dtype=torch.uint8, device=dev)
+        if s["tmp"] is None or s["tmp"].numel() < lay.tmp_bytes:
+            if s["tmp"] is not None:
+                s["tmp"].record_stream(self.stream)
+            s["tmp"] = torch.empty(int(lay.tmp_bytes * 1.25), dtype=torch.uint8, device=dev)
+        return s
+
+    def _stage(self, i, qs, index):
+        """Decode-side work for one batch (runs in the producer thread): pack, copy, launch."""
+        tf = self.tf
+        lay, cls, has_gt = self.layout(qs)
+        sl = self._slot(i, lay)
+        if sl["staged"]:
+            # as EpisodeLoader._stage: the H2D copy of this slot's previous batch may still be reading the pinned bytes
+            sl["copied"].synchronize()
+        lay.fill(sl["host"].numpy())
+        with torch.cuda.stream(self.stream):
+            if sl["released"]:          # the consumer's work on this buffer set's previous batch
+                self.stream.wait_event(sl["release"])
+            sl["dev"][:lay.total].copy_(sl["host"][:lay.total], non_blocking=True)
+            sl["copied"].record(self.stream)
+            sl["staged"] = True
+            r = lay.run(sl["dev"], tf.lut, self.stream.cuda_stream, tmp=sl["tmp"], dst=sl["qry"], bin=sl["qmask"])
+            native = self._native(lay, cls, has_gt, sl["dev"], self.device)
+            sl["event"].record(self.stream)
+        out = dict(query_img=r["images"], native=native, index=list(index), _slot=sl)
+        if r["bin"] is not None:
+            out["query_mask"] = r["bin"]
+        return out
+
+    def __iter__(self):
+        if self.device is None:
+            raise RuntimeError("a host-only QueryLoader (device=None) lays batches out (host_batch); it does not iterate")
+        q = queue.Queue(maxsize=self.depth)
+        stop = threading.Event()
+        nslots = self.depth + 2
+
+        def put(out):
+            while not stop.is_set():
+                try:
+                    q.put(out, timeout=0.1)
+                    return
+                except queue.Full:
+                    continue
+
+        def produce():
+            try:
+                torch.cuda.set_device(self.device)
+                buf, i, pos = [], 0, 0
+                for e in self.src:
+                    if stop.is_set():
+                        return
+                    buf.append(e)
+                    if len(buf) == self.b:
+                        put(self._stage(i % nslots, buf, range(pos, pos + len(buf))))
+                        buf, i, pos = [], i + 1, pos + self.b
+                if buf and not stop.is_set():
+                    put(self._stage(i % nslots, buf, range(pos, pos + len(buf))))
+                put(None)
+            except BaseException as ex:  # surfaced in the consumer
+                put(ex)
 
         th = threading.Thread(target=produce, daemon=True)
         th.start()

@@ -526,6 +526,48 @@ class MarigoldPipelineRGBLatentNoise:
                 del self._graphs[k]
         return self._with_native_labels(self._replay(key, step, ins), native, flags, class_ids)
 
+    def segment_stream(self, support, queries, batch=4, size=None, depth=2, class_value=None, ignore_value=-1,
+                       class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None):
+        """Generator: a stream of decoded images against one prepared support -- `support` a SupportBank (prepare_support;
+        routed to segment_queries) or a SupportBankSet (prepare_support_classes; routed to segment_classes, with
+        `class_ids` and `max_batch`).  `queries` yields dicts with `query_img` (PIL / uint8 [H, W, 3], any size) and
+        optionally `gt` ([H, W] class-id or label map); an input_pipeline.QueryLoader (`batch`, `depth`, `class_value`,
+        `ignore_value`; `size` = processing size, default: the one the support was prepared at) resizes and normalises
+        them on a side stream, one H2D copy and three launches per batch, while the previous batch is in the UNet.
+
+        Yields (index, r): `index` the positions of the batch's queries in the stream, `r` the routed call's dict with
+        `native` present -- masks / labels at every query's own size and, with `gt`, counts against it read in place from
+        the batch's staged bytes.  With `class_value` (SupportBank only) the queries' nearest-resized 0/1 masks also feed
+        r["counts"] at the processing size.  The last batch may be short.
+
+        r is valid until the next item is drawn: its tensors belong to a captured step's outputs and to the loader's
+        recycled slots, and drawing the next item lets both be overwritten.  Consume (or clone) it first, on the current
+        stream; no host synchronisation is needed."""
+        from .input_pipeline import QueryLoader
+        from .unet import SupportBank, SupportBankSet
+        if not isinstance(support, (SupportBank, SupportBankSet)):
+            raise TypeError("support must be a SupportBank (prepare_support) or a SupportBankSet (prepare_support_classes)")
+        nway = isinstance(support, SupportBankSet)
+        if nway and class_value is not None:
+            raise ValueError("class_value belongs to a SupportBank; with a SupportBankSet give class_ids")
+        if not nway and class_ids is not None:
+            raise ValueError("class_ids belongs to a SupportBankSet; with a SupportBank give class_value")
+        if size is None:
+            f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+            size = (support.hw[0] * f, support.hw[1] * f)
+        flags = dict(r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
+        if class_ids is not None:     # staged once, not per batch
+            class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
+        loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, class_value=class_value,
+                             ignore_value=ignore_value)
+        for bt in loader:
+            if nway:
+                r = self.segment_classes(support, bt["query_img"], None, max_batch=max_batch, native=bt["native"],
+                                         class_ids=class_ids, **flags)
+            else:
+                r = self.segment_queries(support, bt["query_img"], bt.get("query_mask"), native=bt["native"], **flags)
+            yield bt["index"], r
+
     @staticmethod
     def _with_native_labels(r, native, flags, class_ids):
         """_with_native for segment_classes: r plus r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags)."""

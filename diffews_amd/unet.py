@@ -788,7 +788,8 @@ class MyUNet2DConditionModel:
         n, s = len(sets), bankset.nshot
         tproj, ehs2d, kv_all, L_ctx = self._conditioning(n * b, timestep, encoder_hidden_states)
         c0 = cfg["block_out_channels"][0]
-        x_in = x_in.unsqueeze(0).expand(n, *x_in.shape).reshape(n * b, *x_in.shape[1:])     # class-major: entry c * b + i
+        # class-major: entry c * b + i (for b == 1 the reshape of the expansion is a stride-0 view: materialise it)
+        x_in = x_in.unsqueeze(0).expand(n, *x_in.shape).reshape(n * b, *x_in.shape[1:]).contiguous()
         x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
         lo, hi = sets.start * s, sets.stop * s
         io = _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b)

@@ -489,6 +489,58 @@ typedef struct {
  * class plane's extent -> DFW_EWORKSPACE. */
 int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_stream_t stream);
 
+/*
+ * Input transform of a whole ragged batch (version >= 107): dfw_image_to_tensor for n_img RGB images and
+ * dfw_mask_to_tensor for n_mask class-id maps of assorted sizes, all going to one out_h x out_w, driven by two
+ * device-resident tables.  Same arithmetic, bit for bit: Pillow's 8-bit two-pass BILINEAR resize (uint8 intermediate
+ * [H][out_w][3], weights from dfw_resample_coeffs, the caller's 256-entry lut) and ATen's nearest rule
+ * (on = id == class_value, index min((int)floorf((float)o * scale), size - 1), scale = (float)in / out in float).
+ * Every offset is in BYTES from the base pointer named; bounds, coefficients, int32 masks and float destinations need
+ * 4-byte alignment.
+ */
+typedef struct {
+  int32_t H, W;                        /* size of the image */
+  int32_t xk, yk;                      /* dfw_resample_ksize(W, out_w), (H, out_h) */
+  int64_t src_off;                     /* from `staged`: [H][W][3] RGB bytes */
+  int64_t xb_off, xc_off;              /* from `staged`: x bounds [out_w][2], x coefficients [out_w][xk] (int32) */
+  int64_t yb_off, yc_off;              /* from `staged`: y bounds [out_h][2], y coefficients [out_h][yk] (int32) */
+  int64_t tmp_off;                     /* from `tmp`: horizontal intermediate [H][out_w][3] bytes */
+  int64_t dst_off;                     /* from `dst`: planar fp32 [3][out_h][out_w] */
+} dfw_input_image_item;
+
+typedef struct {
+  int32_t H, W;                        /* size of the class-id map */
+  int32_t elem;                        /* bytes per id: 1 (uint8) or 4 (int32) */
+  int32_t class_value;                 /* on where id == class_value */
+  int64_t src_off;                     /* from `staged`: [H][W] ids */
+  int64_t pm1_off;                     /* from `pm1`: fp32 [3][out_h][out_w] in (-1, +1); -1 = none */
+  int64_t bin_off;                     /* from `bin`: uint8 [out_h][out_w] in (0, 1); -1 = none */
+} dfw_input_mask_item;
+
+typedef struct {
+  const void* image_items;             /* device, dfw_input_image_item [n_img]: what the kernels read */
+  const void* image_items_host;        /* host mirror of the same table: what this call validates */
+  int32_t n_img;
+  const void* mask_items;              /* device, dfw_input_mask_item [n_mask] */
+  const void* mask_items_host;         /* host mirror */
+  int32_t n_mask;
+  int32_t out_h, out_w;
+  const uint8_t* staged; size_t staged_bytes;     /* device base of image bytes, weights and mask ids */
+  uint8_t* tmp; size_t tmp_bytes;                 /* device scratch of the horizontal intermediates (images only) */
+  float* dst; size_t dst_bytes;                   /* device base of the image outputs */
+  float* pm1; size_t pm1_bytes;                   /* device base of the +-1 mask outputs; may be null when no item uses it */
+  uint8_t* bin; size_t bin_bytes;                 /* device base of the 0/1 mask outputs; may be null when no item uses it */
+  const float* lut;                    /* device, 256 floats: byte v after ToTensor + Normalize (images only) */
+} dfw_inputs_args;
+
+/* Three launches whatever the batch: horizontal pass and vertical pass + table lookup over all images (grid z = image,
+ * x / y sized for the largest one; skipped when n_img == 0), one over all masks (grid z = mask; skipped when
+ * n_mask == 0).  No memset node.  Validated on the host mirrors before the first launch: null pointers / non-positive
+ * sizes / nothing to do / elem not 1 or 4 / a mask with neither destination -> DFW_EINVAL; a ksize that disagrees with
+ * dfw_resample_ksize or a misaligned offset -> DFW_ESHAPE; H, out_h, n_img or n_mask above 65535 -> DFW_ERANGE; an
+ * extent that leaves its buffer -> DFW_EWORKSPACE.  Regions of different items must not overlap (not checked). */
+int dfw_inputs_to_tensor(const dfw_inputs_args* a, dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
