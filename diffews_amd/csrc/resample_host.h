@@ -1,5 +1,5 @@
 // Host-only: Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c) for one axis and a whole-image box,
-// parametrised by the filter function and its support.  preprocess.hip (input side, bilinear) and seg_native.hip
+// parametrised by the filter function and its support.  inputs.hip (input side, bilinear) and seg_native.hip
 // (output side, bicubic) both get their fixed-point weights here, so the two sides cannot drift apart.
 #pragma once
 #include <math.h>
@@ -23,6 +23,11 @@ inline double resample_bicubic(double x) {
   if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
   if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
   return 0.0;
+}
+
+// [off, off + bytes) inside a buffer of `cap` bytes: how both sides validate an item table's offsets
+inline bool extent_fits(int64_t off, uint64_t bytes, size_t cap) {
+  return off >= 0 && (uint64_t)off <= (uint64_t)cap && bytes <= (uint64_t)cap - (uint64_t)off;
 }
 
 typedef double (*resample_filter_fn)(double);

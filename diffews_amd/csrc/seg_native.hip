@@ -1,5 +1,5 @@
 // Native-size masks and scores (the launcher's --use_original_imgsize, main_oss.py:128-155): the output-side counterpart
-// of preprocess.hip.  The reference resizes the uint8 prediction back to the query's own size with
+// of inputs.hip.  The reference resizes the uint8 prediction back to the query's own size with
 // `Image.fromarray(hwc).resize((W, H))` (marigold_pipeline_rgb_latent_noise.py:539 -- Pillow's default filter, BICUBIC)
 // and then thresholds and scores it on the host.  Here that is four launches for a whole RAGGED batch, however many
 // images it holds: zero, horizontal pass, vertical pass + per-image maximum, threshold + count.  Grid z runs over the
@@ -366,11 +366,6 @@ extern "C" int dfw_resample_coeffs_ex(int32_t in_size, int32_t out_size, int32_t
   return resample_coeffs_host(in_size, out_size, fn, support, bounds, coeffs);
 }
 
-// [off, off + bytes) inside a buffer of `cap` bytes
-static bool native_fits(int64_t off, uint64_t bytes, size_t cap) {
-  return off >= 0 && (uint64_t)off <= (uint64_t)cap && bytes <= (uint64_t)cap - (uint64_t)off;
-}
-
 extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream) {
   if (!a || !a->seg_u8 || !a->items || !a->items_host || !a->weights || !a->tmp) return DFW_EINVAL;
   if (a->B <= 0 || a->Hs <= 0 || a->Ws <= 0) return DFW_EINVAL;
@@ -398,16 +393,16 @@ extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream)
       return DFW_ESHAPE;
     if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
     const uint64_t hw = (uint64_t)t.h * t.w;
-    if (!native_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !native_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
-        !native_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !native_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
+    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
+        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
       return DFW_EWORKSPACE;
     const size_t tmp_cap = (!a->out_u8 && need_res) ? a->tmp_res_off : a->tmp_bytes;   // the horizontal intermediates' part
-    if (!native_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
-    if (need_res && !native_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
-    if (a->pred && !native_fits(t.pred_off, hw, a->pred_bytes)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
+    if (need_res && !extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
+    if (a->pred && !extent_fits(t.pred_off, hw, a->pred_bytes)) return DFW_EWORKSPACE;
     if (a->counts) {
       if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
-      if (!native_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
+      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
     }
     max_h = t.h > max_h ? t.h : max_h;
     max_w = t.w > max_w ? t.w : max_w;
@@ -468,15 +463,15 @@ extern "C" int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_st
       return DFW_ESHAPE;
     if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
     const uint64_t hw = (uint64_t)t.h * t.w;
-    if (!native_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !native_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
-        !native_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !native_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
+    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
+        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
       return DFW_EWORKSPACE;
-    if (!native_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
-    if (!native_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
-    if (!native_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
     if (a->counts) {
       if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
-      if (!native_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
+      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
     }
     const uint64_t te = (uint64_t)t.tmp_off + 3ull * a->Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
     tmp_ext = te > tmp_ext ? te : tmp_ext;

@@ -7,7 +7,7 @@ coco.py:36-46 `F.interpolate(nearest)` on the class masks, main_oss.py:100-104 m
 resizes/s/GPU of PIL work on the critical path.  Here the host only decodes (PIL) and hands over raw
 bytes: one pinned staging buffer per batch carries the images, the class masks and Pillow's fixed-point
 filter weights (dfw_resample_coeffs) in ONE H2D copy; the resize / normalise / binarise / nearest
-kernels (csrc/preprocess.hip) run on a side stream while the previous batch is in the UNet, and the
+kernels (csrc/inputs.hip) run on a side stream while the previous batch is in the UNet, and the
 result has exactly the tensor contract of `episodes.make_episode_batch`:
 
     support_imgs [b*s,3,S,S] fp32 in [-1,1], query_img [b,3,S,S], support_masks [b*s,3,S,S] in {-1,+1},
@@ -16,11 +16,11 @@ result has exactly the tensor contract of `episodes.make_episode_batch`:
 Values are bit-identical to the reference's host transform (tests/test_preprocess_gpu.py checks them
 against PIL / torch themselves).  No CPU fallback: the kernels come from libdiffews_hip.so.
 
-A stream of queries against one prepared support has its own route: `InputBatch` /
-`DeviceImageTransform.batch` turn a whole ragged batch into tensors with one staging buffer and one dfw_inputs_to_tensor
-call (csrc/inputs_batch.hip: three launches whatever the batch), `support_tensors` builds a support set that way and
-`QueryLoader` yields what pipeline.segment_queries / segment_classes consume, `NativeTargets` included.  `EpisodeLoader`
-keeps the per-image launches.
+There is one route from bytes to tensors: `InputBatch` / `DeviceImageTransform.batch` turn a whole ragged batch into tensors
+with one staging buffer and one dfw_inputs_to_tensor call (three launches whatever the batch); `image()` / `mask()` are a
+batch of one.  `support_tensors` builds a support set that way, `EpisodeLoader` whole episodes, and `QueryLoader` (a stream
+of queries against one prepared support) what pipeline.segment_queries / segment_classes consume,
+`NativeTargets` included; both loaders prefetch through `_Prefetcher`.
 """
 import ctypes as C
 import queue
@@ -85,8 +85,7 @@ class DeviceImageTransform:
 
     # ---- host side -----------------------------------------------------------------------------
     def coeffs(self, in_size, out_size=None):
-        """Pillow's fixed-point bilinear weights for in_size -> out_size (default: the square self.size; cached, see
-        resample_coeffs)."""
+        """Pillow's fixed-point bilinear weights for in_size -> out_size (default: out_w); cached, see resample_coeffs."""
         return resample_coeffs(in_size, self.out_w if out_size is None else out_size, L.FILTER_BILINEAR)
 
     @staticmethod
@@ -108,86 +107,26 @@ class DeviceImageTransform:
             mask = mask.astype(np.int32)
         return mask
 
-    def plan(self, images, masks):
-        """Byte layout of one staging buffer: [(image, xb, xw, yb, yw) ...][mask ...] -> (items, total)."""
-        off, items = 0, []
-        for im in images:
-            H, W = im.shape[:2]
-            xb, xw, xk = self.coeffs(W, self.out_w)
-            yb, yw, yk = self.coeffs(H, self.out_h)
-            parts = []
-            for arr in (im, xb, xw, yb, yw):
-                parts.append((off, arr))
-                off = _align(off + arr.nbytes)
-            items.append(("image", H, W, xk, yk, parts))
-        for m in masks:
-            items.append(("mask", m.shape[0], m.shape[1], m.dtype.itemsize, 0, [(off, m)]))
-            off = _align(off + m.nbytes)
-        return items, off
-
-    # ---- device side ---------------------------------------------------------------------------
-    def launch(self, items, dev_base, img_out, tmp, mask_pm1, mask_bin, mask_class, stream):
-        """Kernels for a staged batch: image i -> img_out[i]; mask j -> mask_pm1[j] / mask_bin[j] (either
-        may be None per entry)."""
-        oh, ow, ii, mi = self.out_h, self.out_w, 0, 0
-        for kind, H, W, a, b, parts in items:
-            if kind == "image":
-                args = L.ImageArgs()
-                p = [dev_base + o for o, _ in parts]
-                args.src, args.H, args.W, args.out_h, args.out_w = p[0], H, W, oh, ow
-                args.xbounds, args.xcoef, args.xk = p[1], p[2], a
-                args.ybounds, args.ycoef, args.yk = p[3], p[4], b
-                args.tmp, args.dst, args.lut = tmp.data_ptr(), img_out[ii].data_ptr(), self.lut.data_ptr()
-                L.check(self.lib.dfw_image_to_tensor(C.byref(args), stream), "dfw_image_to_tensor")
-                ii += 1
-            else:
-                pm1, bn = mask_pm1[mi], mask_bin[mi]
-                L.check(self.lib.dfw_mask_to_tensor(dev_base + parts[0][0], a, H, W, int(mask_class[mi]), oh, ow,
-                                                    pm1.data_ptr() if pm1 is not None else None,
-                                                    bn.data_ptr() if bn is not None else None, stream),
-                        "dfw_mask_to_tensor")
-                mi += 1
-
-    # ---- one-shot convenience (tests, single images) ---------------------------------------------
-    @torch.no_grad()
+    # ---- device side: one staging buffer, one H2D copy, one library call (three launches); one item = a batch of one
     def image(self, img):
-        im = self.as_rgb_bytes(img)
-        out = torch.empty(1, 3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        self._run([im], [], out, [], [], [])
-        return out[0]
+        """-> fp32 [3, out_h, out_w] in [-1, 1]."""
+        return self.batch([img])["images"][0]
 
-    @torch.no_grad()
     def mask(self, mask_ids, class_sample):
-        """-> (+-1 fp32 [3,S,S], uint8 {0,1} [S,S]) for class id `class_sample` (coco.py:74-75: the
-        PNG stores class_sample + 1)."""
-        m = self.as_mask(mask_ids)
-        pm1 = torch.empty(3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        bn = torch.empty(self.out_h, self.out_w, dtype=torch.uint8, device=self.device)
-        self._run([], [m], None, [pm1], [bn], [class_sample + 1])
-        return pm1, bn
+        """-> (+-1 fp32 [3,S,S], uint8 {0,1} [S,S]) for class id `class_sample` (coco.py:74-75: the PNG stores it + 1)."""
+        r = self.batch([], [mask_ids], [class_sample + 1])
+        return r["pm1"][0], r["bin"][0]
 
-    def _run(self, images, masks, img_out, mask_pm1, mask_bin, mask_class):
-        items, total = self.plan(images, masks)
-        host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
-        fill_staging(host, items)
-        dev = host.to(self.device, non_blocking=True)
-        hmax = max([im.shape[0] for im in images], default=1)
-        tmp = torch.empty(hmax * self.out_w * 3, dtype=torch.uint8, device=self.device)
-        self.launch(items, dev.data_ptr(), img_out, tmp, mask_pm1, mask_bin, mask_class,
-                    torch.cuda.current_stream().cuda_stream)
-
-    # ---- a whole ragged batch: one staging buffer, one H2D copy, one library call (three launches) ----------------
     @torch.no_grad()
     def batch(self, images, masks=(), mask_class=(), want_pm1=True, want_bin=True, guard=0, buffers=None):
         """`images` (PIL / uint8 [H, W, 3], any sizes) and class-id maps `masks` (mask j is on where id == mask_class[j])
         -> dict(images fp32 [n, 3, out_h, out_w] or None, pm1 fp32 [m1, 3, out_h, out_w] in +-1 or None, bin uint8
-        [m2, out_h, out_w] in 0/1 or None, layout = the InputBatch, staged = the device copy of its bytes): what image() /
-        mask() give per item, bit for bit.  want_pm1 / want_bin: one bool or one per mask; pm1 / bin hold the masks that
-        asked for them, in order.  Tables, image bytes, weights and mask ids travel in ONE pinned buffer and one H2D copy
-        on the current stream; one dfw_inputs_to_tensor call: three launches whatever the batch.
-        guard / buffers: see InputBatch (tests put sentinels around every item).
-        On a host-only transform (device=None) nothing is launched: returns the InputBatch, its bytes staged in the
-        numpy buffer `.host`."""
+        [m2, out_h, out_w] in 0/1 or None, layout = the InputBatch, staged = the device copy of its bytes).
+        want_pm1 / want_bin: one bool or one per mask; pm1 / bin hold the masks that asked for them, in order.  Tables,
+        image bytes, weights and mask ids travel in ONE pinned buffer and one H2D copy on the current stream; one
+        dfw_inputs_to_tensor call: three launches whatever the batch.  guard / buffers: see InputBatch (tests put
+        sentinels around every item).  On a host-only transform (device=None) nothing is launched: returns the
+        InputBatch, its bytes staged in the numpy buffer `.host`."""
         lay = InputBatch((self.out_h, self.out_w), [self.as_rgb_bytes(x) for x in images], [self.as_mask(m) for m in masks],
                          mask_class, want_pm1, want_bin, guard=guard)
         if self.device is None:
@@ -200,13 +139,6 @@ class DeviceImageTransform:
         out = lay.run(dev, self.lut, torch.cuda.current_stream(self.device).cuda_stream, **(buffers or {}))
         out.update(layout=lay, staged=dev)
         return out
-
-
-def fill_staging(host, items):
-    hv = host.numpy()
-    for _, _, _, _, _, parts in items:
-        for off, arr in parts:
-            hv[off:off + arr.nbytes] = arr.reshape(-1).view(np.uint8)
 
 
 class InputBatch:
@@ -452,248 +384,72 @@ class NativeTargets:
         return buf, buf.numel()
 
 
-class EpisodeLoader:
-    """Host episodes -> device batches, prefetched on a side stream.
+class _Prefetcher:
+    """Host items -> device batches, prefetched on a side stream: everything EpisodeLoader and QueryLoader share.
 
-    `episodes` yields dicts with the raw material of DatasetCOCO.load_frame (coco.py:77-107):
-        query_img, support_imgs (list): PIL images or uint8 [H,W,3] arrays
-        query_mask, support_masks (list): class-id maps [H,W] (uint8 / int)
-        class_id: the sampled class (masks hold class_id + 1)
-    Iterating yields dicts like episodes.make_episode_batch plus `class_id` [b].  A batch's tensors are
-    recycled: they stay valid for the work enqueued on the consumer's stream before the NEXT batch is
-    drawn (the producer's side stream waits on an event recorded at that point before overwriting).
-    depth + 2 buffer sets: one with the consumer, `depth` queued, one being staged.
+    A producer thread (`self._thread`) draws `batch` items at a time (the last batch may be short), lays them out as one
+    InputBatch and stages it in one of depth + 2 slots -- one with the consumer, `depth` queued, one being staged: one
+    pinned buffer, one H2D copy and one dfw_inputs_to_tensor call on the side stream.  A slot owns its staging (`host`,
+    `dev`), scratch (`tmp`) and output (`dst`, `pm1`, `bin`) buffers; the outputs are sized once for a full batch, the
+    others grow on demand.  Three events order a slot's reuse:
+      copied   the H2D copy has left the pinned bytes: the producer waits for it ON THE CPU before refilling them
+      release  the consumer's work on the slot's previous batch: the side stream waits for it before overwriting
+      event    the batch is complete: the consumer's stream waits for it before the batch is handed out
+    So a batch's tensors stay valid for the work enqueued on the consumer's stream before the NEXT batch is drawn.
+    The producer allocates slots and pinned buffers and synchronises `copied` while the consumer may be capturing a
+    graph: that is why pipeline._replay captures with capture_error_mode="thread_local".
 
-    native=True: every batch also carries `native`, a NativeTargets for pipeline.run_episodes(native=...) /
-    ops.seg_native: each query's own h x w, its class id + 1 as the foreground value, `ignore_value` (-1: none, 255:
-    PASCAL's boundary) and, as ground truth, the query's raw class-id map where it already sits in this batch's staged
-    bytes -- no second copy, so `native` is valid exactly as long as the batch's tensors are.
-    """
+    A subclass says how items become an InputBatch (`_plan`), how many outputs of each kind a full batch has (`_outputs`),
+    what NativeTargets go with a batch (`_native`) and what is yielded (`_result`).  device=None: host-only, for
+    `host_batch` (no GPU needed); such a loader does not iterate."""
 
-    def __init__(self, episodes, size, batch, nshot, device="cuda", depth=2, native=False, ignore_value=-1):
-        self.src, self.b, self.s, self.depth = episodes, int(batch), int(nshot), int(depth)
-        self.native, self.ignore_value = bool(native), int(ignore_value)
-        self.tf = DeviceImageTransform(size, device)
-        self.device = self.tf.device
-        self.stream = torch.cuda.Stream(device=self.device)
-        self._slots = [None] * (self.depth + 2)
-
-    def _slot(self, i, total, hmax, nb):
-        S, dev, s = self.tf.size, self.device, self._slots[i]
-        if s is None or s["b"] != nb:
-            s = dict(b=nb, host=None, dev=None, tmp=None,
-                     sup=torch.empty(nb * self.s, 3, S, S, dtype=torch.float32, device=dev),
-                     qry=torch.empty(nb, 3, S, S, dtype=torch.float32, device=dev),
-                     smask=torch.empty(nb * self.s, 3, S, S, dtype=torch.float32, device=dev),
-                     qmask=torch.empty(nb, S, S, dtype=torch.uint8, device=dev),
-                     event=torch.cuda.Event(), release=torch.cuda.Event(), released=False,
-                     copied=torch.cuda.Event(), staged=False)
-            self._slots[i] = s
-        if s["host"] is None or s["host"].numel() < total:
-            if s["dev"] is not None:
-                s["dev"].record_stream(self.stream)   # still read by kernels queued on the side stream
-            s["host"] = torch.empty(int(total * 1.25) + 64, dtype=torch.uint8, pin_memory=True)
-            s["dev"] = torch.empty(s["host"].numel(), dtype=torch.uint8, device=self.device)
-        need = hmax * S * 3
-        if s["tmp"] is None or s["tmp"].numel() < need:
-            if s["tmp"] is not None:
-                s["tmp"].record_stream(self.stream)
-            s["tmp"] = torch.empty(int(need * 1.25), dtype=torch.uint8, device=self.device)
-        return s
-
-    def _stage(self, i, eps):
-        """Decode-side work for one batch (runs in the producer thread): pack, copy, launch."""
-        tf, nb = self.tf, len(eps)
-        images, masks, mclass, pm1, bins = [], [], [], [], []
-        for e in eps:                                   # support images batch-major episode*nshot + shot
-            if len(e["support_imgs"]) != self.s or len(e["support_masks"]) != self.s:
-                raise ValueError("episode does not hold nshot support images / masks")
-            images += [tf.as_rgb_bytes(x) for x in e["support_imgs"]]
-        images += [tf.as_rgb_bytes(e["query_img"]) for e in eps]
-        for e in eps:
-            masks += [tf.as_mask(m) for m in e["support_masks"]]
-            mclass += [int(e["class_id"]) + 1] * self.s
-        masks += [tf.as_mask(e["query_mask"]) for e in eps]
-        mclass += [int(e["class_id"]) + 1 for e in eps]
-        items, total = tf.plan(images, masks)
-        sl = self._slot(i, total, max(im.shape[0] for im in images), nb)
-        if sl["staged"]:
-            # The H2D copy of this slot's PREVIOUS batch reads the same pinned bytes asynchronously; stream
-            # waits order GPU work only, and a consumer that never synchronises lets this thread run several
-            # batches ahead of the GPU.  Block here (CPU) until that copy has left the host buffer.
-            sl["copied"].synchronize()
-        fill_staging(sl["host"], items)
-        n_sup = nb * self.s
-        img_out = [sl["sup"][j] for j in range(n_sup)] + [sl["qry"][j] for j in range(nb)]
-        pm1 = [sl["smask"][j] for j in range(n_sup)] + [None] * nb
-        bins = [None] * n_sup + [sl["qmask"][j] for j in range(nb)]
-        with torch.cuda.stream(self.stream):
-            if sl["released"]:          # the consumer's work on this buffer set's previous batch
-                self.stream.wait_event(sl["release"])
-            sl["dev"][:total].copy_(sl["host"][:total], non_blocking=True)
-            sl["copied"].record(self.stream)
-            sl["staged"] = True
-            tf.launch(items, sl["dev"].data_ptr(), img_out, sl["tmp"], pm1, bins, mclass, self.stream.cuda_stream)
-            native = None
-            if self.native:
-                qm = items[-nb:]                     # the queries' class-id maps, last in the staging plan
-                for im, it in zip(images[-nb:], qm):
-                    if im.shape[:2] != (it[1], it[2]):
-                        raise ValueError(f"query image {im.shape[:2]} and query mask {(it[1], it[2])} differ in size")
-                native = NativeTargets((tf.size, tf.size), [(it[1], it[2]) for it in qm],
-                                       gt_device=(sl["dev"], [it[5][0][0] for it in qm], [it[3] for it in qm]),
-                                       class_value=mclass[-nb:], ignore_value=self.ignore_value, device=self.device)
-            sl["event"].record(self.stream)
-        cid = torch.tensor([int(e["class_id"]) for e in eps], dtype=torch.long)
-        out = dict(support_imgs=sl["sup"], query_img=sl["qry"], support_masks=sl["smask"], query_mask=sl["qmask"],
-                   class_id=cid, _slot=sl)
-        if native is not None:
-            out["native"] = native
-        return out
-
-    def __iter__(self):
-        q = queue.Queue(maxsize=self.depth)
-        stop = threading.Event()
-
-        def produce():
-            try:
-                torch.cuda.set_device(self.device)
-                buf, i = [], 0
-                for e in self.src:
-                    buf.append(e)
-                    if len(buf) == self.b:
-                        out = self._stage(i % (self.depth + 2), buf)
-                        buf, i = [], i + 1
-                        while not stop.is_set():
-                            try:
-                                q.put(out, timeout=0.1)
-                                break
-                            except queue.Full:
-                                continue
-                        if stop.is_set():
-                            return
-                if buf and not stop.is_set():
-                    q.put(self._stage(i % (self.depth + 2), buf))
-                q.put(None)
-            except BaseException as ex:  # surfaced in the consumer
-                q.put(ex)
-
-        th = threading.Thread(target=produce, daemon=True)
-        th.start()
-        try:
-            while True:
-                item = q.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                sl = item.pop("_slot")
-                torch.cuda.current_stream(self.device).wait_event(sl["event"])
-                yield item
-                sl["release"].record(torch.cuda.current_stream(self.device))
-                sl["released"] = True
-        finally:
-            stop.set()
-
-
-class QueryLoader:
-    """Host queries -> device batches for pipeline.segment_queries / segment_classes, prefetched on a side stream: the
-    input half of "segment a stream of images against the same few annotated examples".
-
-    `queries` yields dicts with
-        query_img: PIL image or uint8 [H, W, 3] array, any size
-        gt (optional): class-id map or label map [H, W] (uint8 / int) of the same size; all queries of a batch carry
-                       one, or none does
-    Iterating yields dicts with
-        query_img  fp32 [b, 3, out_h, out_w] in [-1, 1] (DeviceImageTransform.batch: one pinned buffer, one H2D copy and
-                   three launches per batch, whatever b)
-        native     NativeTargets for the b queries' own sizes; with `gt` its ground truth is read IN PLACE from the
-                   batch's staged bytes (gt_device: no second copy), with `ignore_value` (-1: none, 255: PASCAL's
-                   boundary) and the query's class value as foreground (1 without class_value); without `gt` it carries
-                   sizes only and the native counts are None
-        query_mask (only with class_value and gt) uint8 [b, out_h, out_w]: gt == class value, nearest-resized, so
-                   r["counts"] at the processing size works too
-        index      positions of the batch's queries in the stream (list of int)
-    class_value: one int, or a callable on the query dict.  The last batch may be short.
-
-    Producer thread, side stream, slot recycling and the copied / release / event protocol are EpisodeLoader's: a
-    batch's tensors (and its `native`) stay valid for the work enqueued on the consumer's stream before the NEXT batch
-    is drawn.  depth + 2 buffer sets: one with the consumer, `depth` queued, one being staged.
-    """
-
-    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1):
-        self.src, self.b, self.depth = queries, int(batch), int(depth)
+    def __init__(self, src, size, batch, device, depth):
+        self.src, self.b, self.depth = src, int(batch), int(depth)
         if self.b < 1 or self.depth < 1:
-            raise ValueError("QueryLoader needs batch >= 1 and depth >= 1")
-        self.class_value, self.ignore_value = class_value, int(ignore_value)
+            raise ValueError(f"{type(self).__name__} needs batch >= 1 and depth >= 1")
         self.tf = DeviceImageTransform(size, device)
         self.device = self.tf.device
         self.stream = None if self.device is None else torch.cuda.Stream(device=self.device)
         self._slots = [None] * (self.depth + 2)
+        self._thread = None
 
-    def layout(self, qs):
-        """(InputBatch, per-query class values, has_gt) of one batch of query dicts: the images, then the ground-truth
-        maps -- with class_value each also a mask item with a 0/1 destination, without it staged only."""
-        tf = self.tf
-        images = [tf.as_rgb_bytes(q["query_img"]) for q in qs]
-        with_gt = [q.get("gt") is not None for q in qs]
-        if any(with_gt) and not all(with_gt):
-            raise ValueError("either every query of a batch carries `gt` or none does")
-        gts, cls = [], [1] * len(qs)
-        if all(with_gt):
-            gts = [tf.as_mask(q["gt"]) for q in qs]
-            for im, g in zip(images, gts):
-                if im.shape[:2] != g.shape:
-                    raise ValueError(f"query image {im.shape[:2]} and its gt {g.shape} differ in size")
-            if self.class_value is not None:
-                cls = [int(self.class_value(q)) if callable(self.class_value) else int(self.class_value) for q in qs]
-        want_bin = self.class_value is not None
-        lay = InputBatch((tf.out_h, tf.out_w), images, gts, cls if gts else (), want_pm1=False, want_bin=want_bin)
-        return lay, cls, bool(gts)
-
-    def _native(self, lay, cls, has_gt, staged, device):
-        gt_device = None
-        if has_gt:
-            gt_device = (staged, [o for o, _ in lay.mask_src], [e for _, e in lay.mask_src])
-        return NativeTargets(lay.out_hw, [(it.H, it.W) for it in lay.img_items[:lay.n_img]], gt_device=gt_device,
-                             class_value=cls, ignore_value=self.ignore_value, device=device)
-
-    def host_batch(self, qs):
-        """Host-only layout of one batch of query dicts (a loader built with device=None; no GPU needed): (InputBatch with
-        its bytes in the numpy buffer `.host`, NativeTargets(device=None) whose gt offsets refer to that buffer)."""
-        lay, cls, has_gt = self.layout(qs)
+    def host_batch(self, items):
+        """Host-only layout of one batch of source dicts: (InputBatch with its bytes in the numpy buffer `.host`,
+        NativeTargets(device=None) whose gt offsets refer to that buffer)."""
+        lay, ctx = self._plan(items)
         lay.host = np.zeros(max(lay.total, 16), np.uint8)
         lay.fill(lay.host)
-        return lay, self._native(lay, cls, has_gt, torch.from_numpy(lay.host), None)
+        return lay, self._native(lay, ctx, torch.from_numpy(lay.host), None)
 
     def _slot(self, i, lay):
-        tf, dev, s = self.tf, self.device, self._slots[i]
+        s = self._slots[i]
         if s is None:
-            s = dict(host=None, dev=None, tmp=None,
-                     qry=torch.empty(self.b * lay.dst_stride, dtype=torch.uint8, device=dev),
-                     qmask=torch.empty(self.b * lay.bin_stride, dtype=torch.uint8, device=dev)
-                     if self.class_value is not None else None,
-                     event=torch.cuda.Event(), release=torch.cuda.Event(), released=False,
+            plane = self.tf.out_h * self.tf.out_w
+            s = dict(host=None, dev=None, tmp=None, event=torch.cuda.Event(), release=torch.cuda.Event(), released=False,
                      copied=torch.cuda.Event(), staged=False)
+            for name, n in zip(("dst", "pm1", "bin"), self._outputs()):
+                nbytes = n * plane * (1 if name == "bin" else 12)
+                s[name] = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if n else None
             self._slots[i] = s
         if s["host"] is None or s["host"].numel() < lay.total:
             if s["dev"] is not None:
                 s["dev"].record_stream(self.stream)   # still read by kernels queued on the side stream
             s["host"] = torch.empty(int(lay.total * 1.25) + 64, dtype=torch.uint8, pin_memory=True)
-            s["dev"] = torch.empty(s["host"].numel(), dtype=torch.uint8, device=dev)
+            s["dev"] = torch.empty(s["host"].numel(), dtype=torch.uint8, device=self.device)
         if s["tmp"] is None or s["tmp"].numel() < lay.tmp_bytes:
             if s["tmp"] is not None:
                 s["tmp"].record_stream(self.stream)
-            s["tmp"] = torch.empty(int(lay.tmp_bytes * 1.25), dtype=torch.uint8, device=dev)
+            s["tmp"] = torch.empty(int(lay.tmp_bytes * 1.25), dtype=torch.uint8, device=self.device)
         return s
 
-    def _stage(self, i, qs, index):
+    def _stage(self, i, items, index):
         """Decode-side work for one batch (runs in the producer thread): pack, copy, launch."""
-        tf = self.tf
-        lay, cls, has_gt = self.layout(qs)
+        lay, ctx = self._plan(items)
         sl = self._slot(i, lay)
         if sl["staged"]:
-            # as EpisodeLoader._stage: the H2D copy of this slot's previous batch may still be reading the pinned bytes
+            # The H2D copy of this slot's PREVIOUS batch reads the same pinned bytes asynchronously; stream
+            # waits order GPU work only, and a consumer that never synchronises lets this thread run several
+            # batches ahead of the GPU.  Block here (CPU) until that copy has left the host buffer.
             sl["copied"].synchronize()
         lay.fill(sl["host"].numpy())
         with torch.cuda.stream(self.stream):
@@ -702,22 +458,21 @@ class QueryLoader:
             sl["dev"][:lay.total].copy_(sl["host"][:lay.total], non_blocking=True)
             sl["copied"].record(self.stream)
             sl["staged"] = True
-            r = lay.run(sl["dev"], tf.lut, self.stream.cuda_stream, tmp=sl["tmp"], dst=sl["qry"], bin=sl["qmask"])
-            native = self._native(lay, cls, has_gt, sl["dev"], self.device)
+            r = lay.run(sl["dev"], self.tf.lut, self.stream.cuda_stream, tmp=sl["tmp"], dst=sl["dst"], pm1=sl["pm1"],
+                        bin=sl["bin"])
+            out = self._result(items, index, lay, ctx, r, sl["dev"])    # may stage NativeTargets: on the side stream too
             sl["event"].record(self.stream)
-        out = dict(query_img=r["images"], native=native, index=list(index), _slot=sl)
-        if r["bin"] is not None:
-            out["query_mask"] = r["bin"]
+        out["_slot"] = sl
         return out
 
     def __iter__(self):
         if self.device is None:
-            raise RuntimeError("a host-only QueryLoader (device=None) lays batches out (host_batch); it does not iterate")
+            raise RuntimeError(f"a host-only {type(self).__name__} (device=None) lays batches out (host_batch) only")
         q = queue.Queue(maxsize=self.depth)
         stop = threading.Event()
         nslots = self.depth + 2
 
-        def put(out):
+        def put(out):           # every put gives up once the consumer has left: the thread ends, the slots go
             while not stop.is_set():
                 try:
                     q.put(out, timeout=0.1)
@@ -742,8 +497,8 @@ class QueryLoader:
             except BaseException as ex:  # surfaced in the consumer
                 put(ex)
 
-        th = threading.Thread(target=produce, daemon=True)
-        th.start()
+        self._thread = threading.Thread(target=produce, daemon=True)
+        self._thread.start()
         try:
             while True:
                 item = q.get()
@@ -754,7 +509,131 @@ class QueryLoader:
                 sl = item.pop("_slot")
                 torch.cuda.current_stream(self.device).wait_event(sl["event"])
                 yield item
+                # the generator resumes here when the NEXT batch is drawn: everything the consumer has enqueued on this
+                # batch since lies before the event the side stream waits for before it overwrites the slot
                 sl["release"].record(torch.cuda.current_stream(self.device))
                 sl["released"] = True
         finally:
             stop.set()
+
+
+class EpisodeLoader(_Prefetcher):
+    """Host episodes -> device batches, prefetched on a side stream (protocol and buffer lifetime: _Prefetcher).
+
+    `episodes` yields dicts with the raw material of DatasetCOCO.load_frame (coco.py:77-107):
+        query_img, support_imgs (list): PIL images or uint8 [H,W,3] arrays
+        query_mask, support_masks (list): class-id maps [H,W] (uint8 / int)
+        class_id: the sampled class (masks hold class_id + 1)
+    Iterating yields dicts like episodes.make_episode_batch plus `class_id` [b]: views of the slot's buffers, the first
+    b * nshot images the supports (episode * nshot + shot), the rest the queries.
+
+    native=True: every batch also carries `native`, a NativeTargets for pipeline.run_episodes(native=...) /
+    ops.seg_native: each query's own h x w, its class id + 1 as the foreground value, `ignore_value` (-1: none, 255:
+    PASCAL's boundary) and, as ground truth, the query's raw class-id map where it already sits in this batch's staged
+    bytes -- no second copy, so `native` is valid exactly as long as the batch's tensors are.
+    """
+
+    def __init__(self, episodes, size, batch, nshot, device="cuda", depth=2, native=False, ignore_value=-1):
+        super().__init__(episodes, size, batch, device, depth)
+        self.s, self.native, self.ignore_value = int(nshot), bool(native), int(ignore_value)
+
+    def layout(self, eps):
+        """The InputBatch of one batch of episode dicts: support images (episode * nshot + shot) then query images; masks
+        in the same order, on where id == class_id + 1, the supports' to +-1 planes, the queries' to 0/1 bytes."""
+        tf, n_sup = self.tf, len(eps) * self.s
+        for e in eps:
+            if len(e["support_imgs"]) != self.s or len(e["support_masks"]) != self.s:
+                raise ValueError("episode does not hold nshot support images / masks")
+        images = [tf.as_rgb_bytes(x) for e in eps for x in e["support_imgs"]] + [tf.as_rgb_bytes(e["query_img"]) for e in eps]
+        masks = [tf.as_mask(m) for e in eps for m in e["support_masks"]] + [tf.as_mask(e["query_mask"]) for e in eps]
+        cls = [int(e["class_id"]) + 1 for e in eps for _ in range(self.s)] + [int(e["class_id"]) + 1 for e in eps]
+        sup = [True] * n_sup + [False] * len(eps)
+        return InputBatch((tf.out_h, tf.out_w), images, masks, cls, want_pm1=sup, want_bin=[not v for v in sup])
+
+    def _plan(self, eps):
+        return self.layout(eps), None
+
+    def _outputs(self):
+        return self.b * (self.s + 1), self.b * self.s, self.b
+
+    def _native(self, lay, ctx, staged, device):
+        nb = len(lay.bin_index)                         # the queries: last among the images and among the maps
+        imgs, maps = lay.img_items[lay.n_img - nb:lay.n_img], lay.mask_items[lay.n_mask - nb:lay.n_mask]
+        for im, m in zip(imgs, maps):
+            if (im.H, im.W) != (m.H, m.W):
+                raise ValueError(f"query image {(im.H, im.W)} and query mask {(m.H, m.W)} differ in size")
+        return NativeTargets(lay.out_hw, [(m.H, m.W) for m in maps], gt_device=(staged, *zip(*lay.mask_src[-nb:])),
+                             class_value=[m.class_value for m in maps], ignore_value=self.ignore_value, device=device)
+
+    def _result(self, eps, index, lay, ctx, r, staged):
+        n_sup = len(eps) * self.s
+        out = dict(support_imgs=r["images"][:n_sup], query_img=r["images"][n_sup:], support_masks=r["pm1"],
+                   query_mask=r["bin"], class_id=torch.tensor([int(e["class_id"]) for e in eps], dtype=torch.long))
+        if self.native:
+            out["native"] = self._native(lay, ctx, staged, self.device)
+        return out
+
+
+class QueryLoader(_Prefetcher):
+    """Host queries -> device batches for pipeline.segment_queries / segment_classes, prefetched on a side stream
+    (protocol and buffer lifetime: _Prefetcher): the input half of "segment a stream of images against the same few
+    annotated examples".
+
+    `queries` yields dicts with
+        query_img: PIL image or uint8 [H, W, 3] array, any size
+        gt (optional): class-id map or label map [H, W] (uint8 / int) of the same size; all queries of a batch carry
+                       one, or none does
+    Iterating yields dicts with
+        query_img  fp32 [b, 3, out_h, out_w] in [-1, 1]
+        native     NativeTargets for the b queries' own sizes; with `gt` its ground truth is read IN PLACE from the
+                   batch's staged bytes (gt_device: no second copy), with `ignore_value` (-1: none, 255: PASCAL's
+                   boundary) and the query's class value as foreground (1 without class_value); without `gt` it carries
+                   sizes only and the native counts are None
+        query_mask (only with class_value and gt) uint8 [b, out_h, out_w]: gt == class value, nearest-resized, so
+                   r["counts"] at the processing size works too
+        index      positions of the batch's queries in the stream (list of int)
+    class_value: one int, or a callable on the query dict.
+    """
+
+    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1):
+        super().__init__(queries, size, batch, device, depth)
+        self.class_value, self.ignore_value = class_value, int(ignore_value)
+
+    def layout(self, qs):
+        """(InputBatch, per-query class values, has_gt) of one batch of query dicts: the images, then the ground-truth
+        maps -- with class_value each also a mask item with a 0/1 destination, without it staged only."""
+        tf = self.tf
+        images = [tf.as_rgb_bytes(q["query_img"]) for q in qs]
+        with_gt = [q.get("gt") is not None for q in qs]
+        if any(with_gt) and not all(with_gt):
+            raise ValueError("either every query of a batch carries `gt` or none does")
+        gts, cls = [], [1] * len(qs)
+        if all(with_gt):
+            gts = [tf.as_mask(q["gt"]) for q in qs]
+            for im, g in zip(images, gts):
+                if im.shape[:2] != g.shape:
+                    raise ValueError(f"query image {im.shape[:2]} and its gt {g.shape} differ in size")
+            if self.class_value is not None:
+                cls = [int(self.class_value(q)) if callable(self.class_value) else int(self.class_value) for q in qs]
+        want_bin = self.class_value is not None
+        lay = InputBatch((tf.out_h, tf.out_w), images, gts, cls if gts else (), want_pm1=False, want_bin=want_bin)
+        return lay, cls, bool(gts)
+
+    def _plan(self, qs):
+        lay, cls, has_gt = self.layout(qs)
+        return lay, (cls, has_gt)
+
+    def _outputs(self):
+        return self.b, 0, self.b if self.class_value is not None else 0
+
+    def _native(self, lay, ctx, staged, device):
+        cls, has_gt = ctx
+        gt_device = (staged, *zip(*lay.mask_src)) if has_gt else None
+        return NativeTargets(lay.out_hw, [(it.H, it.W) for it in lay.img_items[:lay.n_img]], gt_device=gt_device,
+                             class_value=cls, ignore_value=self.ignore_value, device=device)
+
+    def _result(self, qs, index, lay, ctx, r, staged):
+        out = dict(query_img=r["images"], native=self._native(lay, ctx, staged, self.device), index=list(index))
+        if r["bin"] is not None:
+            out["query_mask"] = r["bin"]
+        return out

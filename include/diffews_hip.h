@@ -363,6 +363,10 @@ int dfw_meter_update(const int64_t* counts, const int64_t* class_id, int64_t* in
  * dfw_resample_ksize / dfw_resample_coeffs are HOST functions: Pillow's precompute_coeffs +
  * normalize_coeffs_8bpc for one axis; bounds [out_size][2] = (first input index, tap count),
  * coeffs [out_size][ksize].  The caller copies them to the device next to the image bytes.
+ *
+ * dfw_image_to_tensor / dfw_mask_to_tensor are the ONE-ITEM forms: pointers as arguments, two launches per image, one per
+ * mask.  dfw_inputs_to_tensor below runs the same stage bodies (one copy of the arithmetic, csrc/inputs.hip) over a whole
+ * ragged batch in three launches; the Python package calls only that one.
  */
 int32_t dfw_resample_ksize(int32_t in_size, int32_t out_size);
 int dfw_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs);
@@ -492,7 +496,7 @@ int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_stream_t stre
 /*
  * Input transform of a whole ragged batch (version >= 107): dfw_image_to_tensor for n_img RGB images and
  * dfw_mask_to_tensor for n_mask class-id maps of assorted sizes, all going to one out_h x out_w, driven by two
- * device-resident tables.  Same arithmetic, bit for bit: Pillow's 8-bit two-pass BILINEAR resize (uint8 intermediate
+ * device-resident tables.  The same device code computes both: Pillow's 8-bit two-pass BILINEAR resize (uint8 intermediate
  * [H][out_w][3], weights from dfw_resample_coeffs, the caller's 256-entry lut) and ATen's nearest rule
  * (on = id == class_value, index min((int)floorf((float)o * scale), size - 1), scale = (float)in / out in float).
  * Every offset is in BYTES from the base pointer named; bounds, coefficients, int32 masks and float destinations need

@@ -1,7 +1,9 @@
 """Shared by tests/test_query_loader_cpu.py and tests/test_query_loader_gpu.py: the ragged batch both run, and its expected
 tensors from the code the reference runs on the host -- PIL.Image.resize(BILINEAR) + ToTensor + Normalize
 (evaluation_util/data/dataset.py:36-40) and F.interpolate(nearest) on the binarised class map (coco.py:42,46).  Computed
-once per output size and never written."""
+once per output size and never written.  Also the per-item C entry points (dfw_image_to_tensor / dfw_mask_to_tensor),
+which the package itself no longer calls, through ctypes."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -46,3 +48,49 @@ def ragged(out_hw):
     return dict(images=images, masks=masks, mask_class=mask_class, want_pm1=want_pm1, want_bin=want_bin,
                 ref_images=[host_image(im, out_hw) for im in images],
                 ref_masks=[host_mask(m, c, out_hw) for m, c in zip(masks, mask_class)])
+
+
+def _stage_one(arrays, device):
+    """One pinned buffer holding `arrays` at 16-byte aligned offsets, one H2D copy -> (device tensor, addresses)."""
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total = (total + a.nbytes + 15) // 16 * 16
+    host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+    for o, a in zip(offs, arrays):
+        host.numpy()[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    dev = host.to(device, non_blocking=True)
+    return dev, [dev.data_ptr() + o for o in offs]
+
+
+def per_item_image(img_u8, out_hw, lut):
+    """dfw_image_to_tensor for one uint8 [H, W, 3] image -> fp32 [3, out_h, out_w] on lut's device."""
+    from diffews_amd import _lib as L
+    from diffews_amd.input_pipeline import resample_coeffs
+    (H, W), (oh, ow) = img_u8.shape[:2], out_hw
+    xb, xw, xk = resample_coeffs(W, ow)
+    yb, yw, yk = resample_coeffs(H, oh)
+    dev, p = _stage_one([np.ascontiguousarray(img_u8), xb, xw, yb, yw], lut.device)
+    tmp = torch.empty(H * ow * 3, dtype=torch.uint8, device=lut.device)
+    dst = torch.empty(3, oh, ow, dtype=torch.float32, device=lut.device)
+    a = L.ImageArgs()
+    a.src, a.H, a.W, a.out_h, a.out_w = p[0], H, W, oh, ow
+    a.xbounds, a.xcoef, a.xk, a.ybounds, a.ycoef, a.yk = p[1], p[2], xk, p[3], p[4], yk
+    a.tmp, a.dst, a.lut = tmp.data_ptr(), dst.data_ptr(), lut.data_ptr()
+    L.check(L.lib().dfw_image_to_tensor(C.byref(a), torch.cuda.current_stream(lut.device).cuda_stream), "dfw_image_to_tensor")
+    return dst
+
+
+def per_item_mask(ids, value, out_hw, device, want_pm1=True, want_bin=True):
+    """dfw_mask_to_tensor for one uint8 / int32 class-id map -> (fp32 [3, out_h, out_w] in +-1 or None, uint8
+    [out_h, out_w] in 0/1 or None)."""
+    from diffews_amd import _lib as L
+    assert ids.dtype in (np.uint8, np.int32)
+    (H, W), (oh, ow) = ids.shape, out_hw
+    dev, p = _stage_one([np.ascontiguousarray(ids)], device)
+    pm1 = torch.empty(3, oh, ow, dtype=torch.float32, device=device) if want_pm1 else None
+    bn = torch.empty(oh, ow, dtype=torch.uint8, device=device) if want_bin else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(L.lib().dfw_mask_to_tensor(p[0], ids.dtype.itemsize, H, W, int(value), oh, ow, ptr(pm1), ptr(bn),
+                                       torch.cuda.current_stream(device).cuda_stream), "dfw_mask_to_tensor")
+    return pm1, bn

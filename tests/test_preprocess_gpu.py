@@ -1,4 +1,4 @@
-"""GPU: the input-transform kernels (csrc/preprocess.hip via the C ABI) against the code the reference
+"""GPU: the input-transform kernels (csrc/inputs.hip via the C ABI) against the code the reference
 runs on the host -- PIL.Image.resize(BILINEAR) + ToTensor + Normalize (evaluation_util/data/dataset.py:36-40),
 F.interpolate(nearest) on the class mask (coco.py:42,46), mask expansion (main_oss.py:100-104).
 Byte / integer work: BIT-EXACT.  Also the prefetching EpisodeLoader's tensor contract and its hand-off
