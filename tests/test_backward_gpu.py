@@ -50,7 +50,8 @@ def test_linear_wgrad(B, dtype, M, N, K):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("Bn,H,W,Cin,Cout,stride,ups", [(2, 16, 16, 64, 128, 1, 0), (1, 24, 40, 128, 64, 1, 0),
                                                       (2, 16, 16, 64, 64, 2, 0), (1, 8, 8, 64, 128, 1, 1),
-                                                      (3, 4, 4, 128, 128, 1, 0)])
+                                                      (3, 4, 4, 128, 128, 1, 0),
+                                                      (1, 12, 20, 64, 64, 2, 0), (1, 6, 10, 64, 128, 1, 1)])
 def test_conv3x3_backward(B, dtype, Bn, H, W, Cin, Cout, stride, ups):
     """Weight gradient (TN GEMM over the forward's im2col addressing) and data gradient (the forward conv kernel
     on mirrored weights; stride 2 through zero-stuffing, the fused upsample through 2x2 pooling) of every conv
@@ -61,6 +62,8 @@ def test_conv3x3_backward(B, dtype, Bn, H, W, Cin, Cout, stride, ups):
     w = rnd((Cout, Cin, 3, 3), dtype, 2, (9 * Cin) ** -0.5)
     xr, wr = x.float().requires_grad_(), w.float().requires_grad_()
     xin = F.interpolate(xr, scale_factor=2.0, mode="nearest") if ups else xr
+    if ups:
+        xin.retain_grad()
     y = F.conv2d(xin, wr, None, stride=stride, padding=1)
     dy = rnd(tuple(y.shape), dtype, 3)
     y.backward(dy.float())
@@ -77,6 +80,22 @@ def test_conv3x3_backward(B, dtype, Bn, H, W, Cin, Cout, stride, ups):
     else:
         dx = ops.conv3x3(dyh, wd, Cin)
     assert dx.shape == (Bn, H, W, Cin) and rel(dx.permute(0, 3, 1, 2), xr.grad) < TOL[dtype]
+    # Border rows and columns per pixel (where a swap of H and W, or the padding of the transposed conv, goes wrong): dx is
+    # an fp32 sum of exact 16-bit products rounded once to the storage dtype, so |dx - ref| <= u |ref|; the upsample form
+    # rounds each of the four full-resolution values before pool2x2_sum adds them, which adds u * sum |part|.  Both sides
+    # accumulate n = 9 Cout terms in fp32 in their own order: 2 n 2^-24 * sum |dy| |w| covers that.
+    u = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+    ref = xr.grad
+    mag = ref.abs() + (4 * F.avg_pool2d(xin.grad.abs(), 2) if ups else 0)
+    terms = torch.autograd.grad(F.conv2d(xin, w.float().abs(), None, stride=stride, padding=1), xr, dy.float().abs())[0]
+    bound = u * mag + 2 * 9 * Cout * 2.0 ** -24 * terms
+    err = (dx.permute(0, 3, 1, 2).float().cpu() - ref).abs()
+    edge = torch.zeros(H, W, dtype=torch.bool)
+    edge[0], edge[-1], edge[:, 0], edge[:, -1] = True, True, True, True
+    over = (err - bound)[:, :, edge]
+    print(f"[conv3x3-bwd border] {dtype} {(Bn, H, W, Cin, Cout, stride, ups)}: worst err / bound on the border "
+          f"{float((err / bound)[:, :, edge].max()):.3f}")
+    assert float(over.max()) <= 0, float((err / bound)[:, :, edge].max())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -135,6 +135,128 @@ def test_vae_every_tensor_fault_moves_its_stage(dt):
     _sweep("vae", rec, sd, shapes, dt)
 
 
+# ---------------------------------------------------------------------------------------------- backward
+
+# Backward faults no check can see, "<class> <what>": at most 2 % of the (tensor, class) pairs.  The head of the support
+# pass gets no gradient at all (its output is multiplied by zero), so the term it deposits on the last transformer's output
+# is exactly zero and leaving it out changes nothing.
+BWD_UNOBSERVABLE = {"arrived-drop up_blocks.3.attentions.2<-head support"}
+
+_GREC = {}
+
+
+def _grad_rec(dt, b, s, h, w):
+    """The oracle's training graph with gradients, as the GPU test records it (same draws)."""
+    if (dt, b, s, h, w) not in _GREC:
+        ucfg = config.get("tiny_unet")
+        shapes = weights.unet_param_shapes(ucfg)
+        sd = sl.loud_state_dict(shapes, 1234, round_to=dt)
+        ou = OracleUNet(**sl.kw(ucfg)); ou.load_state_dict(sd); ou.eval()
+        te = weights.synthetic_text_embed(ucfg, tokens=77).to(dt).float()
+        g = torch.Generator().manual_seed(1000 + 100 * b + 10 * s + w)
+        zr = torch.randn(b * s, 8, h, w, generator=g) * 0.5
+        zq = torch.randn(b, 4, h, w, generator=g) * 0.5
+        target = torch.randn(b, 4, h, w, generator=g) * 0.5
+        rec = sl.record_unet_grads(ou, shapes, zr, zq, te.repeat(b * s, 1, 1), te.repeat(b, 1, 1), target)
+        _GREC[(dt, b, s, h, w)] = (rec, sd, shapes)
+    return _GREC[(dt, b, s, h, w)]
+
+
+def _dx_effect(rec, st, elow, fault=None, **kw):
+    """Change of the stage's dx (against the recording) as a multiple of e_low_bwd: the largest over passes and images."""
+    with sl.faulted(rec.model, fault or {}):
+        dx, _ = st.grad_run(rec.model, **kw)
+    return max(e / l for p, v in dx.items() for e, l in zip(sl.rel_images(v, st.grad[p]["dx"]), elow[(st.name, p)]) if l is not None)
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=IDS)
+def test_backward_faults_move_the_recorded_gradients(dt):
+    """With the oracle alone: every fault class of the hand-written backward moves the quantity the GPU test records by at
+    least (2 k_bwd + 1) * e_low_bwd (dx, parameter gradients), or beyond the sum of both rounding bounds (arrived).
+    The inputs are the GPU test's 1 x 2-shot cases at 16x16 and 16x24 (a fault counts as seen when either input shows it:
+    the engine runs both) and its 2 x 2-shot case for the episode-to-bank mapping."""
+    scale = sl.LOSS_SCALE[dt]
+    recs = [_grad_rec(dt, 1, 2, 16, 16)[0], _grad_rec(dt, 1, 2, 16, 24)[0]]
+    sd = _grad_rec(dt, 1, 2, 16, 16)[1]
+    lows = [r.e_low_bwd(dt, scale) for r in recs]
+    rec = recs[0]
+    # the recording itself: what the consumers of a stage output send back adds up to the total gradient there
+    for (n, p), cons in rec.consumers.items():
+        total = sum(rec.stages[c].grad[p]["dx"][:, lo:hi] for c, lo, hi in cons)
+        dy = rec.stages[n].grad[p]["dy"]
+        assert float((total - dy).abs().max()) <= 1e-5 * float(dy.abs().max()) + 1e-30, (n, p)
+    wiring = ("transpose", "mirror", "kykx", "geglu_halves", "exchange")
+    pairs, below, mins = 0, [], collections.defaultdict(lambda: (float("inf"), ""))
+
+    def note(cls, what, f, bar):
+        nonlocal pairs
+        pairs += 1
+        mins[cls] = min(mins[cls], (f, what))
+        if not f >= bar:
+            below.append((f, cls + " " + what))
+
+    # (1) dx recomputed with one owned weight faulted (a wrong derived copy: W^T of a Linear, the mirrored conv weight)
+    for n, st in rec.stages.items():
+        if st.kind in ("stem", "time"):
+            continue
+        bar = 2 * sl.k_bwd(dt, st.kind + ".dx") + 1
+        for name in st.owned:
+            if sd[name].dim() < 2:
+                continue
+            for cls, fault in sl.faults_of(name, sd, [q for q in st.owned if sd[q].dim() >= 2]):
+                if cls.split(":")[0] not in wiring:
+                    continue
+                f = 0.0
+                for r, (ex, _) in zip(recs, lows):
+                    f = max(f, _dx_effect(r, r.stages[n], ex, fault))
+                    if f >= bar:
+                        break
+                note("dx-" + cls.split(":")[0], cls + " " + name, f, bar)
+    # (2) a parameter gradient with the same permutations applied to the gradient itself
+    owner = {k: v[0] for k, v in rec.owner().items()}
+    for name in sd:
+        st = rec.stages[owner[name]]
+        bar = 2 * sl.k_bwd(dt, sl.grad_class(st.kind, name)) + 1
+        per_input = [dict(sl.faults_of(name, r.pgrad, st.owned)) for r in recs]
+        for cls in per_input[0]:
+            if cls.split(":")[0] not in wiring:
+                continue
+            f = max(sl.rel_images(v[None], r.pgrad[k][None])[0] / ep[k]
+                    for r, (_, ep), faults in zip(recs, lows, per_input) for k, v in faults[cls].items())
+            note("grad-" + cls.split(":")[0], cls + " " + name, f, bar)
+    # (3) arrived: one consumer's term missing; the two halves of a concat handed out crosswise
+    seen = collections.OrderedDict()
+    for r in recs:
+        for (n, p), cons in r.consumers.items():
+            ref, bound = sl.arrived_ref(r, n, p, dt, scale)
+            for c, lo, hi in cons:
+                kinds = [("arrived-drop", dict(drop=c))]
+                if hi - lo < r.stages[c].rec[p][0][0].shape[1]:
+                    kinds.append(("arrived-halves", dict(exchange=(c,))))
+                for cls, kw_ in kinds:
+                    bad, bbound = sl.arrived_ref(r, n, p, dt, scale, **kw_)
+                    key = (cls, f"{n}<-{c} {p}")
+                    seen[key] = seen.get(key, False) or bool(((bad - ref).abs() > bound + bbound).any())
+    for (cls, what), ok in seen.items():
+        note(cls, what, float("inf") if ok else 0.0, 1.0)
+    # (4) the support rows' dx of a transformer without the bank term, or with the bank term of the other episode
+    rec22 = _grad_rec(dt, 2, 2, 16, 16)[0]
+    ex22 = rec22.e_low_bwd(dt, scale)[0]
+    for n, st in rec22.stages.items():
+        if st.kind == "transformer":
+            bar = 2 * sl.k_bwd(dt, "transformer.dx") + 1
+            note("bank-missing", n, _dx_effect(rec22, st, {k: v for k, v in ex22.items() if k[1] == "support"}, bank=False), bar)
+            note("bank-other-episode", n, _dx_effect(rec22, st, ex22, flip_query=True), bar)
+    print(f"\nbackward faults {dt}: {pairs} (tensor, class) pairs")
+    for c, (f, what) in sorted(mins.items()):
+        print(f"  min f  {c:20s} {f:9.2f}   {what}")
+    for f, what in sorted(below):
+        print(f"  below the bar: {f:6.2f}  {what}")
+    names = {w for _, w in below}
+    assert names <= BWD_UNOBSERVABLE, sorted(names - BWD_UNOBSERVABLE)
+    assert len(BWD_UNOBSERVABLE) <= pairs // 50
+
+
 def test_loud_draw_keeps_layout_and_surgery():
     ucfg = config.get("tiny_unet")
     shapes = weights.unet_param_shapes(ucfg)

@@ -4,9 +4,19 @@ compared per image with the oracle's fp32 output and must stay within k * e_low,
 torch in the storage dtype.  tests/test_stage_local_cpu.py proves that every single-tensor fault moves its stage by at
 least (2 k + 1) * e_low, so these assertions pin every parameter of the three hand-written copies of the wiring.
 
+The trainer's hand-written backward is pinned the same way (test_trainer_backward_stage_by_stage): the oracle's two-pass
+training graph is recorded with its gradients, the engine's tape walks teacher-forced -- every stage receives the oracle's
+dy at its output and its dx is judged alone against k_bwd * e_low_bwd -- and the wiring between the stages is judged by the
+gradient that ARRIVED at each stage output before it was replaced, which must be the sum of what the consumers deposited
+to within one rounding per add.  Every key of grad_dict() is judged per tensor.  Known limit: a stage's forced input is a
+fresh tensor, so `tape.take` ACROSS a stage boundary (the dx_add fusion of a stage's first norm with the gradient its input
+already has from another consumer) is not exercised here and stays with the whole-step tests of test_backward_gpu.py;
+`take` inside a stage (a resnet's norm1 receiving conv2's residual term) is.
+
 A failure names the stage prefix, the pass, the image and the ratio.  Each test prints the worst ratio per stage class;
 the module prints the aggregate per dtype when it finishes (the table of DESIGN.md section 4).
 """
+import contextlib
 import os
 import sys
 
@@ -28,7 +38,12 @@ def _report():
     for dt, tab in _WORST.items():
         print(f"\nworst rel / e_low per stage class, {dt}:")
         for kind, (r, name, p, i) in sorted(tab.items()):
-            print(f"  {kind:12s} {r:5.2f}   (k = {sl.k_of(dt, kind):.2f})   {name}, {p} pass, image {i}")
+            print(f"  {kind:12s} {r:5.2f}   (k = {k_of_any(dt, kind):.2f})   {name}, {p} pass, image {i}")
+
+
+def k_of_any(dt, kind):
+    """The allowance a row class is judged by: forward stage kinds, backward classes, `arrived` (error / its own bound)."""
+    return 1.0 if kind == "arrived" else sl.k_bwd(dt, kind) if "." in kind else sl.k_of(dt, kind)
 
 
 def _finish(rec, tf, dt, label):
@@ -77,7 +92,21 @@ def _build_ctx(dt):
             rec.e_low(dt)
             recs[key] = (rec, zr, zq)
         return recs[key]
-    return dict(dt=dt, ucfg=ucfg, vcfg=vcfg, usd=usd, vsd=vsd, ou=ou, ov=ov, te=te, unet_rec=unet_rec,
+    grecs = {}
+
+    def grad_rec(b, s, h, w, scale):
+        """The oracle's two-pass training graph with its gradients (77-token prompt, seeded target), once per shape."""
+        key = (b, s, h, w)
+        if key not in grecs:
+            g = torch.Generator().manual_seed(1000 + 100 * b + 10 * s + w)
+            zr = torch.randn(b * s, 8, h, w, generator=g) * 0.5
+            zq = torch.randn(b, 4, h, w, generator=g) * 0.5
+            target = torch.randn(b, 4, h, w, generator=g) * 0.5
+            rec = sl.record_unet_grads(ou, ushapes, zr, zq, te[77].repeat(b * s, 1, 1), te[77].repeat(b, 1, 1), target)
+            rec.e_low_bwd(dt, scale)
+            grecs[key] = (rec, zr, zq)
+        return grecs[key]
+    return dict(dt=dt, ucfg=ucfg, vcfg=vcfg, usd=usd, vsd=vsd, ou=ou, ov=ov, te=te, unet_rec=unet_rec, grad_rec=grad_rec,
                 ushapes=ushapes, vshapes=vshapes)
 
 
@@ -216,6 +245,145 @@ def test_trainer_forward_stage_by_stage(ctx, shots):
     assert len(tf.out) == sum(len(st.rec) for st in rec.stages.values())
     rows, bad = _finish(rec, tf, dt, f"trainer {shots}-shot")
     assert not bad, "\n".join(bad)
+
+
+# ---------------------------------------------------------------------------------------------- trainer backward
+
+LOSS_SCALE = sl.LOSS_SCALE      # fp16 runs scaled by 1024: grad_scale / gs are under test
+BWD_CASES = [
+    # id, episodes, shots, latent h, w
+    ("1x1-16x16", 1, 1, 16, 16),
+    ("1x2-16x16", 1, 2, 16, 16),
+    ("2x2-16x16", 2, 2, 16, 16),      # the episode-to-bank mapping and segs = B in the dtproj column sums
+    ("1x2-16x24", 1, 2, 16, 24),      # levels 16x24, 8x12, 4x6, 2x3: non-square at every stride-2 and upsample conv
+]
+
+
+def _bwd_trainer(ctx):
+    from diffews_amd.train import UNetTrainer
+    if "trainer_bwd" not in ctx:
+        ctx["trainer_bwd"] = UNetTrainer(ctx["ucfg"], ctx["usd"], torch_dtype=ctx["dt"], loss_scale=LOSS_SCALE[ctx["dt"]],
+                                         dynamic_loss_scale=False)
+    return ctx["trainer_bwd"]
+
+
+def _run_trainer_bwd(tr, rec, zr, zq, te, zero_grad=True, fault=None):
+    """One teacher-forced forward + backward of the trainer -> (TeacherForce, grad_dict() on the host)."""
+    n_ref, b = zr.shape[0], zq.shape[0]
+    with sl.TeacherForce(rec, tr) as tf, (fault(tf) if fault else contextlib.nullcontext()):
+        tf.at("support", "query")
+        c = tr._forward(zr.cuda(), zq.cuda(), 1, te.repeat(b, 1, 1).cuda(), zero_grad=zero_grad, ehs_ref=te.repeat(n_ref, 1, 1).cuda())
+        tf.seed_head(c)
+        tr._backward(c)
+        torch.cuda.synchronize()
+    return tf, {k: v.float().cpu() for k, v in tr.grad_dict().items()}
+
+
+def _finish_bwd(rec, tf, grads, dt, label):
+    rows, bad, failing = sl.compare_bwd(rec, tf, grads, dt, label)
+    sl.worst_by_kind(rows, _WORST.setdefault(dt, {}))
+    print(f"\n{label} [{dt}]: " + ", ".join(f"{k} {v[0]:.2f}" for k, v in sorted(sl.worst_by_kind(rows).items())))
+    return rows, bad, failing
+
+
+@pytest.mark.parametrize("case", BWD_CASES, ids=[c[0] for c in BWD_CASES])
+def test_trainer_backward_stage_by_stage(ctx, case):
+    """UNetTrainer's tape, teacher-forced on the oracle's recorded gradients: every stage's dx per image, every tensor of
+    grad_dict() and the gradient that arrived at every stage output (see the module docstring)."""
+    label, b, s, h, w = case
+    dt, tr = ctx["dt"], _bwd_trainer(ctx)
+    rec, zr, zq = ctx["grad_rec"](b, s, h, w, tr.loss_scale)
+    tf, grads = _run_trainer_bwd(tr, rec, zr, zq, ctx["te"][77])
+    tf.check_order()
+    # stage coverage: every stage of every pass sent a dx (the stems and the time MLP have no input gradient) and
+    # received a gradient at its output (the head's is the seed); tensor coverage is asserted inside compare_bwd
+    stages = {(n, p): st.kind for n, st in rec.stages.items() for p in st.rec}
+    assert set(tf.dx) == {k for k, kind in stages.items() if kind not in ("stem", "time")}, sorted(set(stages) ^ set(tf.dx))
+    assert set(tf.arrived) == set(rec.consumers) == {k for k, kind in stages.items() if kind not in ("head", "time")}
+    assert set(grads) == set(ctx["usd"])
+    rows, bad, failing = _finish_bwd(rec, tf, grads, dt, "trainer backward " + label)
+    assert sum(r[0].endswith(".grad") for r in rows) == sum(v is not None for v in rec.e_low_bwd(dt, tr.loss_scale)[1].values())
+    assert not bad, "\n".join(bad)
+    if label == "1x2-16x16":
+        # zero_grad=False adds the same gradients once more (P.acc routes every writer to accumulate): twice the first,
+        # to the rounding of fp32 sums taken in another order (1e-5, as test_training_step_gradients_vs_oracle_autograd)
+        tf2, grads2 = _run_trainer_bwd(tr, rec, zr, zq, ctx["te"][77], zero_grad=False)
+        for k, g in grads.items():
+            assert sl.rel_images(grads2[k][None], 2 * g[None])[0] < 1e-5, k
+
+
+@contextlib.contextmanager
+def _drop_residual(tf, stage):
+    """The tape loses the first gradient sent to the stage's input: conv2's `tape.accum(residual, dy)` of a resnet
+    without a shortcut conv."""
+    from diffews_amd import train as T
+    orig, seen = T._Tape.accum, []
+
+    def accum(self, t, g):
+        xf = tf.forced_in.get(stage)
+        if xf is not None and not seen and self._key(t) == self._key(xf):
+            seen.append(1)
+            return None
+        return orig(self, t, g)
+    T._Tape.accum = accum
+    try:
+        yield
+    finally:
+        T._Tape.accum = orig
+    assert seen
+
+
+@contextlib.contextmanager
+def _swap_cat_offsets(tf):
+    """cat_bwd of the first concat the tape walks (up_blocks.3.resnets.2 reads [up_blocks.3.attentions.1 ; stem], 64 + 64
+    channels) hands the two halves out crosswise."""
+    from diffews_amd import ops_bwd
+    orig, calls = ops_bwd.slice_channels, []
+
+    def slice_channels(a, c0, Cc):
+        calls.append(c0)
+        if len(calls) <= 2:
+            assert a.shape[-1] == 2 * Cc and c0 in (0, Cc)
+            c0 = Cc - c0
+        return orig(a, c0, Cc)
+    ops_bwd.slice_channels = slice_channels
+    try:
+        yield
+    finally:
+        ops_bwd.slice_channels = orig
+    assert len(calls) >= 2
+
+
+@contextlib.contextmanager
+def _wrong_derived_copy(tr, name, other):
+    """_d("D", name) answers with the tap-mirrored copy of another conv of the same shape: the forward is untouched."""
+    orig = tr._d
+    tr._d = lambda kind, n: orig(kind, other if (kind, n) == ("D", name) else n)
+    try:
+        yield
+    finally:
+        del tr._d
+
+
+def test_injected_backward_faults_are_caught_and_named(ctx):
+    """Three wiring faults patched into the engine's backward: the stage-local check fails at the stage that owns the
+    faulty gradient and nowhere else (teacher forcing confines a fault to its stage)."""
+    dt, tr = ctx["dt"], _bwd_trainer(ctx)
+    rec, zr, zq = ctx["grad_rec"](1, 2, 16, 16, tr.loss_scale)
+    m0, m1 = "mid_block.resnets.0", "mid_block.resnets.1"
+    faults = [
+        ("dropped residual accum", {m0}, lambda tf: _drop_residual(tf, m0)),
+        ("cat_bwd offsets swapped", {"up_blocks.3.attentions.1", "conv_in", "conv_in_ref"}, _swap_cat_offsets),
+        ("wrong derived D copy", {m1}, lambda tf: _wrong_derived_copy(tr, m1 + ".conv1.weight", m1 + ".conv2.weight")),
+    ]
+    for what, owners, fault in faults:
+        tf, grads = _run_trainer_bwd(tr, rec, zr, zq, ctx["te"][77], fault=fault)
+        rows, bad, failing = sl.compare_bwd(rec, tf, grads, dt, what)
+        print(f"\ninjected {what:24s} [{dt}]: failing stages {sorted(failing)}; {bad[0] if bad else ''}")
+        assert failing == owners, (what, sorted(failing), bad[:3])
+        assert all(any(f"stage {o} " in m for m in bad) for o in owners)
+    tf, grads = _run_trainer_bwd(tr, rec, zr, zq, ctx["te"][77])      # the patches are gone: clean again
+    assert not sl.compare_bwd(rec, tf, grads, dt)[1]
 
 
 def test_fullsize_unet_stage_by_stage(hip_lib):
