@@ -7,6 +7,8 @@
 // batch entry walks it -- bank image = episode*0 + shot (FsaP::bank_stride).
 // Bank sets (dfw_fsa_attention_sets): the bank holds batch/group support sets and `group` consecutive entries share one
 // -- bank image = (entry/group)*nshot + shot (FsaP::bank_div); the class-major batch of an N-way query pass.
+// Ragged bank sets (dfw_fsa_attention_ragged): the same with a shot count of its own per set, sets packed set-major
+// -- bank image = first[entry/group] + shot, shot < shots[entry/group]; the table rides in the kernel arguments (FsaPR).
 //
 // Workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 query rows.
 // Per 64-key tile (K and V tiles double-buffered in LDS, register-staged issue-early/write-late):
@@ -49,6 +51,14 @@ struct FsaP {
   int bank_div;      // consecutive entries that read the same bank images: 1, or `group` of dfw_fsa_attention_sets
 };
 
+// Ragged sets launch: FsaP plus the per-set table, by value in the kernel arguments (no device allocation, no copy, and a
+// captured graph keeps the values).  Set j holds bank images [first[j], first[j] + shots[j]); FsaP::nshot is max(shots).
+constexpr int kFsaMaxSets = 64;
+struct FsaPR : FsaP {
+  int first[kFsaMaxSets];
+  int shots[kFsaMaxSets];
+};
+
 // ------------------------------------------------------------------------------------------------
 // v2: same mathematics and register layout as fsa_kernel, different data movement:
 //   * NW = 8 (or 4) waves share every K/V tile: 256 (128) query rows per workgroup;
@@ -60,8 +70,11 @@ struct FsaP {
 // rounding), so a score needs no multiply, and the running reference maximum rides in as the INITIAL VALUE of
 // the S^T accumulators (S'' = q.k - m_ref comes straight out of the MFMA chain): on a tile that does not move
 // the reference the softmax is max3 + exp2 + add + cvt per element pair -- no fma, no subtract.
-template <typename T, int NW, int QB, bool PRE>
-__global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 ? 2 : 4) * NW / 8 : 1) void fsa_ring_kernel(const FsaP p) {
+// RAG: the ragged sets launch -- p is an FsaPR, and the workgroup's set gives its first bank image and its shot count
+// (two scalar loads from the kernel arguments, once per workgroup) where the other forms derive them from p.nshot.
+template <typename T, int NW, int QB, bool PRE, bool RAG = false>
+__global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 ? 2 : 4) * NW / 8 : 1) void fsa_ring_kernel(
+    const std::conditional_t<RAG, FsaPR, FsaP> p) {
   // QB = 32-row query blocks per wave: with QB = 2 the two blocks are independent dependency chains
   // in one instruction stream, so one block's softmax VALU work overlaps the other's MFMAs, and
   // every K / V fragment read from LDS feeds two MFMAs.
@@ -107,7 +120,15 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
   }
   const int bank_b = b - p.n_plain;          // episode index into the bank (< 0: own keys only)
   // first bank image of this entry (uniform, once per workgroup); only a sets launch (n_plain == 0) has a divisor > 1
-  const int bank_img0 = (p.bank_div > 1 ? bank_b / p.bank_div : bank_b) * p.bank_stride;
+  int bank_img0, nshot;
+  if constexpr (RAG) {                       // n_plain == 0 and set < kFsaMaxSets (checked by the host before the launch)
+    const int set = __builtin_amdgcn_readfirstlane(bank_b / p.bank_div);
+    bank_img0 = p.first[set];
+    nshot = p.shots[set];
+  } else {
+    bank_img0 = (p.bank_div > 1 ? bank_b / p.bank_div : bank_b) * p.bank_stride;
+    nshot = p.nshot;
+  }
   const int q0 = qblk * (NW * 32 * QB) + wave * (32 * QB);
   const uint32_t lds0 = lds_addr(smem);
 
@@ -130,9 +151,9 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
   // lane -> row + (lane>>3), LDS slot lane&7; source chunk = slot ^ swizzle(row)
   const int lrow = lane >> 3, slot = lane & 7;
   const int tiles_own = (p.n_kv + KT - 1) / KT;
-  const int tiles_bank = (p.nshot > 0 && bank_b >= 0) ? (p.n_bank + KT - 1) / KT : 0;
+  const int tiles_bank = (nshot > 0 && bank_b >= 0) ? (p.n_bank + KT - 1) / KT : 0;
   // this instance's key segments [seg0, seg1) of [own ; shot 0 ; ...]
-  const int nseg = 1 + (tiles_bank ? p.nshot : 0);
+  const int nseg = 1 + (tiles_bank ? nshot : 0);
   const bool parted = p.nsplit > 1 && bank_b >= 0;
   const int seg0 = parted ? split * nseg / p.nsplit : 0, seg1 = parted ? (split + 1) * nseg / p.nsplit : nseg;
   const int ntiles = (seg0 == 0 ? tiles_own : 0) + (seg1 - (seg0 == 0 ? 1 : seg0)) * tiles_bank;
@@ -521,7 +542,9 @@ static int64_t extent(int batch, int64_t bs, int n, int ld, int heads) {
 
 // Key split of the bank-reading images (see FsaP::nsplit): the smallest split count whose longest workgroup is no longer
 // the launch's critical path.  Work in key tiles per workgroup column: plain images 1 segment, bank readers 1 + nshot.
-static int fsa_split_count(const dfw_fsa_args* a) {
+// bank_segs: key segments of all bank readers together (nq_img * (1 + nshot) unless the sets are ragged; a->nshot is then
+// the longest set's count, whose workgroups are the critical path).
+static int fsa_split_rule(const dfw_fsa_args* a, long long bank_segs) {
   if (!cfg().fsa_key_split || a->nshot < 2 || a->n_q > 65536) return 1;
   const int nq_img = a->batch - a->n_plain, nseg = 1 + a->nshot;
   if (nq_img <= 0) return 1;
@@ -529,13 +552,17 @@ static int fsa_split_count(const dfw_fsa_args* a) {
   const int rows_per_wg = a->n_q <= 1024 ? 128 : 256;
   const long long wg_per_img = (long long)a->heads * ((a->n_q + rows_per_wg - 1) / rows_per_wg);
   const long long slots = a->n_q <= 1024 ? 1024 : 512;            // resident workgroups (4 x 256-thread / 2 x 512-thread per CU)
-  const double total = (double)wg_per_img * ((double)a->n_plain + (double)nq_img * nseg);   // in units of one segment's tiles
+  const double total = (double)wg_per_img * ((double)a->n_plain + (double)bank_segs);   // in units of one segment's tiles
   const double fair = total / slots > 1.0 ? total / slots : 1.0;
   if (cfg().fsa_force_splits) { const int f = cfg().fsa_force_splits; return f > nseg ? nseg : f; }   // sweeps
   if ((double)nseg <= 1.5 * fair) return 1;
   for (int ns = 2; ns <= nseg; ++ns)
     if ((double)((nseg + ns - 1) / ns) <= 1.25 * fair) return ns;
   return nseg;
+}
+
+static int fsa_split_count(const dfw_fsa_args* a) {
+  return fsa_split_rule(a, (long long)(a->batch - a->n_plain) * (1 + a->nshot));
 }
 
 extern "C" size_t dfw_fsa_workspace_bytes(const dfw_fsa_args* a) {
@@ -562,25 +589,32 @@ static int fsa_check_args(const dfw_fsa_args* a) {
 // The launch dfw_fsa_attention makes: waves per workgroup, key splits taken (only with a caller-provided workspace of
 // dfw_fsa_workspace_bytes(); without one the launch is unsplit) and grid.z.
 struct FsaPlan { int nw, nsplit, grid_z; };
-static FsaPlan fsa_plan(const dfw_fsa_args* a) {
+static size_t fsa_split_bytes(const dfw_fsa_args* a, int ns) {
+  return ns <= 1 ? 0 : (size_t)(a->batch - a->n_plain) * ns * a->heads * a->n_q * 68 * sizeof(float);
+}
+// ns: the split count the rule asks for (fsa_split_count, or fsa_ragged_split_count of a ragged launch)
+static FsaPlan fsa_plan_of(const dfw_fsa_args* a, int ns) {
   FsaPlan pl;
   pl.nw = a->n_q <= 1024 ? 4 : 8;   // 8 waves x 32 query rows per workgroup; short rows: 128-query workgroups balance better
   pl.nsplit = 1;
-  const int ns = fsa_split_count(a);
-  if (ns > 1 && a->workspace && a->workspace_bytes >= dfw_fsa_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0)
+  if (ns > 1 && a->workspace && a->workspace_bytes >= fsa_split_bytes(a, ns) && (((uintptr_t)a->workspace) & 15) == 0)
     pl.nsplit = ns;
   pl.grid_z = a->n_plain + (a->batch - a->n_plain) * pl.nsplit;
   return pl;
 }
+static FsaPlan fsa_plan(const dfw_fsa_args* a) { return fsa_plan_of(a, fsa_split_count(a)); }
 
 // Host-only plan query, e.g. "fsa_ring_kernel<bf16,8,1,pre>+xcd+split3": +xcd when the kernel re-maps its grid onto the
 // XCDs (heads * grid.z % 8 == 0), +splitS when S key splits are merged by fsa_combine_kernel, +shared (last) when every
 // bank reader walks the same nshot bank images.
+static int fsa_name(const dfw_fsa_args* a, const FsaPlan& pl, char* buf, size_t n);
 extern "C" int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n) {
   const int rc = fsa_check_args(a);
   if (rc) return rc;
+  return fsa_name(a, fsa_plan(a), buf, n);
+}
+static int fsa_name(const dfw_fsa_args* a, const FsaPlan& pl, char* buf, size_t n) {
   if (!buf || n == 0) return DFW_EINVAL;
-  const FsaPlan pl = fsa_plan(a);
   const int len = snprintf(buf, n, "fsa_ring_kernel<%s,%d,1,%s>%s", a->dtype == DFW_BF16 ? "bf16" : "f16", pl.nw,
                            a->q_prescaled ? "pre" : "scale", (a->heads * pl.grid_z) % 8 == 0 ? "+xcd" : "");
   int at = len;
@@ -608,7 +642,51 @@ extern "C" int dfw_fsa_sets_kernel_name(const dfw_fsa_args* a, int32_t group, ch
   return 0;
 }
 
-static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream);
+// Ragged bank sets: a sets launch whose set j holds shots[j] images (host array), packed set-major.  Everything a sets
+// launch needs, and a table that fits the kernel arguments and matches the batch; a->nshot is the longest set's count.
+static int fsa_check_ragged(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group) {
+  const int rc = fsa_check_sets(a, group);
+  if (rc) return rc;
+  if (!shots || nsets < 1 || nsets > kFsaMaxSets || nsets != a->batch / group) return DFW_EINVAL;
+  int mx = 0;
+  for (int j = 0; j < nsets; ++j) {
+    if (shots[j] < 1) return DFW_EINVAL;
+    mx = shots[j] > mx ? shots[j] : mx;
+  }
+  return mx == a->nshot ? 0 : DFW_EINVAL;
+}
+
+// fsa_split_count's rule on the longest set (the critical path) with the launch's true total work, then clamped so that
+// every split instance of the SHORTEST set still owns a key segment: the ring kernel and fsa_combine_kernel never run an
+// empty instance.  All counts equal: dfw_fsa_attention_sets' plan.
+static int fsa_ragged_split_count(const dfw_fsa_args* a, const int32_t* shots, int nsets, int group) {
+  long long segs = 0;
+  int mn = shots[0];
+  for (int j = 0; j < nsets; ++j) {
+    segs += 1 + shots[j];
+    mn = shots[j] < mn ? shots[j] : mn;
+  }
+  const int ns = fsa_split_rule(a, segs * group);
+  return ns > 1 + mn ? 1 + mn : ns;
+}
+
+extern "C" size_t dfw_fsa_ragged_workspace_bytes(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group) {
+  if (fsa_check_ragged(a, shots, nsets, group)) return 0;
+  return fsa_split_bytes(a, fsa_ragged_split_count(a, shots, nsets, group));
+}
+
+extern "C" int dfw_fsa_ragged_kernel_name(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group, char* buf,
+                                          size_t n) {
+  int rc = fsa_check_ragged(a, shots, nsets, group);
+  if (rc) return rc;
+  rc = fsa_name(a, fsa_plan_of(a, fsa_ragged_split_count(a, shots, nsets, group)), buf, n);
+  if (rc) return rc;
+  const size_t at = strlen(buf);
+  if (at < n) snprintf(buf + at, n - at, "+ragged");
+  return 0;
+}
+
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots = nullptr);
 
 extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   const int rc = fsa_check_args(a);
@@ -622,9 +700,24 @@ extern "C" int dfw_fsa_attention_sets(const dfw_fsa_args* a, int32_t group, dfw_
   return fsa_launch(a, group, stream);
 }
 
-// `a` has passed fsa_check_args, and fsa_check_sets unless group == 1
-static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream) {
-  FsaP p;
+extern "C" int dfw_fsa_attention_ragged(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group,
+                                       dfw_stream_t stream) {
+  const int rc = fsa_check_ragged(a, shots, nsets, group);
+  if (rc) return rc;
+  return fsa_launch(a, group, stream, shots);
+}
+
+// `a` has passed fsa_check_args, and fsa_check_sets unless group == 1; shots: a ragged launch, past fsa_check_ragged
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots) {
+  FsaPR pr;
+  FsaP& p = pr;
+  const int nsets = shots ? a->batch / group : 0;
+  int nimg = 0;                      // bank images of a ragged stack
+  for (int j = 0; j < kFsaMaxSets; ++j) {
+    pr.first[j] = j < nsets ? nimg : 0;
+    pr.shots[j] = j < nsets ? shots[j] : 0;
+    nimg += pr.shots[j];
+  }
   p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v;
   p.kb = (const char*)a->k_bank; p.vb = (const char*)a->v_bank; p.out = (char*)a->out;
   const int64_t qe = extent(a->batch, a->q_bs, a->n_q, a->ldq, a->heads);
@@ -634,7 +727,7 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream) {
   if (a->nshot > 0) {
     // bank images; a shared bank holds nshot of them however many entries read it (the descriptor must not claim more)
     // and `group` entries share a set of a sets launch (n_plain == 0 there)
-    const int nb = a->bank_shared ? a->nshot : (a->batch - a->n_plain) / group * a->nshot;
+    const int nb = shots ? nimg : a->bank_shared ? a->nshot : (a->batch - a->n_plain) / group * a->nshot;
     if (nb > 0) {
       kbe = extent(nb, a->kb_bs, a->n_bank, a->ldkb, a->heads);
       vbe = extent(nb, a->vb_bs, a->n_bank, a->ldvb, a->heads);
@@ -653,7 +746,7 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream) {
   p.pre = a->q_prescaled ? 1 : 0;
   p.lse = a->lse;
   // key split: only with a caller-provided workspace of dfw_fsa_workspace_bytes(); without one the launch is unsplit
-  const FsaPlan pl = fsa_plan(a);
+  const FsaPlan pl = shots ? fsa_plan_of(a, fsa_ragged_split_count(a, shots, nsets, group)) : fsa_plan(a);
   p.nsplit = pl.nsplit;
   p.part = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
   p.bank_stride = a->bank_shared ? 0 : a->nshot;
@@ -665,7 +758,19 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream) {
     const int nw = pl.nw;
     dim3 grid((a->n_q + nw * 32 - 1) / (nw * 32), a->heads, grid_z);
     const bool pre = a->q_prescaled != 0;
-    if (nw == 8) {
+    if (shots) {
+      if (nw == 8) {
+        if (bf) { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, true, true>), grid, dim3(512), 0, st, pr);
+                  else hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, false, true>), grid, dim3(512), 0, st, pr); }
+        else { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 8, 1, true, true>), grid, dim3(512), 0, st, pr);
+               else hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 8, 1, false, true>), grid, dim3(512), 0, st, pr); }
+      } else {
+        if (bf) { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 4, 1, true, true>), grid, dim3(256), 0, st, pr);
+                  else hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 4, 1, false, true>), grid, dim3(256), 0, st, pr); }
+        else { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 4, 1, true, true>), grid, dim3(256), 0, st, pr);
+               else hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 4, 1, false, true>), grid, dim3(256), 0, st, pr); }
+      }
+    } else if (nw == 8) {
       if (bf) { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, true>), grid, dim3(512), 0, st, p);
                 else hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, false>), grid, dim3(512), 0, st, p); }
       else { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 8, 1, true>), grid, dim3(512), 0, st, p);

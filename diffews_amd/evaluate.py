@@ -105,7 +105,8 @@ def evaluate_support_set(pipe, support_imgs, support_masks, query_batches, class
 @torch.no_grad()
 def evaluate_class_set(pipe, support_imgs, support_masks, query_batches, r_threshold=0.25, threshold=0.0, batch_max=False,
                        max_batch=16, captured=True, use_original_imgsize=False, class_ids=None):
-    """N fixed classes against a stream of queries: the N support sets (support_imgs / support_masks [N, s, 3, H, W]) are
+    """N fixed classes against a stream of queries: the N support sets (support_imgs / support_masks [N, s, 3, H, W], or
+    two lists of N tensors [s_c, 3, H, W] for classes with different numbers of examples) are
     prepared ONCE (pipe.prepare_support_classes), then every item of `query_batches` -- (query_img [b, 3, H, W],
     query_labels uint8 [b, H, W] with 0 = background, 1 + c = class c, 255 = ignore) device tensors, b may vary -- goes
     through pipe.segment_classes and its per-label counts into one int64 [2, N+1] running sum on the device.
@@ -142,8 +143,8 @@ def evaluate_stream(pipe, support_images, support_class_maps, class_id=None, que
     Binary (class_id, the benchmark's class index; the maps hold class_id + 1 as coco.py:74-75 stores it):
       support_images / support_class_maps hold the s examples; returns (miou, fb_iou, meter) as evaluate_support_set does
       under use_original_imgsize.
-    N-way (class_ids, the ground-truth id of each of the N classes): support_images / support_class_maps are N lists of s
-      examples each, class c's maps hold class_ids[c]; returns (miou, iou [N+1], counts [2, N+1]) as evaluate_class_set does
+    N-way (class_ids, the ground-truth id of each of the N classes): support_images / support_class_maps are N lists of
+      examples (the classes may differ in how many), class c's maps hold class_ids[c]; returns (miou, iou [N+1], counts [2, N+1]) as evaluate_class_set does
       under use_original_imgsize with class_ids.
     The supports become tensors through input_pipeline.support_tensors (one copy, three launches) and are prepared ONCE;
     `queries` yields dicts with `query_img` and `gt` and runs through pipe.segment_stream (`size`: processing size; `batch`, `depth`); the meter (binary) or the int64 [2, N+1] running sum
@@ -170,12 +171,17 @@ def evaluate_stream(pipe, support_images, support_class_maps, class_id=None, que
     ids = [int(c) for c in class_ids]
     sets = [list(x) for x in support_images]
     maps = [list(x) for x in support_class_maps]
-    N, s = len(ids), len(sets[0]) if sets else 0
-    if len(sets) != N or len(maps) != N or s < 1 or any(len(x) != s for x in sets + maps):
-        raise ValueError("N-way: support_images / support_class_maps must be N lists of the same number of examples")
+    N = len(ids)
+    if len(sets) != N or len(maps) != N or any(len(x) < 1 for x in sets) or any(len(x) != len(m) for x, m in zip(sets, maps)):
+        raise ValueError("N-way: support_images / support_class_maps must be N lists of at least one example, each class "
+                         "with as many maps as images")
+    shots = [len(x) for x in sets]
     sup, msk = support_tensors([im for x in sets for im in x], [m for x in maps for m in x],
-                               [c for c in ids for _ in range(s)], size, device)
-    bankset = pipe.prepare_support_classes(sup.view(N, s, *sup.shape[1:]), msk.view(N, s, *msk.shape[1:]))
+                               [c for c, s in zip(ids, shots) for _ in range(s)], size, device)
+    if len(set(shots)) == 1:      # equal counts: the uniform stack
+        bankset = pipe.prepare_support_classes(sup.view(N, shots[0], *sup.shape[1:]), msk.view(N, shots[0], *msk.shape[1:]))
+    else:
+        bankset = pipe.prepare_support_classes(list(sup.split(shots)), list(msk.split(shots)))
     total = torch.zeros(2, N + 1, dtype=torch.int64, device=device)
     for index, r in pipe.segment_stream(bankset, queries, class_ids=ids, max_batch=max_batch, **stream):
         if r["native"]["counts"] is None:

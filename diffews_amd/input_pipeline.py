@@ -276,7 +276,8 @@ def support_tensors(images, class_maps, class_values, size, device="cuda"):
     """n annotated examples -- decoded images of any sizes, their class-id maps and the id (one int, or one per example)
     that marks the object -- -> (support_imgs fp32 [n, 3, S, S] in [-1, 1], support_masks fp32 [n, 3, S, S] in +-1)
     through DeviceImageTransform.batch: one H2D copy and three launches for the whole set.  Feed them to
-    pipeline.prepare_support, or to prepare_support_classes after a view to [N, s, 3, S, S]."""
+    pipeline.prepare_support, or to prepare_support_classes after a view to [N, s, 3, S, S] (classes of different
+    sizes: after a split into N tensors [s_c, 3, S, S])."""
     images, class_maps = list(images), list(class_maps)
     if not images or len(images) != len(class_maps):
         raise ValueError("support_tensors needs as many class-id maps as images, and at least one")

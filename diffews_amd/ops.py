@@ -197,7 +197,7 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
 
 
 def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None, out=None, n_plain=0,
-                  q_prescaled=False, lse=None, key_split=True, bank_shared=False, _group=0):
+                  q_prescaled=False, lse=None, key_split=True, bank_shared=False, _group=0, _shots=None):
     """KV-fusion self-attention.  q/k/v: [B, N, heads*64] views (token stride = stride(1));
     k_bank/v_bank: [(B-n_plain)*nshot, Nb, heads*64] views written by the support pass.
     n_plain: the first n_plain batch entries ignore the bank (lock-step [support ; query] launch).
@@ -218,7 +218,10 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
     a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     if nshot:
-        if _group:      # fsa_attention_sets
+        if _shots is not None:      # fsa_attention_ragged: nshot is max(shots)
+            assert n_plain == 0 and not bank_shared and _group and B % _group == 0 and k_bank.shape[0] == sum(_shots)
+            shots_c = (C.c_int32 * len(_shots))(*_shots)
+        elif _group:      # fsa_attention_sets
             assert n_plain == 0 and not bank_shared and B % _group == 0 and k_bank.shape[0] == (B // _group) * nshot
         elif bank_shared:
             assert n_plain == 0 and k_bank.shape[0] == nshot
@@ -236,19 +239,26 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     if lse is not None:   # training: per-row log2-sum-exp2 for the backward
         assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, heads, N)
         a.lse = lse.data_ptr()
-    nbytes = L.lib().dfw_fsa_workspace_bytes(C.byref(a)) if (nshot >= 2 and key_split) else 0   # key split of the bank readers (many shots)
+    if _shots is not None:
+        call = lambda: _fsa_ragged_call(a, shots_c, len(_shots), _group)
+        nbytes = L.lib().dfw_fsa_ragged_workspace_bytes(C.byref(a), shots_c, len(_shots), _group) if key_split else 0
+    else:
+        call = (lambda: _fsa_sets_call(a, _group)) if _group else (lambda: _fsa_call(a))
+        nbytes = L.lib().dfw_fsa_workspace_bytes(C.byref(a)) if (nshot >= 2 and key_split) else 0   # key split of the bank readers (many shots)
     if nbytes:
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     if gemm_hook is not None:   # bench.py roofline leg: QK^T + PV flops of this launch
         keys = n_plain * k.shape[1] + (B - n_plain) * (k.shape[1] + (nshot * k_bank.shape[1] if nshot else 0))
+        if _shots is not None:
+            keys = B * k.shape[1] + _group * sum(_shots) * k_bank.shape[1]
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _fsa_sets_call(a, _group) if _group else _fsa_call(a)
+        call()
         e1.record()
         gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
         return out
-    _fsa_sets_call(a, _group) if _group else _fsa_call(a)
+    call()
     return out
 
 
@@ -270,6 +280,26 @@ def fsa_attention_sets(q, k, v, heads, k_bank, v_bank, nshot, group, scale=None,
         raise ValueError("fsa_attention_sets needs a bank (nshot >= 1) and group >= 1")
     return fsa_attention(q, k, v, heads, k_bank, v_bank, nshot=nshot, scale=scale, out=out, q_prescaled=q_prescaled,
                          lse=lse, key_split=key_split, _group=int(group))
+
+
+def _fsa_ragged_call(a, shots, nsets, group):
+    L.check(L.lib().dfw_fsa_attention_ragged(C.byref(a), shots, nsets, group, _stream()), "dfw_fsa_attention_ragged")
+
+
+def fsa_attention_ragged(q, k, v, heads, k_bank, v_bank, shots, group, scale=None, out=None, q_prescaled=False,
+                         lse=None, key_split=True):
+    """fsa_attention_sets with a shot count per set: `shots` a sequence of B // group counts (each >= 1), k_bank/v_bank
+    [sum(shots), Nb, heads*64] with the sets packed set-major; entries [j*group, (j+1)*group) attend over
+    [own ; the shots[j] images of set j].  Per set the kernel arithmetic, key order and tile sequence of fsa_attention on
+    that set's slice with bank_shared=True; with all counts equal it is fsa_attention_sets bit for bit.  The key split
+    never exceeds 1 + min(shots)."""
+    shots = [int(s) for s in shots]
+    if group < 1 or not shots or min(shots) < 1:
+        raise ValueError("fsa_attention_ragged needs group >= 1 and a count >= 1 for every set")
+    if len(shots) * int(group) != q.shape[0]:
+        raise ValueError(f"{len(shots)} sets of {group} entries are not the batch of {q.shape[0]}")
+    return fsa_attention(q, k, v, heads, k_bank, v_bank, nshot=max(shots), scale=scale, out=out, q_prescaled=q_prescaled,
+                         lse=lse, key_split=key_split, _group=int(group), _shots=shots)
 
 
 def zeros(shape, dtype, device="cuda"):

@@ -432,10 +432,16 @@ class MarigoldPipelineRGBLatentNoise:
         """Prepare the support sets of N classes for segment_classes(): support_imgs / support_masks [N, s, 3, H, W] in
         [-1, 1] (s annotated examples of each class) -> SupportBankSet (diffews_amd.unet).  prepare_support's launches over
         all N * s images at once: one VAE-encoder launch train, quant_conv into cat([z_ref, z_mask_ref]), one support pass
-        of the UNet (unet.prepare_bank_sets).  Valid for what a SupportBank is valid for."""
+        of the UNet (unet.prepare_bank_sets).  Valid for what a SupportBank is valid for.
+
+        Classes with different numbers of examples: give two lists of N tensors [s_c, 3, H, W] instead.  The same launches
+        run over all sum(s_c) images and the result is a ragged SupportBankSet (shots == (s_0, ..., s_{N-1})), which
+        segment_classes takes like any other."""
         t, tt = self._single_step_timestep()
         folded = self._fold_conditioning(tt)
         dev = self.device
+        if isinstance(support_imgs, (list, tuple)):
+            return self._prepare_support_ragged(support_imgs, support_masks, tt, folded)
         sup = support_imgs.to(dev, torch.float32).contiguous()
         msk = support_masks.to(dev, torch.float32).contiguous()
         if sup.shape != msk.shape or sup.dim() != 5:
@@ -452,13 +458,35 @@ class MarigoldPipelineRGBLatentNoise:
         qc(mom[N * s:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)          # z_mask_ref (P:651)
         return self.unet.prepare_bank_sets(cond_ref, N, tt, None if folded else self.encode_clip_feature())
 
+    def _prepare_support_ragged(self, support_imgs, support_masks, tt, folded):
+        dev = self.device
+        if not isinstance(support_masks, (list, tuple)) or len(support_masks) != len(support_imgs) or not support_imgs:
+            raise ValueError("support_imgs and support_masks must be two lists of N tensors [s_c, 3, H, W]")
+        sups = [t.to(dev, torch.float32) for t in support_imgs]
+        msks = [t.to(dev, torch.float32) for t in support_masks]
+        for c, (a, m) in enumerate(zip(sups, msks)):
+            if a.shape != m.shape or a.dim() != 4 or a.shape[0] < 1 or a.shape[1:] != sups[0].shape[1:]:
+                raise ValueError(f"class {c}: support_imgs {tuple(a.shape)} and support_masks {tuple(m.shape)} must both be "
+                                 f"[s_c >= 1, {', '.join(str(d) for d in sups[0].shape[1:])}]")
+        shots = tuple(a.shape[0] for a in sups)
+        sup, msk, n = torch.cat(sups).contiguous(), torch.cat(msks).contiguous(), sum(shots)
+        lc = self.vae.config["latent_channels"]
+        mom = self.vae.encoder([sup, msk])                                        # [2 sum(s_c), 2 lc, h, w] fp32
+        h, w = mom.shape[-2:]
+        cond_ref = torch.empty(n, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
+        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
+        qc(mom[:n], out_scale=sf, out=cond_ref[:, :lc], channels=lc)              # z_ref      (P:649)
+        qc(mom[n:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)              # z_mask_ref (P:651)
+        return self.unet.prepare_bank_sets(cond_ref, len(shots), tt, None if folded else self.encode_clip_feature(),
+                                           shots=shots)
+
     @torch.no_grad()
     def segment_classes(self, bankset, query_img, query_labels=None, r_threshold=0.25, threshold=0.0, batch_max=False,
                         max_batch=16, captured=None, native=None, class_ids=None):
         """N-way segmentation of b query images against the N prepared classes of `bankset` (prepare_support_classes):
         query_img [b, 3, H, W] in [-1, 1]; query_labels optional uint8 [b, H, W] with 0 = background, 1 + c = class c,
         255 (or anything above N) = ignore.  The queries are encoded ONCE; the classes go through the UNet and the decoder
-        in chunks of max(1, max_batch // b) sets, each chunk one class-major batch whose attn1 reads its sets of the stack
+        in chunks of max(1, max_batch // b) sets (64 at the most), each chunk one class-major batch whose attn1 reads its sets of the stack
         in place (unet.forward_query_sets); seg_postprocess writes every chunk into its slice of one uint8 buffer and of
         the maxima, and one ops.seg_labels launch fuses the N masks into labels and counts.
 
@@ -491,7 +519,7 @@ class MarigoldPipelineRGBLatentNoise:
         bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
                       fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
         flags = (float(r_threshold), float(threshold), bool(batch_max))
-        N, per = bankset.nsets, max(1, int(max_batch) // b)
+        N, per = bankset.nsets, min(64, max(1, int(max_batch) // b))     # a ragged launch carries at most 64 sets
 
         def step(query_img, query_labels=None):
             lc = self.vae.config["latent_channels"]

@@ -179,15 +179,33 @@ class SupportBankSet:
 
     k[i] / v[i]: [nsets * nshot, tokens_i, channels_i], image = set * nshot + shot, layers as in SupportBank; the validity
     fields (hw, dtype, residual_dtype, fold_key, weights_id) and `check()` are SupportBank's.  `.bank(c)` is set c as a
-    SupportBank of zero-copy slices, so everything that takes a SupportBank takes one class of the stack."""
+    SupportBank of zero-copy slices, so everything that takes a SupportBank takes one class of the stack.
+
+    `nshot` may be a sequence of nsets counts instead: set c then holds shots[c] images, the stack sum(shots) of them
+    packed set-major (image = offsets[c] + shot), and the query pass goes through ops.fsa_attention_ragged.  `shots` (a
+    tuple) and `offsets` (its prefix sums, nsets + 1 long) are always present; `ragged` says that a sequence was given,
+    and `nshot` is then None (a sequence of equal counts is still a ragged set: it is the caller's choice of route)."""
 
     def __init__(self, k, v, nsets, nshot, hw, dtype, residual_dtype, fold_key, weights_id, layout):
         k, v = tuple(k), tuple(v)
-        if nsets < 1 or nshot < 1:
-            raise ValueError("support bank set: nsets and nshot must be >= 1")
-        # per-layer validation is SupportBank's, on the whole stack as one nsets * nshot-image bank
-        whole = SupportBank(k, v, int(nsets) * int(nshot), hw, dtype, residual_dtype, fold_key, weights_id, layout)
-        object.__setattr__(self, "_f", dict(k=k, v=v, nsets=int(nsets), nshot=int(nshot), hw=whole.hw, dtype=dtype,
+        ragged = hasattr(nshot, "__iter__")
+        if ragged:
+            shots = tuple(int(s) for s in nshot)
+            if nsets < 1 or len(shots) != nsets:
+                raise ValueError(f"support bank set: {len(shots)} shot counts for {nsets} sets")
+            if min(shots) < 1:
+                raise ValueError("support bank set: every set needs at least one image")
+        else:
+            if nsets < 1 or nshot < 1:
+                raise ValueError("support bank set: nsets and nshot must be >= 1")
+            shots = (int(nshot),) * int(nsets)
+        offsets = (0,)
+        for c in shots:
+            offsets += (offsets[-1] + c,)
+        # per-layer validation is SupportBank's, on the whole stack as one sum(shots)-image bank
+        whole = SupportBank(k, v, offsets[-1], hw, dtype, residual_dtype, fold_key, weights_id, layout)
+        object.__setattr__(self, "_f", dict(k=k, v=v, nsets=int(nsets), nshot=None if ragged else int(nshot), shots=shots,
+                                            offsets=offsets, ragged=ragged, hw=whole.hw, dtype=dtype,
                                             residual_dtype=residual_dtype, fold_key=fold_key, weights_id=weights_id,
                                             layout=tuple(layout), uid=SupportBank._next_uid[0], banks={}))
         SupportBank._next_uid[0] += 1      # one counter: a set and a bank never share a uid (captured-graph keys)
@@ -222,16 +240,16 @@ class SupportBankSet:
             raise IndexError(f"set {c} of a support bank set of {self.nsets}")
         banks = object.__getattribute__(self, "_f")["banks"]
         if c not in banks:
-            s = self.nshot
-            banks[c] = SupportBank([t[c * s:(c + 1) * s] for t in self.k], [t[c * s:(c + 1) * s] for t in self.v], s, self.hw,
+            lo, hi = self.offsets[c], self.offsets[c + 1]
+            banks[c] = SupportBank([t[lo:hi] for t in self.k], [t[lo:hi] for t in self.v], hi - lo, self.hw,
                                    self.dtype, self.residual_dtype, self.fold_key, self.weights_id, self.layout)
         return banks[c]
 
     @staticmethod
-    def stack(banks):
+    def stack(banks, ragged=False):
         """A set from existing SupportBanks (one per class, in order), by copying their K / V into one tensor per layer.
         ValueError naming the first of nshot, (h, w), dtype, residual mode, fold key, weights in which a bank differs from
-        the first."""
+        the first.  ragged=True: the banks may differ in nshot (not compared) and the result is a ragged set."""
         banks = list(banks)
         if not banks:
             raise ValueError("support bank set: stack() of no banks")
@@ -240,6 +258,8 @@ class SupportBankSet:
             for name, attr in (("nshot", "nshot"), ("latent (h, w)", "hw"), ("storage dtype", "dtype"),
                                ("residual-stream dtype", "residual_dtype"), ("fold key (timestep, prompt)", "fold_key"),
                                ("weights", "weights_id")):
+                if ragged and attr == "nshot":
+                    continue
                 if getattr(b, attr) != getattr(b0, attr):
                     raise ValueError(f"support bank set: bank {i} differs from bank 0 in {name}: {getattr(b, attr)} "
                                      f"against {getattr(b0, attr)}")
@@ -247,20 +267,22 @@ class SupportBankSet:
         k = [torch.cat([b.k[i] for b in banks], 0) for i in range(n)]
         v = [torch.cat([b.v[i] for b in banks], 0) for i in range(n)]
         layout = [tuple(t.shape[1:]) for t in b0.k]
-        return SupportBankSet(k, v, len(banks), b0.nshot, b0.hw, b0.dtype, b0.residual_dtype, b0.fold_key, b0.weights_id,
+        return SupportBankSet(k, v, len(banks), [b.nshot for b in banks] if ragged else b0.nshot, b0.hw, b0.dtype, b0.residual_dtype, b0.fold_key, b0.weights_id,
                               layout)
 
 
 class _BankIO:
     """One trunk pass' access to a SupportBank under construction (fill) or in use (read), per transformer index.
-    group > 0: the K / V are a stack of support sets and `group` consecutive batch entries read one of them."""
+    group > 0: the K / V are a stack of support sets and `group` consecutive batch entries read one of them; shots: the
+    stack is ragged, set j of it holds shots[j] images."""
 
-    def __init__(self, n, bank=None, k=None, v=None, group=0):
+    def __init__(self, n, bank=None, k=None, v=None, group=0, shots=None):
         self.fill = bank is None
         self.k = [None] * n if bank is None else (bank.k if k is None else k)
         self.v = [None] * n if bank is None else (bank.v if v is None else v)
         self.nshot = 0 if bank is None else bank.nshot
         self.group = group
+        self.shots = shots
 
 
 class _Transformer:
@@ -345,6 +367,9 @@ class _Transformer:
             kv = ops_bwd.slice_channels(qkv, C, 2 * C)
             bank_io.k[self.index], bank_io.v[self.index] = kv[..., :C], kv[..., C:]
             att = ops.fsa_attention(q, k, v, heads, q_prescaled=True)
+        elif bank_io is not None and bank_io.group and bank_io.shots is not None:
+            att = ops.fsa_attention_ragged(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], bank_io.shots,
+                                           bank_io.group, q_prescaled=True)
         elif bank_io is not None and bank_io.group:
             att = ops.fsa_attention_sets(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], bank_io.nshot,
                                          bank_io.group, q_prescaled=True)
@@ -719,16 +744,21 @@ class MyUNet2DConditionModel:
         return self._prepare(cond_ref, timestep, encoder_hidden_states, None)
 
     @torch.no_grad()
-    def prepare_bank_sets(self, cond_ref, nsets, timestep, encoder_hidden_states=None):
+    def prepare_bank_sets(self, cond_ref, nsets, timestep, encoder_hidden_states=None, shots=None):
         """ONE support pass over the nsets * s support images of nsets classes, cond_ref [nsets * s, in_channels_ref, h, w]
         set-major -> SupportBankSet.  The support pass is per-image self-attention, so this is prepare_bank's pass over a
-        larger batch with another handle around the same K/V."""
+        larger batch with another handle around the same K/V.
+        shots (nsets counts): set c has shots[c] images, cond_ref holds sum(shots) of them set-major -> a ragged set."""
         nsets = int(nsets)
-        if nsets < 1 or cond_ref.shape[0] % nsets != 0:
+        if shots is not None:
+            shots = tuple(int(s) for s in shots)
+            if nsets < 1 or len(shots) != nsets or min(shots) < 1 or sum(shots) != cond_ref.shape[0]:
+                raise ValueError(f"{cond_ref.shape[0]} support images are not {nsets} sets of {shots} images")
+        elif nsets < 1 or cond_ref.shape[0] % nsets != 0:
             raise ValueError(f"{cond_ref.shape[0]} support images do not divide into {nsets} sets")
-        return self._prepare(cond_ref, timestep, encoder_hidden_states, nsets)
+        return self._prepare(cond_ref, timestep, encoder_hidden_states, nsets, shots)
 
-    def _prepare(self, cond_ref, timestep, encoder_hidden_states, nsets):
+    def _prepare(self, cond_ref, timestep, encoder_hidden_states, nsets, shots=None):
         cfg, dt, dev = self.config, self.dtype, self.device
         x_in = cond_ref.to(device=dev, dtype=torch.float32).contiguous()
         s, Cin, h, w = x_in.shape
@@ -741,7 +771,7 @@ class MyUNet2DConditionModel:
         io = _BankIO(len(list(self._transformers())))
         self._trunk(x, tproj, ehs2d, L_ctx, 0, 1.0, kv_all, bank_io=io)     # the support pass' output is discarded (P:719)
         if nsets is not None:
-            return SupportBankSet(io.k, io.v, nsets, s // nsets, (h, w), dt, self.residual_dtype, key, self._weights_id,
+            return SupportBankSet(io.k, io.v, nsets, s // nsets if shots is None else shots, (h, w), dt, self.residual_dtype, key, self._weights_id,
                                   bank_layout(cfg, h, w))
         return SupportBank(io.k, io.v, s, (h, w), dt, self.residual_dtype, key, self._weights_id, bank_layout(cfg, h, w))
 
@@ -771,7 +801,8 @@ class MyUNet2DConditionModel:
     def forward_query_sets(self, z_tag, timestep, bankset, encoder_hidden_states=None, out_scale=1.0, sets=None):
         """N-way query pass: the b latents z_tag [b, in_channels, h, w] against the support sets `sets` (a range, default
         all) of `bankset`, in ONE trunk pass of batch n * b -- the latents repeated once per set, class-major, every attn1
-        through ops.fsa_attention_sets(group=b) on the stack's K/V sliced to those sets (views, no copy).  Entry (c, i) is
+        through ops.fsa_attention_sets(group=b) on the stack's K/V sliced to those sets (views, no copy; a ragged set:
+        ops.fsa_attention_ragged with those sets' shot counts).  Entry (c, i) is
         per image the arithmetic of forward_queries(z_tag[i:i+1], bankset.bank(sets[c])).  Returns [n, b, C, h, w] fp32."""
         cfg, dt, dev = self.config, self.dtype, self.device
         if not isinstance(bankset, SupportBankSet):
@@ -785,14 +816,15 @@ class MyUNet2DConditionModel:
             raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
         bankset.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
                       fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
-        n, s = len(sets), bankset.nshot
+        n = len(sets)
         tproj, ehs2d, kv_all, L_ctx = self._conditioning(n * b, timestep, encoder_hidden_states)
         c0 = cfg["block_out_channels"][0]
         # class-major: entry c * b + i (for b == 1 the reshape of the expansion is a stride-0 view: materialise it)
         x_in = x_in.unsqueeze(0).expand(n, *x_in.shape).reshape(n * b, *x_in.shape[1:]).contiguous()
         x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
-        lo, hi = sets.start * s, sets.stop * s
-        io = _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b)
+        lo, hi = bankset.offsets[sets.start], bankset.offsets[sets.stop]
+        io = _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b,
+                     shots=bankset.shots[sets.start:sets.stop] if bankset.ragged else None)
         out = self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
         return out.view(n, b, *out.shape[1:])
 

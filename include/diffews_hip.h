@@ -188,6 +188,20 @@ int dfw_fsa_kernel_name(const dfw_fsa_args* a, char* buf, size_t n);
  * The name is the unshared name + "+sets". */
 int dfw_fsa_attention_sets(const dfw_fsa_args* a, int32_t group, dfw_stream_t stream);
 int dfw_fsa_sets_kernel_name(const dfw_fsa_args* a, int32_t group, char* buf, size_t n);
+/* RAGGED bank sets: a sets launch whose sets hold different numbers of images.  `shots` is a HOST array of nsets counts;
+ * the stack holds the sets packed set-major, set j at images first[j] = shots[0] + ... + shots[j-1], and entries
+ * [j*group, (j+1)*group) walk [own ; image first[j] ; ... ; image first[j]+shots[j]-1].  The (first, shots) table travels by
+ * value in the kernel arguments: no device allocation, no copy, safe under stream capture (the graph keeps the values).
+ * Needs what dfw_fsa_attention_sets needs, and shots != NULL, 1 <= nsets <= 64, nsets == batch / group, every count >= 1,
+ * a->nshot == max(shots) (else DFW_EINVAL, from all three functions -- 0 bytes from the workspace query -- before any
+ * launch); the bank's descriptor extent is exactly sum(shots) images.  Both the pre-scaled and the scaling form exist.
+ * Key split: dfw_fsa_attention's rule on the longest set with the launch's summed work, clamped to 1 + min(shots) so
+ * that every split instance owns a key segment; with all counts equal it is dfw_fsa_attention_sets' plan, kernel
+ * arithmetic and result.  The workspace is a->workspace as ever, sized by dfw_fsa_ragged_workspace_bytes.
+ * The name is the sets name with "+ragged" in place of "+sets". */
+int dfw_fsa_attention_ragged(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group, dfw_stream_t stream);
+int dfw_fsa_ragged_kernel_name(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group, char* buf, size_t n);
+size_t dfw_fsa_ragged_workspace_bytes(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group);
 
 /*
  * Cross-attention over a short context (attn2 of BasicTransformerBlock; L = 2 prompt tokens at
