@@ -112,6 +112,11 @@ class InputsArgs(C.Structure):
                 ("pm1", _vp), ("pm1_bytes", _sz), ("bin", _vp), ("bin_bytes", _sz), ("lut", _vp)]
 
 
+class TilePlan(C.Structure):
+    _fields_ = [("img_h", _i32), ("img_w", _i32), ("tile_h", _i32), ("tile_w", _i32), ("ny", _i32), ("nx", _i32),
+                ("ramp", _i32), ("ys", _i32 * 64), ("xs", _i32 * 64)]
+
+
 class GemmTnArgs(C.Structure):
     _fields_ = [("A", _vp), ("B", _vp), ("out", _vp), ("workspace", _vp), ("workspace_bytes", _sz),
                 ("a_elems", _i64), ("b_elems", _i64),
@@ -256,6 +261,8 @@ SYMBOLS = {
     "dfw_seg_native": (_i32, [C.POINTER(SegNativeArgs), _vp]),
     "dfw_seg_labels_native": (_i32, [C.POINTER(SegLabelsNativeArgs), _vp]),
     "dfw_inputs_to_tensor": (_i32, [C.POINTER(InputsArgs), _vp]),
+    "dfw_tiles_cut": (_i32, [C.POINTER(TilePlan), _vp, _vp, _vp, _i32, _i32, _vp]),
+    "dfw_tiles_merge": (_i32, [C.POINTER(TilePlan), _vp, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

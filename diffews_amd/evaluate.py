@@ -189,3 +189,38 @@ def evaluate_stream(pipe, support_images, support_class_maps, class_id=None, que
         total += r["native"]["counts"].sum(0)
     iou, miou = nway_iou(total)
     return miou, iou, total
+
+
+@torch.no_grad()
+def evaluate_tiled(pipe, support, items, class_id=0, benchmark="coco", fold=0, overlap=None, ramp=None, batch=4,
+                   r_threshold=0.25, threshold=0.0, max_batch=16, captured=True):
+    """Images larger than the processing size against one prepared support, each segmented at its own resolution by
+    pipe.segment_tiled (`overlap`, `ramp`, `batch`, `max_batch`, the thresholding flags and `captured` are its arguments).
+    `items` yields (image, gt): PIL / uint8 [h, w, 3] of any size not below the tile, and a uint8 [h, w] label map (0 =
+    background, 1 + c = class c, 255 = ignored; 0 / 1 / 255 for a bank).
+
+    support a SupportBank: the counts go into the AverageMeter under `class_id` (the support set's class index); returns
+    (miou, fb_iou, meter) as evaluate_stream does for one support set.  A SupportBankSet: the counts are summed into one
+    int64 [2, N+1]; returns (miou, iou [N+1], counts) as evaluate_stream does N-way.  Single process, no sharding."""
+    from .unet import SupportBankSet
+    device = pipe.device
+    flags = dict(overlap=overlap, ramp=ramp, batch=batch, r_threshold=r_threshold, threshold=threshold, max_batch=max_batch,
+                 captured=captured)
+    if not isinstance(support, SupportBankSet):
+        meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
+        cls = torch.full((1,), int(class_id), dtype=torch.int64, device=device)
+        for image, gt in items:
+            if gt is None:
+                raise ValueError("evaluate_tiled needs items that carry a ground truth")
+            meter.update_from_counts(pipe.segment_tiled(support, image, gt, **flags)["counts"].view(1, 4), cls)
+        meter.all_reduce()
+        miou, fb_iou, _ = meter.compute_iou()
+        return float(miou), float(fb_iou), meter
+    from .metrics import nway_iou
+    total = torch.zeros(2, support.nsets + 1, dtype=torch.int64, device=device)
+    for image, gt in items:
+        if gt is None:
+            raise ValueError("evaluate_tiled needs items that carry a ground truth")
+        total += pipe.segment_tiled(support, image, gt, **flags)["counts"]
+    iou, miou = nway_iou(total)
+    return miou, iou, total

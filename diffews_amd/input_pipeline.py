@@ -21,6 +21,9 @@ with one staging buffer and one dfw_inputs_to_tensor call (three launches whatev
 batch of one.  `support_tensors` builds a support set that way, `EpisodeLoader` whole episodes, and `QueryLoader` (a stream
 of queries against one prepared support) what pipeline.segment_queries / segment_classes consume,
 `NativeTargets` included; both loaders prefetch through `_Prefetcher`.
+
+`TilePlan` is the host side of tiled segmentation (pipeline.segment_tiled): where the overlapping windows of an image larger
+than the processing size lie and how their masks are weighted in the merge (csrc/tiles.hip).
 """
 import ctypes as C
 import queue
@@ -139,6 +142,68 @@ class DeviceImageTransform:
         out = lay.run(dev, self.lut, torch.cuda.current_stream(self.device).cuda_stream, **(buffers or {}))
         out.update(layout=lay, staged=dev)
         return out
+
+
+class TilePlan:
+    """Overlapping windows that cover an image at its own resolution, and the weights of their merge (pure host: no GPU).
+
+    img_hw = (h, w); tile = (th, tw), the processing size (need not be square); overlap = the minimum overlap of
+    neighbouring windows in pixels, 0 <= overlap <= min(th, tw) // 2.  Per axis of length L with tile length S: L == S gives
+    one window at 0, otherwise n = 1 + ceil((L - S) / (S - overlap)) windows at o_i = (i * (L - S)) // (n - 1) -- the first
+    at 0, the last ending at the border, neighbours at most S - overlap apart, no padding anywhere.  L < S is a ValueError
+    (pipeline.segment_stream is the route that resizes), as are more than MAX_ORIGINS windows on an axis: the table travels
+    by value in the kernel arguments.  Windows are numbered row-major, t = iy * nx + ix, T = ny * nx.
+
+    ramp (default max(1, overlap)), 1 <= ramp <= min(th, tw) // 2: the weight of pixel (dy, dx) of a window is
+    min(dy + 1, th - dy, ramp) * min(dx + 1, tw - dx, ramp); ramp = 1 is the plain mean of the windows over a pixel."""
+    MAX_ORIGINS = 64
+
+    def __init__(self, img_hw, tile, overlap, ramp=None):
+        self.img_h, self.img_w = (int(v) for v in img_hw)
+        self.tile_h, self.tile_w = (int(tile), int(tile)) if np.isscalar(tile) else (int(v) for v in tile)
+        small = min(self.tile_h, self.tile_w)
+        if small < 1:
+            raise ValueError(f"tile must be >= 1 x 1, got {tile}")
+        self.overlap = int(overlap)
+        if not 0 <= self.overlap <= small // 2:
+            raise ValueError(f"overlap must be in 0..{small // 2} (half the tile's short side), got {overlap}")
+        self.ramp = max(1, self.overlap) if ramp is None else int(ramp)
+        if not 1 <= self.ramp <= max(1, small // 2):
+            raise ValueError(f"ramp must be in 1..{max(1, small // 2)}, got {ramp}")
+        self.ys = self.axis_origins(self.img_h, self.tile_h, self.overlap, "height")
+        self.xs = self.axis_origins(self.img_w, self.tile_w, self.overlap, "width")
+        self.ny, self.nx = len(self.ys), len(self.xs)
+        self.T = self.ny * self.nx
+
+    @classmethod
+    def axis_origins(cls, L_, S, overlap, what="axis"):
+        if L_ < S:
+            raise ValueError(f"image {what} {L_} is smaller than the tile's {S}: tiling never pads or resizes -- use "
+                             "segment_stream, the route that resizes the query to the processing size")
+        if L_ == S:
+            return [0]
+        n = 1 + -(-(L_ - S) // (S - overlap))
+        if n > cls.MAX_ORIGINS:
+            raise ValueError(f"image {what} {L_} needs {n} windows of {S} with overlap {overlap}; at most {cls.MAX_ORIGINS} "
+                             "per axis (the table travels in the kernel arguments)")
+        return [(i * (L_ - S)) // (n - 1) for i in range(n)]
+
+    def origin(self, t):
+        """(y, x) of window t's first pixel."""
+        return self.ys[t // self.nx], self.xs[t % self.nx]
+
+    def window_bytes(self, nclass=1):
+        """Bytes of the [N, T, 3, th, tw] buffer segment_tiled keeps the windows' seg_u8 in: 3 * th * tw per window and class."""
+        return 3 * self.tile_h * self.tile_w * self.T * int(nclass)
+
+    def c_struct(self):
+        """The dfw_tile_plan of this plan (a fresh ctypes record)."""
+        p = L.TilePlan()
+        p.img_h, p.img_w, p.tile_h, p.tile_w = self.img_h, self.img_w, self.tile_h, self.tile_w
+        p.ny, p.nx, p.ramp = self.ny, self.nx, self.ramp
+        p.ys[:self.ny] = self.ys
+        p.xs[:self.nx] = self.xs
+        return p
 
 
 class InputBatch:

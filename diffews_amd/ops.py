@@ -729,3 +729,49 @@ def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_ma
         per = u8[:N * targets.u8_bytes].view(N, targets.u8_bytes)
         planes = [per[:, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w)) for it in targets.items]
     return dict(labels=lab, counts=counts, mx=mx, seg_u8=planes, sizes=list(targets.sizes))
+
+
+def _tile_plan(plan):
+    """input_pipeline.TilePlan (or a ready _lib.TilePlan record) -> the record, its T."""
+    c = plan if isinstance(plan, L.TilePlan) else plan.c_struct()
+    return c, c.ny * c.nx
+
+
+def tiles_cut(plan, img_u8, lut, first=0, count=None, out=None):
+    """Windows first .. first + count - 1 (default: all from `first`) of a staged image: img_u8 uint8 [h, w, 3] on the
+    device, plan an input_pipeline.TilePlan for (h, w), lut the 256-entry fp32 table of DeviceImageTransform -> fp32
+    [count, 3, th, tw], each window bit for bit DeviceImageTransform((th, tw)).image(crop).  One launch; `out`: a
+    caller-owned contiguous fp32 [count, 3, th, tw] instead of a fresh one."""
+    c, T = _tile_plan(plan)
+    assert img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and tuple(img_u8.shape) == (c.img_h, c.img_w, 3)
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and lut.numel() == 256 and lut.device == img_u8.device
+    if count is None:
+        count = T - first
+    shape = (count, 3, c.tile_h, c.tile_w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=img_u8.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == img_u8.device
+    L.check(L.lib().dfw_tiles_cut(C.byref(c), img_u8.data_ptr(), lut.data_ptr(), out.data_ptr(), int(first), int(count),
+                                  _stream()), "dfw_tiles_cut")
+    return out
+
+
+def tiles_merge(plan, win, out=None, mx=None):
+    """Blend the windows' masks back into the image: win uint8 [N, T, 3, th, tw] (the seg_u8 of every window and class) ->
+    (uint8 [N, 3, h, w], mx int32 [N] = the maximum byte of each class' merged image).  Per byte the weighted mean of the
+    windows over it in integers, round half up (csrc/tiles.hip); exact and independent of any order; one window is the
+    identity.  out.view(N, 1, 3, h, w) and mx are seg_labels' inputs.  Two launches; `out` / `mx`: caller-owned buffers."""
+    c, T = _tile_plan(plan)
+    assert win.dtype == torch.uint8 and win.is_contiguous() and win.dim() == 5
+    N = win.shape[0]
+    assert tuple(win.shape) == (N, T, 3, c.tile_h, c.tile_w)
+    if out is None:
+        out = torch.empty(N, 3, c.img_h, c.img_w, dtype=torch.uint8, device=win.device)
+    if mx is None:
+        mx = torch.empty(N, dtype=torch.int32, device=win.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (N, 3, c.img_h, c.img_w)
+    assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == N
+    assert out.device == win.device and mx.device == win.device
+    L.check(L.lib().dfw_tiles_merge(C.byref(c), win.data_ptr(), N, out.data_ptr(), mx.data_ptr(), _stream()),
+            "dfw_tiles_merge")
+    return out, mx

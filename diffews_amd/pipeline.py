@@ -596,6 +596,81 @@ class MarigoldPipelineRGBLatentNoise:
                 r = self.segment_queries(support, bt["query_img"], bt.get("query_mask"), native=bt["native"], **flags)
             yield bt["index"], r
 
+    @torch.no_grad()
+    def segment_tiled(self, support, image, gt=None, overlap=None, ramp=None, batch=4, r_threshold=0.25, threshold=0.0,
+                      max_batch=16, captured=None):
+        """One image LARGER than the processing size, segmented at its own resolution: `image` (PIL / uint8 [h, w, 3]) is
+        covered with overlapping windows of the size `support` was prepared at (input_pipeline.TilePlan: `overlap`, default
+        min(tile) // 8, and `ramp`), every window is one query of segment_queries (`support` a SupportBank) or
+        segment_classes (a SupportBankSet, uniform or ragged, with `max_batch`), the windows' seg_u8 are blended back into
+        one image (ops.tiles_merge) and that image is thresholded ONCE by ops.seg_labels: the dynamic threshold uses the
+        merged image's maximum per class, so a window without the object cannot turn its noise into foreground.
+
+        The image (and `gt`, optional uint8 [h, w]: 0 = background, 1 + c = class c, 255 = ignored; 0 / 1 / 255 for a bank)
+        goes through one pinned buffer and one H2D copy.  Windows are cut on the device (ops.tiles_cut) and run in batches
+        of `batch`, the last one padded by repeating the image's last window, so ONE captured graph serves the whole image;
+        each batch's seg_u8 is copied on the same stream into its slice of one uint8 [N, T, 3, th, tw] buffer (3 * th * tw
+        bytes per window and class) before the next call overwrites it, the padding never.  Cut, merge and labels run
+        eagerly (their sizes vary per image) and are part of no graph.
+
+        Returns dict(seg_u8 uint8 [N, 3, h, w], labels uint8 [h, w], counts, mx int32 [N], plan); N = 1 for a bank, where
+        `pred` is an alias of `labels` and counts is int64 [4] in seg_postprocess' order (inter0, inter1, union0, union1);
+        for a set counts is int64 [2, N+1] (metrics.nway_iou); counts is None without gt.  There is no batch_max: the
+        merged image has one maximum per class.  Scheduler restriction, stale-handle errors and `captured` as in the
+        routed calls; an image smaller than the tile in either axis is a ValueError (segment_stream resizes)."""
+        from .input_pipeline import DeviceImageTransform, TilePlan
+        from .unet import SupportBank, SupportBankSet
+        if not isinstance(support, (SupportBank, SupportBankSet)):
+            raise TypeError("support must be a SupportBank (prepare_support) or a SupportBankSet (prepare_support_classes)")
+        nway = isinstance(support, SupportBankSet)
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"batch must be >= 1, got {batch}")
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        th, tw = support.hw[0] * f, support.hw[1] * f
+        img = DeviceImageTransform.as_rgb_bytes(image)
+        h, w = img.shape[:2]
+        plan = TilePlan((h, w), (th, tw), min(th, tw) // 8 if overlap is None else overlap, ramp)
+        if gt is not None:
+            gt = np.ascontiguousarray(gt.cpu().numpy() if torch.is_tensor(gt) else gt)
+            if gt.dtype != np.uint8 or gt.shape != (h, w):
+                raise ValueError(f"gt must be a uint8 label map [{h}, {w}], got {gt.dtype} {gt.shape}")
+        dev = self.device
+        n_img = 3 * h * w
+        host = torch.empty(n_img + (h * w if gt is not None else 0), dtype=torch.uint8, pin_memory=True)
+        host[:n_img].view(h, w, 3).numpy()[...] = img
+        if gt is not None:
+            host[n_img:].view(h, w).numpy()[...] = gt
+        staged = host.to(dev, non_blocking=True)                               # the one H2D copy
+        img_dev = staged[:n_img].view(h, w, 3)
+        gt_dev = staged[n_img:].view(1, h, w) if gt is not None else None
+        tf = getattr(self, "_tile_tf", None)
+        if tf is None or (tf.out_h, tf.out_w) != (th, tw) or tf.device != torch.device(staged.device):
+            tf = self._tile_tf = DeviceImageTransform((th, tw), staged.device)  # owns the ToTensor + Normalize table
+        N, T = (support.nsets if nway else 1), plan.T
+        cplan = plan.c_struct()
+        win = torch.empty(N, T, 3, th, tw, dtype=torch.uint8, device=staged.device)
+        q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
+        for first in range(0, T, batch):
+            count = min(batch, T - first)
+            ops.tiles_cut(cplan, img_dev, tf.lut, first, count, out=q[:count])
+            if count < batch:
+                q[count:] = q[count - 1]                                      # padding: the last window again
+            if nway:
+                r = self.segment_classes(support, q, None, r_threshold=r_threshold, threshold=threshold,
+                                         max_batch=max_batch, captured=captured)
+                win[:, first:first + count].copy_(r["seg_u8"][:, :count])
+            else:
+                r = self.segment_queries(support, q, None, r_threshold=r_threshold, threshold=threshold, captured=captured)
+                win[0, first:first + count].copy_(r["seg_u8"][:count])
+        seg_u8, mx = ops.tiles_merge(cplan, win)
+        labels, counts = ops.seg_labels(seg_u8.view(N, 1, 3, h, w), mx, gt_dev, r_threshold, threshold, False)
+        out = dict(seg_u8=seg_u8, labels=labels[0], mx=mx, plan=plan,
+                   counts=None if counts is None else (counts[0] if nway else counts.view(4)))
+        if not nway:
+            out["pred"] = out["labels"]
+        return out
+
     @staticmethod
     def _with_native_labels(r, native, flags, class_ids):
         """_with_native for segment_classes: r plus r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags)."""

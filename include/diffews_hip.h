@@ -559,6 +559,46 @@ typedef struct {
  * extent that leaves its buffer -> DFW_EWORKSPACE.  Regions of different items must not overlap (not checked). */
 int dfw_inputs_to_tensor(const dfw_inputs_args* a, dfw_stream_t stream);
 
+/*
+ * Tiled segmentation (version >= 108): an image larger than the processing size is covered with overlapping
+ * tile_h x tile_w windows, each window is one query of the existing routes, and the windows' quantised masks are blended
+ * back into one image that is thresholded ONCE (its maximum is the merged image's, not a window's).
+ *
+ * The window plan is a plain struct the host fills; both entry points read it from HOST memory, validate it and hand it
+ * BY VALUE to their kernels (no device allocation, no copy; a capture keeps the values).  Per axis: n origins in
+ * 1..DFW_TILE_MAX_ORIGINS, strictly ascending, the first 0, the last = image - tile, neighbours at most a tile apart (no
+ * pixel uncovered, no padding).  Windows are numbered row-major, t = iy * nx + ix, T = ny * nx.  The blend weight of pixel
+ * (dy, dx) of a window is min(dy + 1, tile_h - dy, ramp) * min(dx + 1, tile_w - dx, ramp), 1 <= ramp <=
+ * max(1, min(tile_h, tile_w) / 2); ramp = 1 is the plain mean.
+ */
+enum { DFW_TILE_MAX_ORIGINS = 64 };
+typedef struct {
+  int32_t img_h, img_w;                /* size of the image */
+  int32_t tile_h, tile_w;              /* size of a window: the processing size */
+  int32_t ny, nx;                      /* windows per axis */
+  int32_t ramp;
+  int32_t ys[64], xs[64];              /* first row / column of the windows of each axis; entries beyond ny / nx unused */
+} dfw_tile_plan;
+
+/* Windows first .. first + count - 1 of the staged image img (device, uint8 [img_h][img_w][3]) -> out (device, planar fp32
+ * [count][3][tile_h][tile_w]) through lut (device, 256 floats: byte v after ToTensor + Normalize, as dfw_inputs_args.lut).
+ * One launch.  A window is bit for bit what the input transform returns for the same crop at the same size. */
+int dfw_tiles_cut(const dfw_tile_plan* plan, const uint8_t* img, const float* lut, float* out, int32_t first,
+                  int32_t count, dfw_stream_t stream);
+
+/* win (device, uint8 [N][T][3][tile_h][tile_w]: the seg_u8 of every window and class) -> out (device, uint8
+ * [N][3][img_h][img_w]) and mx (device, [N]: the maximum byte of each class' merged image).  Per output byte, over the
+ * windows that cover it, A = sum w * u and W = sum w in integers and the byte is (2 A + W) / (2 W) (round half up); a
+ * gather without float operations or atomics on the image, so the result depends on no order; one window is the
+ * identity.  Two launches: mx zeroed by a library kernel (no memset node), then the merge with one atomicMax per
+ * workgroup.  out viewed as [N][1][3][img_h][img_w] and mx are what dfw_seg_labels takes with B = 1.
+ *
+ * Both validate on the host before the first launch: a null pointer, a plan that breaks a rule above, first / count
+ * outside 0..T, N outside 1..254 -> DFW_EINVAL; img_h above 65535 (merge), or a plan whose sums are not proven to fit 32
+ * bits, 511 * (most windows over a row) * (most windows over a column) * ramp^2 >= 2^32 (merge) -> DFW_ERANGE. */
+int dfw_tiles_merge(const dfw_tile_plan* plan, const uint8_t* win, int32_t N, uint8_t* out, uint32_t* mx,
+                    dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
