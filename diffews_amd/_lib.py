@@ -203,6 +203,9 @@ SYMBOLS = {
     "dfw_fsa_attention_ragged": (_i32, [C.POINTER(FsaArgs), C.POINTER(_i32), _i32, _i32, _vp]),
     "dfw_fsa_ragged_kernel_name": (_i32, [C.POINTER(FsaArgs), C.POINTER(_i32), _i32, _i32, C.c_char_p, _sz]),
     "dfw_fsa_ragged_workspace_bytes": (_sz, [C.POINTER(FsaArgs), C.POINTER(_i32), _i32, _i32]),
+    "dfw_fsa_attention_routed": (_i32, [C.POINTER(FsaArgs), _vp, C.POINTER(_i32), _i32, _i32, _vp]),
+    "dfw_fsa_routed_kernel_name": (_i32, [C.POINTER(FsaArgs), _i32, _i32, C.c_char_p, _sz]),
+    "dfw_fsa_routed_workspace_bytes": (_sz, [C.POINTER(FsaArgs), _i32, _i32]),
     "dfw_cross_attention": (_i32, [C.POINTER(XattnArgs), _vp]),
     "dfw_vae_attention": (_i32, [C.POINTER(VattnArgs), _vp]),
     "dfw_groupnorm": (_i32, [C.POINTER(GroupNormArgs), _vp]),

@@ -9,6 +9,8 @@
 // -- bank image = (entry/group)*nshot + shot (FsaP::bank_div); the class-major batch of an N-way query pass.
 // Ragged bank sets (dfw_fsa_attention_ragged): the same with a shot count of its own per set, sets packed set-major
 // -- bank image = first[entry/group] + shot, shot < shots[entry/group]; the table rides in the kernel arguments (FsaPR).
+// Routed queries (dfw_fsa_attention_routed): entry e walks images [first_e, first_e + shots_e) of a stack, and the pair is
+// row e of a DEVICE table read when the kernel runs (FsaPT) -- a captured launch serves every route.
 //
 // Workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 query rows.
 // Per 64-key tile (K and V tiles double-buffered in LDS, register-staged issue-early/write-late):
@@ -59,6 +61,13 @@ struct FsaPR : FsaP {
   int shots[kFsaMaxSets];
 };
 
+// Routed launch: FsaP plus a pointer to the device table int32 [batch][2], row e = (first image, shots) of entry e.  Only
+// the pointer is baked into a captured launch; the rows are read at run time.  FsaP::nshot is the largest count a row may
+// hold (it sizes the plan, never a loop).
+struct FsaPT : FsaP {
+  const int* table;
+};
+
 // ------------------------------------------------------------------------------------------------
 // v2: same mathematics and register layout as fsa_kernel, different data movement:
 //   * NW = 8 (or 4) waves share every K/V tile: 256 (128) query rows per workgroup;
@@ -72,9 +81,12 @@ struct FsaPR : FsaP {
 // the reference the softmax is max3 + exp2 + add + cvt per element pair -- no fma, no subtract.
 // RAG: the ragged sets launch -- p is an FsaPR, and the workgroup's set gives its first bank image and its shot count
 // (two scalar loads from the kernel arguments, once per workgroup) where the other forms derive them from p.nshot.
-template <typename T, int NW, int QB, bool PRE, bool RAG = false>
+// RT: the routed launch -- p is an FsaPT, and the same two values are row `entry` of p.table in device memory (two loads at
+// a workgroup-uniform address, once per workgroup).  RAG and RT exclude each other.
+template <typename T, int NW, int QB, bool PRE, bool RAG = false, bool RT = false>
 __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 ? 2 : 4) * NW / 8 : 1) void fsa_ring_kernel(
-    const std::conditional_t<RAG, FsaPR, FsaP> p) {
+    const std::conditional_t<RT, FsaPT, std::conditional_t<RAG, FsaPR, FsaP>> p) {
+  static_assert(!(RAG && RT), "one table form per launch");
   // QB = 32-row query blocks per wave: with QB = 2 the two blocks are independent dependency chains
   // in one instruction stream, so one block's softmax VALU work overlaps the other's MFMAs, and
   // every K / V fragment read from LDS feeds two MFMAs.
@@ -125,6 +137,10 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 ? 2 : 4) * NW / 8 > 0 ? (QB == 2 
     const int set = __builtin_amdgcn_readfirstlane(bank_b / p.bank_div);
     bank_img0 = p.first[set];
     nshot = p.shots[set];
+  } else if constexpr (RT) {                 // n_plain == 0: bank_b is the entry, 0 <= bank_b < batch = rows of the table
+    const int* row = p.table + 2 * (size_t)__builtin_amdgcn_readfirstlane(bank_b);
+    bank_img0 = __builtin_amdgcn_readfirstlane(row[0]);
+    nshot = __builtin_amdgcn_readfirstlane(row[1]);
   } else {
     bank_img0 = (p.bank_div > 1 ? bank_b / p.bank_div : bank_b) * p.bank_stride;
     nshot = p.nshot;
@@ -686,7 +702,42 @@ extern "C" int dfw_fsa_ragged_kernel_name(const dfw_fsa_args* a, const int32_t* 
   return 0;
 }
 
-static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots = nullptr);
+// Routed queries: a query-only launch whose entry e reads images [first_e, first_e + shots_e) of a stack of nbank images,
+// (first_e, shots_e) = row e of a device table.  The plan sees a, nbank and min_shots only -- never the table -- so one
+// captured launch serves every route: a->nshot is the largest count a row may hold, min_shots the smallest.
+static int fsa_check_routed(const dfw_fsa_args* a, int32_t nbank, int32_t min_shots) {
+  const int rc = fsa_check_args(a);
+  if (rc) return rc;
+  if (a->n_plain != 0 || a->bank_shared != 0 || a->nshot <= 0) return DFW_EINVAL;
+  if (nbank < 1 || min_shots < 1 || min_shots > a->nshot) return DFW_EINVAL;
+  return 0;
+}
+
+// fsa_split_count's rule as if every entry held the longest set, clamped like the ragged launch so that every split
+// instance of the shortest set a row may name still owns a key segment.
+static int fsa_routed_split_count(const dfw_fsa_args* a, int min_shots) {
+  const int ns = fsa_split_rule(a, (long long)a->batch * (1 + a->nshot));
+  return ns > 1 + min_shots ? 1 + min_shots : ns;
+}
+
+extern "C" size_t dfw_fsa_routed_workspace_bytes(const dfw_fsa_args* a, int32_t nbank, int32_t min_shots) {
+  if (fsa_check_routed(a, nbank, min_shots)) return 0;
+  return fsa_split_bytes(a, fsa_routed_split_count(a, min_shots));
+}
+
+extern "C" int dfw_fsa_routed_kernel_name(const dfw_fsa_args* a, int32_t nbank, int32_t min_shots, char* buf, size_t n) {
+  int rc = fsa_check_routed(a, nbank, min_shots);
+  if (rc) return rc;
+  rc = fsa_name(a, fsa_plan_of(a, fsa_routed_split_count(a, min_shots)), buf, n);
+  if (rc) return rc;
+  const size_t at = strlen(buf);
+  if (at < n) snprintf(buf + at, n - at, "+routed");
+  return 0;
+}
+
+struct FsaRoute { const int32_t* table; int nbank, min_shots; };
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots = nullptr,
+                      const FsaRoute* route = nullptr);
 
 extern "C" int dfw_fsa_attention(const dfw_fsa_args* a, dfw_stream_t stream) {
   const int rc = fsa_check_args(a);
@@ -707,8 +758,33 @@ extern "C" int dfw_fsa_attention_ragged(const dfw_fsa_args* a, const int32_t* sh
   return fsa_launch(a, group, stream, shots);
 }
 
-// `a` has passed fsa_check_args, and fsa_check_sets unless group == 1; shots: a ragged launch, past fsa_check_ragged
-static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots) {
+extern "C" int dfw_fsa_attention_routed(const dfw_fsa_args* a, const int32_t* table, const int32_t* table_host, int32_t nbank,
+                                       int32_t min_shots, dfw_stream_t stream) {
+  const int rc = fsa_check_routed(a, nbank, min_shots);
+  if (rc) return rc;
+  if (!table || !table_host) return DFW_EINVAL;
+  for (int e = 0; e < a->batch; ++e) {       // the host mirror of the rows this launch will read
+    const int32_t first = table_host[2 * e], n = table_host[2 * e + 1];
+    if (first < 0 || n < min_shots || n > a->nshot || (long long)first + n > nbank) return DFW_EINVAL;
+  }
+  const FsaRoute route = {table, nbank, min_shots};
+  return fsa_launch(a, 1, stream, nullptr, &route);
+}
+
+template <bool PRE>
+static void fsa_launch_routed(bool bf, int nw, dim3 grid, hipStream_t st, const FsaPT& pt) {
+  if (nw == 8) {
+    if (bf) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, PRE, false, true>), grid, dim3(512), 0, st, pt);
+    else hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 8, 1, PRE, false, true>), grid, dim3(512), 0, st, pt);
+  } else {
+    if (bf) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 4, 1, PRE, false, true>), grid, dim3(256), 0, st, pt);
+    else hipLaunchKernelGGL((fsa_ring_kernel<_Float16, 4, 1, PRE, false, true>), grid, dim3(256), 0, st, pt);
+  }
+}
+
+// `a` has passed fsa_check_args, and fsa_check_sets unless group == 1; shots: a ragged launch, past fsa_check_ragged;
+// route: a routed launch, past fsa_check_routed (group == 1, no shots)
+static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, const int32_t* shots, const FsaRoute* route) {
   FsaPR pr;
   FsaP& p = pr;
   const int nsets = shots ? a->batch / group : 0;
@@ -727,7 +803,7 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, con
   if (a->nshot > 0) {
     // bank images; a shared bank holds nshot of them however many entries read it (the descriptor must not claim more)
     // and `group` entries share a set of a sets launch (n_plain == 0 there)
-    const int nb = shots ? nimg : a->bank_shared ? a->nshot : (a->batch - a->n_plain) / group * a->nshot;
+    const int nb = route ? route->nbank : shots ? nimg : a->bank_shared ? a->nshot : (a->batch - a->n_plain) / group * a->nshot;
     if (nb > 0) {
       kbe = extent(nb, a->kb_bs, a->n_bank, a->ldkb, a->heads);
       vbe = extent(nb, a->vb_bs, a->n_bank, a->ldvb, a->heads);
@@ -746,7 +822,9 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, con
   p.pre = a->q_prescaled ? 1 : 0;
   p.lse = a->lse;
   // key split: only with a caller-provided workspace of dfw_fsa_workspace_bytes(); without one the launch is unsplit
-  const FsaPlan pl = shots ? fsa_plan_of(a, fsa_ragged_split_count(a, shots, nsets, group)) : fsa_plan(a);
+  const FsaPlan pl = route   ? fsa_plan_of(a, fsa_routed_split_count(a, route->min_shots))
+                     : shots ? fsa_plan_of(a, fsa_ragged_split_count(a, shots, nsets, group))
+                             : fsa_plan(a);
   p.nsplit = pl.nsplit;
   p.part = pl.nsplit > 1 ? (float*)a->workspace : nullptr;
   p.bank_stride = a->bank_shared ? 0 : a->nshot;
@@ -758,7 +836,13 @@ static int fsa_launch(const dfw_fsa_args* a, int group, dfw_stream_t stream, con
     const int nw = pl.nw;
     dim3 grid((a->n_q + nw * 32 - 1) / (nw * 32), a->heads, grid_z);
     const bool pre = a->q_prescaled != 0;
-    if (shots) {
+    if (route) {
+      FsaPT pt;
+      static_cast<FsaP&>(pt) = p;
+      pt.table = (const int*)route->table;
+      if (pre) fsa_launch_routed<true>(bf, nw, grid, st, pt);
+      else fsa_launch_routed<false>(bf, nw, grid, st, pt);
+    } else if (shots) {
       if (nw == 8) {
         if (bf) { if (pre) hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, true, true>), grid, dim3(512), 0, st, pr);
                   else hipLaunchKernelGGL((fsa_ring_kernel<__bf16, 8, 1, false, true>), grid, dim3(512), 0, st, pr); }

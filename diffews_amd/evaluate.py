@@ -192,6 +192,37 @@ def evaluate_stream(pipe, support_images, support_class_maps, class_id=None, que
 
 
 @torch.no_grad()
+def evaluate_routed(pipe, bankset, queries, class_of_set, gt_ids=None, benchmark="coco", fold=0, route="route", batch=4,
+                    size=None, depth=2, r_threshold=0.25, threshold=0.0, batch_max=False, captured=True, ignore_value=-1):
+    """The reference's class-wise protocol over a FIXED library of classes: `bankset` holds the prepared support sets
+    (pipe.prepare_support_classes, uniform or ragged), `queries` yields dicts with `query_img`, `gt` (a class-id map at
+    the image's own size) and the index of the one set the query is scored against (`route`: a key name or a callable on
+    the dict) -- evaluation_util/main_oss.py's episodes, whose class changes from one to the next, without preparing a
+    support set twice.  Every batch runs through pipe.segment_stream(route=...) / segment_routed, and its native-size
+    binary counts go into the AverageMeter under class_of_set[route_i] (the benchmark's class index of set route_i).
+    gt_ids[c]: the id class c's pixels carry in `gt`; default class_of_set[c] + 1, as coco.py:74-75 stores them.
+    Returns (miou, fb_iou, meter) like evaluate_support_set; single process, no sharding."""
+    device = pipe.device
+    cls_of = [int(c) for c in class_of_set]
+    if len(cls_of) != bankset.nsets:
+        raise ValueError(f"class_of_set names {len(cls_of)} classes, the support bank set holds {bankset.nsets}")
+    ids = [c + 1 for c in cls_of] if gt_ids is None else [int(c) for c in gt_ids]
+    if len(ids) != bankset.nsets:
+        raise ValueError(f"{len(ids)} gt_ids for a support bank set of {bankset.nsets}")
+    meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
+    for index, r in pipe.segment_stream(bankset, queries, batch=batch, size=size, depth=depth, class_ids=ids,
+                                        ignore_value=ignore_value, r_threshold=r_threshold, threshold=threshold,
+                                        batch_max=batch_max, captured=captured, route=route):
+        if r["native"]["counts"] is None:
+            raise ValueError("evaluate_routed needs queries that carry `gt`")
+        cls = torch.tensor([cls_of[c] for c in r["route"]], dtype=torch.int64, device=device)
+        meter.update_from_counts(r["native"]["counts"], cls)
+    meter.all_reduce()
+    miou, fb_iou, _ = meter.compute_iou()
+    return float(miou), float(fb_iou), meter
+
+
+@torch.no_grad()
 def evaluate_tiled(pipe, support, items, class_id=0, benchmark="coco", fold=0, overlap=None, ramp=None, batch=4,
                    r_threshold=0.25, threshold=0.0, max_batch=16, captured=True):
     """Images larger than the processing size against one prepared support, each segmented at its own resolution by

@@ -658,12 +658,15 @@ class QueryLoader(_Prefetcher):
         query_mask (only with class_value and gt) uint8 [b, out_h, out_w]: gt == class value, nearest-resized, so
                    r["counts"] at the processing size works too
         index      positions of the batch's queries in the stream (list of int)
+        route      (only with `route`) the set index of each of the batch's queries (list of int), for
+                   pipeline.segment_routed
     class_value: one int, or a callable on the query dict.
+    route: a callable on the query dict that gives the index of the support set the query goes to.
     """
 
-    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1):
+    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1, route=None):
         super().__init__(queries, size, batch, device, depth)
-        self.class_value, self.ignore_value = class_value, int(ignore_value)
+        self.class_value, self.ignore_value, self.route = class_value, int(ignore_value), route
 
     def layout(self, qs):
         """(InputBatch, per-query class values, has_gt) of one batch of query dicts: the images, then the ground-truth
@@ -702,4 +705,6 @@ class QueryLoader(_Prefetcher):
         out = dict(query_img=r["images"], native=self._native(lay, ctx, staged, self.device), index=list(index))
         if r["bin"] is not None:
             out["query_mask"] = r["bin"]
+        if self.route is not None:
+            out["route"] = [int(self.route(q)) for q in qs]
         return out

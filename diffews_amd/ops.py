@@ -302,6 +302,60 @@ def fsa_attention_ragged(q, k, v, heads, k_bank, v_bank, shots, group, scale=Non
                          lse=lse, key_split=key_split, _group=int(group), _shots=shots)
 
 
+def _fsa_routed_call(a, table, table_host, nbank, min_shots):
+    L.check(L.lib().dfw_fsa_attention_routed(C.byref(a), table, table_host, nbank, min_shots, _stream()),
+            "dfw_fsa_attention_routed")
+
+
+def fsa_attention_routed(q, k, v, heads, k_bank, v_bank, table, table_host, max_shots, min_shots, q_prescaled=False,
+                         key_split=True, out=None):
+    """KV-fusion self-attention of a batch in which every entry reads a support set of its own out of a STACK of bank
+    images: q/k/v [B, N, heads*64], k_bank/v_bank [nbank, Nb, heads*64], `table` a DEVICE int32 [B, 2] tensor whose row e =
+    (first image, shots) of entry e -- entry e attends over [own ; images first_e .. first_e + shots_e - 1].  The kernel
+    reads the table when it runs: under stream capture one graph serves every table written into the same tensor.
+    `table_host` is its int32 host mirror, validated by the library before the launch (every count within
+    [min_shots, max_shots], every set inside the stack).  The launch plan and workspace depend on the shapes, max_shots
+    and min_shots only; the key split never exceeds 1 + min_shots.  Per entry the kernel arithmetic, key order and tile
+    sequence of fsa_attention on that set's slice with bank_shared=True."""
+    B, N, Cq = q.shape
+    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    for name, t in (("table", table), ("table_host", table_host)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, 2) or not t.is_contiguous():
+            raise ValueError(f"fsa_attention_routed: {name} must be a contiguous int32 [{B}, 2] tensor")
+    if not table.is_cuda or table.device != q.device or table_host.device.type != "cpu":
+        raise ValueError("fsa_attention_routed: table lives with q on the device, table_host on the host")
+    if out is None:
+        out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
+    assert out.shape == (B, N, Cq) and out.stride(2) == 1 and out.stride(1) == Cq
+    assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1 and k_bank.dtype == q.dtype and v_bank.shape == k_bank.shape
+    a = L.FsaArgs()
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.batch, a.heads, a.n_q, a.n_kv = B, heads, N, k.shape[1]
+    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
+    a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
+    a.n_bank, a.nshot = k_bank.shape[1], int(max_shots)
+    a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
+    a.scale = 64 ** -0.5
+    a.dtype, a.q_prescaled = _dt(q), int(bool(q_prescaled))
+    nbank, min_shots = int(k_bank.shape[0]), int(min_shots)
+    nbytes = L.lib().dfw_fsa_routed_workspace_bytes(C.byref(a), nbank, min_shots) if key_split else 0
+    if nbytes:
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    host = C.cast(table_host.data_ptr(), C.POINTER(C.c_int32))
+    if gemm_hook is not None:   # bench.py roofline leg: QK^T + PV flops of this launch
+        keys = B * k.shape[1] + int(table_host[:, 1].sum()) * k_bank.shape[1]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots)
+        e1.record()
+        gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
+        return out
+    _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots)
+    return out
+
+
 def zeros(shape, dtype, device="cuda"):
     """torch.zeros whose fill is a library kernel (capture-safe: no memset node).  Sizes are padded to 16 bytes."""
     n = 1

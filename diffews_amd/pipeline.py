@@ -554,8 +554,73 @@ class MarigoldPipelineRGBLatentNoise:
                 del self._graphs[k]
         return self._with_native_labels(self._replay(key, step, ins), native, flags, class_ids)
 
+    # ------------------------------------------------------------------ routed queries: one class of a stack per query
+    @torch.no_grad()
+    def segment_routed(self, bankset, query_img, route, query_gt=None, r_threshold=0.25, threshold=0.0, batch_max=False,
+                       captured=None, native=None):
+        """One denoising step for b query images, EACH against one class of `bankset` (prepare_support_classes, uniform or
+        ragged): query_img [b, 3, H, W] in [-1, 1], `route` b set indices (any order, repeats allowed, sets may go
+        unused), query_gt optional uint8 [b, H, W].  Returns segment_queries' dict (z0, dec, seg_u8, counts): entry i is,
+        per image, what segment_queries(bankset.bank(route[i]), query_img[i:i+1]) computes -- in one pass of batch b
+        whose every attn1 reads the stack in place through a device table of (first image, shots) rows
+        (unet.forward_query_routed, ops.fsa_attention_routed), where segment_classes would run all N classes per query.
+
+        Scheduler restriction, stale-handle ValueErrors and `native` as in segment_queries; ValueError for a route that is
+        not b long or names a set outside the stack.
+
+        captured (default: self.use_graph): the route table is one of the step's static inputs -- every call copies it
+        from a pinned host tensor into the graph's buffer and the kernels read it when they run -- so the graph key
+        holds the set's uid, the shapes and the flags but NOT the route: one graph serves every route of that shape.  It
+        counts against MAX_QUERY_GRAPHS like the other query steps.  A replay runs no library-side validation of the
+        table; it needs none, because SupportBankSet.route_table builds every row from the set's own offsets."""
+        from .unet import SupportBankSet
+        if not isinstance(bankset, SupportBankSet):
+            raise ValueError("segment_routed needs a SupportBankSet (prepare_support_classes)")
+        t, tt = self._single_step_timestep()
+        if not self.scheduler.z0_is_neg_v(t):
+            raise NotImplementedError("segment_routed needs the one-step scheduler with z0 = -v (the reference's setting)")
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        prompt = None if folded else self.encode_clip_feature()
+        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
+                   query_gt=None if query_gt is None else query_gt.to(dev).contiguous())
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        b, _, H, W = ins["query_img"].shape
+        table_host = bankset.route_table(route)          # ValueError: empty, or a set outside the stack
+        if table_host.shape[0] != b:
+            raise ValueError(f"a route of {table_host.shape[0]} entries for {b} queries")
+        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
+                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        flags = (float(r_threshold), float(threshold), bool(batch_max))
+        table_host = table_host.pin_memory()
+
+        def step(query_img, table, query_gt=None):
+            lc = self.vae.config["latent_channels"]
+            mom = self.vae.encoder(query_img)
+            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
+            # table_host mirrors `table` whenever this runs (eagerly, or while a graph is warmed up and captured)
+            z0 = self.unet.forward_query_routed(z_tag, tt, bankset, table, table_host, prompt, out_scale=-1.0)
+            dec = self.decode_seg(z0)
+            seg_u8, counts = ops.seg_postprocess(dec, query_gt, *flags)
+            return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
+        if captured is None:
+            captured = self.use_graph
+        if not captured:
+            return self._with_native(step(table=table_host.to(dev, non_blocking=True), **ins), native, flags)
+        ins["table"] = table_host        # _replay: a device buffer at capture, one H2D copy into it per call
+        key = ("queries", "routed", bankset.uid, tuple(ins["query_img"].shape), query_gt is not None, flags, float(tt),
+               folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
+        if key in self._graphs:
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        else:
+            mine = [k for k in self._graphs if k[0] == "queries"]
+            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
+                del self._graphs[k]
+        return self._with_native(self._replay(key, step, ins), native, flags)
+
     def segment_stream(self, support, queries, batch=4, size=None, depth=2, class_value=None, ignore_value=-1,
-                       class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None):
+                       class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None,
+                       route=None):
         """Generator: a stream of decoded images against one prepared support -- `support` a SupportBank (prepare_support;
         routed to segment_queries) or a SupportBankSet (prepare_support_classes; routed to segment_classes, with
         `class_ids` and `max_batch`).  `queries` yields dicts with `query_img` (PIL / uint8 [H, W, 3], any size) and
@@ -570,12 +635,20 @@ class MarigoldPipelineRGBLatentNoise:
 
         r is valid until the next item is drawn: its tensors belong to a captured step's outputs and to the loader's
         recycled slots, and drawing the next item lets both be overwritten.  Consume (or clone) it first, on the current
-        stream; no host synchronisation is needed."""
+        stream; no host synchronisation is needed.
+
+        route (a SupportBankSet only, else ValueError): a callable on the query dict, or the name of one of its keys, that
+        gives the index of the ONE set the query is segmented against -- a stream whose class changes from query to
+        query.  Every batch then goes through segment_routed (r is segment_queries' dict, plus `route`, the batch's set
+        indices) instead of segment_classes; with `class_ids` the ground-truth id of query i is class_ids[route_i], so
+        r["native"]["counts"] and the processing-size r["counts"] are binary counts for the query's own class."""
         from .input_pipeline import QueryLoader
         from .unet import SupportBank, SupportBankSet
         if not isinstance(support, (SupportBank, SupportBankSet)):
             raise TypeError("support must be a SupportBank (prepare_support) or a SupportBankSet (prepare_support_classes)")
         nway = isinstance(support, SupportBankSet)
+        if route is not None and not nway:
+            raise ValueError("route picks one set of a SupportBankSet per query; a SupportBank has only one")
         if nway and class_value is not None:
             raise ValueError("class_value belongs to a SupportBank; with a SupportBankSet give class_ids")
         if not nway and class_ids is not None:
@@ -584,6 +657,26 @@ class MarigoldPipelineRGBLatentNoise:
             f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
             size = (support.hw[0] * f, support.hw[1] * f)
         flags = dict(r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
+        if route is not None:
+            route_of = route if callable(route) else (lambda q, _k=route: q[_k])
+            if class_ids is not None:     # the query's own class is its foreground value (QueryLoader's callable form)
+                ids = [int(c) for c in class_ids]
+                if len(ids) != support.nsets:
+                    raise ValueError(f"{len(ids)} class_ids for a support bank set of {support.nsets}")
+
+                def class_value(q):
+                    c = int(route_of(q))
+                    if not 0 <= c < len(ids):
+                        raise ValueError(f"a query is routed to set {c} of a support bank set of {len(ids)}")
+                    return ids[c]
+            loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, class_value=class_value,
+                                 ignore_value=ignore_value, route=route_of)
+            for bt in loader:
+                r = dict(self.segment_routed(support, bt["query_img"], bt["route"], bt.get("query_mask"),
+                                             native=bt["native"], **flags))
+                r["route"] = bt["route"]
+                yield bt["index"], r
+            return
         if class_ids is not None:     # staged once, not per batch
             class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
         loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, class_value=class_value,
@@ -685,7 +778,8 @@ class MarigoldPipelineRGBLatentNoise:
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""
         ent = self._graphs.get(key)
         if ent is None:
-            static_in = {k: (None if v is None else v.clone()) for k, v in ins.items()}
+            # a host input (segment_routed's pinned route table) gets a device buffer: one H2D copy into it per call
+            static_in = {k: (None if v is None else v.clone() if v.is_cuda else v.to(self.device)) for k, v in ins.items()}
             cur = torch.cuda.current_stream(self.device)
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(cur)

@@ -245,6 +245,19 @@ class SupportBankSet:
                                    self.dtype, self.residual_dtype, self.fold_key, self.weights_id, self.layout)
         return banks[c]
 
+    def route_table(self, route):
+        """The table of a routed query pass (`forward_query_routed`, ops.fsa_attention_routed): an int32 [b, 2] HOST tensor
+        whose row i = (offsets[route[i]], shots[route[i]]) -- where in the stack the set of query i starts and how many
+        images it holds.  `route` is a sequence of set indices, any order, repeats allowed; ValueError when it is empty or
+        names a set outside [0, nsets).  Every row is built from the set's own offsets, so it lies inside the stack."""
+        route = [int(c) for c in (route.tolist() if isinstance(route, torch.Tensor) else route)]
+        if not route:
+            raise ValueError("route_table: an empty route")
+        for i, c in enumerate(route):
+            if not 0 <= c < self.nsets:
+                raise ValueError(f"route_table: query {i} is routed to set {c} of a support bank set of {self.nsets}")
+        return torch.tensor([[self.offsets[c], self.shots[c]] for c in route], dtype=torch.int32)
+
     @staticmethod
     def stack(banks, ragged=False):
         """A set from existing SupportBanks (one per class, in order), by copying their K / V into one tensor per layer.
@@ -274,15 +287,17 @@ class SupportBankSet:
 class _BankIO:
     """One trunk pass' access to a SupportBank under construction (fill) or in use (read), per transformer index.
     group > 0: the K / V are a stack of support sets and `group` consecutive batch entries read one of them; shots: the
-    stack is ragged, set j of it holds shots[j] images."""
+    stack is ragged, set j of it holds shots[j] images.  table: a routed pass -- (device table, host mirror, largest and
+    smallest shot count of the stack), every entry reads the set its row of the table names."""
 
-    def __init__(self, n, bank=None, k=None, v=None, group=0, shots=None):
+    def __init__(self, n, bank=None, k=None, v=None, group=0, shots=None, table=None):
         self.fill = bank is None
         self.k = [None] * n if bank is None else (bank.k if k is None else k)
         self.v = [None] * n if bank is None else (bank.v if v is None else v)
         self.nshot = 0 if bank is None else bank.nshot
         self.group = group
         self.shots = shots
+        self.table = table
 
 
 class _Transformer:
@@ -367,6 +382,10 @@ class _Transformer:
             kv = ops_bwd.slice_channels(qkv, C, 2 * C)
             bank_io.k[self.index], bank_io.v[self.index] = kv[..., :C], kv[..., C:]
             att = ops.fsa_attention(q, k, v, heads, q_prescaled=True)
+        elif bank_io is not None and bank_io.table is not None:
+            table, table_host, max_shots, min_shots = bank_io.table
+            att = ops.fsa_attention_routed(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], table, table_host,
+                                           max_shots, min_shots, q_prescaled=True)
         elif bank_io is not None and bank_io.group and bank_io.shots is not None:
             att = ops.fsa_attention_ragged(q, k, v, heads, bank_io.k[self.index], bank_io.v[self.index], bank_io.shots,
                                            bank_io.group, q_prescaled=True)
@@ -827,6 +846,32 @@ class MyUNet2DConditionModel:
                      shots=bankset.shots[sets.start:sets.stop] if bankset.ragged else None)
         out = self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
         return out.view(n, b, *out.shape[1:])
+
+    @torch.no_grad()
+    def forward_query_routed(self, z_tag, timestep, bankset, table, table_host, encoder_hidden_states=None, out_scale=1.0):
+        """Routed query pass: the b latents z_tag [b, in_channels, h, w], each against ONE support set of `bankset`, in one
+        trunk pass of batch b.  `table` (device int32 [b, 2]) and `table_host` (its host mirror) are
+        bankset.route_table(route): every attn1 goes through ops.fsa_attention_routed on the whole stack's K/V (no slice,
+        no copy), and the kernel reads its row when it runs -- a captured pass follows the table's contents.  Entry i is
+        per image the arithmetic of forward_queries(z_tag[i:i+1], bankset.bank(route[i])).  Returns the sample (fp32
+        NCHW); forward_queries' ValueErrors."""
+        cfg, dt, dev = self.config, self.dtype, self.device
+        if not isinstance(bankset, SupportBankSet):
+            raise TypeError("bankset must be a SupportBankSet (prepare_bank_sets)")
+        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
+        B, Cin, h, w = x_in.shape
+        if Cin != cfg["in_channels"]:
+            raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
+        if tuple(table.shape) != (B, 2) or tuple(table_host.shape) != (B, 2):
+            raise ValueError(f"a routed pass of {B} queries needs a [{B}, 2] route table, got {tuple(table.shape)} "
+                             f"and {tuple(table_host.shape)}")
+        bankset.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
+                      fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
+        tproj, ehs2d, kv_all, L_ctx = self._conditioning(B, timestep, encoder_hidden_states)
+        c0 = cfg["block_out_channels"][0]
+        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
+        io = _BankIO(len(bankset.k), bankset, table=(table, table_host, max(bankset.shots), min(bankset.shots)))
+        return self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
 
     def _trunk(self, x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all=None, bank_io=None):
         # all layers' prompt K/V in one launch: [B*L, sum(2C)]; layers take column slices; the third

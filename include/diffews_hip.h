@@ -202,6 +202,24 @@ int dfw_fsa_sets_kernel_name(const dfw_fsa_args* a, int32_t group, char* buf, si
 int dfw_fsa_attention_ragged(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group, dfw_stream_t stream);
 int dfw_fsa_ragged_kernel_name(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group, char* buf, size_t n);
 size_t dfw_fsa_ragged_workspace_bytes(const dfw_fsa_args* a, const int32_t* shots, int32_t nsets, int32_t group);
+/* ROUTED queries (version >= 109): a query-only launch in which every entry reads a support set of its own choice out of
+ * a stack of `nbank` bank images.  `table` is a DEVICE array int32 [batch][2], row e = (first_e, shots_e): entry e walks
+ * [own ; image first_e ; ... ; image first_e + shots_e - 1].  The kernel reads its row when it RUNS, so a captured launch
+ * follows whatever the table holds at each replay; `table_host` is a host mirror of the rows at the time of the call.
+ * The plan (waves, grid, key split, workspace) is a function of a, nbank and min_shots only, never of the rows:
+ * a->nshot is the LARGEST count a row may hold, min_shots the smallest; the key split is dfw_fsa_attention's rule on
+ * batch * (1 + a->nshot) segments, clamped to 1 + min_shots so that no split instance is ever empty.
+ * Needs n_plain == 0, bank_shared == 0, nshot > 0, nbank >= 1, 1 <= min_shots <= nshot (else DFW_EINVAL from all three
+ * functions, 0 bytes from the workspace query); the launch also needs table and table_host non-NULL and every mirrored
+ * row with first >= 0, min_shots <= shots <= nshot, first + shots <= nbank -- all checked before any launch.  Rows written
+ * later (a replayed graph) are the caller's to keep inside those rules.  The bank descriptors claim exactly nbank
+ * images and every bank read goes through them: a bad row gives wrong numbers, never a read outside the stack.
+ * Per entry the arithmetic, key order and tile sequence of dfw_fsa_attention on that set with bank_shared = 1.
+ * The name is the unshared name + "+routed". */
+int dfw_fsa_attention_routed(const dfw_fsa_args* a, const int32_t* table, const int32_t* table_host, int32_t nbank,
+                             int32_t min_shots, dfw_stream_t stream);
+int dfw_fsa_routed_kernel_name(const dfw_fsa_args* a, int32_t nbank, int32_t min_shots, char* buf, size_t n);
+size_t dfw_fsa_routed_workspace_bytes(const dfw_fsa_args* a, int32_t nbank, int32_t min_shots);
 
 /*
  * Cross-attention over a short context (attn2 of BasicTransformerBlock; L = 2 prompt tokens at
