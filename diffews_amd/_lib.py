@@ -225,6 +225,8 @@ SYMBOLS = {
     "dfw_seg_postprocess": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "dfw_seg_postprocess_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
     "dfw_seg_labels": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _vp]),
+    "dfw_seg_labels_cand": (_i32, [_vp, _vp, _vp, C.POINTER(_i32), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32,
+                                   _vp]),
     "dfw_meter_update": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "dfw_gemm_tn": (_i32, [C.POINTER(GemmTnArgs), _vp]),
     "dfw_gemm_tn_workspace_bytes": (_sz, [C.POINTER(GemmTnArgs)]),

@@ -660,13 +660,21 @@ class QueryLoader(_Prefetcher):
         index      positions of the batch's queries in the stream (list of int)
         route      (only with `route`) the set index of each of the batch's queries (list of int), for
                    pipeline.segment_routed
+        candidates (only with `candidates`) the candidate set indices of each of the batch's queries (list of lists), for
+                   pipeline.segment_candidates; then also
+        query_labels (only when every query of the batch carries `labels`) uint8 HOST tensor [b, out_h, out_w]: the
+                   queries' label maps, which are already at the processing size (ValueError for another size, or when
+                   only some queries of a batch carry one)
     class_value: one int, or a callable on the query dict.
     route: a callable on the query dict that gives the index of the support set the query goes to.
+    candidates: a callable on the query dict that gives the indices of the support sets the query is segmented against.
     """
 
-    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1, route=None):
+    def __init__(self, queries, size, batch, device="cuda", depth=2, class_value=None, ignore_value=-1, route=None,
+                 candidates=None):
         super().__init__(queries, size, batch, device, depth)
         self.class_value, self.ignore_value, self.route = class_value, int(ignore_value), route
+        self.candidates = candidates
 
     def layout(self, qs):
         """(InputBatch, per-query class values, has_gt) of one batch of query dicts: the images, then the ground-truth
@@ -707,4 +715,16 @@ class QueryLoader(_Prefetcher):
             out["query_mask"] = r["bin"]
         if self.route is not None:
             out["route"] = [int(self.route(q)) for q in qs]
+        if self.candidates is not None:
+            out["candidates"] = [[int(c) for c in self.candidates(q)] for q in qs]
+            have = [q.get("labels") is not None for q in qs]
+            if any(have) and not all(have):
+                raise ValueError("either every query of a batch carries `labels` or none does")
+            if all(have):
+                maps = [torch.as_tensor(np.asarray(q["labels"])).to(torch.uint8) for q in qs]
+                for m in maps:
+                    if tuple(m.shape) != (self.tf.out_h, self.tf.out_w):
+                        raise ValueError(f"`labels` is a label map at the processing size {(self.tf.out_h, self.tf.out_w)}, "
+                                         f"got {tuple(m.shape)}")
+                out["query_labels"] = torch.stack(maps)
         return out

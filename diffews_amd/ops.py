@@ -668,6 +668,49 @@ def seg_labels(seg_u8, mx, gt=None, r_threshold=0.25, threshold=0.0, batch_max=F
     return labels, counts
 
 
+def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.25, threshold=0.0, want_area=False,
+                    labels_out=None, counts_out=None):
+    """Label fusion over candidate classes per query: seg_labels' rule per ENTRY.  seg_u8: uint8 [E_cap, 3, H, W],
+    entry-major -- entry e is one (query, candidate class) pair, a query's entries adjacent; mx: int32 [E_cap], the maxima
+    a gt-less seg_postprocess left (may be None with the fixed threshold).  `tab`: a DEVICE int32 [B + 1 + E_cap] tensor,
+    offsets off[0..B] (query q owns entries [off[q], off[q+1]), an empty range gives label 0 everywhere) then the label
+    byte lab[e] of every entry (1..nlabels; entries from off[B] on are padding and never read); `tab_host`: its int32 host
+    mirror, validated by the library before the launch.  The kernel reads `tab` when it runs: under stream capture one
+    graph serves every table written into the same tensor.  Returns (labels uint8 [B, H, W], counts int64
+    [B, 2, nlabels+1] or None, area int64 [E_cap, 2] or None): the label is lab[e] of the foreground entry with the largest
+    score, earliest entry on a tie; counts as seg_labels gives them (gt uint8 [B, H, W]: 0..nlabels, 255 and anything
+    above nlabels ignored; a gt label outside the query's candidates is a miss in that label's union); area[e] = (pixels
+    where e is foreground on its own, pixels where e won), ignore pixels included."""
+    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    E_cap, _, H, W = seg_u8.shape
+    for name, t in (("tab", tab), ("tab_host", tab_host)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
+            raise ValueError(f"seg_labels_cand: {name} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
+    if tab.numel() != tab_host.numel():
+        raise ValueError(f"seg_labels_cand: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
+    if not tab.is_cuda or tab.device != seg_u8.device or tab_host.device.type != "cpu":
+        raise ValueError("seg_labels_cand: tab lives with seg_u8 on the device, tab_host on the host")
+    B, nlabels = tab.numel() - 1 - E_cap, int(nlabels)
+    if mx is not None:
+        assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == E_cap
+    elif r_threshold > 0:
+        raise ValueError("the dynamic threshold needs the per-entry maxima (mx)")
+    labels = labels_out if labels_out is not None else torch.empty(B, H, W, dtype=torch.uint8, device=seg_u8.device)
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.shape == (B, H, W)
+    counts = None
+    if gt is not None:
+        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, H, W)
+        shape = (B, 2, nlabels + 1)
+        counts = counts_out if counts_out is not None else torch.empty(shape, dtype=torch.int64, device=seg_u8.device)
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == shape
+    area = torch.empty(E_cap, 2, dtype=torch.int64, device=seg_u8.device) if want_area else None
+    host = C.cast(tab_host.data_ptr(), C.POINTER(C.c_int32))
+    L.check(L.lib().dfw_seg_labels_cand(seg_u8.data_ptr(), _p(mx), tab.data_ptr(), host, _p(gt), labels.data_ptr(),
+                                        _p(counts), _p(area), B, E_cap, nlabels, H, W, float(r_threshold),
+                                        float(threshold), _stream()), "dfw_seg_labels_cand")
+    return labels, counts, area
+
+
 def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False, want_u8=True, want_pred=True,
                u8_out=None, pred_out=None, tmp=None):
     """Native-size masks and scores: seg_u8 uint8 [b, 3, Hs, Ws] (seg_postprocess' output) resized back to every query's

@@ -618,9 +618,128 @@ class MarigoldPipelineRGBLatentNoise:
                 del self._graphs[k]
         return self._with_native(self._replay(key, step, ins), native, flags)
 
+    # ------------------------------------------------------------------ candidate classes per query, one label map
+    @torch.no_grad()
+    def segment_candidates(self, bankset, query_img, candidates, query_labels=None, r_threshold=0.25, threshold=0.0,
+                           entry_batch=8, labels="set", captured=None):
+        """One label map per query over a SUBSET of `bankset`'s classes, a different subset per query: query_img
+        [b, 3, H, W] in [-1, 1]; `candidates` b sequences of set indices (sorted here, so the lowest class wins a tie; a
+        query may have none, the batch needs at least one); query_labels optional uint8 [b, H, W] in the labels the call
+        writes (0 = background, 255 or anything above nlabels = ignore).  It sits between segment_classes (all N classes
+        for every query) and segment_routed (one class per query, a binary mask): the cost is one UNet entry per
+        (query, candidate) pair -- E = sum of the list lengths -- whatever N is.
+
+        The b queries are VAE-encoded ONCE, however many candidates they have -- in chunks of entry_batch queries, the last
+        chunk padded by repeating the last query, so that the encoder too runs at batch entry_batch: GEMM plans (tile,
+        split-K), and with them the bits, depend on the batch, and with every kernel of the step at ONE batch an entry is
+        bit for bit what segment_routed computes at that batch, whatever b and the other candidates are.  An entry_batch
+        that divides b pads nothing.  The E entries, query-major, are padded to E_pad (a multiple of entry_batch;
+        SupportBankSet.candidate_tables) and run as E_pad / entry_batch passes of entry_batch entries: the pass's latents
+        are gathered by index_select on a device index tensor, the pass goes through unet.forward_query_routed on its rows
+        of the (first image, shots) table, decode_seg, and a gt-less ops.seg_postprocess into its slice of one seg_u8 / maxima
+        buffer; one ops.seg_labels_cand launch then fuses every query's entries into its label map.  There is no batch_max
+        form: a maximum over "the class' b images" has no meaning when every query has its own classes.
+
+        labels="set": label = 1 + set index, nlabels = nsets.  labels="local": label = 1 + position in the query's sorted
+        list, nlabels = the longest list (a library of more than 254 classes; query_labels is then in local labels).
+
+        Returns dict(z0 [E, 4, h, w], dec [E, 3, H, W], seg_u8 [E, 3, H, W], labels uint8 [b, H, W], counts int64
+        [b, 2, nlabels+1] or None, area int64 [E, 2] = per entry (pixels foreground on its own, pixels where it won the
+        label), entries = the (query, set) pair of every entry, offsets = b + 1 ints, query i owns entries
+        [offsets[i], offsets[i+1])).  Entry e is what segment_routed computes for the same pass batch; a gt label that is
+        not among the query's candidates counts as a miss in that label's union.
+
+        Scheduler restriction, bankset.check(...) and stale-handle ValueErrors as in segment_routed; ValueError for a
+        number of lists other than b and for what candidate_tables rejects.
+
+        captured (default: self.use_graph): the entry indices, the rows and the label table are pinned host tensors and
+        static inputs of the step -- each is one H2D copy per call into the graph's buffer, and the kernels read them when
+        they run.  The graph key holds the set's uid, the query shape, E_pad, entry_batch, labels, nlabels, whether
+        query_labels were given and the flags, but NOT the candidates: one graph serves every assignment with the same b
+        and number of passes (with labels="local" also the same longest list).  It counts against MAX_QUERY_GRAPHS like
+        the other query steps.
+
+        entry_batch = 8 is a choice, not a measurement.  It bounds the decoder's batch: 16 entries at 512 x 512 reach the
+        VAE decoder's 2 GiB buffer-descriptor range (DFW_ERANGE)."""
+        from .unet import SupportBankSet
+        if not isinstance(bankset, SupportBankSet):
+            raise ValueError("segment_candidates needs a SupportBankSet (prepare_support_classes)")
+        t, tt = self._single_step_timestep()
+        if not self.scheduler.z0_is_neg_v(t):
+            raise NotImplementedError("segment_candidates needs the one-step scheduler with z0 = -v (the reference's setting)")
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        prompt = None if folded else self.encode_clip_feature()
+        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
+                   query_labels=None if query_labels is None else query_labels.to(dev).contiguous())
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        b, _, H, W = ins["query_img"].shape
+        candidates = list(candidates)
+        if len(candidates) != b:
+            raise ValueError(f"{len(candidates)} candidate lists for {b} queries")
+        ct = bankset.candidate_tables(candidates, entry_batch, labels)       # ValueError: see candidate_tables
+        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
+                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        E, E_pad, nlabels, eb = ct["E"], ct["E_pad"], ct["nlabels"], int(entry_batch)
+        flags = (float(r_threshold), float(threshold))
+        entries_host, rows_host, tab_host = ct["entries"].pin_memory(), ct["rows"].pin_memory(), ct["tab"].pin_memory()
+
+        def step(query_img, entries, rows, tab, query_labels=None):
+            lc = self.vae.config["latent_channels"]
+            # every query is encoded once, in chunks of entry_batch (the last one padded with the last query): GEMM plans,
+            # and so the bits, depend on the batch, and this way every kernel of the step runs at batch entry_batch
+            pad = -b % eb
+            qs = query_img if not pad else torch.cat([query_img, query_img[-1:].expand(pad, -1, -1, -1)])
+            zs = []
+            for c0 in range(0, b + pad, eb):
+                mom = self.vae.encoder(qs[c0:c0 + eb])
+                zs.append(self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc))   # z_tag (P:650)
+            z_tag = zs[0] if len(zs) == 1 else torch.cat(zs)
+            seg_u8 = torch.empty(E_pad, 3, H, W, dtype=torch.uint8, device=query_img.device)
+            mx = torch.empty(E_pad, dtype=torch.int32, device=query_img.device)
+            z0s, decs = [], []
+            for e0 in range(0, E_pad, eb):
+                # the indices and rows are read on the device: a capture bakes in the pointers, not the candidates.
+                # rows_host mirrors `rows` whenever this runs (eagerly, or while a graph is warmed up and captured)
+                zp = z_tag.index_select(0, entries[e0:e0 + eb])
+                z0 = self.unet.forward_query_routed(zp, tt, bankset, rows[e0:e0 + eb], rows_host[e0:e0 + eb], prompt,
+                                                    out_scale=-1.0)
+                dec = self.decode_seg(z0)
+                # gt-less call: zeroes this pass's maxima, quantises, takes the per-entry maxima
+                ops.seg_postprocess(dec, None, *flags, False, u8_out=seg_u8[e0:e0 + eb], scratch=mx[e0:e0 + eb])
+                z0s.append(z0)
+                decs.append(dec)
+            lab, counts, area = ops.seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, query_labels, *flags, want_area=True)
+            z0 = z0s[0] if len(z0s) == 1 else torch.cat(z0s)
+            dec = decs[0] if len(decs) == 1 else torch.cat(decs)
+            return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=lab, counts=counts, area=area)
+
+        def trimmed(r):       # the padding entries are dropped from what the caller sees; the candidates are the call's own
+            out = {k: r[k][:E] for k in ("z0", "dec", "seg_u8", "area")}
+            out.update(labels=r["labels"], counts=r["counts"],
+                       entries=[(i, c) for i, cs in enumerate(ct["sets"]) for c in cs],
+                       offsets=ct["tab"][:b + 1].tolist())
+            return out
+        if captured is None:
+            captured = self.use_graph
+        if not captured:
+            return trimmed(step(entries=entries_host.to(dev, non_blocking=True), rows=rows_host.to(dev, non_blocking=True),
+                                tab=tab_host.to(dev, non_blocking=True), **ins))
+        ins.update(entries=entries_host, rows=rows_host, tab=tab_host)   # _replay: device buffers, one H2D copy each per call
+        key = ("queries", "candidates", bankset.uid, tuple(ins["query_img"].shape), E_pad, eb, labels, nlabels,
+               query_labels is not None, flags, float(tt), folded, getattr(self, "_fold_key", None),
+               self.unet.residual_dtype, self.vae.residual_dtype)
+        if key in self._graphs:
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        else:
+            mine = [k for k in self._graphs if k[0] == "queries"]
+            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
+                del self._graphs[k]
+        return trimmed(self._replay(key, step, ins))
+
     def segment_stream(self, support, queries, batch=4, size=None, depth=2, class_value=None, ignore_value=-1,
                        class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None,
-                       route=None):
+                       route=None, candidates=None, entry_batch=8, labels="set"):
         """Generator: a stream of decoded images against one prepared support -- `support` a SupportBank (prepare_support;
         routed to segment_queries) or a SupportBankSet (prepare_support_classes; routed to segment_classes, with
         `class_ids` and `max_batch`).  `queries` yields dicts with `query_img` (PIL / uint8 [H, W, 3], any size) and
@@ -641,7 +760,15 @@ class MarigoldPipelineRGBLatentNoise:
         gives the index of the ONE set the query is segmented against -- a stream whose class changes from query to
         query.  Every batch then goes through segment_routed (r is segment_queries' dict, plus `route`, the batch's set
         indices) instead of segment_classes; with `class_ids` the ground-truth id of query i is class_ids[route_i], so
-        r["native"]["counts"] and the processing-size r["counts"] are binary counts for the query's own class."""
+        r["native"]["counts"] and the processing-size r["counts"] are binary counts for the query's own class.
+
+        candidates (a SupportBankSet only, and not together with `route`, else ValueError): a callable on the query dict,
+        or the name of one of its keys, that gives the indices of the sets the query is segmented against -- a handful
+        of the library's classes, a different handful per query.  Every batch then goes through segment_candidates with
+        `entry_batch` and `labels` (r is its dict, plus `candidates`, the batch's lists as given).  The ground truth of
+        the processing-size r["counts"] is q["labels"] when the queries carry one: a label map ALREADY at the processing
+        size, in the labels the call writes.  Native-size labels and counts are not computed on this route: r["native"]
+        is absent, and `class_value`, `class_ids` and `batch_max` do not apply (ValueError when given)."""
         from .input_pipeline import QueryLoader
         from .unet import SupportBank, SupportBankSet
         if not isinstance(support, (SupportBank, SupportBankSet)):
@@ -656,6 +783,23 @@ class MarigoldPipelineRGBLatentNoise:
         if size is None:
             f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
             size = (support.hw[0] * f, support.hw[1] * f)
+        if candidates is not None:
+            if not nway:
+                raise ValueError("candidates name sets of a SupportBankSet; a SupportBank has only one")
+            if route is not None:
+                raise ValueError("give `route` (one set per query, a binary mask) or `candidates` (a label map), not both")
+            if class_ids is not None or batch_max:
+                raise ValueError("class_ids and batch_max do not apply to candidates (no native-size pass, no batch_max form)")
+            cand_of = candidates if callable(candidates) else (lambda q, _k=candidates: q[_k])
+            loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, ignore_value=ignore_value,
+                                 candidates=cand_of)
+            for bt in loader:
+                r = dict(self.segment_candidates(support, bt["query_img"], bt["candidates"], bt.get("query_labels"),
+                                                 r_threshold=r_threshold, threshold=threshold, entry_batch=entry_batch,
+                                                 labels=labels, captured=captured))
+                r["candidates"] = bt["candidates"]
+                yield bt["index"], r
+            return
         flags = dict(r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
         if route is not None:
             route_of = route if callable(route) else (lambda q, _k=route: q[_k])

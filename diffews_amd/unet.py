@@ -258,6 +258,59 @@ class SupportBankSet:
                 raise ValueError(f"route_table: query {i} is routed to set {c} of a support bank set of {self.nsets}")
         return torch.tensor([[self.offsets[c], self.shots[c]] for c in route], dtype=torch.int32)
 
+    def candidate_tables(self, candidates, entry_batch, labels="set"):
+        """The tables of a candidate pass (pipeline.segment_candidates): `candidates` is a sequence of b sequences of set
+        indices, the classes query i is segmented against.  Every list is sorted ascending (the lowest class wins a tie,
+        as in segment_classes); a query may have none, the batch must have at least one.  ValueError for a duplicate
+        within a query, an index outside [0, nsets), more than 254 candidates of one query, or no candidate at all.
+
+        An ENTRY is one (query, candidate) pair, query-major.  E entries are padded to E_pad, the next multiple of
+        `entry_batch`; padding entries repeat the last real entry's query and row (every row stays inside the stack) and
+        carry label 0.  Returns a dict of HOST tensors and ints:
+            entries  int64 [E_pad]          the query index of each entry
+            rows     int32 [E_pad, 2]       (first image, shots) of the entry's set, built as route_table builds them
+            tab      int32 [b + 1 + E_pad]  ops.seg_labels_cand's table: offsets off[0..b], then the label of every entry
+            E, E_pad, nlabels, sets (the sorted lists, a tuple of tuples)
+        labels="set": lab = 1 + set index, nlabels = nsets (ValueError when nsets > 254: a label is a byte -- use "local").
+        labels="local": lab = 1 + position in the query's sorted list, nlabels = the longest list; this is how a library
+        of more than 254 classes is used, and the caller's ground truth is then in local labels."""
+        if labels not in ("set", "local"):
+            raise ValueError(f"candidate_tables: labels is 'set' or 'local', not {labels!r}")
+        if labels == "set" and self.nsets > 254:
+            raise ValueError(f"candidate_tables: a label is a byte, {self.nsets} sets do not fit labels='set'; use "
+                             "labels='local' (1 + position in the query's own list)")
+        entry_batch = int(entry_batch)
+        if entry_batch < 1:
+            raise ValueError("candidate_tables: entry_batch must be >= 1")
+        sets = []
+        for i, cand in enumerate(candidates):
+            cs = sorted(int(c) for c in (cand.tolist() if isinstance(cand, torch.Tensor) else cand))
+            for c in cs:
+                if not 0 <= c < self.nsets:
+                    raise ValueError(f"candidate_tables: query {i} names set {c} of a support bank set of {self.nsets}")
+            if len(set(cs)) != len(cs):
+                raise ValueError(f"candidate_tables: query {i} names a set twice ({cs})")
+            if len(cs) > 254:
+                raise ValueError(f"candidate_tables: query {i} has {len(cs)} candidates, at most 254 fit one label map")
+            sets.append(tuple(cs))
+        E = sum(len(cs) for cs in sets)
+        if E == 0:
+            raise ValueError("candidate_tables: no candidate for any query")
+        E_pad = -(-E // entry_batch) * entry_batch
+        entries, rows, off, lab = [], [], [0], []
+        for i, cs in enumerate(sets):
+            for pos, c in enumerate(cs):
+                entries.append(i)
+                rows.append([self.offsets[c], self.shots[c]])
+                lab.append(1 + (c if labels == "set" else pos))
+            off.append(len(entries))
+        entries += [entries[-1]] * (E_pad - E)
+        rows += [rows[-1]] * (E_pad - E)
+        lab += [0] * (E_pad - E)
+        nlabels = self.nsets if labels == "set" else max(len(cs) for cs in sets)
+        return dict(entries=torch.tensor(entries, dtype=torch.int64), rows=torch.tensor(rows, dtype=torch.int32),
+                    tab=torch.tensor(off + lab, dtype=torch.int32), E=E, E_pad=E_pad, nlabels=nlabels, sets=tuple(sets))
+
     @staticmethod
     def stack(banks, ragged=False):
         """A set from existing SupportBanks (one per class, in order), by copying their K / V into one tensor per layer.

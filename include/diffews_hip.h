@@ -379,6 +379,34 @@ int dfw_seg_labels(const uint8_t* seg_u8, const uint32_t* mx, const uint8_t* gt,
                    int32_t N, int32_t B, int32_t H, int32_t Wd, float r_threshold, float threshold,
                    int32_t batch_max, dfw_stream_t stream);
 
+/* Label fusion over CANDIDATE classes per query (version >= 110): dfw_seg_labels' rule per ENTRY instead of per class.
+ * seg_u8 [E_cap][3][H][W] is entry-major: entry e is one (query, candidate class) pair, the entries of one query are
+ * adjacent; mx [E_cap] are the per-entry maxima a gt-less dfw_seg_postprocess_ex leaves (NULL allowed with the fixed
+ * threshold).  `tab` is a DEVICE array int32 [B + 1 + E_cap]: offsets off[0 .. B] (non-decreasing, off[0] = 0,
+ * off[B] = E <= E_cap; query q owns entries [off[q], off[q+1]), an empty range gives labels 0), then lab[e], the label
+ * byte written where entry e wins, 1..nlabels for e < E; entries e >= E are padding and never read.  The kernel reads
+ * `tab` when it RUNS, so a captured launch follows whatever the table holds at each replay; `tab_host` is its host mirror
+ * at the time of the call and is what the call validates.  What the kernel reads it clamps (0 <= lo <= hi <= E_cap,
+ * hi - lo <= 254): a bad table written later gives wrong numbers, never a read outside seg_u8 / mx / tab.
+ *   score_e = ((u0/255.0f + u1/255.0f) + u2/255.0f) / 3.0f; e is foreground when score_e > thr_e,
+ *   thr_e = (mx[e]/255.0f) * r_threshold when r_threshold > 0, else the fixed `threshold` (there is no batch_max form);
+ *   label = 0 with no foreground entry, else lab[e] of the foreground entry with the largest score, earliest e on a tie.
+ * labels uint8 [B][H][W].  counts (optional; then gt is required) int64 [B][2][nlabels+1]: row 0 label == gt == l, row 1
+ * pred_l + gt_l - inter_l, gt uint8 [B][H][W] as dfw_seg_labels takes it (0..nlabels, 255 = ignore, values in
+ * (nlabels, 255) dropped); a gt label that is not among the query's candidates counts in that label's union, as a miss.
+ * area (optional) int64 [E_cap][2]: per entry, pixels where e is foreground on its own and pixels where e won the label;
+ * ignore pixels included, independent of gt, rows e >= E left 0.  counts and area are zeroed by this call (a library
+ * kernel).  With off = (0, N, 2N, ...), lab[qN + c] = 1 + c and seg_u8 / mx permuted from class-major to query-major,
+ * labels and counts are those of dfw_seg_labels(..., batch_max = 0), bit for bit.
+ * DFW_EINVAL, all on the host before any launch: NULL seg_u8 / tab / tab_host / labels; B, H, Wd or E_cap < 1; nlabels
+ * outside 1..254; counts without gt; r_threshold > 0 without mx; neither threshold > 0; offsets not starting at 0,
+ * decreasing or ending above E_cap; a query with more than 254 entries; a lab[e] outside 1..nlabels for e < E.
+ * DFW_ERANGE: B above 65535 (also E_cap above 2^24 or H * Wd above 2^30). */
+int dfw_seg_labels_cand(const uint8_t* seg_u8, const uint32_t* mx, const int32_t* tab, const int32_t* tab_host,
+                        const uint8_t* gt, uint8_t* labels, int64_t* counts, int64_t* area,
+                        int32_t B, int32_t E_cap, int32_t nlabels, int32_t H, int32_t Wd,
+                        float r_threshold, float threshold, dfw_stream_t stream);
+
 /* AverageMeter.update on device (evaluation_util/common/logger.py:35-37): for every episode b,
  * inter_buf[k][class_id[b]] += counts[b][k], union_buf[k][class_id[b]] += counts[b][2+k], k = 0, 1.
  * Buffers are int64 [2][nclass] (exact, order-independent sums); class ids outside [0, nclass) are skipped. */
