@@ -29,6 +29,12 @@ class GemmArgs(C.Structure):
                 ("colscale", _f32), ("colscale_n", _i32), ("residual_f32", _i32), ("W_blocked", _vp)]
 
 
+class ConvUp2xArgs(C.Structure):
+    _fields_ = [("x", _vp), ("W", _vp), ("y", _vp), ("bias", _vp), ("x_elems", _i64), ("w_elems", _i64),
+                ("B", _i32), ("Hi", _i32), ("Wi", _i32), ("Cin", _i32), ("Cout", _i32), ("ldx", _i32), ("ldy", _i32),
+                ("dtype", _i32), ("gn_partial", _vp), ("gn_groups", _i32)]
+
+
 class FsaArgs(C.Structure):
     _fields_ = [("q", _vp), ("k", _vp), ("v", _vp), ("k_bank", _vp), ("v_bank", _vp), ("out", _vp),
                 ("batch", _i32), ("heads", _i32), ("n_q", _i32), ("n_kv", _i32), ("n_bank", _i32), ("nshot", _i32),
@@ -195,6 +201,9 @@ SYMBOLS = {
     "dfw_gemm_workspace_bytes": (_sz, [C.POINTER(GemmArgs)]),
     "dfw_gemm_kernel_name": (_i32, [C.POINTER(GemmArgs), C.c_char_p, _sz]),
     "dfw_gemm_gn_chunks": (_i32, [C.POINTER(GemmArgs)]),
+    "dfw_conv_up2x": (_i32, [C.POINTER(ConvUp2xArgs), _vp]),
+    "dfw_conv_up2x_kernel_name": (_i32, [C.POINTER(ConvUp2xArgs), C.c_char_p, _sz]),
+    "dfw_conv_up2x_gn_chunks": (_i32, [C.POINTER(ConvUp2xArgs)]),
     "dfw_fsa_attention": (_i32, [C.POINTER(FsaArgs), _vp]),
     "dfw_fsa_workspace_bytes": (_sz, [C.POINTER(FsaArgs)]),
     "dfw_fsa_kernel_name": (_i32, [C.POINTER(FsaArgs), C.c_char_p, _sz]),

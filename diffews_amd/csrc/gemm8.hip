@@ -30,9 +30,19 @@ namespace dfw {
 
 // BN = 256: wave grid 2 (M) x 4 (N), wave tile 128 x 64 (the scheme above).  BN = 128: wave grid 4 x 2, wave tile 64 x 64, ONE W
 // half-tile per K-tile, 16-MFMA phases; the wave groups (wave >> 2) still own the A half-tiles 0 / 1.
-template <typename T, bool CONV, int BN>
+//
+// UP2X (conv only; dfw_conv_up2x below): nearest-2x upsample + conv3x3 as four 2x2 convs on the LOW-resolution input, one per
+// output parity (py, px).  Under a 3x3 window an upsampled pixel has four distinct source pixels, so the nine taps fold onto
+// (ty, tx) in {0,1}^2 at source offset (ty - 1 + py, tx - 1 + px); W is the folded pack [N][(py, px, ty, tx, cin)] (row stride
+// 16 Cin).  A tile is a 16 x 16 block of low-resolution positions of ONE parity: tile index = (m-tile, n-tile) * 4 + parity, so
+// that the four parities of a block run side by side and share their A lines in L2; K-tiles per tile = 4 Cin / 64, chunk-major.
+// Output row r of a tile is output pixel (2 (oy0 + (r >> 4)) + py, 2 (ox0 + (r & 15)) + px); p.Hi / p.Wi are the low-resolution
+// limits (the upsampled image's zero padding is exactly the source image's), p.Ho / p.Wo the output size, p.K = 4 Cin.
+template <typename T, bool CONV, int BN, bool UP2X = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
   constexpr int BM = 256, HT = 16384;
+  static_assert(!UP2X || (CONV && BN != 160), "the folded upsample conv is a conv mode of the 256 / 128 wide tiles");
+  constexpr int KW = UP2X ? 4 : 1;                      // W row stride in units of p.K
   // BN = 160 (Linear only; the N = 320 layers of the UNet's 64^2 level: 128 x 2 = 256 tiles on the lock-step batch): wave grid 4 x 2,
   // wave tile 64 x 80 (five 16-column blocks), ONE 160-row W stage per K-tile (three wave-instructions per wave, the third of waves
   // 4-7 zero-fills 32 pad rows) in two 24 KiB buffers behind the A half-tile slots, 160-byte staging rows (conv_patch8.hip's tile)
@@ -77,6 +87,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
 
   auto tile_coords = [&](int t) -> TileC {
     TileC c;
+    c.par = 0;
+    if constexpr (UP2X) {
+      c.par = t & 3;
+      t >>= 2;
+    }
     const int tn = t % p.ntn, tm = t / p.ntn;
     c.m0 = tm * BM;
     c.n0 = tn * BN;
@@ -90,7 +105,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
     return c;
   };
   auto row_to_m = [&](const TileC& c, int r) -> int {
-    if constexpr (CONV) return (c.img * p.Ho + c.oy0 + (r >> 4)) * p.Wo + c.ox0 + (r & 15);
+    if constexpr (UP2X) return (c.img * p.Ho + 2 * (c.oy0 + (r >> 4)) + (c.par >> 1)) * p.Wo + 2 * (c.ox0 + (r & 15)) + (c.par & 1);
+    else if constexpr (CONV) return (c.img * p.Ho + c.oy0 + (r >> 4)) * p.Wo + c.ox0 + (r & 15);
     else return c.m0 + r;
   };
 
@@ -115,6 +131,10 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
       a_iy0 = (c.oy0 + (wave >> 1)) * p.stride - p.pad;
       a_ix0 = (c.ox0 + (wave & 1) * 8 + lrow) * p.stride - p.pad;
       a_pix = (uint32_t)c.img * (uint32_t)(p.Hi * p.Wi);
+      if constexpr (UP2X) {                // (stride 1, pad 1) source offset ty - 1 + py, tx - 1 + px
+        a_iy0 += c.par >> 1;
+        a_ix0 += c.par & 1;
+      }
     }
   };
   auto a_advance = [&]() {
@@ -126,7 +146,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
   };
   auto issue_a = [&](int buf) __attribute__((always_inline)) {   // both halves of the cursor's K-tile -> buffer buf
     int ky = 0, kx = 0, cc = 0;
-    if constexpr (CONV) {
+    if constexpr (UP2X) {
+      cc = a_kt >> 2;                      // chunk-major: the four folded taps of one 64-channel chunk back to back
+      ky = (a_kt >> 1) & 1;
+      kx = a_kt & 1;
+    } else if constexpr (CONV) {
       cc = a_kt / 9;                       // chunk-major K walk: the nine taps of one 64-channel chunk back to back
       const int tap = a_kt - cc * 9;
       ky = tap / 3;
@@ -157,14 +181,18 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
   int w_kt = 0, w_ti = 0;
   bool w_live = true;
   uint32_t w_v0 = 0;
-  int w_n = 0;
+  int w_n = 0, w_par = 0;
   auto w_setup = [&](const TileC& c) {
     w_n = c.n0 + wave * 8 + lrow;
-    w_v0 = (uint32_t)(((size_t)w_n * p.K + kc * 8) * sizeof(T));
+    w_par = c.par;
+    w_v0 = (uint32_t)(((size_t)w_n * p.K * KW + kc * 8) * sizeof(T));
   };
   auto issue_w = [&](int buf) __attribute__((always_inline)) {
     uint32_t koff = (uint32_t)w_kt * 128u;
-    if constexpr (CONV) {
+    if constexpr (UP2X) {
+      const int cc = w_kt >> 2, tap = w_kt & 3;
+      koff = (uint32_t)((w_par * 4 + tap) * p.Cin + cc * 64) * (uint32_t)sizeof(T);
+    } else if constexpr (CONV) {
       const int cc = w_kt / 9, tap = w_kt - cc * 9;
       koff = (uint32_t)(tap * p.Cin + cc * 64) * (uint32_t)sizeof(T);
     }
@@ -182,7 +210,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
       const uint32_t dst = lds0 + (uint32_t)((2 + h) * 32768 + buf * HT) + (uint32_t)wave * 1024u;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const uint32_t off = w_v0 + (uint32_t)(h * 128 + j * 64) * (uint32_t)p.K * (uint32_t)sizeof(T) + koff;
+        const uint32_t off = w_v0 + (uint32_t)(h * 128 + j * 64) * (uint32_t)(p.K * KW) * (uint32_t)sizeof(T) + koff;
         bool ok = w_live;
         if constexpr (BN == 128) ok = ok && (w_n + j * 64 < p.N);
         dma16(rw, ok ? off : kOOB, dst + j * 8192);
@@ -191,7 +219,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
     if (++w_kt == nkt) {
       w_kt = 0;
       if (++w_ti < my_tiles) {
-        if (p.ntn > 1) w_setup(tile_coords(tile0 + w_ti * nxb));
+        if (UP2X || p.ntn > 1) w_setup(tile_coords(tile0 + w_ti * nxb));
       } else w_live = false;
     }
   };
@@ -407,8 +435,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
       }
       const int cp = lane & 31;
       if (lane < 32 && (cp & (ppg - 1)) == 0) {
-        const int tm = tile_id / p.ntn;
-        const int chunk = (tm - c.img * p.tpi) * WGM + wm;
+        const int tm = (UP2X ? tile_id >> 2 : tile_id) / p.ntn;
+        const int chunk = ((tm - c.img * p.tpi) * KW + c.par) * WGM + wm;   // UP2X: one chunk per (low-resolution tile, parity, wave row)
         const int grp = (c.n0 + wc * 64 + 2 * cp) / cpg;
         float* o2 = p.gn_partial + (((size_t)c.img * p.gn_chunks + chunk) * p.gn_groups + grp) * 2;
         o2[0] = s2;
@@ -539,4 +567,95 @@ int launch_gemm8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   return DFW_BY_DTYPE(p, launch8<T, 128>(p, pl, st));
 }
 
+// ---- dfw_conv_up2x: the folded nearest-2x upsample conv (UP2X above); its own entry point and argument struct, dfw_gemm's
+// planner never sees it.  Host validation first, every rejection before any launch.
+template <typename T, int BN>
+static int launch_up2x(const GemmP& p, hipStream_t st) {
+  constexpr size_t lds = (size_t)(2 + BN / 128) * 32768 + 32768;
+  int nwg = p.ntm * p.ntn;
+  if (nwg > 256) nwg = 256;
+  nwg = (nwg + 7) & ~7;
+  auto kfn = gemm8_kernel<T, true, BN, true>;
+  (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfn, dim3(nwg), dim3(512), lds, st, p);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}
+
+static int up2x_gn_chunks(const dfw_conv_up2x_args* a, int bn) {
+  if (a->gn_groups <= 0 || (a->Cout % a->gn_groups) != 0) return 0;
+  const int cpg = a->Cout / a->gn_groups;
+  if (cpg < 4 || cpg > 64 || (cpg & (cpg - 1))) return 0;          // groups must tile the 64-channel wave tiles
+  return 4 * (a->Hi / 16) * (a->Wi / 16) * (8 / (bn / 64));        // (low-resolution tile, parity, wave row)
+}
+
+// 0 and the N tile in bn, or the DFW_E* code dfw_conv_up2x returns for these arguments
+static int up2x_plan(const dfw_conv_up2x_args* a, int& bn) {
+  if (!a || !a->x || !a->W || !a->y) return DFW_EINVAL;
+  if (a->B <= 0 || a->Hi <= 0 || a->Wi <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->x_elems <= 0 || a->w_elems <= 0) return DFW_EINVAL;
+  if (a->dtype != DFW_BF16 && a->dtype != DFW_F16) return DFW_EINVAL;
+  if (a->gn_groups < 0 || (a->gn_partial && a->gn_groups == 0)) return DFW_EINVAL;
+  if ((a->Hi % 16) != 0 || (a->Wi % 16) != 0 || (a->Cin % 64) != 0 || (a->Cout % 64) != 0) return DFW_ESHAPE;
+  if (a->ldx < a->Cin || (a->ldx % 8) != 0 || a->ldy < a->Cout || (a->ldy % 8) != 0) return DFW_ESHAPE;
+  if (((uintptr_t)a->x & 15) || ((uintptr_t)a->W & 15) || ((uintptr_t)a->y & 15)) return DFW_ESHAPE;   // 16-byte loads and stores
+  if ((a->bias && ((uintptr_t)a->bias & 15)) || (a->gn_partial && ((uintptr_t)a->gn_partial & 3))) return DFW_ESHAPE;
+  const int64_t pix = (int64_t)a->B * a->Hi * a->Wi;
+  if (a->x_elems * 2 >= (1ll << 31) || a->w_elems * 2 >= (1ll << 31) || 4 * pix >= (1ll << 31)) return DFW_ERANGE;
+  if (a->x_elems < pix * a->ldx - (a->ldx - a->Cin) || a->w_elems < (int64_t)a->Cout * 16 * a->Cin) return DFW_EINVAL;
+  bn = (a->Cout % 256) == 0 ? 256 : 128;
+  if (a->gn_partial && up2x_gn_chunks(a, bn) == 0) return DFW_ESHAPE;
+  return 0;
+}
+
 }  // namespace dfw
+
+using namespace dfw;
+
+extern "C" int dfw_conv_up2x_kernel_name(const dfw_conv_up2x_args* a, char* buf, size_t n) {
+  if (!buf || n == 0) return DFW_EINVAL;
+  buf[0] = 0;                                   // not eligible: the empty name next to the code
+  int bn = 0;
+  const int rc = up2x_plan(a, bn);
+  if (rc) return rc;
+  snprintf(buf, n, "gemm8_kernel<%s,256,%d,64,up2x>", a->dtype == DFW_BF16 ? "bf16" : "f16", bn);
+  return 0;
+}
+
+extern "C" int32_t dfw_conv_up2x_gn_chunks(const dfw_conv_up2x_args* a) {
+  int bn = 0;
+  if (!a) return 0;
+  dfw_conv_up2x_args q = *a;
+  q.gn_partial = nullptr;                       // a query: the buffer is sized from the answer
+  return up2x_plan(&q, bn) ? 0 : up2x_gn_chunks(&q, bn);
+}
+
+extern "C" int dfw_conv_up2x(const dfw_conv_up2x_args* a, dfw_stream_t stream) {
+  int bn = 0;
+  const int rc = up2x_plan(a, bn);
+  if (rc) return rc;
+  GemmP p = {};
+  p.A = (const char*)a->x; p.W = (const char*)a->W; p.C = (char*)a->y;
+  p.bias = a->bias;
+  p.a_bytes = (uint32_t)(a->x_elems * 2);
+  p.w_bytes = (uint32_t)(a->w_elems * 2);
+  p.Hi = a->Hi; p.Wi = a->Wi; p.Ho = 2 * a->Hi; p.Wo = 2 * a->Wi;
+  p.M = a->B * p.Ho * p.Wo; p.N = a->Cout; p.K = 4 * a->Cin;        // K of ONE parity; W rows are 16 Cin long
+  p.lda = a->ldx; p.ldc = a->ldy;
+  p.taps = 4; p.Cin = a->Cin; p.stride = 1; p.pad = 1; p.ups = 0;
+  p.rows_per_img = p.Ho * p.Wo;
+  p.out_scale = 1.0f; p.out_mode = DFW_OUT_T; p.splitk = 1; p.batch = 1;
+  p.nk = p.K / 64; p.cpt = a->Cin / 64;
+  p.dtype_bf16 = a->dtype == DFW_BF16;
+  p.tw = 16; p.tw_log2 = 4;
+  p.tpr = a->Wi / 16;
+  p.tpi = p.tpr * (a->Hi / 16);
+  p.ntm = 4 * a->B * p.tpi;                     // four parity tiles per low-resolution block
+  p.ntn = (a->Cout + bn - 1) / bn;
+  if (a->gn_partial) {
+    p.gn_partial = a->gn_partial; p.gn_groups = a->gn_groups;
+    p.gn_chunks = up2x_gn_chunks(a, bn);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (bn == 256) return DFW_BY_DTYPE(p, launch_up2x<T, 256>(p, st));
+  return DFW_BY_DTYPE(p, launch_up2x<T, 128>(p, st));
+}

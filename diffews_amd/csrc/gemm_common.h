@@ -237,6 +237,7 @@ struct GnRegSums {
 struct TileC {
   int m0, n0;                 // first output row (linear tiles) / first output channel
   int img, oy0, ox0;          // 2-D conv tiles: image and top-left output pixel
+  int par;                    // gemm8_kernel's folded upsample conv only: output parity 2 py + px of the tile
 };
 
 // Launch plan of one dfw_gemm call: host side only, never a kernel argument.  gemm_plan() (gemm.hip) decides it once per

@@ -388,12 +388,19 @@ def linear_stream(x, w, bias=None, residual=None):
     return linear(lo, w, residual=y, out_f32=True)
 
 
-def conv3x3_stream(x, w, cout, bias=None, lo=True, **kw):
+def conv3x3_stream(x, w, cout, bias=None, lo=True, w_up2x=None, **kw):
     """conv3x3 whose INPUT is the residual stream (Downsample2D / Upsample2D convs): as linear_stream.
+    w_up2x (with ups=True): the folded pack of w (packing.fold_up2x).  A 16-bit stream then takes conv3x3_up2x where the
+    library accepts the shape (Hi, Wi multiples of 16, Cin and Cout of 64) and UP2X_FOLD is on; the fp32 stream, small maps
+    and every other caller run the unfolded conv below, unchanged.
     lo=False: the fp32 stream is fed as ONE operand rounded once (no second GEMM, a convert instead of the split): each such
     conv adds one storage rounding of its input (2.5e-4 relative in fp16, in quadrature) -- the VAE encoder's two LARGEST
     downsample convs take this form (round 4): they were 2.2 ms of the parity mode for 0.8e-4 of its 7.5e-4."""
     if x.dtype != torch.float32:
+        if w_up2x is not None and UP2X_FOLD and kw.get("ups") and set(kw) <= {"ups", "gn_groups"}:
+            y = conv3x3_up2x(x, w_up2x, cout, bias=bias, gn_groups=kw.get("gn_groups", 0))
+            if y is not None:
+                return y
         return conv3x3(x, w, cout, bias=bias, **kw)
     if not lo:
         return conv3x3(to_storage(x, w.dtype), w, cout, bias=bias, out_f32=True, **kw)
@@ -401,6 +408,54 @@ def conv3x3_stream(x, w, cout, bias=None, lo=True, **kw):
     gn_groups = kw.pop("gn_groups", 0)
     y = conv3x3(hi, w, cout, bias=bias, out_f32=True, **kw)
     return conv3x3(lo, w, cout, residual=y, out_f32=True, gn_groups=gn_groups, **kw)     # the FINAL values carry the statistics
+
+
+# A/B switch of the folded upsample conv: False keeps conv3x3_stream(..., ups=True, w_up2x=...) on the unfolded route (dfw_gemm,
+# ups = 1) everywhere.
+UP2X_FOLD = True
+
+
+def conv3x3_up2x(x, w_folded, cout, bias=None, gn_groups=0):
+    """Upsample2D's nearest-2x + conv3x3 on NHWC x [B, Hi, Wi, Cin] as four 2x2 parity convs on x itself (dfw_conv_up2x):
+    w_folded [Cout, 16*Cin] from packing.fold_up2x.  Returns [B, 2Hi, 2Wi, Cout] with `_gn_stats` attached as conv3x3 does,
+    or None when the library declines the shape (its name query answers DFW_ESHAPE): the caller then runs
+    conv3x3(..., ups=True) on the unfolded weights.  The hook sees the FLOPs executed, 2 M N 4 Cin."""
+    assert x.dim() == 4 and x.is_contiguous()
+    B, Hi, Wi, Cin = x.shape
+    assert w_folded.shape == (cout, 16 * Cin) and w_folded.dtype == x.dtype and w_folded.is_contiguous()
+    out = torch.empty(B, 2 * Hi, 2 * Wi, cout, dtype=x.dtype, device=x.device)
+    a = L.ConvUp2xArgs()
+    a.x, a.W, a.y = x.data_ptr(), w_folded.data_ptr(), out.data_ptr()
+    a.bias = _p(_f32(bias, "bias"))
+    a.x_elems, a.w_elems = x.numel(), w_folded.numel()
+    a.B, a.Hi, a.Wi, a.Cin, a.Cout, a.ldx, a.ldy = B, Hi, Wi, Cin, cout, Cin, cout
+    a.dtype = _dt(x)
+    lib = L.lib()
+    name = C.create_string_buffer(64)
+    rc = lib.dfw_conv_up2x_kernel_name(C.byref(a), name, 64)
+    if rc == -2:      # DFW_ESHAPE
+        return None
+    L.check(rc, "dfw_conv_up2x_kernel_name")
+    stats = None
+    if gn_groups:
+        a.gn_groups = gn_groups
+        chunks = lib.dfw_conv_up2x_gn_chunks(C.byref(a))
+        if chunks > 0:
+            part = torch.empty(B, chunks, gn_groups, 2, dtype=torch.float32, device=x.device)
+            a.gn_partial = part.data_ptr()
+            stats = (part, chunks, gn_groups)
+    if gemm_hook is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L.check(lib.dfw_conv_up2x(C.byref(a), _stream()), "dfw_conv_up2x")
+        e1.record()
+        M = B * 4 * Hi * Wi
+        gemm_hook(name.value.decode(), 2.0 * M * cout * 4 * Cin, e0, e1, (M, cout, 4 * Cin, 4, 1, 1, 1, 1))
+    else:
+        L.check(lib.dfw_conv_up2x(C.byref(a), _stream()), "dfw_conv_up2x")
+    if stats is not None:
+        out._gn_stats = stats
+    return out
 
 
 FSA_QSCALE = 64 ** -0.5 * math.log2(math.e)   # attn.scale (A:269-271, head_dim 64) in exp2 units

@@ -18,6 +18,29 @@ def block_conv3x3(wp):
     return wp.view(co, 9, ci // 32, 32).permute(1, 2, 0, 3).contiguous()
 
 
+# Nearest-2x upsample + conv3x3 as four 2x2 convs (dfw_conv_up2x): the 3x3 taps that land on source tap t of parity p
+UP2X_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))   # UP2X_TAPS[p][t] = S(p, t)
+
+
+def fold_up2x(wp, dtype=None):
+    """packed [Cout, 9*Cin] (pack_conv3x3) -> folded [Cout, 16*Cin] in (py, px, ty, tx, cin) order:
+    Wf[py][px][ty][tx] = sum of w[ky][kx] over ky in S(py, ty), kx in S(px, tx).  Summed in fp32 (float64 stays float64) and
+    rounded ONCE to `dtype` (default: wp's): fold the checkpoint's weights, not their 16-bit copies."""
+    co, k = wp.shape
+    ci = k // 9
+    assert k == 9 * ci
+    w = (wp if wp.dtype == torch.float64 else wp.float()).view(co, 3, 3, ci)
+    out = torch.zeros(co, 2, 2, 2, 2, ci, dtype=w.dtype, device=wp.device)
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    for ky in UP2X_TAPS[py][ty]:
+                        for kx in UP2X_TAPS[px][tx]:
+                            out[:, py, px, ty, tx] += w[:, ky, kx]
+    return out.reshape(co, 16 * ci).to(dtype if dtype is not None else wp.dtype).contiguous()
+
+
 def pack_conv1x1(w):
     return w.reshape(w.shape[0], w.shape[1]).contiguous()
 

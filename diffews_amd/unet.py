@@ -492,8 +492,12 @@ class _Transformer:
 
 
 class _Conv:
-    def __init__(self, sd, p, dev, dt):
-        self.w = packing.pack_conv3x3(sd[p + "weight"]).to(dev, dt)
+    def __init__(self, sd, p, dev, dt, up2x=False):
+        wp = packing.pack_conv3x3(sd[p + "weight"])
+        self.w = wp.to(dev, dt)
+        # the VAE decoder's Upsample2D convs keep a second, folded pack (ops.conv3x3_stream's w_up2x): four 2x2 parity convs on the
+        # low-resolution input
+        self.wf = packing.fold_up2x(wp, dt).to(dev) if up2x else None
         self.b = sd[p + "bias"].float().to(dev)
         self.cout = sd[p + "weight"].shape[0]
 
@@ -955,6 +959,9 @@ class MyUNet2DConditionModel:
                     x = blk["attn"][j](x, ehs2d, L_ctx, n_ref, bank_io)
             if blk["up"] is not None:
                 u = blk["up"]
+                # unfolded on purpose (no w_up2x): the fold's one extra weight rounding on the 16^2 / 32^2 layers, which replace the
+                # whole stream at K = 11520 / 5760, moves z0 by 9e-3 -- as much as ANY one-rounding change of those weights does
+                # (profiles/up2x_timing.md section 4); the VAE decoder's three layers sit downstream of z0 and take the fold
                 x = ops.conv3x3_stream(x, u.w, u.cout, bias=u.b, ups=True)
         # ---- 6. out (U:1246-1249); out_scale lets the pipeline fold z0 = -v into the epilogue
         x = ops.groupnorm(x, *self.gn_out, self.groups, self.eps, silu=True, out_dtype=self.dtype)

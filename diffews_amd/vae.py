@@ -151,7 +151,7 @@ class _Decoder:
         self.blocks = []
         for i in range(len(boc)):
             res = [_VaeResnet(sd, f"decoder.up_blocks.{i}.resnets.{j}.", dev, dt, g) for j in range(lpb + 1)]
-            up = _Conv(sd, f"decoder.up_blocks.{i}.upsamplers.0.conv.", dev, dt) if i != len(boc) - 1 else None
+            up = _Conv(sd, f"decoder.up_blocks.{i}.upsamplers.0.conv.", dev, dt, up2x=True) if i != len(boc) - 1 else None
             self.blocks.append((res, up))
         self.gn_out = (sd["decoder.conv_norm_out.weight"].float().to(dev),
                        sd["decoder.conv_norm_out.bias"].float().to(dev))
@@ -167,7 +167,7 @@ class _Decoder:
             for r in res:
                 h = r(h)
             if up is not None:
-                h = ops.conv3x3_stream(h, up.w, up.cout, bias=up.b, ups=True, gn_groups=self.groups)
+                h = ops.conv3x3_stream(h, up.w, up.cout, bias=up.b, ups=True, gn_groups=self.groups, w_up2x=up.wf)
         h = ops.groupnorm(h, *self.gn_out, self.groups, 1e-6, silu=True, out_dtype=self.dt)
         co = self.conv_out
         return ops.conv3x3(h, co.w, co.cout, bias=co.b, out_nchw_f32=True,

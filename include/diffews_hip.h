@@ -134,6 +134,39 @@ int dfw_gemm_kernel_name(const dfw_gemm_args* a, char* buf, size_t n);
 int32_t dfw_gemm_gn_chunks(const dfw_gemm_args* a);
 
 /*
+ * Upsample2D's nearest-2x + conv3x3 (U:1243; VAE decoder P:902) as four 2x2 convs on the LOW-resolution input
+ * (version >= 111).  Under a 3x3 window an upsampled pixel has only four distinct source pixels, so for output parity
+ * (py, px) = (Y & 1, X & 1) the nine taps fold onto a 2x2 window: tap (ty, tx) in {0,1}^2 reads source pixel
+ * (y + ty - 1 + py, x + tx - 1 + px) with the SUM of the 3x3 weights that land there, ky in S(py, ty), kx in S(px, tx),
+ * S(0,0) = {0}, S(0,1) = {1,2}, S(1,0) = {0,1}, S(1,1) = {2}.  The upsampled image's zero padding is the source image's
+ * bounds check.  4 taps instead of 9: the same output on 2.25x fewer multiply-adds.
+ *   x [B][Hi][Wi][ldx >= Cin] NHWC -> y [B][2 Hi][2 Wi][ldy >= Cout] NHWC, both the storage dtype; y = fold + bias.
+ *   W is the folded pack [Cout][16 Cin], k = (((py*2 + px)*2 + ty)*2 + tx)*Cin + c, summed in fp32 and rounded once at
+ *   load time (packing.fold_up2x).
+ * Supported: Hi % 16 == 0, Wi % 16 == 0, Cin % 64 == 0, Cout % 64 == 0 (256-wide tiles when Cout % 256 == 0, else
+ * 128-wide), ldx % 8 == 0, ldy % 8 == 0, x / W / y 16-byte aligned; anything else is DFW_ESHAPE and belongs on
+ * dfw_gemm with ups = 1.  Null pointers, non-positive sizes, extents smaller than the shape: DFW_EINVAL.
+ * gn_partial / gn_groups: as dfw_gemm_args, [B][chunks][gn_groups][2] floats with chunks from the query below; passing
+ * gn_partial for a group count the query answers 0 for is DFW_ESHAPE.
+ */
+typedef struct {
+  const void* x; const void* W; void* y; const float* bias;
+  int64_t x_elems, w_elems;           /* extent of x / W in elements (for bounds-checked loads) */
+  int32_t B, Hi, Wi, Cin, Cout;
+  int32_t ldx, ldy;
+  int32_t dtype;
+  float* gn_partial; int32_t gn_groups;
+} dfw_conv_up2x_args;
+
+int dfw_conv_up2x(const dfw_conv_up2x_args* a, dfw_stream_t stream);
+/* HOST-only plan queries, the same validation as the launch.  The name is e.g. "gemm8_kernel<bf16,256,256,64,up2x>";
+ * for arguments the launch would reject the query returns that DFW_E* code and leaves the empty string in buf.  The chunk
+ * count is 4 * (Hi/16) * (Wi/16) * wave rows of the tile (0: rejected arguments, or a group count whose groups do not
+ * tile 64 channels -- run dfw_groupnorm's own statistics pass); gn_partial itself is not read by the query. */
+int dfw_conv_up2x_kernel_name(const dfw_conv_up2x_args* a, char* buf, size_t n);
+int32_t dfw_conv_up2x_gn_chunks(const dfw_conv_up2x_args* a);
+
+/*
  * KV-fusion self-attention (the DiffewS-specific op): out = softmax(q [k_own ; k_bank]^T * scale) [v_own ; v_bank]
  * Replaces xformers.ops.memory_efficient_attention + the bank concat of MyXFormersAttnProcessor
  * (A:247-271).  q/k/v/out are [batch][tokens][heads*64] views with element row strides; the bank
