@@ -101,6 +101,15 @@ class SegLabelsNativeArgs(C.Structure):
                 ("r_threshold", _f32), ("threshold", _f32), ("batch_max", _i32)]
 
 
+class SegLabelsCandNativeArgs(C.Structure):
+    _fields_ = [("seg_u8", _vp), ("B", _i32), ("E_cap", _i32), ("nlabels", _i32), ("Hs", _i32), ("Ws", _i32),
+                ("tab", _vp), ("tab_host", _vp), ("items", _vp), ("items_host", _vp),
+                ("weights", _vp), ("weights_bytes", _sz), ("gt", _vp), ("gt_bytes", _sz), ("tmp", _vp), ("tmp_bytes", _sz),
+                ("tmp_res_off", _sz), ("tmp_cls_stride", _sz), ("u8_cls_stride", _sz), ("out_u8", _vp), ("out_u8_bytes", _sz),
+                ("labels", _vp), ("labels_bytes", _sz), ("mx", _vp), ("counts", _vp), ("area", _vp), ("class_ids", _vp),
+                ("entry_ids", _vp), ("r_threshold", _f32), ("threshold", _f32)]
+
+
 class InputImageItem(C.Structure):
     _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
                 ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
@@ -274,6 +283,7 @@ SYMBOLS = {
     "dfw_resample_coeffs_ex": (_i32, [_i32, _i32, _i32, _vp, _vp]),
     "dfw_seg_native": (_i32, [C.POINTER(SegNativeArgs), _vp]),
     "dfw_seg_labels_native": (_i32, [C.POINTER(SegLabelsNativeArgs), _vp]),
+    "dfw_seg_labels_cand_native": (_i32, [C.POINTER(SegLabelsCandNativeArgs), _vp]),
     "dfw_inputs_to_tensor": (_i32, [C.POINTER(InputsArgs), _vp]),
     "dfw_tiles_cut": (_i32, [C.POINTER(TilePlan), _vp, _vp, _vp, _i32, _i32, _vp]),
     "dfw_tiles_merge": (_i32, [C.POINTER(TilePlan), _vp, _i32, _vp, _vp, _vp]),

@@ -15,6 +15,11 @@
 // kernels run over N * B planes-of-3 (grid z = c * B + i, one item per image, a byte stride per class), the fourth launch
 // is seg_labels_kernel's label rule and LDS histograms at native size.
 //
+// dfw_seg_labels_cand_native is the same for the ENTRIES of seg_candidates.hip (seg_u8 [E_cap][3][Hs][Ws], one entry per
+// (query, candidate class) pair): the two resize kernels run over E planes-of-3 (grid z = e; the entry's query is looked up
+// in the device table, its position k in the query's list takes the part of the class above, so the scratch is K strides
+// with K the longest list), the fourth launch is seg_cand_kernel's rule, histograms and area at native size.
+//
 // Byte work bound by HBM / L2: a thread produces 4 adjacent bytes of one channel row, one 32-bit store where the
 // address is 4-byte aligned (row starts are when w % 4 == 0: every offset of the table is 16-byte aligned), byte stores
 // otherwise.
@@ -46,12 +51,14 @@ __global__ void native_zero_kernel(uint32_t* mx, int n_mx, unsigned long long* c
 // y -> row of the flat 3 * Hs rows of the image's planes.  With classes (dfw_seg_labels_native) seg_u8 is [N][B][3][Hs][Ws]
 // and grid z = c * B + i: class c of image i uses item i, its intermediates lie tmp_cls bytes after class c - 1's.  The
 // binary path launches B planes with tmp_cls = 0.
-__global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict__ seg_u8,
-                                                       const dfw_native_item* __restrict__ items,
-                                                       const uint8_t* __restrict__ weights, uint8_t* __restrict__ tmp,
-                                                       int Hs, int Ws, int B, size_t tmp_cls) {
-  const int cls = blockIdx.z / B;
-  const dfw_native_item it = items[blockIdx.z - cls * B];
+//
+// One copy of the arithmetic for both forms: `cls` is the plane's position among its item's planes (class c, or position k
+// in a query's candidate list), `item` the index of its item; both are workgroup-uniform.
+__device__ __forceinline__ void native_h_body(const uint8_t* __restrict__ seg_u8,
+                                              const dfw_native_item* __restrict__ items, uint32_t item, int cls,
+                                              const uint8_t* __restrict__ weights, uint8_t* __restrict__ tmp, int Hs,
+                                              int Ws, size_t tmp_cls) {
+  const dfw_native_item it = items[item];
   const int w = it.w;
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
   const int row = blockIdx.y * 4 + threadIdx.y;
@@ -72,15 +79,48 @@ __global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict
   native_store4(tmp + cls * tmp_cls + it.tmp_off + (size_t)row * w + x4, word, nx);
 }
 
+__global__ __launch_bounds__(256) void native_h_kernel(const uint8_t* __restrict__ seg_u8,
+                                                       const dfw_native_item* __restrict__ items,
+                                                       const uint8_t* __restrict__ weights, uint8_t* __restrict__ tmp,
+                                                       int Hs, int Ws, int B, size_t tmp_cls) {
+  const int cls = blockIdx.z / B;
+  native_h_body(seg_u8, items, blockIdx.z - cls * B, cls, weights, tmp, Hs, Ws, tmp_cls);
+}
+
+// The candidate form (dfw_seg_labels_cand_native): seg_u8 is ENTRY-major [E_cap][3][Hs][Ws] and grid z = e, one plane-of-3
+// per entry.  Which query q owns entry e is searched in the device table's offsets -- the largest q in [0, B) with
+// off[q] <= e, a bisection at workgroup-uniform addresses that ends whatever the table holds -- and k = e - off[q] is the
+// entry's position in q's list, clamped to [0, Kcap) (the longest list of the host mirror, what the workspace was
+// validated for): a table rewritten after the call was made gives wrong numbers, never a byte outside the workspace.
+__device__ __forceinline__ void native_cand_plane(const int32_t* __restrict__ tab, int B, int Kcap, int e, int& q, int& k) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  q = lo;
+  k = min(max(e - tab[lo], 0), Kcap - 1);
+}
+
+__global__ __launch_bounds__(256) void native_h_cand_kernel(const uint8_t* __restrict__ seg_u8,
+                                                            const dfw_native_item* __restrict__ items,
+                                                            const int32_t* __restrict__ tab,
+                                                            const uint8_t* __restrict__ weights,
+                                                            uint8_t* __restrict__ tmp, int Hs, int Ws, int B, int Kcap,
+                                                            size_t tmp_cls) {
+  int q, k;
+  native_cand_plane(tab, B, Kcap, (int)blockIdx.z, q, k);
+  native_h_body(seg_u8, items, q, k, weights, tmp, Hs, Ws, tmp_cls);
+}
+
 // vertical + maximum: tmp[i] -> res + u8_off = [3][h_i][w_i] (res may be null: maximum only).  Block (64, 4) over
 // (4 adjacent columns, row of the flat 3 * h_i output rows).  One atomicMax per workgroup, as seg_u8_kernel does.
 // Grid z = c * B + i as in native_h_kernel: mx is [N][B], class c's resized bytes lie res_cls bytes after class c - 1's.
-__global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __restrict__ items,
-                                                       const uint8_t* __restrict__ weights,
-                                                       const uint8_t* __restrict__ tmp, uint8_t* __restrict__ res,
-                                                       uint32_t* mx, int Hs, int B, size_t tmp_cls, size_t res_cls) {
-  const int cls = blockIdx.z / B;
-  const dfw_native_item it = items[blockIdx.z - cls * B];
+__device__ __forceinline__ void native_v_body(const dfw_native_item* __restrict__ items, uint32_t item, int cls,
+                                              const uint8_t* __restrict__ weights, const uint8_t* __restrict__ tmp,
+                                              uint8_t* __restrict__ res, uint32_t* mx, int Hs, size_t tmp_cls,
+                                              size_t res_cls, uint32_t* wmax) {
+  const dfw_native_item it = items[item];
   const int w = it.w, h = it.h;
   if ((int)blockIdx.x * 256 >= w || (int)blockIdx.y * 4 >= 3 * h) return;   // whole block beyond this image
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4;
@@ -125,11 +165,32 @@ __global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __
   if (!mx) return;   // kernel argument: uniform
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  __shared__ uint32_t wmax[4];
-  const int tid = threadIdx.y * 64 + threadIdx.x;
+  const int tid = threadIdx.y * 64 + threadIdx.x;   // wmax: the kernel's own 4 words of LDS
   if ((tid & 63) == 0) wmax[tid >> 6] = m;
   __syncthreads();
   if (tid == 0) atomicMax(mx + blockIdx.z, max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+}
+
+__global__ __launch_bounds__(256) void native_v_kernel(const dfw_native_item* __restrict__ items,
+                                                       const uint8_t* __restrict__ weights,
+                                                       const uint8_t* __restrict__ tmp, uint8_t* __restrict__ res,
+                                                       uint32_t* mx, int Hs, int B, size_t tmp_cls, size_t res_cls) {
+  __shared__ uint32_t wmax[4];
+  const int cls = blockIdx.z / B;
+  native_v_body(items, blockIdx.z - cls * B, cls, weights, tmp, res, mx, Hs, tmp_cls, res_cls, wmax);
+}
+
+// The candidate form: grid z = e as in native_h_cand_kernel, mx is [E_cap].
+__global__ __launch_bounds__(256) void native_v_cand_kernel(const dfw_native_item* __restrict__ items,
+                                                            const int32_t* __restrict__ tab,
+                                                            const uint8_t* __restrict__ weights,
+                                                            const uint8_t* __restrict__ tmp, uint8_t* __restrict__ res,
+                                                            uint32_t* mx, int Hs, int B, int Kcap, size_t tmp_cls,
+                                                            size_t res_cls) {
+  __shared__ uint32_t wmax[4];
+  int q, k;
+  native_cand_plane(tab, B, Kcap, (int)blockIdx.z, q, k);
+  native_v_body(items, q, k, weights, tmp, res, mx, Hs, tmp_cls, res_cls, wmax);
 }
 
 // threshold + counts per image over h_i * w_i: seg_count_kernel's expressions and reduction, the ground truth read in
@@ -347,6 +408,180 @@ __global__ __launch_bounds__(256) void native_labels_kernel(const dfw_native_ite
   }
 }
 
+// ---- candidate classes per query at native size (dfw_seg_labels_cand_native) ----
+constexpr int kNativeCandMax = 254;   // entries of one query, as seg_candidates.hip's kCandMax
+
+__global__ void native_cand_zero_kernel(uint32_t* mx, int n_mx, unsigned long long* counts, int n_counts,
+                                        unsigned long long* area, int n_area) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (mx && e < n_mx) mx[e] = 0u;
+  if (counts && e < n_counts) counts[e] = 0ull;
+  if (area && e < n_area) area[e] = 0ull;
+}
+
+// label + counts + area per query over h_q * w_q: native_labels_kernel's structure with seg_cand_kernel's per-query entry
+// range.  Entry e = lo + k of query q lies at res + k * res_cls + u8_off (the resized bytes), its threshold comes from
+// mx[e], the maximum of ITS resized planes, and its label byte from the table.  The range is clamped as seg_cand_kernel
+// clamps it and to Kcap, the longest list the workspace was validated for.  Ground truth in place at native size: the
+// item's ignore_value dropped; no id table: id = label, ids outside 0..NLab dropped; class_ids [NLab]: 1 + the lowest c with
+// class_ids[c] == id; entry_ids [E_cap]: lab[e] of the query's earliest entry with entry_ids[e] == id; every other id is
+// background.  Ids 0..255 go through an LDS table built once per workgroup.  Histograms indexed by label byte.
+__global__ __launch_bounds__(256) void native_labels_cand_kernel(const dfw_native_item* __restrict__ items,
+                                                                 const uint8_t* __restrict__ res, size_t res_cls,
+                                                                 const uint8_t* gt, const uint32_t* mx,
+                                                                 const int32_t* tab, const int32_t* class_ids,
+                                                                 const int32_t* entry_ids, uint8_t* labels,
+                                                                 unsigned long long* counts, unsigned long long* area,
+                                                                 int E_cap, int Kcap, int NLab, float r_thr,
+                                                                 float fixed_thr) {
+  __shared__ float lut[256];
+  __shared__ float thr[256];
+  __shared__ uint32_t lbl[256];
+  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][label byte]
+  __shared__ unsigned ahist[2 * 256];   // [foreground | won][entry of this query]
+  __shared__ int idmap[256];            // ground-truth id 0..255 -> label
+  const int q = blockIdx.y, B = gridDim.y;
+  const dfw_native_item it = items[q];
+  // the query's range: two loads at a uniform address, clamped before anything is indexed with them
+  int lo = tab[q], hi = tab[q + 1];
+  lo = min(max(lo, 0), E_cap);
+  hi = min(max(hi, lo), E_cap);
+  hi = min(hi, lo + min(Kcap, kNativeCandMax));
+  const int K = hi - lo;
+  const int32_t* labt = tab + B + 1;
+  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  if ((int)threadIdx.x < K) {
+    float t = fixed_thr;
+    if (r_thr > 0.f) t = ((float)mx[lo + threadIdx.x] / 255.0f) * r_thr;
+    thr[threadIdx.x] = t;
+    lbl[threadIdx.x] = (uint32_t)labt[lo + threadIdx.x] & 255u;
+  }
+  if (class_ids) {
+    int l = 0;
+    for (int c = NLab - 1; c >= 0; --c)
+      if (class_ids[c] == (int)threadIdx.x) l = c + 1;   // descending: the lowest c stays
+    idmap[threadIdx.x] = l;
+  } else if (entry_ids) {
+    int l = 0;
+    for (int k = K - 1; k >= 0; --k)
+      if (entry_ids[lo + k] == (int)threadIdx.x) l = labt[lo + k] & 255;   // descending: the earliest entry stays
+    idmap[threadIdx.x] = l;
+  }
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) hist[i] = 0u;
+  for (int i = threadIdx.x; i < 2 * 256; i += 256) ahist[i] = 0u;
+  __syncthreads();
+  const int HW = it.h * it.w;
+  const uint8_t* ub = res + it.u8_off;            // position 0 of this query
+  uint8_t* lb = labels + it.pred_off;
+  const uint8_t* g8 = counts ? gt + it.gt_off : nullptr;
+  const int32_t* g32 = (const int32_t*)g8;
+  const bool wide = it.gt_elem == 4;
+  const int ign = it.ignore_value;
+  auto count = [&](uint32_t l, int id) {
+    if (ign >= 0 && id == ign) return;            // ignore value: dropped from every histogram
+    int g;
+    if (class_ids) {
+      if ((unsigned)id < 256u) {
+        g = idmap[id];
+      } else {
+        g = 0;
+        for (int c = NLab - 1; c >= 0; --c)
+          if (class_ids[c] == id) g = c + 1;
+      }
+    } else if (entry_ids) {
+      if ((unsigned)id < 256u) {
+        g = idmap[id];
+      } else {
+        g = 0;
+        for (int k = K - 1; k >= 0; --k)
+          if (entry_ids[lo + k] == id) g = (int)lbl[k];
+      }
+    } else {
+      if (id < 0 || id > NLab) return;            // no bin: dropped as well (dfw_seg_labels_cand's rule)
+      g = id;
+    }
+    atomicAdd(&hist[256 + l], 1u);
+    atomicAdd(&hist[512 + g], 1u);
+    if ((int)l == g) atomicAdd(&hist[l], 1u);
+  };
+  if ((HW & 3) == 0 && (res_cls & 3) == 0 && (((uintptr_t)ub | (uintptr_t)lb | (uintptr_t)g8) & 3) == 0) {
+    const int n4 = HW >> 2;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
+      const size_t o = 4 * (size_t)e;
+      float best[4] = {-1.f, -1.f, -1.f, -1.f};
+      uint32_t lab[4] = {0u, 0u, 0u, 0u};
+      int win[4] = {-1, -1, -1, -1};
+      const uint8_t* uc = ub + o;
+      for (int c = 0; c < K; ++c, uc += res_cls) {
+        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
+        const float t = thr[c];
+        const uint32_t l = lbl[c];
+        unsigned nfg = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
+          if (sc > t) {
+            ++nfg;
+            if (sc > best[k]) { best[k] = sc; lab[k] = l; win[k] = c; }
+          }
+        }
+        if (area && nfg) atomicAdd(&ahist[c], nfg);
+      }
+      *(uint32_t*)(lb + o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+      if (area) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (win[k] >= 0) atomicAdd(&ahist[256 + win[k]], 1u);
+      }
+      if (g8) {
+        if (wide) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) count(lab[k], g32[o + k]);
+        } else {
+          const uint32_t wg = *(const uint32_t*)(g8 + o);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) count(lab[k], (int)((wg >> (8 * k)) & 255u));
+        }
+      }
+    }
+  } else {
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
+      float best = -1.f;
+      uint32_t lab = 0u;
+      int win = -1;
+      const uint8_t* uc = ub + e;
+      for (int c = 0; c < K; ++c, uc += res_cls) {
+        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
+        if (sc > thr[c]) {
+          if (area) atomicAdd(&ahist[c], 1u);
+          if (sc > best) { best = sc; lab = lbl[c]; win = c; }
+        }
+      }
+      lb[e] = (uint8_t)lab;
+      if (area && win >= 0) atomicAdd(&ahist[256 + win], 1u);
+      if (g8) count(lab, wide ? g32[e] : (int)g8[e]);
+    }
+  }
+  if (!counts && !area) return;   // kernel arguments: uniform
+  __syncthreads();
+  if (counts) {
+    const int NB = NLab + 1;
+    unsigned long long* cb = counts + (size_t)q * 2 * NB;
+    for (int l = threadIdx.x; l < NB; l += 256) {
+      const unsigned in = hist[l], un = hist[256 + l] + hist[512 + l] - in;
+      if (in) atomicAdd(cb + l, (unsigned long long)in);
+      if (un) atomicAdd(cb + NB + l, (unsigned long long)un);
+    }
+  }
+  if (area) {
+    for (int c = threadIdx.x; c < K; c += 256) {
+      const unsigned fg = ahist[c], won = ahist[256 + c];
+      if (fg) atomicAdd(area + 2 * (size_t)(lo + c), (unsigned long long)fg);
+      if (won) atomicAdd(area + 2 * (size_t)(lo + c) + 1, (unsigned long long)won);
+    }
+  }
+}
+
 }  // namespace dfw
 
 using namespace dfw;
@@ -507,6 +742,102 @@ extern "C" int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_st
   hipLaunchKernelGGL(native_labels_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->u8_cls_stride,
                      a->gt, (const uint32_t*)a->mx, a->class_ids, a->labels, (unsigned long long*)a->counts, N,
                      a->r_threshold, a->threshold, a->batch_max ? 1 : 0);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfw_seg_labels_cand_native(const dfw_seg_labels_cand_native_args* a, dfw_stream_t stream) {
+  if (!a || !a->seg_u8 || !a->tab || !a->tab_host || !a->items || !a->items_host || !a->weights || !a->tmp || !a->labels)
+    return DFW_EINVAL;
+  if (a->B < 1 || a->E_cap < 1 || a->Hs < 1 || a->Ws < 1 || a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
+  if (a->counts && !a->gt) return DFW_EINVAL;
+  if (a->class_ids && a->entry_ids) return DFW_EINVAL;
+  if (a->r_threshold > 0.f && !a->mx) return DFW_EINVAL;
+  if (!(a->r_threshold > 0.f) && !(a->threshold > 0.f)) return DFW_EINVAL;
+  // before the table is read: it is B + 1 + E_cap words
+  if (a->B > 65535 || a->Hs > 65535 || a->Ws > 65535 || a->E_cap > (1 << 24)) return DFW_ERANGE;
+  // the table's host mirror, as dfw_seg_labels_cand validates it; K = the longest list
+  const int32_t* th = a->tab_host;
+  if (th[0] != 0) return DFW_EINVAL;
+  int K = 0;
+  for (int q = 0; q < a->B; ++q) {
+    const int32_t lo = th[q], hi = th[q + 1];
+    if (hi < lo || hi > a->E_cap || hi - lo > kNativeCandMax) return DFW_EINVAL;
+    K = hi - lo > K ? hi - lo : K;
+  }
+  const int E = th[a->B];
+  for (int e = 0; e < E; ++e) {
+    const int32_t l = th[a->B + 1 + e];
+    if (l < 1 || l > a->nlabels) return DFW_EINVAL;
+  }
+  if (E > 65535) return DFW_ERANGE;                                          // grid z = E
+  if (!a->out_u8 && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
+  uint8_t* res = a->out_u8 ? a->out_u8 : a->tmp + a->tmp_res_off;
+  const size_t tmp_cap = a->out_u8 ? a->tmp_bytes : a->tmp_res_off;
+  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off;
+  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
+  int max_h = 0, max_w = 0;
+  long long max_hw = 0;
+  uint64_t tmp_ext = 0, res_ext = 0;    // extent of one list position in tmp / in the resized bytes
+  for (int i = 0; i < a->B; ++i) {
+    const dfw_native_item& t = it[i];
+    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
+    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
+    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
+    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
+        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
+      return DFW_ESHAPE;
+    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
+    const uint64_t hw = (uint64_t)t.h * t.w;
+    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
+        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
+      return DFW_EWORKSPACE;
+    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
+    if (!extent_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
+    if (a->counts) {
+      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
+      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
+    }
+    const uint64_t te = (uint64_t)t.tmp_off + 3ull * a->Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
+    tmp_ext = te > tmp_ext ? te : tmp_ext;
+    res_ext = re > res_ext ? re : res_ext;
+    max_h = t.h > max_h ? t.h : max_h;
+    max_w = t.w > max_w ? t.w : max_w;
+    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
+  }
+  // position k lies k strides after position 0: a stride holds one position, and position K - 1 ends inside its buffer
+  const uint64_t more = K > 1 ? (uint64_t)(K - 1) : 0;
+  if (a->tmp_cls_stride < tmp_ext || a->u8_cls_stride < res_ext) return DFW_EWORKSPACE;
+  if (more && (a->tmp_cls_stride > (tmp_cap - tmp_ext) / more || a->u8_cls_stride > (res_cap - res_ext) / more))
+    return DFW_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const dfw_native_item* items = (const dfw_native_item*)a->items;
+  const int B = a->B, n_mx = a->mx ? a->E_cap : 0, n_counts = a->counts ? B * 2 * (a->nlabels + 1) : 0;
+  const int n_area = a->area ? 2 * a->E_cap : 0;
+  if (n_mx || n_counts || n_area) {
+    int n = n_mx > n_counts ? n_mx : n_counts;
+    n = n_area > n ? n_area : n;
+    hipLaunchKernelGGL(native_cand_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a->mx, n_mx,
+                       (unsigned long long*)a->counts, n_counts, (unsigned long long*)a->area, n_area);
+    DFW_CHECK_LAUNCH();
+  }
+  if (E > 0) {   // K >= 1
+    const dim3 blk(64, 4);
+    hipLaunchKernelGGL(native_h_cand_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, E), blk, 0, st, a->seg_u8, items,
+                       a->tab, a->weights, a->tmp, a->Hs, a->Ws, B, K, a->tmp_cls_stride);
+    DFW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(native_v_cand_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, E), blk, 0, st, items, a->tab,
+                       a->weights, (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, K, a->tmp_cls_stride, a->u8_cls_stride);
+    DFW_CHECK_LAUNCH();
+  }
+  int cx = (int)((max_hw / 4 + 255) / 256);
+  if (cx > 64) cx = 64;
+  if (cx < 1) cx = 1;
+  hipLaunchKernelGGL(native_labels_cand_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->u8_cls_stride,
+                     a->gt, (const uint32_t*)a->mx, a->tab, a->class_ids, a->entry_ids, a->labels,
+                     (unsigned long long*)a->counts, (unsigned long long*)a->area, a->E_cap, K, a->nlabels, a->r_threshold,
+                     a->threshold);
   DFW_CHECK_LAUNCH();
   return 0;
 }

@@ -223,23 +223,37 @@ def evaluate_routed(pipe, bankset, queries, class_of_set, gt_ids=None, benchmark
 
 
 @torch.no_grad()
-def evaluate_candidates(pipe, library, items, r_threshold=0.25, threshold=0.0, entry_batch=8, labels="set", captured=True):
+def evaluate_candidates(pipe, library, items, r_threshold=0.25, threshold=0.0, entry_batch=8, labels="set", captured=True,
+                        use_original_imgsize=False, class_ids=None):
     """A library of classes against queries that each name their own candidate classes: `library` is a prepared
     SupportBankSet (pipe.prepare_support_classes, uniform or ragged), every item of `items` is (query_img [b, 3, H, W],
     candidates: b lists of set indices, label_map uint8 [b, H, W] in the labels pipe.segment_candidates writes -- 0 =
     background, 255 = ignore), b may vary.  Every item goes through pipe.segment_candidates and its per-label counts into
     one int64 running sum on the device; a ground-truth label outside a query's candidates is a miss in that label's
     union.  Returns (miou, iou [L+1], counts [2, L+1]) as evaluate_class_set does (metrics.nway_iou), L = the library's
-    number of sets with labels="set", the longest candidate list seen with labels="local".  Processing size only (native-size
-    scoring of candidates is not built); single process, no sharding."""
+    number of sets with labels="set", the longest candidate list seen with labels="local".
+    use_original_imgsize: every item is (query_img, candidates, input_pipeline.NativeTargets) -- the b queries' own sizes
+    and their ground truth at those sizes, label maps or, with class_ids (the ground-truth id of each set), class-id maps
+    -- and the running sum is fed from r["native"]["counts"] (ops.seg_labels_cand_native): labels scored at every image's
+    own h x w.  Single process, no sharding."""
     from .metrics import nway_iou
     total = torch.zeros(2, 255, dtype=torch.int64, device=pipe.device)
     width = library.nsets + 1 if labels == "set" else 0
+    if class_ids is not None and not use_original_imgsize:
+        raise ValueError("class_ids maps a native-size ground truth: give use_original_imgsize=True with it")
     for query_img, candidates, label_map in items:
-        r = pipe.segment_candidates(library, query_img, candidates, label_map, r_threshold=r_threshold, threshold=threshold,
-                                    entry_batch=entry_batch, labels=labels, captured=captured)
-        n = r["counts"].shape[2]
-        total[:, :n] += r["counts"].sum(0)
+        if use_original_imgsize:
+            r = pipe.segment_candidates_native(library, query_img, candidates, label_map, class_ids, r_threshold=r_threshold,
+                                               threshold=threshold, entry_batch=entry_batch, labels=labels, captured=captured)
+            counts = r["native"]["counts"]
+            if counts is None:
+                raise ValueError("use_original_imgsize needs NativeTargets that carry a ground truth")
+        else:
+            r = pipe.segment_candidates(library, query_img, candidates, label_map, r_threshold=r_threshold,
+                                        threshold=threshold, entry_batch=entry_batch, labels=labels, captured=captured)
+            counts = r["counts"]
+        n = counts.shape[2]
+        total[:, :n] += counts.sum(0)
         width = max(width, n)
     total = total[:, :width].contiguous()
     iou, miou = nway_iou(total)

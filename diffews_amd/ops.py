@@ -883,6 +883,103 @@ def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_ma
     return dict(labels=lab, counts=counts, mx=mx, seg_u8=planes, sizes=list(targets.sizes))
 
 
+def cand_native_workspace(targets, K, want_u8=False):
+    """(tmp bytes, tmp_res_off, out_u8 bytes) of seg_labels_cand_native for a longest candidate list of K entries: K
+    strides of targets.tmp_bytes for the horizontal intermediates and K of targets.u8_bytes for the resized bytes -- behind
+    the intermediates in tmp, or in out_u8 with want_u8.  K, not E_cap: a query's entries share the strides by position."""
+    K = max(int(K), 1)
+    tmp_part, u8_part = K * targets.tmp_bytes, K * targets.u8_bytes
+    return (tmp_part if want_u8 else tmp_part + u8_part), tmp_part, (u8_part if want_u8 else 0)
+
+
+def seg_labels_cand_native(seg_u8, targets, tab, tab_host, nlabels, r_threshold=0.25, threshold=0.0, class_ids=None,
+                           entry_ids=None, want_area=False, want_u8=False, labels_out=None, u8_out=None, tmp=None):
+    """Candidate classes per query at every query's own size: seg_u8 uint8 [E_cap, 3, Hs, Ws], entry-major, and `tab` /
+    `tab_host` as seg_labels_cand takes them (offsets off[0..b], then the label byte of every entry; the device table is
+    read when the kernels run, the host mirror is validated).  Every entry is resized to ITS query's h x w as
+    seg_labels_native resizes a class (Pillow's default BICUBIC, exact), then seg_labels_cand's rule runs on the RESIZED
+    bytes: thresholds from the maxima of the resized planes, label = lab[e] of the foreground entry with the largest
+    score, earliest entry on a tie, 0 with none.
+
+    targets: input_pipeline.NativeTargets for the b queries and this (Hs, Ws).  With a ground truth it is read in place
+    at native size; pixels equal to the targets' ignore_value are dropped, and an id becomes a label
+      with neither table: as it is (ids outside 0..nlabels dropped);
+      class_ids (nlabels ints or an int32 tensor; labels are 1 + set index): 1 + the lowest c with class_ids[c] == id,
+        every other id background -- a class outside the query's candidates is a miss in its own label's union;
+      entry_ids (E_cap ints or an int32 tensor: the ground-truth id of every entry's class; labels local to the query):
+        the label of the query's earliest entry with that id, every other id background (local labels have no bin for a
+        class the query did not name).
+    Giving both is a ValueError.  Four launches whatever b and E.  The workspace is K strides, K the longest list
+    (cand_native_workspace).  Returns dict(labels=[uint8 views [h_i, w_i]], counts=int64 [b, 2, nlabels+1] or None,
+    area=int64 [E_cap, 2] or None (want_area; counted on the resized bytes), mx=int32 [E_cap] resized maxima,
+    seg_u8=[uint8 views [K_i, 3, h_i, w_i], K_i the query's entries] or None (want_u8), sizes=[(h_i, w_i)])."""
+    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    E_cap, _, Hs, Ws = seg_u8.shape
+    for name, t in (("tab", tab), ("tab_host", tab_host)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
+            raise ValueError(f"seg_labels_cand_native: {name} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
+    if tab.numel() != tab_host.numel():
+        raise ValueError(f"seg_labels_cand_native: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
+    if not tab.is_cuda or tab.device != seg_u8.device or tab_host.device.type != "cpu":
+        raise ValueError("seg_labels_cand_native: tab lives with seg_u8 on the device, tab_host on the host")
+    if class_ids is not None and entry_ids is not None:
+        raise ValueError("seg_labels_cand_native: give class_ids (labels = 1 + set index) or entry_ids (local labels), not both")
+    b, nlabels = tab.numel() - 1 - E_cap, int(nlabels)
+    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
+        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, the table names {b} and seg_u8 "
+                         f"is {tuple(seg_u8.shape)}")
+    dev = seg_u8.device
+    if not torch.cuda.is_current_stream_capturing():
+        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
+
+    def buf(given, n):
+        if given is None:
+            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+        return given
+
+    def ids(t, n, name):
+        if t is None:
+            return None
+        t = torch.as_tensor(t, dtype=torch.int32).to(dev).contiguous()
+        if t.shape != (n,):
+            raise ValueError(f"{name} must hold {n} ids, got {tuple(t.shape)}")
+        return t
+    class_ids, entry_ids = ids(class_ids, nlabels, "class_ids"), ids(entry_ids, E_cap, "entry_ids")
+    off = tab_host[:b + 1].tolist()
+    K = max(max(hi - lo for lo, hi in zip(off, off[1:])), 1)
+    tmp_bytes, tmp_res_off, u8_bytes = cand_native_workspace(targets, K, want_u8)
+    a = L.SegLabelsCandNativeArgs()
+    u8 = buf(u8_out, u8_bytes) if want_u8 else None
+    tmp = buf(tmp, tmp_bytes)
+    labels = buf(labels_out, targets.pred_bytes)
+    gt, gt_bytes = targets.gt_base
+    counts = torch.empty(b, 2, nlabels + 1, dtype=torch.int64, device=dev) if gt is not None else None
+    area = torch.empty(E_cap, 2, dtype=torch.int64, device=dev) if want_area else None
+    mx = torch.empty(E_cap, dtype=torch.int32, device=dev)
+    a.seg_u8, a.B, a.E_cap, a.nlabels, a.Hs, a.Ws = seg_u8.data_ptr(), b, E_cap, nlabels, Hs, Ws
+    a.tab, a.tab_host = tab.data_ptr(), tab_host.data_ptr()
+    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
+    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
+    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
+    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), tmp_res_off
+    a.tmp_cls_stride, a.u8_cls_stride = targets.tmp_bytes, targets.u8_bytes
+    if u8 is not None:
+        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
+    a.labels, a.labels_bytes = labels.data_ptr(), labels.numel()
+    a.mx, a.counts, a.area = mx.data_ptr(), _p(counts), _p(area)
+    a.class_ids, a.entry_ids = _p(class_ids), _p(entry_ids)
+    a.r_threshold, a.threshold = float(r_threshold), float(threshold)
+    L.check(L.lib().dfw_seg_labels_cand_native(C.byref(a), _stream()), "dfw_seg_labels_cand_native")
+    lab = [labels[it.pred_off:it.pred_off + it.h * it.w].view(it.h, it.w) for it in targets.items]
+    planes = None
+    if u8 is not None:
+        per = u8[:K * targets.u8_bytes].view(K, targets.u8_bytes)
+        planes = [per[:hi - lo, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w))
+                  for it, lo, hi in zip(targets.items, off, off[1:])]
+    return dict(labels=lab, counts=counts, area=area, mx=mx, seg_u8=planes, sizes=list(targets.sizes))
+
+
 def _tile_plan(plan):
     """input_pipeline.TilePlan (or a ready _lib.TilePlan record) -> the record, its T."""
     c = plan if isinstance(plan, L.TilePlan) else plan.c_struct()

@@ -660,7 +660,36 @@ class MarigoldPipelineRGBLatentNoise:
         the other query steps.
 
         entry_batch = 8 is a choice, not a measurement.  It bounds the decoder's batch: 16 entries at 512 x 512 reach the
-        VAE decoder's 2 GiB buffer-descriptor range (DFW_ERANGE)."""
+        VAE decoder's 2 GiB buffer-descriptor range (DFW_ERANGE).
+
+        segment_candidates_native is this call plus labels and counts at every query's own size."""
+        return self._segment_candidates(bankset, query_img, candidates, query_labels, r_threshold, threshold, entry_batch,
+                                        labels, captured)
+
+    @torch.no_grad()
+    def segment_candidates_native(self, bankset, query_img, candidates, native, class_ids=None, query_labels=None,
+                                  r_threshold=0.25, threshold=0.0, entry_batch=8, labels="set", captured=None):
+        """segment_candidates with its result scored at every query's OWN size: the same arguments, the same step, the same
+        graph and key, and the same dict with one more entry.
+
+        native (input_pipeline.NativeTargets for these b queries): the dict gains `native` = dict(labels [uint8 [h_i, w_i]],
+        counts int64 [b, 2, nlabels+1] or None, area int64 [E, 2], mx int32 [E], sizes) -- ops.seg_labels_cand_native on the
+        step's seg_u8 and this call's table and flags: every entry resized to its query's own h x w, the label rule on the
+        resized bytes, counts against the targets' ground truth read in place.  As in segment_classes it runs eagerly on
+        the same stream after the step, captured or not, and is neither part of the graph nor of its key; every other
+        entry is bit for bit what segment_candidates returns.  ValueError without `native`.  class_ids: the
+        ground-truth id of each SET, nsets ints, for targets that hold class-id maps.  With labels="set" it is the table
+        from id to label 1 + set; a class outside the query's candidates is a miss in its label's union.  With
+        labels="local" it is gathered per entry, and an id none of the query's candidates carries is background (local
+        labels have no bin for it).  Without class_ids the targets hold label maps in the labels the call writes."""
+        if native is None:
+            raise ValueError("segment_candidates_native needs NativeTargets for the queries; without them call segment_candidates")
+        return self._segment_candidates(bankset, query_img, candidates, query_labels, r_threshold, threshold, entry_batch,
+                                        labels, captured, native, class_ids)
+
+    def _segment_candidates(self, bankset, query_img, candidates, query_labels, r_threshold, threshold, entry_batch, labels,
+                            captured, native=None, class_ids=None):
+        """The body of segment_candidates / segment_candidates_native (callers hold torch.no_grad)."""
         from .unet import SupportBankSet
         if not isinstance(bankset, SupportBankSet):
             raise ValueError("segment_candidates needs a SupportBankSet (prepare_support_classes)")
@@ -712,13 +741,27 @@ class MarigoldPipelineRGBLatentNoise:
             lab, counts, area = ops.seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, query_labels, *flags, want_area=True)
             z0 = z0s[0] if len(z0s) == 1 else torch.cat(z0s)
             dec = decs[0] if len(decs) == 1 else torch.cat(decs)
-            return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=lab, counts=counts, area=area)
+            return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=lab, counts=counts, area=area, tab=tab)
+
+        ids_kw = {}
+        if class_ids is not None:
+            ids = torch.as_tensor(class_ids, dtype=torch.int32)
+            if ids.shape != (bankset.nsets,):
+                raise ValueError(f"class_ids must hold one id per set ({bankset.nsets}), got {tuple(ids.shape)}")
+            # "set": the table from id to label 1 + set; "local": the id of every entry's own set
+            ids_kw = dict(class_ids=ids) if labels == "set" else \
+                dict(entry_ids=ids[ct["entry_sets"].to(ids.device, non_blocking=True).long()])
 
         def trimmed(r):       # the padding entries are dropped from what the caller sees; the candidates are the call's own
             out = {k: r[k][:E] for k in ("z0", "dec", "seg_u8", "area")}
             out.update(labels=r["labels"], counts=r["counts"],
                        entries=[(i, c) for i, cs in enumerate(ct["sets"]) for c in cs],
                        offsets=ct["tab"][:b + 1].tolist())
+            if native is not None:
+                # eagerly after the step, on its seg_u8 (padding entries included: the table never names them) and its table
+                n = ops.seg_labels_cand_native(r["seg_u8"], native, r["tab"], tab_host, nlabels, *flags, want_area=True, **ids_kw)
+                out["native"] = dict(labels=n["labels"], counts=n["counts"], area=n["area"][:E], mx=n["mx"][:E],
+                                     sizes=n["sizes"])
             return out
         if captured is None:
             captured = self.use_graph
@@ -739,7 +782,7 @@ class MarigoldPipelineRGBLatentNoise:
 
     def segment_stream(self, support, queries, batch=4, size=None, depth=2, class_value=None, ignore_value=-1,
                        class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None,
-                       route=None, candidates=None, entry_batch=8, labels="set"):
+                       route=None, candidates=None, entry_batch=8, labels="set", native=False):
         """Generator: a stream of decoded images against one prepared support -- `support` a SupportBank (prepare_support;
         routed to segment_queries) or a SupportBankSet (prepare_support_classes; routed to segment_classes, with
         `class_ids` and `max_batch`).  `queries` yields dicts with `query_img` (PIL / uint8 [H, W, 3], any size) and
@@ -767,8 +810,11 @@ class MarigoldPipelineRGBLatentNoise:
         of the library's classes, a different handful per query.  Every batch then goes through segment_candidates with
         `entry_batch` and `labels` (r is its dict, plus `candidates`, the batch's lists as given).  The ground truth of
         the processing-size r["counts"] is q["labels"] when the queries carry one: a label map ALREADY at the processing
-        size, in the labels the call writes.  Native-size labels and counts are not computed on this route: r["native"]
-        is absent, and `class_value`, `class_ids` and `batch_max` do not apply (ValueError when given)."""
+        size, in the labels the call writes.  `class_value` and `batch_max` do not apply (ValueError when given).
+        native (read with `candidates` only -- the other routes always return `native`; default False, and then r has no
+        `native` and `class_ids` is a ValueError): every batch goes through segment_candidates_native with the loader's
+        NativeTargets, so r["native"] holds the native-size labels, area and -- when the queries carry `gt` -- counts against it read in place from the batch's staged bytes; `class_ids` is then the
+        ground-truth id of each set, as segment_candidates_native takes it."""
         from .input_pipeline import QueryLoader
         from .unet import SupportBank, SupportBankSet
         if not isinstance(support, (SupportBank, SupportBankSet)):
@@ -788,15 +834,23 @@ class MarigoldPipelineRGBLatentNoise:
                 raise ValueError("candidates name sets of a SupportBankSet; a SupportBank has only one")
             if route is not None:
                 raise ValueError("give `route` (one set per query, a binary mask) or `candidates` (a label map), not both")
-            if class_ids is not None or batch_max:
-                raise ValueError("class_ids and batch_max do not apply to candidates (no native-size pass, no batch_max form)")
+            if batch_max:
+                raise ValueError("batch_max does not apply to candidates (there is no batch_max form)")
+            if class_ids is not None and not native:
+                raise ValueError("class_ids maps the ground truth of the native-size pass: give native=True with it")
+            if class_ids is not None:     # staged once, not per batch
+                class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
             cand_of = candidates if callable(candidates) else (lambda q, _k=candidates: q[_k])
             loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, ignore_value=ignore_value,
                                  candidates=cand_of)
             for bt in loader:
-                r = dict(self.segment_candidates(support, bt["query_img"], bt["candidates"], bt.get("query_labels"),
-                                                 r_threshold=r_threshold, threshold=threshold, entry_batch=entry_batch,
-                                                 labels=labels, captured=captured))
+                kw = dict(query_labels=bt.get("query_labels"), r_threshold=r_threshold, threshold=threshold,
+                          entry_batch=entry_batch, labels=labels, captured=captured)
+                if native:
+                    r = dict(self.segment_candidates_native(support, bt["query_img"], bt["candidates"], bt["native"],
+                                                            class_ids, **kw))
+                else:
+                    r = dict(self.segment_candidates(support, bt["query_img"], bt["candidates"], **kw))
                 r["candidates"] = bt["candidates"]
                 yield bt["index"], r
             return

@@ -270,7 +270,10 @@ class SupportBankSet:
             entries  int64 [E_pad]          the query index of each entry
             rows     int32 [E_pad, 2]       (first image, shots) of the entry's set, built as route_table builds them
             tab      int32 [b + 1 + E_pad]  ops.seg_labels_cand's table: offsets off[0..b], then the label of every entry
-            E, E_pad, nlabels, sets (the sorted lists, a tuple of tuples)
+            entry_sets int32 [E_pad]        the set index of each entry (padding repeats the last): gathered through a
+                                            list of one ground-truth id per set it is ops.seg_labels_cand_native's entry_ids
+            E, E_pad, nlabels, sets (the sorted lists, a tuple of tuples), K (the longest list: what sizes
+            ops.seg_labels_cand_native's workspace)
         labels="set": lab = 1 + set index, nlabels = nsets (ValueError when nsets > 254: a label is a byte -- use "local").
         labels="local": lab = 1 + position in the query's sorted list, nlabels = the longest list; this is how a library
         of more than 254 classes is used, and the caller's ground truth is then in local labels."""
@@ -297,19 +300,23 @@ class SupportBankSet:
         if E == 0:
             raise ValueError("candidate_tables: no candidate for any query")
         E_pad = -(-E // entry_batch) * entry_batch
-        entries, rows, off, lab = [], [], [0], []
+        entries, rows, off, lab, esets = [], [], [0], [], []
         for i, cs in enumerate(sets):
             for pos, c in enumerate(cs):
                 entries.append(i)
+                esets.append(c)
                 rows.append([self.offsets[c], self.shots[c]])
                 lab.append(1 + (c if labels == "set" else pos))
             off.append(len(entries))
         entries += [entries[-1]] * (E_pad - E)
         rows += [rows[-1]] * (E_pad - E)
         lab += [0] * (E_pad - E)
-        nlabels = self.nsets if labels == "set" else max(len(cs) for cs in sets)
+        esets += [esets[-1]] * (E_pad - E)
+        K = max(len(cs) for cs in sets)
+        nlabels = self.nsets if labels == "set" else K
         return dict(entries=torch.tensor(entries, dtype=torch.int64), rows=torch.tensor(rows, dtype=torch.int32),
-                    tab=torch.tensor(off + lab, dtype=torch.int32), E=E, E_pad=E_pad, nlabels=nlabels, sets=tuple(sets))
+                    tab=torch.tensor(off + lab, dtype=torch.int32), E=E, E_pad=E_pad, nlabels=nlabels, sets=tuple(sets),
+                    K=K, entry_sets=torch.tensor(esets, dtype=torch.int32))
 
     @staticmethod
     def stack(banks, ragged=False):

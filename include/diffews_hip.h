@@ -586,6 +586,69 @@ typedef struct {
  * class plane's extent -> DFW_EWORKSPACE. */
 int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_stream_t stream);
 
+/* Candidate classes per query at native size (version >= 112): dfw_seg_labels_native's resize for the ENTRIES of
+ * dfw_seg_labels_cand, then dfw_seg_labels_cand's rule on the RESIZED bytes.  seg_u8 [E_cap][3][Hs][Ws] is entry-major
+ * and `tab` / `tab_host` are the same int32 [B + 1 + E_cap] table and host mirror as dfw_seg_labels_cand takes: offsets
+ * off[0 .. B], then lab[e]; entries e >= E = off[B] are padding and never read.  The ragged batch is the same
+ * dfw_native_item [B] table, weights and in-place ground truth as dfw_seg_labels_native: entry e of query q uses item q
+ * (its class_value is not read).  Position k = e - off[q] in the query's list plays the part class c plays there: the
+ * horizontal intermediates of entry e lie at tmp + k * tmp_cls_stride + tmp_off and its resized bytes at out_u8 (or
+ * tmp + tmp_res_off) + k * u8_cls_stride + u8_off, so the workspace is K strides with K the LONGEST list, not E_cap:
+ *   tmp_cls_stride >= max_i(tmp_off_i + 3 * Hs * w_i), u8_cls_stride >= max_i(u8_off_i + 3 * h_i * w_i), and
+ *   (K - 1) * stride + that extent inside tmp (tmp_res_off without out_u8) / inside out_u8 (tmp_bytes - tmp_res_off).
+ *   score_e = ((u0/255.0f + u1/255.0f) + u2/255.0f) / 3.0f from the resized bytes; e is foreground when score_e > thr_e,
+ *   thr_e = (mx[e]/255.0f) * r_threshold when r_threshold > 0, else the fixed `threshold` (there is no batch_max form);
+ *   label = 0 with no foreground entry, else lab[e] of the foreground entry with the largest score, earliest e on a tie;
+ *   a query with no entries gets labels 0.
+ * Ground truth (with counts): read in place at native size, gt_elem 1 or 4; a pixel equal to the item's ignore_value (when
+ * >= 0) is dropped.  The id of every other pixel becomes a label in one of three ways:
+ *   neither table   the id is the label; ids outside 0..nlabels are dropped;
+ *   class_ids       device int32 [nlabels] (labels are 1 + set index): 1 + the lowest c with class_ids[c] == id, every
+ *                   other id background -- a class that is not among the query's candidates still counts in its own
+ *                   label's union, as a miss, as in dfw_seg_labels_cand;
+ *   entry_ids       device int32 [E_cap] (labels are local to the query): lab[e] of the earliest entry e OF THIS QUERY with
+ *                   entry_ids[e] == id, every other id background -- local labels have no bin for a class the query did
+ *                   not name, so such a pixel is background (a false positive where it is labelled, never a miss).
+ * counts [B][2][nlabels+1]: row 0 label == gt == l, row 1 pred_l + gt_l - inter_l.  area [E_cap][2]: per entry, pixels of
+ * the RESIZED image where e is foreground on its own and where e won the label; ignore pixels included, rows e >= E 0.
+ * The kernels read `tab` when they run and clamp what they read (0 <= lo <= hi <= E_cap, hi - lo <= min(254, K), the
+ * query of an entry inside 0 .. B-1, its position inside 0 .. K-1 with K from the host mirror): a table rewritten after
+ * the call gives wrong numbers, never an access outside the buffers. */
+typedef struct {
+  const uint8_t* seg_u8;               /* device, planar [E_cap][3][Hs][Ws], entry-major */
+  int32_t B, E_cap, nlabels, Hs, Ws;
+  const int32_t* tab;                  /* device, int32 [B + 1 + E_cap]: what the kernels read */
+  const int32_t* tab_host;             /* host mirror of the same table: what this call validates */
+  const void* items;                   /* device, dfw_native_item [B]: what the kernels read */
+  const void* items_host;              /* host mirror of the same table: what this call validates */
+  const uint8_t* weights; size_t weights_bytes;   /* device base of the bounds / coefficient offsets */
+  const uint8_t* gt; size_t gt_bytes;             /* device base of the ground-truth offsets; required with counts */
+  uint8_t* tmp; size_t tmp_bytes;                 /* device scratch */
+  size_t tmp_res_off;                  /* without out_u8 the resized bytes are staged from tmp + tmp_res_off */
+  size_t tmp_cls_stride;               /* bytes between two list positions' horizontal intermediates */
+  size_t u8_cls_stride;                /* bytes between two list positions' resized bytes */
+  uint8_t* out_u8; size_t out_u8_bytes;           /* optional: per list position, packed planar [3][h_i][w_i] per query */
+  uint8_t* labels; size_t labels_bytes;           /* packed [h_i][w_i] label bytes, at the items' pred_off */
+  uint32_t* mx;                        /* optional, [E_cap]: maximum of each entry's resized planes; required with
+                                          r_threshold > 0.  Zeroed by this call. */
+  int64_t* counts;                     /* optional, [B][2][nlabels+1]; zeroed by this call */
+  int64_t* area;                       /* optional, [E_cap][2]; zeroed by this call */
+  const int32_t* class_ids;            /* optional, device int32 [nlabels]: ground-truth id of label 1 + c */
+  const int32_t* entry_ids;            /* optional, device int32 [E_cap]: ground-truth id of entry e's class */
+  float r_threshold, threshold;        /* as dfw_seg_labels_cand; the maximum is the RESIZED planes' */
+} dfw_seg_labels_cand_native_args;
+
+/* Four launches whatever B and E: zero (mx / counts / area, a library kernel), horizontal pass and vertical pass + maximum
+ * over the E planes-of-3 (grid z = E from the host mirror), label + count + area over the B queries.  Everything is
+ * validated on the host before the first launch, with dfw_seg_labels_native's and dfw_seg_labels_cand's codes: null
+ * pointers / sizes < 1 / nlabels outside 1..254 / counts without gt / class_ids together with entry_ids / r_threshold > 0
+ * without mx / neither threshold > 0 / a bad table (offsets not from 0, decreasing, above E_cap, more than 254 entries a
+ * query, lab[e] outside 1..nlabels for e < E) / h or w < 1 / gt_elem not 1 or 4 -> DFW_EINVAL; ksize mismatch or a
+ * misaligned offset -> DFW_ESHAPE; h, w, Hs, Ws or B above 65535, E_cap above 2^24, E above 65535 -> DFW_ERANGE; an extent
+ * that leaves its buffer, a stride smaller than one position's extent, or (K - 1) * stride + extent outside its buffer ->
+ * DFW_EWORKSPACE. */
+int dfw_seg_labels_cand_native(const dfw_seg_labels_cand_native_args* a, dfw_stream_t stream);
+
 /*
  * Input transform of a whole ragged batch (version >= 107): dfw_image_to_tensor for n_img RGB images and
  * dfw_mask_to_tensor for n_mask class-id maps of assorted sizes, all going to one out_h x out_w, driven by two
