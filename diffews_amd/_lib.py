@@ -287,6 +287,8 @@ SYMBOLS = {
     "dfw_inputs_to_tensor": (_i32, [C.POINTER(InputsArgs), _vp]),
     "dfw_tiles_cut": (_i32, [C.POINTER(TilePlan), _vp, _vp, _vp, _i32, _i32, _vp]),
     "dfw_tiles_merge": (_i32, [C.POINTER(TilePlan), _vp, _i32, _vp, _vp, _vp]),
+    "dfw_tiles_labels_cand": (_i32, [C.POINTER(TilePlan), _vp, _vp, C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32,
+                                     _f32, _vp]),
 }
 
 _lib = None

@@ -1012,7 +1012,7 @@ extern "C" void dfw_get_config(dfw_config* out) {
   if (out) *out = g_cfg;
 }
 
-extern "C" int dfw_version(void) { return 112; }
+extern "C" int dfw_version(void) { return 113; }
 
 extern "C" const char* dfw_error_string(int code) {
   switch (code) {

@@ -262,11 +262,12 @@ def evaluate_candidates(pipe, library, items, r_threshold=0.25, threshold=0.0, e
 
 @torch.no_grad()
 def evaluate_tiled(pipe, support, items, class_id=0, benchmark="coco", fold=0, overlap=None, ramp=None, batch=4,
-                   r_threshold=0.25, threshold=0.0, max_batch=16, captured=True):
+                   r_threshold=0.25, threshold=0.0, max_batch=16, captured=True, entry_batch=8):
     """Images larger than the processing size against one prepared support, each segmented at its own resolution by
     pipe.segment_tiled (`overlap`, `ramp`, `batch`, `max_batch`, the thresholding flags and `captured` are its arguments).
     `items` yields (image, gt): PIL / uint8 [h, w, 3] of any size not below the tile, and a uint8 [h, w] label map (0 =
-    background, 1 + c = class c, 255 = ignored; 0 / 1 / 255 for a bank).
+    background, 1 + c = class c, 255 = ignored; 0 / 1 / 255 for a bank).  An item may be (image, gt, candidates): that
+    item goes through segment_tiled's candidate route (a SupportBankSet only) with `entry_batch`; the returns are unchanged.
 
     support a SupportBank: the counts go into the AverageMeter under `class_id` (the support set's class index); returns
     (miou, fb_iou, meter) as evaluate_stream does for one support set.  A SupportBankSet: the counts are summed into one
@@ -278,18 +279,23 @@ def evaluate_tiled(pipe, support, items, class_id=0, benchmark="coco", fold=0, o
     if not isinstance(support, SupportBankSet):
         meter = AverageMeter(benchmark, fold_class_ids(benchmark, fold), device=device)
         cls = torch.full((1,), int(class_id), dtype=torch.int64, device=device)
-        for image, gt in items:
+        for item in items:
+            image, gt = item[0], item[1]
             if gt is None:
                 raise ValueError("evaluate_tiled needs items that carry a ground truth")
+            if len(item) > 2:
+                raise ValueError("candidates name sets of a SupportBankSet; a SupportBank has only one")
             meter.update_from_counts(pipe.segment_tiled(support, image, gt, **flags)["counts"].view(1, 4), cls)
         meter.all_reduce()
         miou, fb_iou, _ = meter.compute_iou()
         return float(miou), float(fb_iou), meter
     from .metrics import nway_iou
     total = torch.zeros(2, support.nsets + 1, dtype=torch.int64, device=device)
-    for image, gt in items:
+    for item in items:
+        image, gt = item[0], item[1]
         if gt is None:
             raise ValueError("evaluate_tiled needs items that carry a ground truth")
-        total += pipe.segment_tiled(support, image, gt, **flags)["counts"]
+        cand = dict(candidates=item[2], entry_batch=entry_batch) if len(item) > 2 else {}
+        total += pipe.segment_tiled(support, image, gt, **flags, **cand)["counts"]
     iou, miou = nway_iou(total)
     return miou, iou, total

@@ -196,6 +196,59 @@ class TilePlan:
         """Bytes of the [N, T, 3, th, tw] buffer segment_tiled keeps the windows' seg_u8 in: 3 * th * tw per window and class."""
         return 3 * self.tile_h * self.tile_w * self.T * int(nclass)
 
+    def candidate_table(self, candidates, nsets):
+        """The table of ops.tiles_labels_cand for per-window candidate classes: `candidates` is T sequences of set indices,
+        the classes window t is segmented against (sorted here; a window may have none, and so may all of them).
+        ValueError for a number of lists other than T, a duplicate within a list, an index outside [0, nsets), nsets > 254
+        (a label is a byte).  Returns dict(tab int32 [T + 1 + max(E, 1)] = offsets off[0..T] then the class of every
+        entry, E = the number of (window, class) entries, sets = the sorted lists, a tuple of tuples)."""
+        nsets = int(nsets)
+        if not 1 <= nsets <= 254:
+            raise ValueError(f"candidate_table: a label is a byte, nsets must be in 1..254, got {nsets}")
+        candidates = list(candidates)
+        if len(candidates) != self.T:
+            raise ValueError(f"candidate_table: {len(candidates)} candidate lists for {self.T} windows")
+        sets, off, cls = [], [0], []
+        for t, cand in enumerate(candidates):
+            cs = sorted(int(c) for c in (cand.tolist() if isinstance(cand, (torch.Tensor, np.ndarray)) else cand))
+            for c in cs:
+                if not 0 <= c < nsets:
+                    raise ValueError(f"candidate_table: window {t} names set {c} of {nsets}")
+            if len(set(cs)) != len(cs):
+                raise ValueError(f"candidate_table: window {t} names a set twice ({cs})")
+            sets.append(tuple(cs))
+            cls += cs
+            off.append(len(cls))
+        E = len(cls)
+        return dict(tab=torch.tensor(off + cls + [0] * (max(E, 1) - E), dtype=torch.int32), E=E, sets=tuple(sets))
+
+    def candidates_from_labels(self, label_map, min_pixels=1, margin=0):
+        """Per-window candidate lists from a label map of ANY size: label_map uint8 [lh, lw], 0 and 255 ignored, 1 + c =
+        class c (a coarse pass' labels, or a ground truth).  Window t's footprint in the map is rows (y0 * lh) // h up to
+        ceil((y0 + th) * lh / h) and the columns alike -- at least one pixel, grown by `margin` map pixels on every side,
+        clipped to the map; at (lh, lw) = (h, w) and margin 0 it is the window's exact crop.  Returns T lists: the
+        ascending classes with at least `min_pixels` pixels inside the footprint."""
+        lm = np.asarray(label_map.cpu() if torch.is_tensor(label_map) else label_map)
+        if lm.dtype != np.uint8 or lm.ndim != 2 or lm.size == 0:
+            raise ValueError(f"candidates_from_labels: label_map must be a non-empty uint8 [lh, lw], got {lm.dtype} {lm.shape}")
+        lh, lw = lm.shape
+        margin, min_pixels = int(margin), max(1, int(min_pixels))
+        if margin < 0:
+            raise ValueError(f"candidates_from_labels: margin must be >= 0, got {margin}")
+
+        def span(o, tile, full, n):
+            a, b = (o * n) // full, -(-((o + tile) * n) // full)
+            b = max(b, a + 1)
+            return max(0, a - margin), min(n, b + margin)
+        out = []
+        for t in range(self.T):
+            y0, x0 = self.origin(t)
+            ya, yb = span(y0, self.tile_h, self.img_h, lh)
+            xa, xb = span(x0, self.tile_w, self.img_w, lw)
+            n = np.bincount(lm[ya:yb, xa:xb].ravel(), minlength=256)
+            out.append([c - 1 for c in range(1, 255) if n[c] >= min_pixels])
+        return out
+
     def c_struct(self):
         """The dfw_tile_plan of this plan (a fresh ctypes record)."""
         p = L.TilePlan()

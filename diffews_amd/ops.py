@@ -1024,3 +1024,53 @@ def tiles_merge(plan, win, out=None, mx=None):
     L.check(L.lib().dfw_tiles_merge(C.byref(c), win.data_ptr(), N, out.data_ptr(), mx.data_ptr(), _stream()),
             "dfw_tiles_merge")
     return out, mx
+
+
+def tiles_labels_cand(plan, ent, tab, tab_host, N, gt=None, r_threshold=0.25, threshold=0.0, want_area=False,
+                      labels_out=None, counts_out=None, mx_out=None, area_out=None):
+    """tiles_merge + seg_labels over a SPARSE set of (window, class) entries: ent uint8 [E_cap, 3, th, tw], entry-major, the
+    entries of one window adjacent in ascending class (None when no window lists anything); `tab` a DEVICE int32
+    [T + 1 + E_cap] tensor -- offsets off[0..T] (window t owns entries [off[t], off[t+1])), then the class 0..N-1 of every
+    entry -- and `tab_host` its host mirror, validated by the library before the launch (input_pipeline.TilePlan.
+    candidate_table builds it).  A (window, class) pair that is not listed counts as an all-zero mask, so the result is bit
+    for bit tiles_merge + seg_labels on the dense [N, T, 3, th, tw] buffer that holds the entries and zeros elsewhere --
+    the blend weight of a window counts at every pixel it covers, whatever it lists -- without that buffer and without the
+    merged [N, 3, h, w] image.  gt: optional uint8 [h, w] as seg_labels takes it.
+
+    Returns (labels uint8 [h, w], counts int64 [2, N+1] or None, mx int32 [N] = the maximum byte of every class' merged
+    image, area int64 [N, 2] or None = per class (pixels foreground on its own, pixels where it won), ignore pixels
+    included).  Two or three launches, no memset node; labels_out / counts_out / mx_out / area_out: caller-owned buffers."""
+    c, T = _tile_plan(plan)
+    N = int(N)
+    for name, t in (("tab", tab), ("tab_host", tab_host)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < T + 2:
+            raise ValueError(f"tiles_labels_cand: {name} must be a contiguous int32 [{T} + 1 + E_cap] tensor")
+    if tab.numel() != tab_host.numel():
+        raise ValueError(f"tiles_labels_cand: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
+    if not tab.is_cuda or tab_host.device.type != "cpu":
+        raise ValueError("tiles_labels_cand: tab lives on the device, tab_host on the host")
+    E_cap, dev = tab.numel() - T - 1, tab.device
+    if ent is not None:
+        assert ent.dtype == torch.uint8 and ent.is_contiguous() and ent.device == dev
+        if tuple(ent.shape) != (E_cap, 3, c.tile_h, c.tile_w):
+            raise ValueError(f"tiles_labels_cand: ent must be [{E_cap}, 3, {c.tile_h}, {c.tile_w}] for a table of {tab.numel()} "
+                             f"words, got {tuple(ent.shape)}")
+    hw = (c.img_h, c.img_w)
+
+    def buf(given, shape, dtype):
+        if given is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        assert given.dtype == dtype and given.is_contiguous() and tuple(given.shape) == shape and given.device == dev
+        return given
+    labels = buf(labels_out, hw, torch.uint8)
+    mx = buf(mx_out, (N,), torch.int32)
+    counts = None
+    if gt is not None:
+        assert gt.dtype == torch.uint8 and gt.is_contiguous() and tuple(gt.shape) == hw and gt.device == dev
+        counts = buf(counts_out, (2, N + 1), torch.int64)
+    area = buf(area_out, (N, 2), torch.int64) if want_area or area_out is not None else None
+    host = C.cast(tab_host.data_ptr(), C.POINTER(C.c_int32))
+    L.check(L.lib().dfw_tiles_labels_cand(C.byref(c), _p(ent), tab.data_ptr(), host, _p(gt), labels.data_ptr(),
+                                          mx.data_ptr(), _p(counts), _p(area), E_cap, N, float(r_threshold),
+                                          float(threshold), _stream()), "dfw_tiles_labels_cand")
+    return labels, counts, mx, area

@@ -889,7 +889,7 @@ class MarigoldPipelineRGBLatentNoise:
 
     @torch.no_grad()
     def segment_tiled(self, support, image, gt=None, overlap=None, ramp=None, batch=4, r_threshold=0.25, threshold=0.0,
-                      max_batch=16, captured=None):
+                      max_batch=16, captured=None, candidates=None, entry_batch=8):
         """One image LARGER than the processing size, segmented at its own resolution: `image` (PIL / uint8 [h, w, 3]) is
         covered with overlapping windows of the size `support` was prepared at (input_pipeline.TilePlan: `overlap`, default
         min(tile) // 8, and `ramp`), every window is one query of segment_queries (`support` a SupportBank) or
@@ -908,12 +908,32 @@ class MarigoldPipelineRGBLatentNoise:
         `pred` is an alias of `labels` and counts is int64 [4] in seg_postprocess' order (inter0, inter1, union0, union1);
         for a set counts is int64 [2, N+1] (metrics.nway_iou); counts is None without gt.  There is no batch_max: the
         merged image has one maximum per class.  Scheduler restriction, stale-handle errors and `captured` as in the
-        routed calls; an image smaller than the tile in either axis is a ValueError (segment_stream resizes)."""
+        routed calls; an image smaller than the tile in either axis is a ValueError (segment_stream resizes).
+
+        candidates (a SupportBankSet only, else ValueError; default None: everything above, launch for launch): T lists of
+        set indices, or a callable on the TilePlan that returns them (plan.candidates_from_labels, or
+        propose_tile_candidates' lists) -- the classes each WINDOW is segmented against.  A (window, class) pair that is
+        not listed is DECLARED to have returned an all-zero mask: the result is bit for bit the dense route's merge and
+        labels on a window buffer that holds the listed pairs' seg_u8 and zeros elsewhere, so a class ramps down to 0 toward
+        a neighbouring window that does not list it, and a class no window lists is never foreground.  The cost follows
+        the scene: the windows with a non-empty list, in ascending order, run in groups of `batch` (the last group padded
+        by repeating its last window with an EMPTY list: no entry more, the same graph key) through segment_candidates
+        (`entry_batch`, labels="set"), one UNet entry per listed pair; each group's seg_u8 is copied on the same stream
+        into its slice of one uint8 [E, 3, th, tw] buffer, and one ops.tiles_labels_cand call merges and labels them.  No
+        buffer is sized by N * T or by N * h * w; with every list empty no UNet runs and the labels are all 0.
+
+        With candidates the call returns dict(labels uint8 [h, w], counts int64 [2, N+1] or None, mx int32 [N], area int64
+        [N, 2] = per class (pixels foreground on its own, pixels where it won), entries = the (window, set) pair of every
+        entry, offsets = T + 1 ints, window t owns entries [offsets[t], offsets[t+1]), groups = the (windows, lists)
+        passed to each segment_candidates call, padding included -- enough to replay the calls --, plan).  There is no
+        seg_u8 key: the merged [N, 3, h, w] image is what this route exists not to build."""
         from .input_pipeline import DeviceImageTransform, TilePlan
         from .unet import SupportBank, SupportBankSet
         if not isinstance(support, (SupportBank, SupportBankSet)):
             raise TypeError("support must be a SupportBank (prepare_support) or a SupportBankSet (prepare_support_classes)")
         nway = isinstance(support, SupportBankSet)
+        if candidates is not None and not nway:
+            raise ValueError("candidates name sets of a SupportBankSet; a SupportBank has only one")
         batch = int(batch)
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
@@ -940,6 +960,38 @@ class MarigoldPipelineRGBLatentNoise:
             tf = self._tile_tf = DeviceImageTransform((th, tw), staged.device)  # owns the ToTensor + Normalize table
         N, T = (support.nsets if nway else 1), plan.T
         cplan = plan.c_struct()
+        if candidates is not None:
+            ct = plan.candidate_table(candidates(plan) if callable(candidates) else candidates, N)   # ValueError: see there
+            sets, E = ct["sets"], ct["E"]
+            tab_host = ct["tab"].pin_memory()
+            tab = tab_host.to(staged.device, non_blocking=True)
+            ent = torch.empty(E, 3, th, tw, dtype=torch.uint8, device=staged.device) if E else None
+            q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
+            live = [t for t in range(T) if sets[t]]
+            groups, e0 = [], 0
+            for g0 in range(0, len(live), batch):
+                ws = live[g0:g0 + batch]
+                i = 0
+                while i < len(ws):                                            # one cut per run of adjacent windows
+                    j = i + 1
+                    while j < len(ws) and ws[j] == ws[j - 1] + 1:
+                        j += 1
+                    ops.tiles_cut(cplan, img_dev, tf.lut, ws[i], j - i, out=q[i:j])
+                    i = j
+                pad = batch - len(ws)
+                if pad:
+                    q[len(ws):] = q[len(ws) - 1]                              # padding: the last window again, no candidate
+                group = (tuple(ws) + (ws[-1],) * pad, tuple(sets[t] for t in ws) + ((),) * pad)
+                r = self.segment_candidates(support, q, group[1], None, r_threshold=r_threshold, threshold=threshold,
+                                            entry_batch=entry_batch, labels="set", captured=captured)
+                n = r["seg_u8"].shape[0]                                      # the group's entries, window-major
+                ent[e0:e0 + n].copy_(r["seg_u8"])                             # before the next call overwrites it
+                e0 += n
+                groups.append(group)
+            labels, counts, mx, area = ops.tiles_labels_cand(cplan, ent, tab, tab_host, N, None if gt is None else gt_dev[0],
+                                                             r_threshold, threshold, want_area=True)
+            return dict(labels=labels, counts=counts, mx=mx, area=area, plan=plan, groups=groups,
+                        entries=[(t, c) for t, cs in enumerate(sets) for c in cs], offsets=ct["tab"][:T + 1].tolist())
         win = torch.empty(N, T, 3, th, tw, dtype=torch.uint8, device=staged.device)
         q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
         for first in range(0, T, batch):
@@ -961,6 +1013,34 @@ class MarigoldPipelineRGBLatentNoise:
         if not nway:
             out["pred"] = out["labels"]
         return out
+
+    @torch.no_grad()
+    def propose_tile_candidates(self, library, image, overlap=None, ramp=None, min_pixels=1, margin=1,
+                                **segment_classes_flags):
+        """The simplest way to CHOOSE segment_tiled's candidates: one coarse pass over the whole image.  `image` (PIL /
+        uint8 [h, w, 3]) is squeezed to the processing size `library` (a SupportBankSet) was prepared at by
+        DeviceImageTransform, ONE segment_classes call with b = 1 (`segment_classes_flags` are its keywords) labels it
+        against all N classes, the labels are brought to the host -- the one host synchronisation of this call -- and
+        TilePlan.candidates_from_labels(labels, min_pixels, margin) reads off, per window of the plan segment_tiled will
+        build for the same `overlap` / `ramp`, the classes seen inside the window's footprint (grown by `margin` pixels of
+        the coarse map).
+
+        Returns (plan_args, lists): plan_args = dict(overlap=, ramp=) and lists = T lists of set indices, usable as
+        segment_tiled(library, image, **plan_args, candidates=lists).  A composition of existing calls; how good the
+        proposals are depends on the weights and is not claimed here."""
+        from .input_pipeline import DeviceImageTransform, TilePlan
+        from .unet import SupportBankSet
+        if not isinstance(library, SupportBankSet):
+            raise ValueError("propose_tile_candidates needs a SupportBankSet (prepare_support_classes)")
+        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        th, tw = library.hw[0] * f, library.hw[1] * f
+        img = DeviceImageTransform.as_rgb_bytes(image)
+        overlap = min(th, tw) // 8 if overlap is None else overlap
+        plan = TilePlan(img.shape[:2], (th, tw), overlap, ramp)
+        q = DeviceImageTransform((th, tw), self.device).image(img)
+        r = self.segment_classes(library, q[None], None, **segment_classes_flags)
+        coarse = r["labels"][0].cpu()                                          # the one host synchronisation
+        return dict(overlap=overlap, ramp=ramp), plan.candidates_from_labels(coarse.numpy(), min_pixels, margin)
 
     @staticmethod
     def _with_native_labels(r, native, flags, class_ids):

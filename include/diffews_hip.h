@@ -741,6 +741,41 @@ int dfw_tiles_cut(const dfw_tile_plan* plan, const uint8_t* img, const float* lu
 int dfw_tiles_merge(const dfw_tile_plan* plan, const uint8_t* win, int32_t N, uint8_t* out, uint32_t* mx,
                     dfw_stream_t stream);
 
+/* Candidate classes per WINDOW, merged sparsely (version >= 113): dfw_tiles_merge + dfw_seg_labels(B = 1, batch_max = 0)
+ * on a window buffer [N][T][3][tile_h][tile_w] in which only the listed (window, class) pairs hold a mask and every other
+ * pair is zero -- bit for bit, without that buffer and without the merged [N][3][img_h][img_w] image.
+ *
+ *   ent       device, uint8 [E_cap][3][tile_h][tile_w]: entry-major, the entries of one window adjacent, in ascending class;
+ *             may be null only when the table lists no entry
+ *   tab       device, int32 [T + 1 + E_cap]: offsets off[0..T] (window t owns entries [off[t], off[t + 1]), off[0] = 0,
+ *             off[T] = E <= E_cap, E = 0 allowed, E_cap >= 1), then the class cls[e] in 0..N-1 of every entry, strictly
+ *             ascending within a window.  The kernels read it when they RUN and clamp what they read (offsets into
+ *             0..E_cap, classes into 0..N-1): a table overwritten later gives wrong numbers, never a read outside ent / tab
+ *             or a bin outside a histogram
+ *   tab_host  its host mirror: what this call validates
+ *   gt        optional, device uint8 [img_h][img_w] as dfw_seg_labels takes it (0..N; 255 and anything above N ignored)
+ *   labels    device, uint8 [img_h][img_w]: 0, or 1 + the foreground class of the largest score, lowest class on a tie
+ *   mx        device, [N]: the maximum byte of each class' (virtual) merged image over its 3 channels; 0 for a class no
+ *             window lists, which is therefore never foreground
+ *   counts    optional (needs gt), device int64 [2][N+1]: dfw_seg_labels' counts for B = 1
+ *   area      optional, device int64 [N][2]: (pixels where the class is foreground on its own, pixels where it won the
+ *             label), ignore pixels included
+ *
+ * Per pixel, channel and class c: A = sum w * u over the covering windows that list c, W = sum w over ALL covering windows
+ * (dfw_tiles_merge's weights), byte = (2 A + W) / (2 W) in 32-bit integers -- a class ramps down to 0 toward a
+ * neighbouring window that does not list it.  Score, threshold (r_threshold > 0: mx[c] / 255 * r_threshold, else the
+ * fixed `threshold`) and tie rule are dfw_seg_labels' fp32 expressions on those bytes.  No float operation and no atomic
+ * on the image: the result depends on no order.  Launches: one library kernel that zeroes mx / counts / area (no memset
+ * node), the maximum pass (only with r_threshold > 0 and E > 0), the label pass.
+ *
+ * Validated on the host before the first launch: a null plan / tab / tab_host / labels / mx, ent null with E > 0, a plan
+ * that breaks a rule above, N outside 1..254, E_cap < 1, counts without gt, neither threshold > 0, offsets that do not
+ * start at 0, decrease or end above E_cap, a class outside 0..N-1, classes not strictly ascending within a window ->
+ * DFW_EINVAL; dfw_tiles_merge's img_h limit and its 32-bit proof -> DFW_ERANGE. */
+int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* ent, const int32_t* tab, const int32_t* tab_host,
+                          const uint8_t* gt, uint8_t* labels, uint32_t* mx, int64_t* counts, int64_t* area, int32_t E_cap,
+                          int32_t N, float r_threshold, float threshold, dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
