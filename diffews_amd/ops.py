@@ -55,12 +55,8 @@ def _gemm_call(a):
     if gemm_hook is not None:
         buf = C.create_string_buffer(64)
         L.check(lib.dfw_gemm_kernel_name(C.byref(a), buf, 64), "dfw_gemm_kernel_name")
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _gemm_launch(lib, a)
-        e1.record()
-        gemm_hook(buf.value.decode(), 2.0 * a.M * a.N * a.K * max(1, a.batch), e0, e1,
-                  (a.M, a.N, a.K, a.taps, a.stride, a.ups, a.splitk, max(1, a.batch)))
+        _timed(buf.value.decode(), 2.0 * a.M * a.N * a.K * max(1, a.batch),
+               (a.M, a.N, a.K, a.taps, a.stride, a.ups, a.splitk, max(1, a.batch)), lambda: _gemm_launch(lib, a))
         return
     _gemm_launch(lib, a)
 
@@ -194,6 +190,51 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
     return out
 
 
+def _timed(name, flops, shape, call):
+    """call() bracketed by two events on the launch stream and reported as gemm_hook(name, flops, start, end, shape)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call()
+    e1.record()
+    gemm_hook(name, flops, e0, e1, shape)
+
+
+def _fsa_args(q, k, v, out, heads):
+    """(FsaArgs with the q / k / v / out fields and the dtype filled, out): q / k / v [B, N, heads*64] views with unit
+    channel stride, `out` [B, N, heads*64] with dense rows, allocated when None."""
+    B, N, Cq = q.shape
+    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    if out is None:
+        out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
+    assert out.shape == (B, N, Cq) and out.stride(2) == 1 and out.stride(1) == Cq
+    a = L.FsaArgs()
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.batch, a.heads, a.n_q, a.n_kv = B, heads, N, k.shape[1]
+    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
+    a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    a.dtype = _dt(q)
+    return a, out
+
+
+def _fsa_bank(a, k_bank, v_bank, nshot):
+    """The bank fields of an FsaArgs from _fsa_args: k_bank / v_bank [images, Nb, heads*64] views in q's dtype."""
+    assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1
+    assert _DT.get(k_bank.dtype) == a.dtype and v_bank.shape == k_bank.shape
+    a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
+    a.n_bank, a.nshot = k_bank.shape[1], nshot
+    a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
+
+
+def _fsa_launch(a, q, nbytes, call, keys):
+    """call() with `nbytes` of key-split scratch behind a.workspace; keys() -- the keys the launch's B * n_q query rows read
+    in all -- is evaluated for the hook only (bench.py roofline leg: QK^T + PV flops of this launch)."""
+    if nbytes:
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    if gemm_hook is None:
+        return call()
+    n = keys()
+    _timed("fsa_attention", 4.0 * a.heads * 64 * a.n_q * n, (a.batch, a.heads, a.n_q, n), call)
 
 
 def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None, out=None, n_plain=0,
@@ -207,16 +248,8 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     bank_shared: k_bank/v_bank hold ONE support set, [nshot, Nb, heads*64], and every batch entry attends over
     [own ; that set] (a prepared SupportBank read by a batch of queries) -- same kernel, same key order as the bank
     repeated B times."""
-    B, N, Cq = q.shape
-    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
-    if out is None:
-        out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
-    assert out.shape == (B, N, Cq) and out.stride(2) == 1 and out.stride(1) == Cq
-    a = L.FsaArgs()
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.batch, a.heads, a.n_q, a.n_kv = B, heads, N, k.shape[1]
-    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
-    a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
+    B, N = q.shape[:2]
+    a, out = _fsa_args(q, k, v, out, heads)
     if nshot:
         if _shots is not None:      # fsa_attention_ragged: nshot is max(shots)
             assert n_plain == 0 and not bank_shared and _group and B % _group == 0 and k_bank.shape[0] == sum(_shots)
@@ -227,15 +260,12 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
             assert n_plain == 0 and k_bank.shape[0] == nshot
         else:
             assert k_bank.shape[0] == (B - n_plain) * nshot
-        assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1
-        assert k_bank.dtype == q.dtype and v_bank.shape == k_bank.shape
-        a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
-        a.n_bank, a.nshot, a.bank_shared = k_bank.shape[1], nshot, int(bool(bank_shared))
-        a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
+        _fsa_bank(a, k_bank, v_bank, nshot)
+        a.bank_shared = int(bool(bank_shared))
     elif bank_shared:
         raise ValueError("bank_shared needs a bank (nshot > 0)")
     a.scale = scale if scale is not None else 64 ** -0.5
-    a.dtype, a.n_plain, a.q_prescaled = _dt(q), n_plain, int(bool(q_prescaled))
+    a.n_plain, a.q_prescaled = n_plain, int(bool(q_prescaled))
     if lse is not None:   # training: per-row log2-sum-exp2 for the backward
         assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, heads, N)
         a.lse = lse.data_ptr()
@@ -245,20 +275,11 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     else:
         call = (lambda: _fsa_sets_call(a, _group)) if _group else (lambda: _fsa_call(a))
         nbytes = L.lib().dfw_fsa_workspace_bytes(C.byref(a)) if (nshot >= 2 and key_split) else 0   # key split of the bank readers (many shots)
-    if nbytes:
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-    if gemm_hook is not None:   # bench.py roofline leg: QK^T + PV flops of this launch
-        keys = n_plain * k.shape[1] + (B - n_plain) * (k.shape[1] + (nshot * k_bank.shape[1] if nshot else 0))
-        if _shots is not None:
-            keys = B * k.shape[1] + _group * sum(_shots) * k_bank.shape[1]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call()
-        e1.record()
-        gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
-        return out
-    call()
+    if _shots is not None:
+        keys = lambda: B * k.shape[1] + _group * sum(_shots) * k_bank.shape[1]
+    else:
+        keys = lambda: n_plain * k.shape[1] + (B - n_plain) * (k.shape[1] + (nshot * k_bank.shape[1] if nshot else 0))
+    _fsa_launch(a, q, nbytes, call, keys)
     return out
 
 
@@ -317,42 +338,20 @@ def fsa_attention_routed(q, k, v, heads, k_bank, v_bank, table, table_host, max_
     [min_shots, max_shots], every set inside the stack).  The launch plan and workspace depend on the shapes, max_shots
     and min_shots only; the key split never exceeds 1 + min_shots.  Per entry the kernel arithmetic, key order and tile
     sequence of fsa_attention on that set's slice with bank_shared=True."""
-    B, N, Cq = q.shape
-    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    B = q.shape[0]
     for name, t in (("table", table), ("table_host", table_host)):
         if t.dtype != torch.int32 or tuple(t.shape) != (B, 2) or not t.is_contiguous():
             raise ValueError(f"fsa_attention_routed: {name} must be a contiguous int32 [{B}, 2] tensor")
     if not table.is_cuda or table.device != q.device or table_host.device.type != "cpu":
         raise ValueError("fsa_attention_routed: table lives with q on the device, table_host on the host")
-    if out is None:
-        out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
-    assert out.shape == (B, N, Cq) and out.stride(2) == 1 and out.stride(1) == Cq
-    assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1 and k_bank.dtype == q.dtype and v_bank.shape == k_bank.shape
-    a = L.FsaArgs()
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.batch, a.heads, a.n_q, a.n_kv = B, heads, N, k.shape[1]
-    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), Cq
-    a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-    a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
-    a.n_bank, a.nshot = k_bank.shape[1], int(max_shots)
-    a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
-    a.scale = 64 ** -0.5
-    a.dtype, a.q_prescaled = _dt(q), int(bool(q_prescaled))
+    a, out = _fsa_args(q, k, v, out, heads)
+    _fsa_bank(a, k_bank, v_bank, int(max_shots))
+    a.scale, a.q_prescaled = 64 ** -0.5, int(bool(q_prescaled))
     nbank, min_shots = int(k_bank.shape[0]), int(min_shots)
     nbytes = L.lib().dfw_fsa_routed_workspace_bytes(C.byref(a), nbank, min_shots) if key_split else 0
-    if nbytes:
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     host = C.cast(table_host.data_ptr(), C.POINTER(C.c_int32))
-    if gemm_hook is not None:   # bench.py roofline leg: QK^T + PV flops of this launch
-        keys = B * k.shape[1] + int(table_host[:, 1].sum()) * k_bank.shape[1]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots)
-        e1.record()
-        gemm_hook("fsa_attention", 4.0 * heads * 64 * N * keys, e0, e1, (B, heads, N, keys))
-        return out
-    _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots)
+    _fsa_launch(a, q, nbytes, lambda: _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots),
+                lambda: B * k.shape[1] + int(table_host[:, 1].sum()) * k_bank.shape[1])
     return out
 
 
@@ -444,15 +443,12 @@ def conv3x3_up2x(x, w_folded, cout, bias=None, gn_groups=0):
             part = torch.empty(B, chunks, gn_groups, 2, dtype=torch.float32, device=x.device)
             a.gn_partial = part.data_ptr()
             stats = (part, chunks, gn_groups)
+    call = lambda: L.check(lib.dfw_conv_up2x(C.byref(a), _stream()), "dfw_conv_up2x")
     if gemm_hook is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(lib.dfw_conv_up2x(C.byref(a), _stream()), "dfw_conv_up2x")
-        e1.record()
         M = B * 4 * Hi * Wi
-        gemm_hook(name.value.decode(), 2.0 * M * cout * 4 * Cin, e0, e1, (M, cout, 4 * Cin, 4, 1, 1, 1, 1))
+        _timed(name.value.decode(), 2.0 * M * cout * 4 * Cin, (M, cout, 4 * Cin, 4, 1, 1, 1, 1), call)
     else:
-        L.check(lib.dfw_conv_up2x(C.byref(a), _stream()), "dfw_conv_up2x")
+        call()
     if stats is not None:
         out._gn_stats = stats
     return out
@@ -723,6 +719,19 @@ def seg_labels(seg_u8, mx, gt=None, r_threshold=0.25, threshold=0.0, batch_max=F
     return labels, counts
 
 
+def _check_table(name, tab, tab_host, E_cap, device):
+    """ValueError (in `name`'s name) unless tab / tab_host are seg_labels_cand's table for E_cap entries -- contiguous int32
+    [B + 1 + E_cap], equally long, tab on `device` and tab_host on the host.  Returns B."""
+    for what, t in (("tab", tab), ("tab_host", tab_host)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
+            raise ValueError(f"{name}: {what} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
+    if tab.numel() != tab_host.numel():
+        raise ValueError(f"{name}: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
+    if not tab.is_cuda or tab.device != device or tab_host.device.type != "cpu":
+        raise ValueError(f"{name}: tab lives with seg_u8 on the device, tab_host on the host")
+    return tab.numel() - 1 - E_cap
+
+
 def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.25, threshold=0.0, want_area=False,
                     labels_out=None, counts_out=None):
     """Label fusion over candidate classes per query: seg_labels' rule per ENTRY.  seg_u8: uint8 [E_cap, 3, H, W],
@@ -738,14 +747,7 @@ def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.2
     where e is foreground on its own, pixels where e won), ignore pixels included."""
     assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
     E_cap, _, H, W = seg_u8.shape
-    for name, t in (("tab", tab), ("tab_host", tab_host)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
-            raise ValueError(f"seg_labels_cand: {name} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
-    if tab.numel() != tab_host.numel():
-        raise ValueError(f"seg_labels_cand: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
-    if not tab.is_cuda or tab.device != seg_u8.device or tab_host.device.type != "cpu":
-        raise ValueError("seg_labels_cand: tab lives with seg_u8 on the device, tab_host on the host")
-    B, nlabels = tab.numel() - 1 - E_cap, int(nlabels)
+    B, nlabels = _check_table("seg_labels_cand", tab, tab_host, E_cap, seg_u8.device), int(nlabels)
     if mx is not None:
         assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == E_cap
     elif r_threshold > 0:
@@ -766,6 +768,55 @@ def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.2
     return labels, counts, area
 
 
+def _u8_buf(given, n, dev):
+    """`given` (a caller-owned uint8 buffer of at least n bytes on dev) or a fresh one."""
+    if given is None:
+        return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+    return given
+
+
+def _native_setup(a, seg_u8, targets, b, n, want_u8, u8_out, tmp, r_threshold, threshold):
+    """What seg_native, seg_labels_native and seg_labels_cand_native share: ValueError unless `targets` were built for these
+    b queries and seg_u8's (Hs, Ws); the targets' staged table made safe to read on this stream; and the fields the three
+    argument records share by name -- source, item / weight tables, ground truth, thresholds, and the workspace of `n` planes
+    per query (1, the classes, the longest candidate list): n strides of targets.tmp_bytes for the horizontal intermediates
+    and n of targets.u8_bytes for the resized bytes, behind them in tmp or, with want_u8, in out_u8.  Returns (u8 or None,
+    tmp, whether there is a ground truth); the caller keeps the buffers until it has launched."""
+    Hs, Ws = seg_u8.shape[-2:]
+    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
+        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, the call has {b} and seg_u8 is "
+                         f"{tuple(seg_u8.shape)}")
+    dev = seg_u8.device
+    if not torch.cuda.is_current_stream_capturing():
+        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
+    u8 = _u8_buf(u8_out, n * targets.u8_bytes, dev) if want_u8 else None
+    tmp = _u8_buf(tmp, n * targets.tmp_bytes + (0 if want_u8 else n * targets.u8_bytes), dev)
+    gt, gt_bytes = targets.gt_base
+    a.seg_u8, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), b, Hs, Ws
+    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
+    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
+    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
+    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), n * targets.tmp_bytes
+    if u8 is not None:
+        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
+    a.r_threshold, a.threshold = float(r_threshold), float(threshold)
+    return u8, tmp, gt is not None
+
+
+def _native_views(targets, lab, u8, n, rows=None):
+    """Per-query views of the packed outputs: ([h_i, w_i] of lab, [rows_i (default n), 3, h_i, w_i] of u8's n planes), None
+    for a buffer that is None."""
+    items = list(targets.items)
+    if lab is not None:
+        lab = [lab[it.pred_off:it.pred_off + it.h * it.w].view(it.h, it.w) for it in items]
+    if u8 is not None:
+        per = u8[:n * targets.u8_bytes].view(n, targets.u8_bytes)
+        u8 = [per[:r, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w))
+              for it, r in zip(items, rows or [n] * len(items))]
+    return lab, u8
+
+
 def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False, want_u8=True, want_pred=True,
                u8_out=None, pred_out=None, tmp=None):
     """Native-size masks and scores: seg_u8 uint8 [b, 3, Hs, Ws] (seg_postprocess' output) resized back to every query's
@@ -780,47 +831,18 @@ def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False
     are backed by one packed buffer.  u8_out / pred_out / tmp: caller-owned uint8 buffers of at least targets.u8_bytes /
     pred_bytes / tmp_bytes (tmp_bytes + u8_bytes without want_u8) instead of fresh ones."""
     assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
-    b, _, Hs, Ws = seg_u8.shape
-    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
-        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, seg_u8 is {tuple(seg_u8.shape)}")
-    dev = seg_u8.device
-    if not torch.cuda.is_current_stream_capturing():
-        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
-
-    def buf(given, n):
-        if given is None:
-            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
-        return given
+    b, dev = seg_u8.shape[0], seg_u8.device
     a = L.SegNativeArgs()
-    u8 = buf(u8_out, targets.u8_bytes) if want_u8 else None
-    tmp = buf(tmp, targets.tmp_bytes + (0 if want_u8 else targets.u8_bytes))
-    pred = buf(pred_out, targets.pred_bytes) if want_pred else None
-    gt, gt_bytes = targets.gt_base
-    counts = torch.empty(b, 4, dtype=torch.int64, device=dev) if gt is not None else None
+    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, 1, want_u8, u8_out, tmp, r_threshold, threshold)
+    pred = _u8_buf(pred_out, targets.pred_bytes, dev) if want_pred else None
+    counts = torch.empty(b, 4, dtype=torch.int64, device=dev) if has_gt else None
     mx = torch.empty(b, dtype=torch.int32, device=dev)
-    a.seg_u8, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), b, Hs, Ws
-    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
-    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
-    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
-    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), targets.tmp_bytes
-    if u8 is not None:
-        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
     if pred is not None:
         a.pred, a.pred_bytes = pred.data_ptr(), pred.numel()
-    a.mx, a.counts = mx.data_ptr(), _p(counts)
-    a.r_threshold, a.threshold, a.batch_max = float(r_threshold), float(threshold), int(bool(batch_max))
+    a.mx, a.counts, a.batch_max = mx.data_ptr(), _p(counts), int(bool(batch_max))
     L.check(L.lib().dfw_seg_native(C.byref(a), _stream()), "dfw_seg_native")
-
-    def views(t, chans):
-        out = []
-        for it in targets.items:
-            o = it.u8_off if chans == 3 else it.pred_off
-            v = t[o:o + chans * it.h * it.w]
-            out.append(v.view(3, it.h, it.w) if chans == 3 else v.view(it.h, it.w))
-        return out
-    return dict(seg_u8=views(u8, 3) if u8 is not None else None, pred=views(pred, 1) if pred is not None else None,
-                counts=counts, mx=mx, sizes=list(targets.sizes))
+    pred, planes = _native_views(targets, pred, u8, 1)
+    return dict(seg_u8=planes and [p[0] for p in planes], pred=pred, counts=counts, mx=mx, sizes=list(targets.sizes))
 
 
 def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False, class_ids=None, want_u8=False,
@@ -840,46 +862,21 @@ def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_ma
     packed buffer, classes targets.u8_bytes apart.  labels_out / u8_out / tmp: caller-owned uint8 buffers of at least
     targets.pred_bytes / N * u8_bytes / N * tmp_bytes (N * (tmp_bytes + u8_bytes) without want_u8) instead of fresh ones."""
     assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 5 and seg_u8.shape[2] == 3
-    N, b, _, Hs, Ws = seg_u8.shape
-    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
-        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, seg_u8 is {tuple(seg_u8.shape)}")
-    dev = seg_u8.device
-    if not torch.cuda.is_current_stream_capturing():
-        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
-
-    def buf(given, n):
-        if given is None:
-            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
-        return given
+    N, b, dev = seg_u8.shape[0], seg_u8.shape[1], seg_u8.device
+    a = L.SegLabelsNativeArgs()
+    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, N, want_u8, u8_out, tmp, r_threshold, threshold)
     if class_ids is not None:
         class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(dev).contiguous()
         if class_ids.shape != (N,):
             raise ValueError(f"class_ids must hold one id per class ({N}), got {tuple(class_ids.shape)}")
-    a = L.SegLabelsNativeArgs()
-    u8 = buf(u8_out, N * targets.u8_bytes) if want_u8 else None
-    tmp = buf(tmp, N * targets.tmp_bytes + (0 if want_u8 else N * targets.u8_bytes))
-    labels = buf(labels_out, targets.pred_bytes)
-    gt, gt_bytes = targets.gt_base
-    counts = torch.empty(b, 2, N + 1, dtype=torch.int64, device=dev) if gt is not None else None
+    labels = _u8_buf(labels_out, targets.pred_bytes, dev)
+    counts = torch.empty(b, 2, N + 1, dtype=torch.int64, device=dev) if has_gt else None
     mx = torch.empty(N, b, dtype=torch.int32, device=dev)
-    a.seg_u8, a.N, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), N, b, Hs, Ws
-    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
-    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
-    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
-    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), N * targets.tmp_bytes
-    a.tmp_cls_stride, a.u8_cls_stride = targets.tmp_bytes, targets.u8_bytes
-    if u8 is not None:
-        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
+    a.N, a.tmp_cls_stride, a.u8_cls_stride = N, targets.tmp_bytes, targets.u8_bytes
     a.labels, a.labels_bytes = labels.data_ptr(), labels.numel()
-    a.mx, a.counts, a.class_ids = mx.data_ptr(), _p(counts), _p(class_ids)
-    a.r_threshold, a.threshold, a.batch_max = float(r_threshold), float(threshold), int(bool(batch_max))
+    a.mx, a.counts, a.class_ids, a.batch_max = mx.data_ptr(), _p(counts), _p(class_ids), int(bool(batch_max))
     L.check(L.lib().dfw_seg_labels_native(C.byref(a), _stream()), "dfw_seg_labels_native")
-    lab = [labels[it.pred_off:it.pred_off + it.h * it.w].view(it.h, it.w) for it in targets.items]
-    planes = None
-    if u8 is not None:
-        per = u8[:N * targets.u8_bytes].view(N, targets.u8_bytes)
-        planes = [per[:, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w)) for it in targets.items]
+    lab, planes = _native_views(targets, labels, u8, N)
     return dict(labels=lab, counts=counts, mx=mx, seg_u8=planes, sizes=list(targets.sizes))
 
 
@@ -914,29 +911,15 @@ def seg_labels_cand_native(seg_u8, targets, tab, tab_host, nlabels, r_threshold=
     area=int64 [E_cap, 2] or None (want_area; counted on the resized bytes), mx=int32 [E_cap] resized maxima,
     seg_u8=[uint8 views [K_i, 3, h_i, w_i], K_i the query's entries] or None (want_u8), sizes=[(h_i, w_i)])."""
     assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
-    E_cap, _, Hs, Ws = seg_u8.shape
-    for name, t in (("tab", tab), ("tab_host", tab_host)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
-            raise ValueError(f"seg_labels_cand_native: {name} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
-    if tab.numel() != tab_host.numel():
-        raise ValueError(f"seg_labels_cand_native: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
-    if not tab.is_cuda or tab.device != seg_u8.device or tab_host.device.type != "cpu":
-        raise ValueError("seg_labels_cand_native: tab lives with seg_u8 on the device, tab_host on the host")
+    E_cap, dev = seg_u8.shape[0], seg_u8.device
+    b, nlabels = _check_table("seg_labels_cand_native", tab, tab_host, E_cap, dev), int(nlabels)
     if class_ids is not None and entry_ids is not None:
         raise ValueError("seg_labels_cand_native: give class_ids (labels = 1 + set index) or entry_ids (local labels), not both")
-    b, nlabels = tab.numel() - 1 - E_cap, int(nlabels)
-    if targets.dev is None or targets.b != b or targets.src_hw != (Hs, Ws):
-        raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, the table names {b} and seg_u8 "
-                         f"is {tuple(seg_u8.shape)}")
-    dev = seg_u8.device
-    if not torch.cuda.is_current_stream_capturing():
-        targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
-
-    def buf(given, n):
-        if given is None:
-            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
-        return given
+    off = tab_host[:b + 1].tolist()
+    rows = [hi - lo for lo, hi in zip(off, off[1:])]
+    K = max(max(rows), 1)                  # cand_native_workspace(targets, K, want_u8) is what _native_setup lays out
+    a = L.SegLabelsCandNativeArgs()
+    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, K, want_u8, u8_out, tmp, r_threshold, threshold)
 
     def ids(t, n, name):
         if t is None:
@@ -946,37 +929,17 @@ def seg_labels_cand_native(seg_u8, targets, tab, tab_host, nlabels, r_threshold=
             raise ValueError(f"{name} must hold {n} ids, got {tuple(t.shape)}")
         return t
     class_ids, entry_ids = ids(class_ids, nlabels, "class_ids"), ids(entry_ids, E_cap, "entry_ids")
-    off = tab_host[:b + 1].tolist()
-    K = max(max(hi - lo for lo, hi in zip(off, off[1:])), 1)
-    tmp_bytes, tmp_res_off, u8_bytes = cand_native_workspace(targets, K, want_u8)
-    a = L.SegLabelsCandNativeArgs()
-    u8 = buf(u8_out, u8_bytes) if want_u8 else None
-    tmp = buf(tmp, tmp_bytes)
-    labels = buf(labels_out, targets.pred_bytes)
-    gt, gt_bytes = targets.gt_base
-    counts = torch.empty(b, 2, nlabels + 1, dtype=torch.int64, device=dev) if gt is not None else None
+    labels = _u8_buf(labels_out, targets.pred_bytes, dev)
+    counts = torch.empty(b, 2, nlabels + 1, dtype=torch.int64, device=dev) if has_gt else None
     area = torch.empty(E_cap, 2, dtype=torch.int64, device=dev) if want_area else None
     mx = torch.empty(E_cap, dtype=torch.int32, device=dev)
-    a.seg_u8, a.B, a.E_cap, a.nlabels, a.Hs, a.Ws = seg_u8.data_ptr(), b, E_cap, nlabels, Hs, Ws
-    a.tab, a.tab_host = tab.data_ptr(), tab_host.data_ptr()
-    a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
-    a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
-    a.gt, a.gt_bytes = (gt.data_ptr(), gt_bytes) if gt is not None else (None, 0)
-    a.tmp, a.tmp_bytes, a.tmp_res_off = tmp.data_ptr(), tmp.numel(), tmp_res_off
+    a.E_cap, a.nlabels, a.tab, a.tab_host = E_cap, nlabels, tab.data_ptr(), tab_host.data_ptr()
     a.tmp_cls_stride, a.u8_cls_stride = targets.tmp_bytes, targets.u8_bytes
-    if u8 is not None:
-        a.out_u8, a.out_u8_bytes = u8.data_ptr(), u8.numel()
     a.labels, a.labels_bytes = labels.data_ptr(), labels.numel()
     a.mx, a.counts, a.area = mx.data_ptr(), _p(counts), _p(area)
     a.class_ids, a.entry_ids = _p(class_ids), _p(entry_ids)
-    a.r_threshold, a.threshold = float(r_threshold), float(threshold)
     L.check(L.lib().dfw_seg_labels_cand_native(C.byref(a), _stream()), "dfw_seg_labels_cand_native")
-    lab = [labels[it.pred_off:it.pred_off + it.h * it.w].view(it.h, it.w) for it in targets.items]
-    planes = None
-    if u8 is not None:
-        per = u8[:K * targets.u8_bytes].view(K, targets.u8_bytes)
-        planes = [per[:hi - lo, it.u8_off:it.u8_off + 3 * it.h * it.w].unflatten(1, (3, it.h, it.w))
-                  for it, lo, hi in zip(targets.items, off, off[1:])]
+    lab, planes = _native_views(targets, labels, u8, K, rows)
     return dict(labels=lab, counts=counts, area=area, mx=mx, seg_u8=planes, sizes=list(targets.sizes))
 
 

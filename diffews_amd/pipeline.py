@@ -276,8 +276,8 @@ class MarigoldPipelineRGBLatentNoise:
             seg, lat = self.single_infer(support_imgs, query_img, support_masks, return_latents=True)
             dec = (seg / 255.0 * 2.0 - 1.0).contiguous()
             seg_u8, counts = ops.seg_postprocess(dec, query_gt, r_threshold, threshold, batch_max)
-            return self._with_native(dict(z0=lat["z0"], dec=dec, seg_u8=seg_u8, counts=counts), native,
-                                     (r_threshold, threshold, batch_max))
+            return self._with_native(dict(z0=lat["z0"], dec=dec, seg_u8=seg_u8, counts=counts), native, ops.seg_native,
+                                     r_threshold, threshold, batch_max)
         tt = t * self.test_timestep
         folded = self._fold_conditioning(tt)      # host + load-time work: never inside a capture
         dev = self.device
@@ -292,20 +292,26 @@ class MarigoldPipelineRGBLatentNoise:
         if captured is None:
             captured = self.use_graph
         if not captured:
-            return self._with_native(step(**ins), native, flags)
-        key = (tuple(ins["support_imgs"].shape), tuple(ins["query_img"].shape), query_gt is not None, flags,
-               float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
-        return self._with_native(self._replay(key, step, ins), native, flags)
+            return self._with_native(step(**ins), native, ops.seg_native, *flags)
+        key = self._graph_key((tuple(ins["support_imgs"].shape), tuple(ins["query_img"].shape), query_gt is not None, flags),
+                              tt, folded)
+        return self._with_native(self._replay(key, step, ins), native, ops.seg_native, *flags)
 
     @staticmethod
-    def _with_native(r, native, flags):
-        """r plus r["native"] = ops.seg_native(r["seg_u8"], native, *flags), eagerly on the current stream (r itself may be
-        a captured step's cached output dict: it is copied, not written)."""
+    def _with_native(r, native, op, *args, **kw):
+        """r plus r["native"] = op(r["seg_u8"], native, *args, **kw) -- ops.seg_native or ops.seg_labels_native with the call's
+        flags --, eagerly on the current stream (r itself may be a captured step's cached output dict: it is copied, not
+        written)."""
         if native is None:
             return r
         r = dict(r)
-        r["native"] = ops.seg_native(r["seg_u8"], native, *flags)
+        r["native"] = op(r["seg_u8"], native, *args, **kw)
         return r
+
+    def _graph_key(self, head, tt, folded):
+        """The key of a captured step: `head` (the route, its support's uid, shapes and flags) plus what every step depends
+        on -- the timestep, the fold and both residual-stream modes."""
+        return head + (float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
 
     def _episodes_step(self, support_imgs, query_img, support_masks, query_gt, tt, folded, flags):
         """The kernels of one step; every buffer it touches is written by a library kernel (no torch.cat /
@@ -337,7 +343,32 @@ class MarigoldPipelineRGBLatentNoise:
         return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
 
     # ------------------------------------------------------------------ shared support bank
-    MAX_QUERY_GRAPHS = 4    # captured segment_queries steps kept per pipeline (least recently used goes first)
+    # prepare_support / prepare_support_classes turn support images into a SupportBank / SupportBankSet (diffews_amd.unet);
+    # segment_queries, segment_classes, segment_routed and segment_candidates(_native) run query images against one.  The
+    # five routes are one scaffold around a `step` closure -- _query_context (every check, on the host, before anything is
+    # launched or replayed), the step (_query_latents, a unet.forward_query* pass with z0 = -v folded into conv_out,
+    # decode_seg, the ops.seg_* post-processing) and _run_query_step -- and share these rules, stated here once:
+    #   scheduler  the reference's degenerate one-step scheduler (z0 = -v) is required; any other raises
+    #              NotImplementedError (run_episodes, which falls back to single_infer, takes any).
+    #   stale      a support prepared under another test_timestep, prompt, residual-stream mode, resolution or set of
+    #              weights raises ValueError (SupportBank.check names the first mismatch).
+    #   captured   (default: self.use_graph) as in run_episodes: the step is ONE HIP graph per key -- the route, the
+    #              support's uid (its tensors are read in place, so two supports of equal shape never share a graph), the
+    #              query shape, whether a ground truth was given, the flags and _graph_key's tail.  Tables of a route
+    #              (routed, candidates) are pinned host tensors among the step's static inputs: one H2D copy each per call
+    #              into the graph's buffer, read by the kernels when they run, so they are NOT part of the key.  At most
+    #              MAX_QUERY_GRAPHS captured query steps are kept per pipeline, over all routes: capturing one more drops
+    #              the least recently used (its buffers with it; outputs returned from it must have been consumed).
+    #   native     (input_pipeline.NativeTargets for the b queries) the dict gains `native`, the route's ops.seg_*_native on
+    #              the step's seg_u8 with the call's flags: launched on the same stream after the step, eagerly even after
+    #              a replay (sizes vary per batch), neither part of the graph nor of its key; every other entry is what
+    #              the call without `native` returns.
+    MAX_QUERY_GRAPHS = 4    # captured query steps kept per pipeline (least recently used goes first)
+
+    @property
+    def _vae_factor(self):
+        """Image pixels per latent pixel: the encoder halves (floor) once per level but the last."""
+        return 2 ** (len(self.vae.config["block_out_channels"]) - 1)
 
     def _single_step_timestep(self):
         sched = self.scheduler
@@ -345,12 +376,86 @@ class MarigoldPipelineRGBLatentNoise:
         t = sched.timesteps[0]
         return t, t * self.test_timestep
 
+    def _support_latents(self, sup, msk):
+        """Support images and masks [n, 3, H, W] -> cond_ref [n, 2 lc, h, w] fp32: one VAE-encoder launch train over the 2n
+        images, quant_conv straight into the halves of cat([z_ref, z_mask_ref]) (P:674), as _episodes_step does."""
+        n, lc = sup.shape[0], self.vae.config["latent_channels"]
+        mom = self.vae.encoder([sup, msk])                                        # [2n, 2 lc, h, w] fp32
+        h, w = mom.shape[-2:]
+        cond_ref = torch.empty(n, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
+        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
+        qc(mom[:n], out_scale=sf, out=cond_ref[:, :lc], channels=lc)              # z_ref      (P:649)
+        qc(mom[n:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)              # z_mask_ref (P:651)
+        return cond_ref
+
+    def _query_latents(self, query_img, chunk=None):
+        """Query images [b, 3, H, W] -> z_tag [b, lc, h, w] fp32 (P:650): the VAE encoder, then quant_conv.  chunk: encode in
+        chunks of `chunk` queries, the last one padded by repeating the last query (the padding's latents are returned
+        too): GEMM plans, and so the bits, depend on the batch, and this way the encoder runs at batch `chunk` only."""
+        lc, sf = self.vae.config["latent_channels"], self.rgb_latent_scale_factor
+        if chunk is None:
+            return self.vae.quant_conv(self.vae.encoder(query_img), out_scale=sf, channels=lc)
+        b = query_img.shape[0]
+        pad = -b % chunk
+        qs = query_img if not pad else torch.cat([query_img, query_img[-1:].expand(pad, -1, -1, -1)])
+        zs = [self.vae.quant_conv(self.vae.encoder(qs[c0:c0 + chunk]), out_scale=sf, channels=lc)
+              for c0 in range(0, b + pad, chunk)]
+        return zs[0] if len(zs) == 1 else torch.cat(zs)
+
+    def _query_context(self, name, support, wrong, query_img, gt, tables=None):
+        """The checks of query route `name`, in the order callers rely on (the first two read no model): `support` is a
+        SupportBankSet, else the exception class `wrong` (None: the route takes a SupportBank and leaves the type to
+        unet.forward_queries); the scheduler restriction; fold and prompt; the inputs staged on the device as contiguous fp32
+        / uint8; tables(b) -- the route's own argument checks, which may raise and whose result is handed back --; and
+        support.check against this resolution and the engines' current state.
+        Returns (tt, folded, prompt, ins = dict(query_img=, gt=), tables' result)."""
+        from .unet import SupportBankSet
+        if wrong is not None and not isinstance(support, SupportBankSet):
+            raise wrong("bankset must be a SupportBankSet (prepare_support_classes)" if wrong is TypeError else
+                        f"{name} needs a SupportBankSet (prepare_support_classes)")
+        t, tt = self._single_step_timestep()
+        if not self.scheduler.z0_is_neg_v(t):
+            raise NotImplementedError(f"{name} needs the one-step scheduler with z0 = -v (the reference's setting); "
+                                      "run_episodes() takes any scheduler (the generic single_infer path)")
+        folded = self._fold_conditioning(tt)
+        dev = self.device
+        prompt = None if folded else self.encode_clip_feature()
+        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(), gt=None if gt is None else gt.to(dev).contiguous())
+        made = None if tables is None else tables(ins["query_img"].shape[0])
+        H, W = ins["query_img"].shape[-2:]
+        support.check(hw=(H // self._vae_factor, W // self._vae_factor), dtype=self.unet.dtype,
+                      residual_dtype=self.unet.residual_dtype, fold_key=self.unet._fold_key(tt, prompt),
+                      weights_id=self.unet._weights_id)
+        return tt, folded, prompt, ins, made
+
+    def _touch_query_graph(self, key):
+        """Least-recently-used bookkeeping of the captured query steps (keys that start with "queries"; run_episodes' graphs
+        are neither counted nor dropped): a known key moves to the end, a new one first drops the oldest until fewer than
+        MAX_QUERY_GRAPHS are left."""
+        if key in self._graphs:
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        else:
+            mine = [k for k in self._graphs if k[0] == "queries"]
+            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
+                del self._graphs[k]
+
+    def _run_query_step(self, key_head, step, ins, tt, folded, captured, finish):
+        """finish(the step's dict), the step run eagerly -- pinned host inputs (a route's tables) copied to the device first
+        -- or, captured, replayed from the graph keyed _graph_key(key_head, tt, folded)."""
+        if captured is None:
+            captured = self.use_graph
+        if not captured:
+            dev = self.device
+            return finish(step(**{k: v if v is None or v.is_cuda else v.to(dev, non_blocking=True) for k, v in ins.items()}))
+        key = self._graph_key(key_head, tt, folded)
+        self._touch_query_graph(key)
+        return finish(self._replay(key, step, ins))
+
     @torch.no_grad()
     def prepare_support(self, support_imgs, support_masks):
         """Prepare ONE support set for any number of segment_queries() calls: support_imgs / support_masks [s, 3, H, W] in
-        [-1, 1] -> SupportBank (diffews_amd.unet), the K/V of the s support images in every self-attention layer.
-        One VAE-encoder launch train over the 2s images, quant_conv straight into cat([z_ref, z_mask_ref]) (P:674) as in
-        run_episodes, then one support pass of the UNet (unet.prepare_bank).  The bank is valid for this pipeline's
+        [-1, 1] -> SupportBank (diffews_amd.unet), the K/V of the s support images in every self-attention layer:
+        _support_latents, then one support pass of the UNet (unet.prepare_bank).  The bank is valid for this pipeline's
         current test_timestep, prompt, residual-stream mode and weights, and for queries of the same H x W."""
         t, tt = self._single_step_timestep()
         folded = self._fold_conditioning(tt)
@@ -359,15 +464,7 @@ class MarigoldPipelineRGBLatentNoise:
         msk = support_masks.to(dev, torch.float32).contiguous()
         if sup.shape != msk.shape or sup.dim() != 4:
             raise ValueError(f"support_imgs {tuple(sup.shape)} and support_masks {tuple(msk.shape)} must both be [s, 3, H, W]")
-        s = sup.shape[0]
-        lc = self.vae.config["latent_channels"]
-        mom = self.vae.encoder([sup, msk])                                        # [2s, 2 lc, h, w] fp32
-        h, w = mom.shape[-2:]
-        cond_ref = torch.empty(s, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
-        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
-        qc(mom[:s], out_scale=sf, out=cond_ref[:, :lc], channels=lc)              # z_ref      (P:649)
-        qc(mom[s:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)              # z_mask_ref (P:651)
-        return self.unet.prepare_bank(cond_ref, tt, None if folded else self.encode_clip_feature())
+        return self.unet.prepare_bank(self._support_latents(sup, msk), tt, None if folded else self.encode_clip_feature())
 
     @torch.no_grad()
     def segment_queries(self, bank, query_img, query_gt=None, r_threshold=0.25, threshold=0.0, batch_max=False,
@@ -376,63 +473,28 @@ class MarigoldPipelineRGBLatentNoise:
         [b, 3, H, W] in [-1, 1], any b >= 1; query_gt optional uint8 [b, H, W].  Returns run_episodes' dict (z0, dec,
         seg_u8, counts) -- per image what run_episodes computes with the supports replicated b times, without encoding
         the supports or running them through the UNet again: only the queries are encoded, every attn1 reads the bank
-        (unet.forward_queries, z0 = -v folded into conv_out), decode, seg_postprocess.
+        (unet.forward_queries), decode, seg_postprocess.
 
-        Needs the reference's degenerate one-step scheduler (z0 = -v); any other scheduler raises NotImplementedError
-        (use run_episodes, which falls back to single_infer).  A bank prepared under another test_timestep, prompt,
-        residual-stream mode, resolution or set of weights raises ValueError.
-
-        captured (default: self.use_graph): as in run_episodes, one HIP graph per (bank, query shape, flags, ...); the
-        bank's identity is part of the key and its tensors are read in place, so two banks of equal shape never share a
-        graph.  At most MAX_QUERY_GRAPHS captured query steps are kept per pipeline: capturing one more drops the least
-        recently used (its buffers with it; outputs returned from it must have been consumed).
-
-        native: as in run_episodes -- the dict gains `native`, ops.seg_native on seg_u8, run eagerly after the step."""
-        t, tt = self._single_step_timestep()
-        if not self.scheduler.z0_is_neg_v(t):
-            raise NotImplementedError("segment_queries needs the one-step scheduler with z0 = -v (the reference's setting); "
-                                      "with this scheduler use run_episodes(), which runs the generic single_infer path")
-        folded = self._fold_conditioning(tt)
-        dev = self.device
-        prompt = None if folded else self.encode_clip_feature()
-        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
-                   query_gt=None if query_gt is None else query_gt.to(dev).contiguous())
-        # the whole validity check on the host, before anything is launched or replayed
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)     # the encoder halves (floor) once per level but the last
-        H, W = ins["query_img"].shape[-2:]
-        bank.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
-                   fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        Scheduler, stale banks, `captured` and `native` (ops.seg_native): the rules at the head of this section."""
+        tt, folded, prompt, ins, _ = self._query_context("segment_queries", bank, None, query_img, query_gt)
         flags = (float(r_threshold), float(threshold), bool(batch_max))
 
-        def step(query_img, query_gt=None):
-            lc = self.vae.config["latent_channels"]
-            mom = self.vae.encoder(query_img)
-            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
-            z0 = self.unet.forward_queries(z_tag, tt, bank, prompt, out_scale=-1.0)
+        def step(query_img, gt=None):
+            z0 = self.unet.forward_queries(self._query_latents(query_img), tt, bank, prompt, out_scale=-1.0)
             dec = self.decode_seg(z0)
-            seg_u8, counts = ops.seg_postprocess(dec, query_gt, *flags)
+            seg_u8, counts = ops.seg_postprocess(dec, gt, *flags)
             return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
-        if captured is None:
-            captured = self.use_graph
-        if not captured:
-            return self._with_native(step(**ins), native, flags)
-        key = ("queries", bank.uid, tuple(ins["query_img"].shape), query_gt is not None, flags, float(tt), folded,
-               getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
-        if key in self._graphs:
-            self._graphs[key] = self._graphs.pop(key)          # most recently used last
-        else:
-            mine = [k for k in self._graphs if k[0] == "queries"]
-            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
-                del self._graphs[k]
-        return self._with_native(self._replay(key, step, ins), native, flags)
+        head = ("queries", bank.uid, tuple(ins["query_img"].shape), query_gt is not None, flags)
+        return self._run_query_step(head, step, ins, tt, folded, captured,
+                                    lambda r: self._with_native(r, native, ops.seg_native, *flags))
 
     # ------------------------------------------------------------------ N-way: a stack of class banks
     @torch.no_grad()
     def prepare_support_classes(self, support_imgs, support_masks):
         """Prepare the support sets of N classes for segment_classes(): support_imgs / support_masks [N, s, 3, H, W] in
         [-1, 1] (s annotated examples of each class) -> SupportBankSet (diffews_amd.unet).  prepare_support's launches over
-        all N * s images at once: one VAE-encoder launch train, quant_conv into cat([z_ref, z_mask_ref]), one support pass
-        of the UNet (unet.prepare_bank_sets).  Valid for what a SupportBank is valid for.
+        all N * s images at once: _support_latents, then one support pass of the UNet (unet.prepare_bank_sets).  Valid for
+        what a SupportBank is valid for.
 
         Classes with different numbers of examples: give two lists of N tensors [s_c, 3, H, W] instead.  The same launches
         run over all sum(s_c) images and the result is a ragged SupportBankSet (shots == (s_0, ..., s_{N-1})), which
@@ -441,44 +503,26 @@ class MarigoldPipelineRGBLatentNoise:
         folded = self._fold_conditioning(tt)
         dev = self.device
         if isinstance(support_imgs, (list, tuple)):
-            return self._prepare_support_ragged(support_imgs, support_masks, tt, folded)
-        sup = support_imgs.to(dev, torch.float32).contiguous()
-        msk = support_masks.to(dev, torch.float32).contiguous()
-        if sup.shape != msk.shape or sup.dim() != 5:
-            raise ValueError(f"support_imgs {tuple(sup.shape)} and support_masks {tuple(msk.shape)} must both be "
-                             "[N, s, 3, H, W]")
-        N, s = sup.shape[:2]
-        sup, msk = sup.view(N * s, *sup.shape[2:]), msk.view(N * s, *msk.shape[2:])
-        lc = self.vae.config["latent_channels"]
-        mom = self.vae.encoder([sup, msk])                                        # [2 N s, 2 lc, h, w] fp32
-        h, w = mom.shape[-2:]
-        cond_ref = torch.empty(N * s, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
-        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
-        qc(mom[:N * s], out_scale=sf, out=cond_ref[:, :lc], channels=lc)          # z_ref      (P:649)
-        qc(mom[N * s:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)          # z_mask_ref (P:651)
-        return self.unet.prepare_bank_sets(cond_ref, N, tt, None if folded else self.encode_clip_feature())
-
-    def _prepare_support_ragged(self, support_imgs, support_masks, tt, folded):
-        dev = self.device
-        if not isinstance(support_masks, (list, tuple)) or len(support_masks) != len(support_imgs) or not support_imgs:
-            raise ValueError("support_imgs and support_masks must be two lists of N tensors [s_c, 3, H, W]")
-        sups = [t.to(dev, torch.float32) for t in support_imgs]
-        msks = [t.to(dev, torch.float32) for t in support_masks]
-        for c, (a, m) in enumerate(zip(sups, msks)):
-            if a.shape != m.shape or a.dim() != 4 or a.shape[0] < 1 or a.shape[1:] != sups[0].shape[1:]:
-                raise ValueError(f"class {c}: support_imgs {tuple(a.shape)} and support_masks {tuple(m.shape)} must both be "
-                                 f"[s_c >= 1, {', '.join(str(d) for d in sups[0].shape[1:])}]")
-        shots = tuple(a.shape[0] for a in sups)
-        sup, msk, n = torch.cat(sups).contiguous(), torch.cat(msks).contiguous(), sum(shots)
-        lc = self.vae.config["latent_channels"]
-        mom = self.vae.encoder([sup, msk])                                        # [2 sum(s_c), 2 lc, h, w] fp32
-        h, w = mom.shape[-2:]
-        cond_ref = torch.empty(n, 2 * lc, h, w, dtype=torch.float32, device=mom.device)
-        qc, sf = self.vae.quant_conv, self.rgb_latent_scale_factor
-        qc(mom[:n], out_scale=sf, out=cond_ref[:, :lc], channels=lc)              # z_ref      (P:649)
-        qc(mom[n:], out_scale=sf, out=cond_ref[:, lc:], channels=lc)              # z_mask_ref (P:651)
-        return self.unet.prepare_bank_sets(cond_ref, len(shots), tt, None if folded else self.encode_clip_feature(),
-                                           shots=shots)
+            if not isinstance(support_masks, (list, tuple)) or len(support_masks) != len(support_imgs) or not support_imgs:
+                raise ValueError("support_imgs and support_masks must be two lists of N tensors [s_c, 3, H, W]")
+            sups = [t.to(dev, torch.float32) for t in support_imgs]
+            msks = [t.to(dev, torch.float32) for t in support_masks]
+            for c, (a, m) in enumerate(zip(sups, msks)):
+                if a.shape != m.shape or a.dim() != 4 or a.shape[0] < 1 or a.shape[1:] != sups[0].shape[1:]:
+                    raise ValueError(f"class {c}: support_imgs {tuple(a.shape)} and support_masks {tuple(m.shape)} must both be "
+                                     f"[s_c >= 1, {', '.join(str(d) for d in sups[0].shape[1:])}]")
+            shots = tuple(a.shape[0] for a in sups)
+            N, sup, msk = len(shots), torch.cat(sups).contiguous(), torch.cat(msks).contiguous()
+        else:
+            sup = support_imgs.to(dev, torch.float32).contiguous()
+            msk = support_masks.to(dev, torch.float32).contiguous()
+            if sup.shape != msk.shape or sup.dim() != 5:
+                raise ValueError(f"support_imgs {tuple(sup.shape)} and support_masks {tuple(msk.shape)} must both be "
+                                 "[N, s, 3, H, W]")
+            N, shots = sup.shape[0], None
+            sup, msk = sup.flatten(0, 1), msk.flatten(0, 1)
+        return self.unet.prepare_bank_sets(self._support_latents(sup, msk), N, tt,
+                                           None if folded else self.encode_clip_feature(), shots=shots)
 
     @torch.no_grad()
     def segment_classes(self, bankset, query_img, query_labels=None, r_threshold=0.25, threshold=0.0, batch_max=False,
@@ -496,35 +540,16 @@ class MarigoldPipelineRGBLatentNoise:
         the label is 0 where none is, else 1 + the foreground class of the largest mean mask value, lowest class on a
         tie; counts rows are per-label intersections and unions (metrics.nway_iou).
 
-        Scheduler restriction, stale-handle ValueErrors and `captured` as in segment_queries; the graph key holds the
-        set's uid, the shapes, max_batch and the flags, and the graphs share segment_queries' MAX_QUERY_GRAPHS.
-
-        native (input_pipeline.NativeTargets for these b queries): the dict gains `native` = ops.seg_labels_native on seg_u8
-        with this call's flags and `class_ids` -- labels, and per-label counts against the targets' ground truth, at every
-        query's own h x w.  As in run_episodes it runs eagerly on the same stream after the step, captured or not, and is
-        neither part of the graph nor of its key; every other entry is what the call without `native` returns."""
-        from .unet import SupportBankSet
-        if not isinstance(bankset, SupportBankSet):
-            raise TypeError("bankset must be a SupportBankSet (prepare_support_classes)")
-        t, tt = self._single_step_timestep()
-        if not self.scheduler.z0_is_neg_v(t):
-            raise NotImplementedError("segment_classes needs the one-step scheduler with z0 = -v (the reference's setting)")
-        folded = self._fold_conditioning(tt)
-        dev = self.device
-        prompt = None if folded else self.encode_clip_feature()
-        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
-                   query_labels=None if query_labels is None else query_labels.to(dev).contiguous())
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        TypeError for anything but a SupportBankSet.  Scheduler, stale sets, `captured` (max_batch is part of the key) and
+        `native`: the rules at the head of this section; `native` is ops.seg_labels_native with this call's flags and
+        `class_ids` -- labels, and per-label counts against the targets' ground truth, at every query's own h x w."""
+        tt, folded, prompt, ins, _ = self._query_context("segment_classes", bankset, TypeError, query_img, query_labels)
         b, _, H, W = ins["query_img"].shape
-        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
-                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
         flags = (float(r_threshold), float(threshold), bool(batch_max))
         N, per = bankset.nsets, min(64, max(1, int(max_batch) // b))     # a ragged launch carries at most 64 sets
 
-        def step(query_img, query_labels=None):
-            lc = self.vae.config["latent_channels"]
-            mom = self.vae.encoder(query_img)
-            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
+        def step(query_img, gt=None):
+            z_tag = self._query_latents(query_img)
             seg_u8 = torch.empty(N, b, 3, H, W, dtype=torch.uint8, device=query_img.device)
             mx = torch.empty(N * b, dtype=torch.int32, device=query_img.device)
             z0s, decs = [], []
@@ -536,23 +561,13 @@ class MarigoldPipelineRGBLatentNoise:
                 ops.seg_postprocess(dec, None, *flags, u8_out=seg_u8[c0:c1].view(-1, 3, H, W), scratch=mx[c0 * b:c1 * b])
                 z0s.append(z0)
                 decs.append(dec.view(c1 - c0, b, *dec.shape[1:]))
-            labels, counts = ops.seg_labels(seg_u8, mx, query_labels, *flags)
+            labels, counts = ops.seg_labels(seg_u8, mx, gt, *flags)
             z0 = z0s[0] if len(z0s) == 1 else torch.cat(z0s)
             dec = decs[0] if len(decs) == 1 else torch.cat(decs)
             return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=labels, counts=counts)
-        if captured is None:
-            captured = self.use_graph
-        if not captured:
-            return self._with_native_labels(step(**ins), native, flags, class_ids)
-        key = ("queries", "classes", bankset.uid, tuple(ins["query_img"].shape), query_labels is not None, flags, int(max_batch),
-               float(tt), folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
-        if key in self._graphs:
-            self._graphs[key] = self._graphs.pop(key)          # most recently used last
-        else:
-            mine = [k for k in self._graphs if k[0] == "queries"]
-            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
-                del self._graphs[k]
-        return self._with_native_labels(self._replay(key, step, ins), native, flags, class_ids)
+        head = ("queries", "classes", bankset.uid, tuple(ins["query_img"].shape), query_labels is not None, flags, int(max_batch))
+        return self._run_query_step(head, step, ins, tt, folded, captured,
+                                    lambda r: self._with_native(r, native, ops.seg_labels_native, *flags, class_ids=class_ids))
 
     # ------------------------------------------------------------------ routed queries: one class of a stack per query
     @torch.no_grad()
@@ -565,58 +580,31 @@ class MarigoldPipelineRGBLatentNoise:
         whose every attn1 reads the stack in place through a device table of (first image, shots) rows
         (unet.forward_query_routed, ops.fsa_attention_routed), where segment_classes would run all N classes per query.
 
-        Scheduler restriction, stale-handle ValueErrors and `native` as in segment_queries; ValueError for a route that is
-        not b long or names a set outside the stack.
-
-        captured (default: self.use_graph): the route table is one of the step's static inputs -- every call copies it
-        from a pinned host tensor into the graph's buffer and the kernels read it when they run -- so the graph key
-        holds the set's uid, the shapes and the flags but NOT the route: one graph serves every route of that shape.  It
-        counts against MAX_QUERY_GRAPHS like the other query steps.  A replay runs no library-side validation of the
-        table; it needs none, because SupportBankSet.route_table builds every row from the set's own offsets."""
-        from .unet import SupportBankSet
-        if not isinstance(bankset, SupportBankSet):
-            raise ValueError("segment_routed needs a SupportBankSet (prepare_support_classes)")
-        t, tt = self._single_step_timestep()
-        if not self.scheduler.z0_is_neg_v(t):
-            raise NotImplementedError("segment_routed needs the one-step scheduler with z0 = -v (the reference's setting)")
-        folded = self._fold_conditioning(tt)
-        dev = self.device
-        prompt = None if folded else self.encode_clip_feature()
-        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
-                   query_gt=None if query_gt is None else query_gt.to(dev).contiguous())
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
-        b, _, H, W = ins["query_img"].shape
-        table_host = bankset.route_table(route)          # ValueError: empty, or a set outside the stack
-        if table_host.shape[0] != b:
-            raise ValueError(f"a route of {table_host.shape[0]} entries for {b} queries")
-        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
-                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
+        ValueError for anything but a SupportBankSet and for a route that is not b long or names a set outside the stack.
+        Scheduler, stale sets, `captured` and `native` (ops.seg_native): the rules at the head of this section.  The
+        route table is the step's one table: one graph serves every route of that shape.  A replay runs no library-side
+        validation of the table; it needs none, because SupportBankSet.route_table builds every row from the set's own
+        offsets."""
+        def tables(b):
+            table_host = bankset.route_table(route)          # ValueError: empty, or a set outside the stack
+            if table_host.shape[0] != b:
+                raise ValueError(f"a route of {table_host.shape[0]} entries for {b} queries")
+            return table_host
+        tt, folded, prompt, ins, table_host = self._query_context("segment_routed", bankset, ValueError, query_img, query_gt,
+                                                                  tables)
         flags = (float(r_threshold), float(threshold), bool(batch_max))
-        table_host = table_host.pin_memory()
+        ins["table"] = table_host = table_host.pin_memory()
 
-        def step(query_img, table, query_gt=None):
-            lc = self.vae.config["latent_channels"]
-            mom = self.vae.encoder(query_img)
-            z_tag = self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc)       # z_tag (P:650)
+        def step(query_img, table, gt=None):
             # table_host mirrors `table` whenever this runs (eagerly, or while a graph is warmed up and captured)
-            z0 = self.unet.forward_query_routed(z_tag, tt, bankset, table, table_host, prompt, out_scale=-1.0)
+            z0 = self.unet.forward_query_routed(self._query_latents(query_img), tt, bankset, table, table_host, prompt,
+                                                out_scale=-1.0)
             dec = self.decode_seg(z0)
-            seg_u8, counts = ops.seg_postprocess(dec, query_gt, *flags)
+            seg_u8, counts = ops.seg_postprocess(dec, gt, *flags)
             return dict(z0=z0, dec=dec, seg_u8=seg_u8, counts=counts)
-        if captured is None:
-            captured = self.use_graph
-        if not captured:
-            return self._with_native(step(table=table_host.to(dev, non_blocking=True), **ins), native, flags)
-        ins["table"] = table_host        # _replay: a device buffer at capture, one H2D copy into it per call
-        key = ("queries", "routed", bankset.uid, tuple(ins["query_img"].shape), query_gt is not None, flags, float(tt),
-               folded, getattr(self, "_fold_key", None), self.unet.residual_dtype, self.vae.residual_dtype)
-        if key in self._graphs:
-            self._graphs[key] = self._graphs.pop(key)          # most recently used last
-        else:
-            mine = [k for k in self._graphs if k[0] == "queries"]
-            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
-                del self._graphs[k]
-        return self._with_native(self._replay(key, step, ins), native, flags)
+        head = ("queries", "routed", bankset.uid, tuple(ins["query_img"].shape), query_gt is not None, flags)
+        return self._run_query_step(head, step, ins, tt, folded, captured,
+                                    lambda r: self._with_native(r, native, ops.seg_native, *flags))
 
     # ------------------------------------------------------------------ candidate classes per query, one label map
     @torch.no_grad()
@@ -630,11 +618,11 @@ class MarigoldPipelineRGBLatentNoise:
         (query, candidate) pair -- E = sum of the list lengths -- whatever N is.
 
         The b queries are VAE-encoded ONCE, however many candidates they have -- in chunks of entry_batch queries, the last
-        chunk padded by repeating the last query, so that the encoder too runs at batch entry_batch: GEMM plans (tile,
-        split-K), and with them the bits, depend on the batch, and with every kernel of the step at ONE batch an entry is
-        bit for bit what segment_routed computes at that batch, whatever b and the other candidates are.  An entry_batch
-        that divides b pads nothing.  The E entries, query-major, are padded to E_pad (a multiple of entry_batch;
-        SupportBankSet.candidate_tables) and run as E_pad / entry_batch passes of entry_batch entries: the pass's latents
+        chunk padded by repeating the last query, so that the encoder too runs at batch entry_batch (_query_latents): with
+        every kernel of the step at ONE batch an entry is bit for bit what segment_routed computes at that batch, whatever
+        b and the other candidates are.  An entry_batch that divides b pads nothing.  The E entries, query-major, are
+        padded to E_pad (a multiple of entry_batch; SupportBankSet.candidate_tables) and run as E_pad / entry_batch passes
+        of entry_batch entries: the pass's latents
         are gathered by index_select on a device index tensor, the pass goes through unet.forward_query_routed on its rows
         of the (first image, shots) table, decode_seg, and a gt-less ops.seg_postprocess into its slice of one seg_u8 / maxima
         buffer; one ops.seg_labels_cand launch then fuses every query's entries into its label map.  There is no batch_max
@@ -649,15 +637,11 @@ class MarigoldPipelineRGBLatentNoise:
         [offsets[i], offsets[i+1])).  Entry e is what segment_routed computes for the same pass batch; a gt label that is
         not among the query's candidates counts as a miss in that label's union.
 
-        Scheduler restriction, bankset.check(...) and stale-handle ValueErrors as in segment_routed; ValueError for a
-        number of lists other than b and for what candidate_tables rejects.
-
-        captured (default: self.use_graph): the entry indices, the rows and the label table are pinned host tensors and
-        static inputs of the step -- each is one H2D copy per call into the graph's buffer, and the kernels read them when
-        they run.  The graph key holds the set's uid, the query shape, E_pad, entry_batch, labels, nlabels, whether
-        query_labels were given and the flags, but NOT the candidates: one graph serves every assignment with the same b
-        and number of passes (with labels="local" also the same longest list).  It counts against MAX_QUERY_GRAPHS like
-        the other query steps.
+        ValueError for anything but a SupportBankSet, for a number of lists other than b and for what candidate_tables
+        rejects.  Scheduler, stale sets and `captured`: the rules at the head of this section.  The entry indices, the
+        rows and the label table are the step's tables; the key also holds E_pad, entry_batch, labels and nlabels, so one
+        graph serves every assignment with the same b and number of passes (with labels="local" also the same longest
+        list).
 
         entry_batch = 8 is a choice, not a measurement.  It bounds the decoder's batch: 16 entries at 512 x 512 reach the
         VAE decoder's 2 GiB buffer-descriptor range (DFW_ERANGE).
@@ -675,11 +659,10 @@ class MarigoldPipelineRGBLatentNoise:
         native (input_pipeline.NativeTargets for these b queries): the dict gains `native` = dict(labels [uint8 [h_i, w_i]],
         counts int64 [b, 2, nlabels+1] or None, area int64 [E, 2], mx int32 [E], sizes) -- ops.seg_labels_cand_native on the
         step's seg_u8 and this call's table and flags: every entry resized to its query's own h x w, the label rule on the
-        resized bytes, counts against the targets' ground truth read in place.  As in segment_classes it runs eagerly on
-        the same stream after the step, captured or not, and is neither part of the graph nor of its key; every other
-        entry is bit for bit what segment_candidates returns.  ValueError without `native`.  class_ids: the
-        ground-truth id of each SET, nsets ints, for targets that hold class-id maps.  With labels="set" it is the table
-        from id to label 1 + set; a class outside the query's candidates is a miss in its label's union.  With
+        resized bytes, counts against the targets' ground truth read in place; otherwise the section's `native` rule.
+        ValueError without `native`.
+        class_ids: the ground-truth id of each SET, nsets ints, for targets that hold class-id maps.  With labels="set" it
+        is the table from id to label 1 + set; a class outside the query's candidates is a miss in its label's union.  With
         labels="local" it is gathered per entry, and an id none of the query's candidates carries is background (local
         labels have no bin for it).  Without class_ids the targets hold label maps in the labels the call writes."""
         if native is None:
@@ -690,40 +673,21 @@ class MarigoldPipelineRGBLatentNoise:
     def _segment_candidates(self, bankset, query_img, candidates, query_labels, r_threshold, threshold, entry_batch, labels,
                             captured, native=None, class_ids=None):
         """The body of segment_candidates / segment_candidates_native (callers hold torch.no_grad)."""
-        from .unet import SupportBankSet
-        if not isinstance(bankset, SupportBankSet):
-            raise ValueError("segment_candidates needs a SupportBankSet (prepare_support_classes)")
-        t, tt = self._single_step_timestep()
-        if not self.scheduler.z0_is_neg_v(t):
-            raise NotImplementedError("segment_candidates needs the one-step scheduler with z0 = -v (the reference's setting)")
-        folded = self._fold_conditioning(tt)
-        dev = self.device
-        prompt = None if folded else self.encode_clip_feature()
-        ins = dict(query_img=query_img.to(dev, torch.float32).contiguous(),
-                   query_labels=None if query_labels is None else query_labels.to(dev).contiguous())
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
+        def tables(b):
+            cands = list(candidates)
+            if len(cands) != b:
+                raise ValueError(f"{len(cands)} candidate lists for {b} queries")
+            return bankset.candidate_tables(cands, entry_batch, labels)       # ValueError: see candidate_tables
+        tt, folded, prompt, ins, ct = self._query_context("segment_candidates", bankset, ValueError, query_img, query_labels,
+                                                          tables)
         b, _, H, W = ins["query_img"].shape
-        candidates = list(candidates)
-        if len(candidates) != b:
-            raise ValueError(f"{len(candidates)} candidate lists for {b} queries")
-        ct = bankset.candidate_tables(candidates, entry_batch, labels)       # ValueError: see candidate_tables
-        bankset.check(hw=(H // f, W // f), dtype=self.unet.dtype, residual_dtype=self.unet.residual_dtype,
-                      fold_key=self.unet._fold_key(tt, prompt), weights_id=self.unet._weights_id)
         E, E_pad, nlabels, eb = ct["E"], ct["E_pad"], ct["nlabels"], int(entry_batch)
         flags = (float(r_threshold), float(threshold))
-        entries_host, rows_host, tab_host = ct["entries"].pin_memory(), ct["rows"].pin_memory(), ct["tab"].pin_memory()
+        rows_host, tab_host = ct["rows"].pin_memory(), ct["tab"].pin_memory()
+        ins.update(entries=ct["entries"].pin_memory(), rows=rows_host, tab=tab_host)
 
-        def step(query_img, entries, rows, tab, query_labels=None):
-            lc = self.vae.config["latent_channels"]
-            # every query is encoded once, in chunks of entry_batch (the last one padded with the last query): GEMM plans,
-            # and so the bits, depend on the batch, and this way every kernel of the step runs at batch entry_batch
-            pad = -b % eb
-            qs = query_img if not pad else torch.cat([query_img, query_img[-1:].expand(pad, -1, -1, -1)])
-            zs = []
-            for c0 in range(0, b + pad, eb):
-                mom = self.vae.encoder(qs[c0:c0 + eb])
-                zs.append(self.vae.quant_conv(mom, out_scale=self.rgb_latent_scale_factor, channels=lc))   # z_tag (P:650)
-            z_tag = zs[0] if len(zs) == 1 else torch.cat(zs)
+        def step(query_img, entries, rows, tab, gt=None):
+            z_tag = self._query_latents(query_img, eb)      # every kernel of the step runs at batch entry_batch
             seg_u8 = torch.empty(E_pad, 3, H, W, dtype=torch.uint8, device=query_img.device)
             mx = torch.empty(E_pad, dtype=torch.int32, device=query_img.device)
             z0s, decs = [], []
@@ -738,7 +702,7 @@ class MarigoldPipelineRGBLatentNoise:
                 ops.seg_postprocess(dec, None, *flags, False, u8_out=seg_u8[e0:e0 + eb], scratch=mx[e0:e0 + eb])
                 z0s.append(z0)
                 decs.append(dec)
-            lab, counts, area = ops.seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, query_labels, *flags, want_area=True)
+            lab, counts, area = ops.seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt, *flags, want_area=True)
             z0 = z0s[0] if len(z0s) == 1 else torch.cat(z0s)
             dec = decs[0] if len(decs) == 1 else torch.cat(decs)
             return dict(z0=z0, dec=dec, seg_u8=seg_u8, labels=lab, counts=counts, area=area, tab=tab)
@@ -763,22 +727,9 @@ class MarigoldPipelineRGBLatentNoise:
                 out["native"] = dict(labels=n["labels"], counts=n["counts"], area=n["area"][:E], mx=n["mx"][:E],
                                      sizes=n["sizes"])
             return out
-        if captured is None:
-            captured = self.use_graph
-        if not captured:
-            return trimmed(step(entries=entries_host.to(dev, non_blocking=True), rows=rows_host.to(dev, non_blocking=True),
-                                tab=tab_host.to(dev, non_blocking=True), **ins))
-        ins.update(entries=entries_host, rows=rows_host, tab=tab_host)   # _replay: device buffers, one H2D copy each per call
-        key = ("queries", "candidates", bankset.uid, tuple(ins["query_img"].shape), E_pad, eb, labels, nlabels,
-               query_labels is not None, flags, float(tt), folded, getattr(self, "_fold_key", None),
-               self.unet.residual_dtype, self.vae.residual_dtype)
-        if key in self._graphs:
-            self._graphs[key] = self._graphs.pop(key)          # most recently used last
-        else:
-            mine = [k for k in self._graphs if k[0] == "queries"]
-            for k in mine[:max(0, len(mine) - (self.MAX_QUERY_GRAPHS - 1))]:
-                del self._graphs[k]
-        return trimmed(self._replay(key, step, ins))
+        head = ("queries", "candidates", bankset.uid, tuple(ins["query_img"].shape), E_pad, eb, labels, nlabels,
+                query_labels is not None, flags)
+        return self._run_query_step(head, step, ins, tt, folded, captured, trimmed)
 
     def segment_stream(self, support, queries, batch=4, size=None, depth=2, class_value=None, ignore_value=-1,
                        class_ids=None, r_threshold=0.25, threshold=0.0, batch_max=False, max_batch=16, captured=None,
@@ -827,8 +778,10 @@ class MarigoldPipelineRGBLatentNoise:
         if not nway and class_ids is not None:
             raise ValueError("class_ids belongs to a SupportBankSet; with a SupportBank give class_value")
         if size is None:
-            f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
-            size = (support.hw[0] * f, support.hw[1] * f)
+            size = (support.hw[0] * self._vae_factor, support.hw[1] * self._vae_factor)
+        getter = lambda g: g if callable(g) else (lambda q: q[g])     # a callable on the query dict, or the name of a key
+        flags = dict(r_threshold=r_threshold, threshold=threshold, captured=captured)
+        # per route: the QueryLoader's own keywords and call(bt) -> r; every argument error before the first batch is drawn
         if candidates is not None:
             if not nway:
                 raise ValueError("candidates name sets of a SupportBankSet; a SupportBank has only one")
@@ -840,23 +793,17 @@ class MarigoldPipelineRGBLatentNoise:
                 raise ValueError("class_ids maps the ground truth of the native-size pass: give native=True with it")
             if class_ids is not None:     # staged once, not per batch
                 class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
-            cand_of = candidates if callable(candidates) else (lambda q, _k=candidates: q[_k])
-            loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, ignore_value=ignore_value,
-                                 candidates=cand_of)
-            for bt in loader:
-                kw = dict(query_labels=bt.get("query_labels"), r_threshold=r_threshold, threshold=threshold,
-                          entry_batch=entry_batch, labels=labels, captured=captured)
+            loader_kw = dict(candidates=getter(candidates))
+
+            def call(bt):
+                kw = dict(query_labels=bt.get("query_labels"), entry_batch=entry_batch, labels=labels, **flags)
                 if native:
-                    r = dict(self.segment_candidates_native(support, bt["query_img"], bt["candidates"], bt["native"],
-                                                            class_ids, **kw))
+                    r = self.segment_candidates_native(support, bt["query_img"], bt["candidates"], bt["native"], class_ids, **kw)
                 else:
-                    r = dict(self.segment_candidates(support, bt["query_img"], bt["candidates"], **kw))
-                r["candidates"] = bt["candidates"]
-                yield bt["index"], r
-            return
-        flags = dict(r_threshold=r_threshold, threshold=threshold, batch_max=batch_max, captured=captured)
-        if route is not None:
-            route_of = route if callable(route) else (lambda q, _k=route: q[_k])
+                    r = self.segment_candidates(support, bt["query_img"], bt["candidates"], **kw)
+                return dict(r, candidates=bt["candidates"])
+        elif route is not None:
+            route_of = getter(route)
             if class_ids is not None:     # the query's own class is its foreground value (QueryLoader's callable form)
                 ids = [int(c) for c in class_ids]
                 if len(ids) != support.nsets:
@@ -867,25 +814,64 @@ class MarigoldPipelineRGBLatentNoise:
                     if not 0 <= c < len(ids):
                         raise ValueError(f"a query is routed to set {c} of a support bank set of {len(ids)}")
                     return ids[c]
-            loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, class_value=class_value,
-                                 ignore_value=ignore_value, route=route_of)
-            for bt in loader:
-                r = dict(self.segment_routed(support, bt["query_img"], bt["route"], bt.get("query_mask"),
-                                             native=bt["native"], **flags))
-                r["route"] = bt["route"]
-                yield bt["index"], r
-            return
-        if class_ids is not None:     # staged once, not per batch
-            class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
-        loader = QueryLoader(queries, size, batch, device=self.device, depth=depth, class_value=class_value,
-                             ignore_value=ignore_value)
-        for bt in loader:
-            if nway:
-                r = self.segment_classes(support, bt["query_img"], None, max_batch=max_batch, native=bt["native"],
-                                         class_ids=class_ids, **flags)
-            else:
-                r = self.segment_queries(support, bt["query_img"], bt.get("query_mask"), native=bt["native"], **flags)
-            yield bt["index"], r
+            loader_kw = dict(class_value=class_value, route=route_of)
+
+            def call(bt):
+                r = self.segment_routed(support, bt["query_img"], bt["route"], bt.get("query_mask"), native=bt["native"],
+                                        batch_max=batch_max, **flags)
+                return dict(r, route=bt["route"])
+        else:
+            if class_ids is not None:     # staged once, not per batch
+                class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(self.device)
+            loader_kw = dict(class_value=class_value)
+
+            def call(bt):
+                if nway:
+                    return self.segment_classes(support, bt["query_img"], None, max_batch=max_batch, native=bt["native"],
+                                                class_ids=class_ids, batch_max=batch_max, **flags)
+                return self.segment_queries(support, bt["query_img"], bt.get("query_mask"), native=bt["native"],
+                                            batch_max=batch_max, **flags)
+        for bt in QueryLoader(queries, size, batch, device=self.device, depth=depth, ignore_value=ignore_value, **loader_kw):
+            yield bt["index"], call(bt)
+
+    def _tile_stage(self, support, image, gt, overlap, ramp, batch):
+        """segment_tiled's staging: the TilePlan of `image` for windows of the size `support` was prepared at; image and gt
+        through one pinned buffer and one H2D copy; the window transform (kept on the pipeline between calls); and one fp32
+        [batch, 3, th, tw] query buffer.  Returns (plan, its C record, gt on the device [1, h, w] or None, cut), where
+        cut(runs) fills that buffer -- one ops.tiles_cut per (first window, count) run, in order, the rest of the batch
+        padded by repeating the last window cut -- and returns it."""
+        from .input_pipeline import DeviceImageTransform, TilePlan
+        th, tw = support.hw[0] * self._vae_factor, support.hw[1] * self._vae_factor
+        img = DeviceImageTransform.as_rgb_bytes(image)
+        h, w = img.shape[:2]
+        plan = TilePlan((h, w), (th, tw), min(th, tw) // 8 if overlap is None else overlap, ramp)
+        if gt is not None:
+            gt = np.ascontiguousarray(gt.cpu().numpy() if torch.is_tensor(gt) else gt)
+            if gt.dtype != np.uint8 or gt.shape != (h, w):
+                raise ValueError(f"gt must be a uint8 label map [{h}, {w}], got {gt.dtype} {gt.shape}")
+        n_img = 3 * h * w
+        host = torch.empty(n_img + (h * w if gt is not None else 0), dtype=torch.uint8, pin_memory=True)
+        host[:n_img].view(h, w, 3).numpy()[...] = img
+        if gt is not None:
+            host[n_img:].view(h, w).numpy()[...] = gt
+        staged = host.to(self.device, non_blocking=True)                       # the one H2D copy
+        img_dev = staged[:n_img].view(h, w, 3)
+        gt_dev = staged[n_img:].view(1, h, w) if gt is not None else None
+        tf = getattr(self, "_tile_tf", None)
+        if tf is None or (tf.out_h, tf.out_w) != (th, tw) or tf.device != torch.device(staged.device):
+            tf = self._tile_tf = DeviceImageTransform((th, tw), staged.device)  # owns the ToTensor + Normalize table
+        cplan = plan.c_struct()
+        q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
+
+        def cut(runs):
+            n = 0
+            for first, count in runs:
+                ops.tiles_cut(cplan, img_dev, tf.lut, first, count, out=q[n:n + count])
+                n += count
+            if n < batch:
+                q[n:] = q[n - 1]                                              # padding: the last window again
+            return q
+        return plan, cplan, gt_dev, cut
 
     @torch.no_grad()
     def segment_tiled(self, support, image, gt=None, overlap=None, ramp=None, batch=4, r_threshold=0.25, threshold=0.0,
@@ -907,8 +893,8 @@ class MarigoldPipelineRGBLatentNoise:
         Returns dict(seg_u8 uint8 [N, 3, h, w], labels uint8 [h, w], counts, mx int32 [N], plan); N = 1 for a bank, where
         `pred` is an alias of `labels` and counts is int64 [4] in seg_postprocess' order (inter0, inter1, union0, union1);
         for a set counts is int64 [2, N+1] (metrics.nway_iou); counts is None without gt.  There is no batch_max: the
-        merged image has one maximum per class.  Scheduler restriction, stale-handle errors and `captured` as in the
-        routed calls; an image smaller than the tile in either axis is a ValueError (segment_stream resizes).
+        merged image has one maximum per class.  Scheduler, stale supports and `captured`: the rules at the head of the
+        support-bank section; an image smaller than the tile in either axis is a ValueError (segment_stream resizes).
 
         candidates (a SupportBankSet only, else ValueError; default None: everything above, launch for launch): T lists of
         set indices, or a callable on the TilePlan that returns them (plan.candidates_from_labels, or
@@ -927,7 +913,6 @@ class MarigoldPipelineRGBLatentNoise:
         entry, offsets = T + 1 ints, window t owns entries [offsets[t], offsets[t+1]), groups = the (windows, lists)
         passed to each segment_candidates call, padding included -- enough to replay the calls --, plan).  There is no
         seg_u8 key: the merged [N, 3, h, w] image is what this route exists not to build."""
-        from .input_pipeline import DeviceImageTransform, TilePlan
         from .unet import SupportBank, SupportBankSet
         if not isinstance(support, (SupportBank, SupportBankSet)):
             raise TypeError("support must be a SupportBank (prepare_support) or a SupportBankSet (prepare_support_classes)")
@@ -937,50 +922,27 @@ class MarigoldPipelineRGBLatentNoise:
         batch = int(batch)
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
-        th, tw = support.hw[0] * f, support.hw[1] * f
-        img = DeviceImageTransform.as_rgb_bytes(image)
-        h, w = img.shape[:2]
-        plan = TilePlan((h, w), (th, tw), min(th, tw) // 8 if overlap is None else overlap, ramp)
-        if gt is not None:
-            gt = np.ascontiguousarray(gt.cpu().numpy() if torch.is_tensor(gt) else gt)
-            if gt.dtype != np.uint8 or gt.shape != (h, w):
-                raise ValueError(f"gt must be a uint8 label map [{h}, {w}], got {gt.dtype} {gt.shape}")
-        dev = self.device
-        n_img = 3 * h * w
-        host = torch.empty(n_img + (h * w if gt is not None else 0), dtype=torch.uint8, pin_memory=True)
-        host[:n_img].view(h, w, 3).numpy()[...] = img
-        if gt is not None:
-            host[n_img:].view(h, w).numpy()[...] = gt
-        staged = host.to(dev, non_blocking=True)                               # the one H2D copy
-        img_dev = staged[:n_img].view(h, w, 3)
-        gt_dev = staged[n_img:].view(1, h, w) if gt is not None else None
-        tf = getattr(self, "_tile_tf", None)
-        if tf is None or (tf.out_h, tf.out_w) != (th, tw) or tf.device != torch.device(staged.device):
-            tf = self._tile_tf = DeviceImageTransform((th, tw), staged.device)  # owns the ToTensor + Normalize table
+        plan, cplan, gt_dev, cut = self._tile_stage(support, image, gt, overlap, ramp, batch)
+        h, w, th, tw, dev = plan.img_h, plan.img_w, plan.tile_h, plan.tile_w, self.device
         N, T = (support.nsets if nway else 1), plan.T
-        cplan = plan.c_struct()
         if candidates is not None:
             ct = plan.candidate_table(candidates(plan) if callable(candidates) else candidates, N)   # ValueError: see there
             sets, E = ct["sets"], ct["E"]
             tab_host = ct["tab"].pin_memory()
-            tab = tab_host.to(staged.device, non_blocking=True)
-            ent = torch.empty(E, 3, th, tw, dtype=torch.uint8, device=staged.device) if E else None
-            q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
+            tab = tab_host.to(dev, non_blocking=True)
+            ent = torch.empty(E, 3, th, tw, dtype=torch.uint8, device=dev) if E else None
             live = [t for t in range(T) if sets[t]]
             groups, e0 = [], 0
             for g0 in range(0, len(live), batch):
                 ws = live[g0:g0 + batch]
-                i = 0
-                while i < len(ws):                                            # one cut per run of adjacent windows
-                    j = i + 1
-                    while j < len(ws) and ws[j] == ws[j - 1] + 1:
-                        j += 1
-                    ops.tiles_cut(cplan, img_dev, tf.lut, ws[i], j - i, out=q[i:j])
-                    i = j
-                pad = batch - len(ws)
-                if pad:
-                    q[len(ws):] = q[len(ws) - 1]                              # padding: the last window again, no candidate
+                runs = []                                                     # one cut per run of adjacent windows
+                for t in ws:
+                    if runs and t == runs[-1][0] + runs[-1][1]:
+                        runs[-1][1] += 1
+                    else:
+                        runs.append([t, 1])
+                q = cut(runs)
+                pad = batch - len(ws)                                         # padding: the last window again, no candidate
                 group = (tuple(ws) + (ws[-1],) * pad, tuple(sets[t] for t in ws) + ((),) * pad)
                 r = self.segment_candidates(support, q, group[1], None, r_threshold=r_threshold, threshold=threshold,
                                             entry_batch=entry_batch, labels="set", captured=captured)
@@ -992,13 +954,10 @@ class MarigoldPipelineRGBLatentNoise:
                                                              r_threshold, threshold, want_area=True)
             return dict(labels=labels, counts=counts, mx=mx, area=area, plan=plan, groups=groups,
                         entries=[(t, c) for t, cs in enumerate(sets) for c in cs], offsets=ct["tab"][:T + 1].tolist())
-        win = torch.empty(N, T, 3, th, tw, dtype=torch.uint8, device=staged.device)
-        q = torch.empty(batch, 3, th, tw, dtype=torch.float32, device=staged.device)
+        win = torch.empty(N, T, 3, th, tw, dtype=torch.uint8, device=dev)
         for first in range(0, T, batch):
             count = min(batch, T - first)
-            ops.tiles_cut(cplan, img_dev, tf.lut, first, count, out=q[:count])
-            if count < batch:
-                q[count:] = q[count - 1]                                      # padding: the last window again
+            q = cut([(first, count)])
             if nway:
                 r = self.segment_classes(support, q, None, r_threshold=r_threshold, threshold=threshold,
                                          max_batch=max_batch, captured=captured)
@@ -1032,8 +991,7 @@ class MarigoldPipelineRGBLatentNoise:
         from .unet import SupportBankSet
         if not isinstance(library, SupportBankSet):
             raise ValueError("propose_tile_candidates needs a SupportBankSet (prepare_support_classes)")
-        f = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
-        th, tw = library.hw[0] * f, library.hw[1] * f
+        th, tw = library.hw[0] * self._vae_factor, library.hw[1] * self._vae_factor
         img = DeviceImageTransform.as_rgb_bytes(image)
         overlap = min(th, tw) // 8 if overlap is None else overlap
         plan = TilePlan(img.shape[:2], (th, tw), overlap, ramp)
@@ -1041,15 +999,6 @@ class MarigoldPipelineRGBLatentNoise:
         r = self.segment_classes(library, q[None], None, **segment_classes_flags)
         coarse = r["labels"][0].cpu()                                          # the one host synchronisation
         return dict(overlap=overlap, ramp=ramp), plan.candidates_from_labels(coarse.numpy(), min_pixels, margin)
-
-    @staticmethod
-    def _with_native_labels(r, native, flags, class_ids):
-        """_with_native for segment_classes: r plus r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags)."""
-        if native is None:
-            return r
-        r = dict(r)
-        r["native"] = ops.seg_labels_native(r["seg_u8"], native, *flags, class_ids=class_ids)
-        return r
 
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one

@@ -865,20 +865,9 @@ class MyUNet2DConditionModel:
         that filled the module bank with the same support set; the bank is only read.  Returns the sample (fp32 NCHW).
         ValueError if `bank` was prepared for another latent size, dtype, residual-stream mode, timestep / prompt or
         other weights."""
-        cfg, dt, dev = self.config, self.dtype, self.device
         if not isinstance(bank, SupportBank):
             raise TypeError("bank must be a SupportBank (prepare_bank)")
-        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
-        B, Cin, h, w = x_in.shape
-        if Cin != cfg["in_channels"]:
-            raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
-        bank.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
-                   fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
-        tproj, ehs2d, kv_all, L_ctx = self._conditioning(B, timestep, encoder_hidden_states)
-        c0 = cfg["block_out_channels"][0]
-        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
-        io = _BankIO(len(bank.k), bank)
-        return self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
+        return self._query_pass(z_tag, timestep, bank, encoder_hidden_states, out_scale, lambda b: _BankIO(len(bank.k), bank))
 
     @torch.no_grad()
     def forward_query_sets(self, z_tag, timestep, bankset, encoder_hidden_states=None, out_scale=1.0, sets=None):
@@ -887,29 +876,18 @@ class MyUNet2DConditionModel:
         through ops.fsa_attention_sets(group=b) on the stack's K/V sliced to those sets (views, no copy; a ragged set:
         ops.fsa_attention_ragged with those sets' shot counts).  Entry (c, i) is
         per image the arithmetic of forward_queries(z_tag[i:i+1], bankset.bank(sets[c])).  Returns [n, b, C, h, w] fp32."""
-        cfg, dt, dev = self.config, self.dtype, self.device
         if not isinstance(bankset, SupportBankSet):
             raise TypeError("bankset must be a SupportBankSet (prepare_bank_sets)")
         sets = range(bankset.nsets) if sets is None else sets
         if not isinstance(sets, range) or sets.step != 1 or len(sets) < 1 or sets.start < 0 or sets.stop > bankset.nsets:
             raise ValueError(f"sets must be a non-empty contiguous range within [0, {bankset.nsets}), got {sets}")
-        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
-        b, Cin, h, w = x_in.shape
-        if Cin != cfg["in_channels"]:
-            raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
-        bankset.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
-                      fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
-        n = len(sets)
-        tproj, ehs2d, kv_all, L_ctx = self._conditioning(n * b, timestep, encoder_hidden_states)
-        c0 = cfg["block_out_channels"][0]
-        # class-major: entry c * b + i (for b == 1 the reshape of the expansion is a stride-0 view: materialise it)
-        x_in = x_in.unsqueeze(0).expand(n, *x_in.shape).reshape(n * b, *x_in.shape[1:]).contiguous()
-        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
         lo, hi = bankset.offsets[sets.start], bankset.offsets[sets.stop]
-        io = _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b,
-                     shots=bankset.shots[sets.start:sets.stop] if bankset.ragged else None)
-        out = self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
-        return out.view(n, b, *out.shape[1:])
+
+        def make_io(b):
+            return _BankIO(len(bankset.k), bankset, [t[lo:hi] for t in bankset.k], [t[lo:hi] for t in bankset.v], group=b,
+                           shots=bankset.shots[sets.start:sets.stop] if bankset.ragged else None)
+        out = self._query_pass(z_tag, timestep, bankset, encoder_hidden_states, out_scale, make_io, repeat=len(sets))
+        return out.view(len(sets), -1, *out.shape[1:])
 
     @torch.no_grad()
     def forward_query_routed(self, z_tag, timestep, bankset, table, table_host, encoder_hidden_states=None, out_scale=1.0):
@@ -919,22 +897,35 @@ class MyUNet2DConditionModel:
         no copy), and the kernel reads its row when it runs -- a captured pass follows the table's contents.  Entry i is
         per image the arithmetic of forward_queries(z_tag[i:i+1], bankset.bank(route[i])).  Returns the sample (fp32
         NCHW); forward_queries' ValueErrors."""
-        cfg, dt, dev = self.config, self.dtype, self.device
         if not isinstance(bankset, SupportBankSet):
             raise TypeError("bankset must be a SupportBankSet (prepare_bank_sets)")
-        x_in = z_tag.to(device=dev, dtype=torch.float32).contiguous()
-        B, Cin, h, w = x_in.shape
+
+        def make_io(B):
+            if tuple(table.shape) != (B, 2) or tuple(table_host.shape) != (B, 2):
+                raise ValueError(f"a routed pass of {B} queries needs a [{B}, 2] route table, got {tuple(table.shape)} "
+                                 f"and {tuple(table_host.shape)}")
+            return _BankIO(len(bankset.k), bankset, table=(table, table_host, max(bankset.shots), min(bankset.shots)))
+        return self._query_pass(z_tag, timestep, bankset, encoder_hidden_states, out_scale, make_io)
+
+    def _query_pass(self, z_tag, timestep, support, encoder_hidden_states, out_scale, make_io, repeat=1):
+        """What the three query passes share: z_tag [b, in_channels, h, w] staged as fp32, the channel check, make_io(b) --
+        the pass' _BankIO, which may raise for arguments that depend on b --, support.check(...) against this latent size
+        and the module's current dtype, residual-stream mode, conditioning and weights, the conditioning rows, conv_in and
+        the trunk.  repeat = n: a class-major batch of n * b, the latents once per set.  Returns the sample [repeat * b, C, h,
+        w] fp32."""
+        cfg, dt = self.config, self.dtype
+        x_in = z_tag.to(device=self.device, dtype=torch.float32).contiguous()
+        b, Cin, h, w = x_in.shape
         if Cin != cfg["in_channels"]:
             raise ValueError(f"query pass expects {cfg['in_channels']} channels, got {Cin}")
-        if tuple(table.shape) != (B, 2) or tuple(table_host.shape) != (B, 2):
-            raise ValueError(f"a routed pass of {B} queries needs a [{B}, 2] route table, got {tuple(table.shape)} "
-                             f"and {tuple(table_host.shape)}")
-        bankset.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
+        io = make_io(b)
+        support.check(hw=(h, w), dtype=dt, residual_dtype=self.residual_dtype,
                       fold_key=self._fold_key(timestep, encoder_hidden_states), weights_id=self._weights_id)
-        tproj, ehs2d, kv_all, L_ctx = self._conditioning(B, timestep, encoder_hidden_states)
-        c0 = cfg["block_out_channels"][0]
-        x = ops.conv_small(x_in, self.w_in, self.b_in, c0, 9, dt, out_f32=self._f32s)
-        io = _BankIO(len(bankset.k), bankset, table=(table, table_host, max(bankset.shots), min(bankset.shots)))
+        tproj, ehs2d, kv_all, L_ctx = self._conditioning(repeat * b, timestep, encoder_hidden_states)
+        if repeat != 1:
+            # class-major: entry c * b + i (for b == 1 the reshape of the expansion is a stride-0 view: materialise it)
+            x_in = x_in.unsqueeze(0).expand(repeat, *x_in.shape).reshape(repeat * b, *x_in.shape[1:]).contiguous()
+        x = ops.conv_small(x_in, self.w_in, self.b_in, cfg["block_out_channels"][0], 9, dt, out_f32=self._f32s)
         return self._trunk(x, tproj, ehs2d, L_ctx, 0, out_scale, kv_all, bank_io=io)
 
     def _trunk(self, x, tproj, ehs2d, L_ctx, n_ref, out_scale, kv_all=None, bank_io=None):
