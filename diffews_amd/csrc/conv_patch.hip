@@ -249,39 +249,49 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(const GemmP p) {
       return;
     }
     float gs0 = 0.f, gs1 = 0.f, gq0 = 0.f, gq1 = 0.f;
+    // bias + per-image row bias: a lane's four channel quads are the same for every row of the tile -- loaded once per tile
+    f32x4 add[NB6];
+    const BiasSrc bsrc(p.bias, p.rowbias);
 #pragma unroll
-    for (int i = 0; i < MB6 / 2; ++i) {
-      f32x4 add[2][NB6];
-      i32x2 res[2][NB6];
+    for (int j = 0; j < NB6; ++j) {
+      const int n = c.n0 + wn * 64 + j * 16 + 4 * l4;
+      add[j] = bsrc.quad(n, (size_t)c.img * p.ldrb + n);
+    }
+    // The residual of round i + 1 is loaded at the top of round i, BEFORE round i's stores: vmcnt retires in order and counts
+    // stores, and the residual may alias the output, so a load issued behind a round's stores would wait for their round trip
+    // (four of them per tile: the epilogue was 24k cycles with a residual, 12k without, on 8 workgroups as on 256).  Round
+    // i + 1 then waits with round i's four stores still in flight.  The registers are those of the per-round bias copies.
+    // The epilogue is straight-line code, bias and residual read through descriptors that are empty for a null pointer: around a
+    // uniform branch hipcc's s_waitcnt insertion falls back to waiting for the stores.
+    const ResidualSrc<T> rsrc(p, row_to_m(c, 0), c.n0);
+    i32x2 res[MB6 / 2][2][NB6];
+    auto load_res = [&](int i) __attribute__((always_inline)) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
 #pragma unroll
         for (int j = 0; j < NB6; ++j) {
-          const int n = c.n0 + wn * 64 + j * 16 + 4 * l4;
-          f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-          if (p.bias) bb = *(const f32x4*)(p.bias + n);
-          if (p.rowbias) {
-            const f32x4 r = *(const f32x4*)(p.rowbias + (size_t)c.img * p.ldrb + n);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bb[e] += r[e];
-          }
-          add[h][j] = bb;
-          res[h][j] = i32x2{0, 0};
-          if (p.residual) res[h][j] = *(const i32x2*)(p.residual + ((size_t)m * p.ldr + n) * sizeof(T));
+          res[i][h][j] = rsrc.quad(m, wn * 64 + j * 16 + 4 * l4);
         }
       }
+    };
+    load_res(0);
+#pragma unroll
+    for (int i = 0; i < MB6 / 2; ++i) {
+      if (i + 1 < MB6 / 2) load_res(i + 1);
+      __builtin_amdgcn_sched_barrier(0);      // (the epilogue is straight-line code: keep the scheduler inside a round's steps)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int j = 0; j < NB6; ++j) {
-          float v[4], r[4] = {0.f, 0.f, 0.f, 0.f};
-          if (p.residual) unpack4<T>(res[h][j], r);
+          float v[4], r[4];
+          unpack4<T>(res[i][h][j], r);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[h][j][e] + r[e]) * p.out_scale;
+          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[j][e] + r[e]) * p.out_scale;
           const int row = h * 16 + l15, quad = j * 4 + l4;
           *(i32x2*)(stg + row * 128 + (((quad >> 1) ^ (row & 7)) << 4) + (quad & 1) * 8) = pack4<T>(v);
         }
+      __builtin_amdgcn_sched_barrier(0);
       if (p.gn_partial) {
         const int cp = lane & 31, rh = lane >> 5;
 #pragma unroll
@@ -294,6 +304,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(const GemmP p) {
           gs1 += a1; gq1 += a1 * a1;
         }
       }
+      __builtin_amdgcn_sched_barrier(0);
       const int c16 = lane & 7;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -401,9 +412,12 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(const GemmP p) {
   };
   for (int ti = 0; ti < my_tiles; ++ti) {
     zero6();
+    DFW_TILE_STAMP(p, wave, lane, ti, 0);
     if (wave >= 4) ktile(std::true_type{});
     else ktile(std::false_type{});
+    DFW_TILE_STAMP(p, wave, lane, ti, 1);
     epilogue6(ct, stgbase + wave * 4096, tile0 + ti * nxb);   // per-wave staging: no barrier needed around it
+    DFW_TILE_STAMP(p, wave, lane, ti, 2);
     if (ti + 1 < my_tiles) ct = tile_coords(tile0 + (ti + 1) * nxb);
   }
 }
@@ -423,6 +437,7 @@ static int launch_patch(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   int nwg = q.ntm * q.ntn;
   if (nwg > 256) nwg = 256;
   nwg = (nwg + 7) & ~7;
+  DFW_STAMP_LAUNCH(q, nwg);
   auto kfn = conv_patch_kernel<T, BM, BN, F32O>;
   (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(nwg), dim3(512), lds, st, q);

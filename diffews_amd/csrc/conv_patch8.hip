@@ -234,41 +234,46 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
     const int l15 = lane_e & 15, l4 = lane_e >> 4, lane = lane_e;
+    // straight-line code: bias, row bias and residual are read through descriptors that are empty for a null pointer (around a
+    // uniform branch hipcc's s_waitcnt insertion falls back to waiting for the stores)
+    const ResidualSrc<T> rsrc(p, row_to_m(c, 0), c.n0);
     if constexpr (N160) {
       // 64 x 80 wave tile: 32 rows per round through 160-byte staging rows (5 KiB per wave, `stg` is this wave's), stored as ten
       // 16-byte chunks per row = one contiguous 160-byte run of the output row; no fused statistics (10 channels per group)
+      f32x4 add[NBW];          // bias + per-image row bias, once per tile; the residual one round ahead (see below)
+      const BiasSrc bsrc(p.bias, p.rowbias);
 #pragma unroll
-      for (int i = 0; i < MB6 / 2; ++i) {
-        f32x4 add[2][NBW];
-        i32x2 res[2][NBW];
+      for (int j = 0; j < NBW; ++j) {
+        const int n = c.n0 + wc * 80 + j * 16 + 4 * l4;
+        add[j] = bsrc.quad(n, (size_t)c.img * p.ldrb + n);
+      }
+      i32x2 res[MB6 / 2][2][NBW];
+      auto load_res = [&](int i) __attribute__((always_inline)) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
 #pragma unroll
           for (int j = 0; j < NBW; ++j) {
-            const int n = c.n0 + wc * 80 + j * 16 + 4 * l4;
-            f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-            if (p.bias) bb = *(const f32x4*)(p.bias + n);
-            if (p.rowbias) {
-              const f32x4 r = *(const f32x4*)(p.rowbias + (size_t)c.img * p.ldrb + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) bb[e] += r[e];
-            }
-            add[h][j] = bb;
-            res[h][j] = i32x2{0, 0};
-            if (p.residual) res[h][j] = *(const i32x2*)(p.residual + ((size_t)m * p.ldr + n) * sizeof(T));
+            res[i][h][j] = rsrc.quad(m, wc * 80 + j * 16 + 4 * l4);
           }
         }
+      };
+      load_res(0);
+#pragma unroll
+      for (int i = 0; i < MB6 / 2; ++i) {
+        if (i + 1 < MB6 / 2) load_res(i + 1);
+        __builtin_amdgcn_sched_barrier(0);    // (the epilogue is straight-line code: keep the scheduler inside a round's steps)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
           for (int j = 0; j < NBW; ++j) {
-            float v[4], r[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p.residual) unpack4<T>(res[h][j], r);
+            float v[4], r[4];
+            unpack4<T>(res[i][h][j], r);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[h][j][e] + r[e]) * p.out_scale;
+            for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[j][e] + r[e]) * p.out_scale;
             *(i32x2*)(stg + (h * 16 + l15) * 160 + j * 32 + l4 * 8) = pack4<T>(v);
           }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
           const int idx = lane + 64 * t;               // 320 chunks of the round
@@ -281,39 +286,45 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
       return;
     }
     float gs0 = 0.f, gs1 = 0.f, gq0 = 0.f, gq1 = 0.f;
+    // bias + per-image row bias: a lane's four channel quads are the same for every row of the tile -- loaded once per tile
+    f32x4 add[NB6];
+    const BiasSrc bsrc(p.bias, p.rowbias);
 #pragma unroll
-    for (int i = 0; i < MB6 / 2; ++i) {
-      f32x4 add[2][NB6];
-      i32x2 res[2][NB6];
+    for (int j = 0; j < NB6; ++j) {
+      const int n = c.n0 + wc * 64 + j * 16 + 4 * l4;
+      add[j] = bsrc.quad(n, (size_t)c.img * p.ldrb + n);
+    }
+    // The residual of round i + 1 is loaded at the top of round i, BEFORE round i's stores: vmcnt retires in order and counts
+    // stores, and the residual may alias the output, so a load issued behind a round's stores would wait for their round trip.
+    // Round i + 1 then waits with round i's stores still in flight.  The registers are those of the per-round bias copies.
+    i32x2 res[MB6 / 2][2][NB6];
+    auto load_res = [&](int i) __attribute__((always_inline)) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
 #pragma unroll
         for (int j = 0; j < NB6; ++j) {
-          const int n = c.n0 + wc * 64 + j * 16 + 4 * l4;
-          f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-          if (p.bias) bb = *(const f32x4*)(p.bias + n);
-          if (p.rowbias) {
-            const f32x4 r = *(const f32x4*)(p.rowbias + (size_t)c.img * p.ldrb + n);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bb[e] += r[e];
-          }
-          add[h][j] = bb;
-          res[h][j] = i32x2{0, 0};
-          if (p.residual) res[h][j] = *(const i32x2*)(p.residual + ((size_t)m * p.ldr + n) * sizeof(T));
+          res[i][h][j] = rsrc.quad(m, wc * 64 + j * 16 + 4 * l4);
         }
       }
+    };
+    load_res(0);
+#pragma unroll
+    for (int i = 0; i < MB6 / 2; ++i) {
+      if (i + 1 < MB6 / 2) load_res(i + 1);
+      __builtin_amdgcn_sched_barrier(0);      // (the epilogue is straight-line code: keep the scheduler inside a round's steps)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int j = 0; j < NB6; ++j) {
-          float v[4], r[4] = {0.f, 0.f, 0.f, 0.f};
-          if (p.residual) unpack4<T>(res[h][j], r);
+          float v[4], r[4];
+          unpack4<T>(res[i][h][j], r);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[h][j][e] + r[e]) * p.out_scale;
+          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[j][e] + r[e]) * p.out_scale;
           const int row = h * 16 + l15, quad = j * 4 + l4;   // 8-byte piece `quad` of the staged 128-byte row
           *(i32x2*)(stg + row * 128 + (((quad >> 1) ^ (row & 7)) << 4) + (quad & 1) * 8) = pack4<T>(v);
         }
+      __builtin_amdgcn_sched_barrier(0);
       if (p.gn_partial) {
         const int cp = lane & 31, rh = lane >> 5;
 #pragma unroll
@@ -326,6 +337,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
           gs1 += a1; gq1 += a1 * a1;
         }
       }
+      __builtin_amdgcn_sched_barrier(0);
       const int c16 = lane & 7;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -361,6 +373,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
   TileC ct = tile_coords(tile0);
   nx_set(ct);
   w_setup(ct);
+  DFW_TILE_STAMP(p, wave, lane, 0, 0);
 #pragma unroll
   for (int i = 0; i < 6; ++i) issue_piece(i, 0);
   nx_advance();
@@ -417,7 +430,10 @@ __global__ __launch_bounds__(512, 2) void conv_patch8_kernel(const GemmP p) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) ab[kx][rr] += d;
           if (last) {
+            DFW_TILE_STAMP(p, wave, lane, ti, 1);
             epilogue6(ct, smem + pb * PATCH + wave * (N160 ? 5120 : 4096), tile0 + ti * nxb);
+            DFW_TILE_STAMP(p, wave, lane, ti, 2);
+            DFW_TILE_STAMP(p, wave, lane, ti + 1, 0);      // (the next tile's K walk starts where this epilogue ends)
             zero6();
             if (ti + 1 < my_tiles) ct = tile_coords(tile0 + (ti + 1) * nxb);
             if (wr == 1) bar();
@@ -445,6 +461,7 @@ static int launch_patch8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   int nwg = q.ntm * q.ntn;
   if (nwg > 256) nwg = 256;
   nwg = (nwg + 7) & ~7;
+  DFW_STAMP_LAUNCH(q, nwg);
   auto kfn = conv_patch8_kernel<T, BN>;
   (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(nwg), dim3(512), lds, st, q);

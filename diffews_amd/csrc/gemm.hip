@@ -523,6 +523,9 @@ static int fill_params(const dfw_gemm_args* a, GemmP& p) {
   p.nk = a->K / 64; p.cpt = a->Cin / 64; p.ntn = 0; p.ntm = 0;
   p.dtype_bf16 = a->dtype == DFW_BF16;
   p.gn_partial = a->gn_partial; p.gn_groups = a->gn_groups; p.gn_chunks = 0;
+#ifdef DFW_TILE_STAMPS
+  p.stamps = nullptr; p.stamp_tiles = 0;
+#endif
   p.conv_chunk_major = a->taps == 9 ? 1 : 0;   // channel-chunk-major K walk (the tap-major one measured 4.5-6 % slower)
   if (p.splitk > p.nk) p.splitk = p.nk;
   plan_gemm(p, p.plan_bm, p.plan_bn);

@@ -297,42 +297,59 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
     const int l15 = lane_e & 15, l4 = lane_e >> 4, lane = lane_e;
+    // bias -- and the conv forms' row bias, which is per image and so per tile -- once per tile: a lane's channel quads are the
+    // same for every row.  The residual of round i + 1 is loaded at the top of round i, BEFORE round i's stores: vmcnt retires
+    // in order and counts stores, and the residual may alias the output, so a load issued behind a round's stores waits for
+    // their round trip (the epilogue was 24k cycles with a residual, 12k without, on 8 workgroups as on 256).  Round i + 1
+    // then waits with round i's stores still in flight.  The rounds are straight-line code, bias and residual read through
+    // descriptors that are empty for a null pointer: around a uniform branch hipcc's s_waitcnt insertion falls back to waiting
+    // for the stores.  A Linear layer's row bias (per row; no model layer has one) stays a branch and a load of its round.
+    const BiasSrc bsrc(p.bias, CONV ? p.rowbias : nullptr);
+    const int img_rb = (long long)c.img * p.rows_per_img < p.M ? c.img : 0;
+    const ResidualSrc<T> rsrc(p, row_to_m(c, 0), c.n0);
+    auto rowbias_at = [&](f32x4 bb, int m, int n) __attribute__((always_inline)) -> f32x4 {
+      if constexpr (!CONV) {
+        if (p.rowbias && m < p.M) {
+          const f32x4 rb = *(const f32x4*)(p.rowbias + (size_t)(m / p.rows_per_img) * p.ldrb + n);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bb[e] += rb[e];
+        }
+      }
+      return bb;
+    };
     if constexpr (N160) {
       // 64 x 80 wave tile: 32 rows per round through 160-byte staging rows (5 KiB per wave), stored as ten 16-byte chunks per row
+      f32x4 base[NBW];
 #pragma unroll
-      for (int i = 0; i < MB6 / 2; ++i) {
-        f32x4 add[2][NBW];
-        i32x2 res[2][NBW];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int m = c.m0 + wm * WTM + i * 32 + h * 16 + l15;
-          const int img_ = (p.rowbias && m < p.M) ? m / p.rows_per_img : 0;
-#pragma unroll
-          for (int j = 0; j < NBW; ++j) {
-            const int n = c.n0 + wc * 80 + j * 16 + 4 * l4;
-            f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-            if (p.bias) bb = *(const f32x4*)(p.bias + n);
-            if (p.rowbias && m < p.M) {
-              const f32x4 r = *(const f32x4*)(p.rowbias + (size_t)img_ * p.ldrb + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) bb[e] += r[e];
-            }
-            add[h][j] = bb;
-            res[h][j] = i32x2{0, 0};
-            if (p.residual && m < p.M) res[h][j] = *(const i32x2*)(p.residual + ((size_t)m * p.ldr + n) * sizeof(T));
-          }
-        }
+      for (int j = 0; j < NBW; ++j) base[j] = bsrc.quad(c.n0 + wc * 80 + j * 16 + 4 * l4, 0);
+      i32x2 res[MB6 / 2][2][NBW];
+      auto load_res = [&](int i) __attribute__((always_inline)) {
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
+          for (int j = 0; j < NBW; ++j)
+            res[i][h][j] = rsrc.quad(c.m0 + wm * WTM + i * 32 + h * 16 + l15, wc * 80 + j * 16 + 4 * l4);
+      };
+      load_res(0);
+#pragma unroll
+      for (int i = 0; i < MB6 / 2; ++i) {
+        if (i + 1 < MB6 / 2) load_res(i + 1);
+        __builtin_amdgcn_sched_barrier(0);    // (the epilogue is straight-line code: keep the scheduler inside a round's steps)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int m = c.m0 + wm * WTM + i * 32 + h * 16 + l15;
+#pragma unroll
           for (int j = 0; j < NBW; ++j) {
-            float v[4], r[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p.residual) unpack4<T>(res[h][j], r);
+            const f32x4 bb = rowbias_at(base[j], m, c.n0 + wc * 80 + j * 16 + 4 * l4);
+            float v[4], r[4];
+            unpack4<T>(res[i][h][j], r);
             const float osc = (c.n0 + wc * 80 + j * 16) < p.cs_n ? p.cs : p.out_scale;     // cs_n is a multiple of 64: whole 16-column blocks
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[h][j][e] + r[e]) * osc;
+            for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + bb[e] + r[e]) * osc;
             *(i32x2*)(stg + (h * 16 + l15) * 160 + j * 32 + l4 * 8) = pack4<T>(v);
           }
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
           const int idx = lane + 64 * t;               // 320 chunks of the round
@@ -345,10 +362,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
       }
       return;
     }
-    float gs0 = 0.f, gs1 = 0.f, gq0 = 0.f, gq1 = 0.f;
+    if (p.geglu) {         // (Linear and conv forms alike: dfw_gemm accepts GEGLU with taps == 9; rows through row_to_m)
 #pragma unroll
-    for (int i = 0; i < MB6 / 2; ++i) {
-      if (p.geglu) {
+      for (int i = 0; i < MB6 / 2; ++i) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
@@ -364,44 +380,47 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
             *(i32x2*)(Cb + ((size_t)m * p.ldc + no) * sizeof(T)) = pack4<T>(v);
           }
         }
-        continue;
       }
-      f32x4 add[2][NB6];
-      i32x2 res[2][NB6];
+      return;
+    }
+    float gs0 = 0.f, gs1 = 0.f, gq0 = 0.f, gq1 = 0.f;
+    f32x4 base[NB6];
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
-        int img_ = c.img;
-        if constexpr (!CONV) img_ = (p.rowbias && m < p.M) ? m / p.rows_per_img : 0;
+    for (int j = 0; j < NB6; ++j) {
+      const int n = c.n0 + wc * 64 + j * 16 + 4 * l4;
+      base[j] = bsrc.quad(n, (size_t)img_rb * p.ldrb + n);
+    }
+    i32x2 res[MB6 / 2][2][NB6];
+    auto load_res = [&](int i) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < NB6; ++j) {
-          const int n = c.n0 + wc * 64 + j * 16 + 4 * l4;
-          f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-          if (p.bias) bb = *(const f32x4*)(p.bias + n);
-          if (p.rowbias && m < p.M) {
-            const f32x4 r = *(const f32x4*)(p.rowbias + (size_t)img_ * p.ldrb + n);
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) bb[e] += r[e];
-          }
-          add[h][j] = bb;
-          res[h][j] = i32x2{0, 0};
-          if (p.residual && m < p.M) res[h][j] = *(const i32x2*)(p.residual + ((size_t)m * p.ldr + n) * sizeof(T));
-        }
-      }
+        for (int j = 0; j < NB6; ++j)
+          res[i][h][j] = rsrc.quad(row_to_m(c, wm * WTM + i * 32 + h * 16 + l15), wc * 64 + j * 16 + 4 * l4);
+    };
+    load_res(0);
+#pragma unroll
+    for (int i = 0; i < MB6 / 2; ++i) {
+      if (i + 1 < MB6 / 2) load_res(i + 1);
+      __builtin_amdgcn_sched_barrier(0);      // (the epilogue is straight-line code: keep the scheduler inside a round's steps)
       float osc6[NB6];
 #pragma unroll
       for (int j = 0; j < NB6; ++j) osc6[j] = (c.n0 + wc * 64 + j * 16 + 4 * l4) < p.cs_n ? p.cs : p.out_scale;
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+      for (int h = 0; h < 2; ++h) {
+        const int m = row_to_m(c, wm * WTM + i * 32 + h * 16 + l15);
 #pragma unroll
         for (int j = 0; j < NB6; ++j) {
-          float v[4], r[4] = {0.f, 0.f, 0.f, 0.f};
-          if (p.residual) unpack4<T>(res[h][j], r);
+          const f32x4 bb = rowbias_at(base[j], m, c.n0 + wc * 64 + j * 16 + 4 * l4);
+          float v[4], r[4];
+          unpack4<T>(res[i][h][j], r);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + add[h][j][e] + r[e]) * osc6[j];
+          for (int e = 0; e < 4; ++e) v[e] = (acc6[2 * i + h][j][e] + bb[e] + r[e]) * osc6[j];
           const int row = h * 16 + l15, quad = j * 4 + l4;   // 8-byte piece `quad` of the staged 128-byte row
           *(i32x2*)(stg + row * 128 + (((quad >> 1) ^ (row & 7)) << 4) + (quad & 1) * 8) = pack4<T>(v);
         }
+      }
+      __builtin_amdgcn_sched_barrier(0);
       if (p.gn_partial) {
         const int cp = lane & 31, rh = lane >> 5;
 #pragma unroll
@@ -414,6 +433,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
           gs1 += a1; gq1 += a1 * a1;
         }
       }
+      __builtin_amdgcn_sched_barrier(0);
       const int c16 = lane & 7;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -449,6 +469,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
   TileC ct = tile_coords(tile0);
   a_setup(ct);
   w_setup(ct);
+  DFW_TILE_STAMP(p, wave, lane, 0, 0);
   issue_w(0);
   issue_a(0);
   issue_w(1);
@@ -494,7 +515,10 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const GemmP p) {
     if constexpr (N160) { wb0 = wbase160 + (uint32_t)(buf * WS160); wb1 = wb0 ^ 64u; }
     else { wb0 ^= (uint32_t)HT; wb1 ^= (uint32_t)HT; }
     if (last) {
+      DFW_TILE_STAMP(p, wave, lane, ti, 1);
       epilogue6(ct, smem + STG + wave * (N160 ? 5120 : 4096), tile0 + ti * nxb);
+      DFW_TILE_STAMP(p, wave, lane, ti, 2);
+      DFW_TILE_STAMP(p, wave, lane, ti + 1, 0);        // (the next tile's K walk starts where this epilogue ends)
       zero6();
       kt = 0;
       ++ti;
@@ -526,6 +550,7 @@ static int launch8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
   int nwg = q.ntm * q.ntn;
   if (nwg > 256) nwg = 256;
   nwg = (nwg + 7) & ~7;
+  if (p.taps == 9) DFW_STAMP_LAUNCH(q, nwg);
   dim3 grid(nwg, zdim);
   if (p.taps == 1) {
     auto kfn = gemm8_kernel<T, false, BN>;
@@ -570,11 +595,13 @@ int launch_gemm8(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
 // ---- dfw_conv_up2x: the folded nearest-2x upsample conv (UP2X above); its own entry point and argument struct, dfw_gemm's
 // planner never sees it.  Host validation first, every rejection before any launch.
 template <typename T, int BN>
-static int launch_up2x(const GemmP& p, hipStream_t st) {
+static int launch_up2x(const GemmP& p0, hipStream_t st) {
   constexpr size_t lds = (size_t)(2 + BN / 128) * 32768 + 32768;
+  GemmP p = p0;
   int nwg = p.ntm * p.ntn;
   if (nwg > 256) nwg = 256;
   nwg = (nwg + 7) & ~7;
+  DFW_STAMP_LAUNCH(p, nwg);
   auto kfn = gemm8_kernel<T, true, BN, true>;
   (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(nwg), dim3(512), lds, st, p);

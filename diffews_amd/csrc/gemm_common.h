@@ -22,6 +22,76 @@ struct GemmP {
   float* gn_partial; int gn_groups, gn_chunks;   // fused GroupNorm partial sums of the output (optional)
   int conv_chunk_major;                          // gemm_big conv: K walk = (channel chunk, tap) instead of (tap, chunk)
   int tw, tw_log2, tpr, tpi;  // 2-D output-pixel tiles (conv): tile width, tiles per row / per image; tw == 0: linear rows
+#ifdef DFW_TILE_STAMPS
+  unsigned long long* stamps; int stamp_tiles;   // diagnostic build only: [workgroup][tile < stamp_tiles][4] clock values (tile_stamp)
+#endif
+};
+
+#ifdef DFW_TILE_STAMPS
+// Diagnostic build (profiles/tile_phase.py; never the default library): wave 0 records s_memtime at K-loop start (k = 0),
+// epilogue start (1) and epilogue end (2) of its workgroup's tile `ti`, and s_memrealtime -- the clock all workgroups share --
+// at epilogue start (3).  Lane 0 writes them with plain vector stores.
+__device__ __forceinline__ void tile_stamp(const GemmP& p, int wave, int lane, int ti, int k) {
+  if (p.stamps == nullptr || wave != 0 || ti >= p.stamp_tiles) return;
+  const unsigned long long t = __builtin_amdgcn_s_memtime();
+  const unsigned long long rt = __builtin_amdgcn_s_memrealtime();
+  unsigned long long* rec = p.stamps + ((size_t)blockIdx.x * p.stamp_tiles + ti) * 4;
+  if (lane == 0) {
+    rec[k] = t;
+    if (k == 1) rec[3] = rt;
+  }
+}
+struct TileStampCfg { unsigned long long* buf; int tiles; int grid_cap; };
+const TileStampCfg& tile_stamp_cfg();        // misc.hip: dfw_debug_tile_stamps()
+#define DFW_TILE_STAMP(p, wave, lane, ti, k) tile_stamp(p, wave, lane, ti, k)
+// launchers: the stamp buffer into the kernel's parameters, the grid cut to grid_cap workgroups (a multiple of 8)
+#define DFW_STAMP_LAUNCH(q, nwg)                                                  \
+  do {                                                                            \
+    (q).stamps = tile_stamp_cfg().buf; (q).stamp_tiles = tile_stamp_cfg().tiles;  \
+    if (tile_stamp_cfg().grid_cap > 0 && (nwg) > tile_stamp_cfg().grid_cap) (nwg) = tile_stamp_cfg().grid_cap; \
+  } while (0)
+#else
+#define DFW_TILE_STAMP(p, wave, lane, ti, k) ((void)0)
+#define DFW_STAMP_LAUNCH(q, nwg) ((void)0)
+#endif
+
+// Bias + per-image row bias of the channel quad n .. n + 3, without a branch on either pointer: each is read through a buffer
+// descriptor whose range is EMPTY for a null pointer (the load then returns zeros), and the row bias is added under a select.
+// The staged epilogues of the persistent walks use it: with uniform branches around their loads, the s_waitcnt vmcnt that hipcc
+// placed in front of a round's first use of its residual also waited for the previous round's stores (read in the ISA).
+// Same values as `bb = bias ? bias[n..] : 0; if (rowbias) bb += rowbias[rb_index..]`.
+struct BiasSrc {
+  __amdgpu_buffer_rsrc_t bias, rowbias;
+  bool has_rowbias;
+  __device__ __forceinline__ BiasSrc(const float* b, const float* rb)
+      : bias(make_rsrc(b, b ? 0x7ffffff0u : 0u)), rowbias(make_rsrc(rb, rb ? 0x7ffffff0u : 0u)), has_rowbias(rb != nullptr) {}
+  __device__ __forceinline__ f32x4 quad(int n, size_t rb_index) const {
+    f32x4 bb = __builtin_bit_cast(f32x4, buf_load16(bias, (uint32_t)n * 4u));
+    const f32x4 r = __builtin_bit_cast(f32x4, buf_load16(rowbias, (uint32_t)rb_index * 4u));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bb[e] = has_rowbias ? bb[e] + r[e] : bb[e];
+    return bb;
+  }
+};
+
+// The 16-bit residual of one output tile through a buffer descriptor based at the tile's first element (row m00, channel n0):
+// element (row m, channel n) is at offset ((m - m00) * ldr + n - n0) * sizeof(T), 32 bits whatever the tensor's size; rows
+// past M read as zero; and WITHOUT a residual the range is empty, so the same loads return zeros and, again, no branch
+// surrounds them (x + 0.f is what the epilogues computed without a residual before).
+template <typename T>
+struct ResidualSrc {
+  __amdgpu_buffer_rsrc_t r;
+  int m00, ldr;
+  __device__ __forceinline__ ResidualSrc(const GemmP& p, int m00_, int n0) : m00(m00_), ldr(p.ldr) {
+    const bool on = p.residual != nullptr && m00_ < p.M;
+    const size_t e00 = on ? (size_t)m00_ * p.ldr + n0 : 0;
+    const size_t left = on ? ((size_t)(p.M - 1 - m00_) * p.ldr + (size_t)(p.N - n0)) * sizeof(T) : 0;
+    r = make_rsrc(p.residual + e00 * sizeof(T), (uint32_t)(left < 0x7ffffff0u ? left : 0x7ffffff0u));
+  }
+  // four channels n_in_tile .. + 3 (n_in_tile = n - n0) of row m
+  __device__ __forceinline__ i32x2 quad(int m, int n_in_tile) const {
+    return __builtin_bit_cast(i32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)(((uint32_t)(m - m00) * (uint32_t)ldr + (uint32_t)n_in_tile) * (uint32_t)sizeof(T)), 0, 0));
+  }
 };
 
 // Epilogue for 4 consecutive output channels n..n+3 of output row m (raw fp32 accumulators in v).

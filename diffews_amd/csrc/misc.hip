@@ -1,6 +1,9 @@
 // Small HBM-bound kernels around the MFMA path: boundary convs with tiny channel counts, row
 // softmax, transpose, channel concat, timestep embedding, segmentation post-processing + metric.
 #include "common.h"
+#ifdef DFW_TILE_STAMPS
+#include "gemm_common.h"      // TileStampCfg (dfw_debug_tile_stamps below)
+#endif
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -1011,6 +1014,18 @@ extern "C" int dfw_configure(const dfw_config* c) {
 extern "C" void dfw_get_config(dfw_config* out) {
   if (out) *out = g_cfg;
 }
+
+#ifdef DFW_TILE_STAMPS
+// Diagnostic build only (profiles/tile_phase.py): where the conv walks record their tile stamps -- buf holds 256 x tiles x 4
+// uint64 (NULL: no stamps) -- and a cap on their grids (0: none; else a multiple of 8).
+static dfw::TileStampCfg g_stamps = {nullptr, 0, 0};
+namespace dfw { const TileStampCfg& tile_stamp_cfg() { return g_stamps; } }
+extern "C" int dfw_debug_tile_stamps(void* buf, int32_t tiles, int32_t grid_cap) {
+  if (tiles < 0 || grid_cap < 0 || (grid_cap & 7) || (buf && tiles == 0)) return DFW_EINVAL;
+  g_stamps = {(unsigned long long*)buf, buf ? tiles : 0, grid_cap};
+  return 0;
+}
+#endif
 
 extern "C" int dfw_version(void) { return 113; }
 
