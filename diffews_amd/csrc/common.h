@@ -9,6 +9,14 @@ namespace dfw {
 
 const dfw_config& cfg();   // the record of dfw_configure() (misc.hip)
 
+// Host helpers of the segmentation output side, each defined once.
+// Zeroes mx [nm], counts [nc] and area [na] (64-bit cells) in one launch of seg_zero_kernel (misc.hip, where the comment
+// says why it is a kernel); a null array counts as empty, and nothing is launched when all three are.  Returns the error.
+int seg_zero_launch(hipStream_t st, uint32_t* mx, int nm, void* counts, int nc, void* area = nullptr, int na = 0);
+// The host mirror of a candidate table off[0 .. B] | lab[0 .. E_cap) (seg_candidates.hip): offsets from 0, non-decreasing,
+// at most E_cap, at most 254 entries a query; labels 1..nlabels.  *K = the longest list, *E = off[B].  Returns the error.
+int cand_table_check(const int32_t* tab_host, int B, int E_cap, int nlabels, int* K, int* E);
+
 using f32x16 = float __attribute__((ext_vector_type(16)));
 using f32x4 = float __attribute__((ext_vector_type(4)));
 using i32x4 = int __attribute__((ext_vector_type(4)));

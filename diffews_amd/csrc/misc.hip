@@ -1,6 +1,7 @@
 // Small HBM-bound kernels around the MFMA path: boundary convs with tiny channel counts, row
 // softmax, transpose, channel concat, timestep embedding, segmentation post-processing + metric.
 #include "common.h"
+#include "seg_fuse.h"
 #ifdef DFW_TILE_STAMPS
 #include "gemm_common.h"      // TileStampCfg (dfw_debug_tile_stamps below)
 #endif
@@ -512,13 +513,7 @@ __global__ __launch_bounds__(256) void seg_count_kernel(const uint8_t* u8, const
   lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
   __syncthreads();
   const int b = blockIdx.y;
-  // r_thr > 0: dynamic threshold max * r_threshold (main_oss.py:129-132) with the max taken over this image
-  // or (batch_max) over the whole batch tensor, as `pred_mask.max()` literally does; else the fixed
-  // `--threshold` (main_oss.py:134-135)
-  uint32_t m = mx[b];
-  if (batch_max)
-    for (int i = 0; i < (int)gridDim.y; ++i) m = max(m, mx[i]);
-  const float thr = r_thr > 0.f ? ((float)m / 255.0f) * r_thr : fixed_thr;
+  const float thr = seg_threshold(mx, b, gridDim.y, r_thr, fixed_thr, batch_max);
   // inter0, inter1, pred0, pred1, gt0, gt1
   unsigned c[6] = {0, 0, 0, 0, 0, 0};
   const uint8_t* ub = u8 + (size_t)b * 3 * HW;
@@ -543,130 +538,48 @@ __global__ __launch_bounds__(256) void seg_count_kernel(const uint8_t* u8, const
   } else {
     for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) pixel(ub[e], ub[HW + e], ub[2 * HW + e], gb[e]);
   }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-    c[k] = v;
-  }
-  // one set of integer atomics per workgroup
-  __shared__ unsigned wc[4][6];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) wc[threadIdx.x >> 6][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t[k] = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
-    // counts[b] = {inter0, inter1, union0, union1}; union = pred + gt - inter
-    atomicAdd((unsigned long long*)(counts + b * 4 + 0), (unsigned long long)t[0]);
-    atomicAdd((unsigned long long*)(counts + b * 4 + 1), (unsigned long long)t[1]);
-    atomicAdd((unsigned long long*)(counts + b * 4 + 2), (unsigned long long)(t[2] + t[4] - t[0]));
-    atomicAdd((unsigned long long*)(counts + b * 4 + 3), (unsigned long long)(t[3] + t[5] - t[1]));
-  }
+  seg_count_reduce(c, counts + 4 * b);
 }
 
 // Zeroes the per-image max words and the count cells.  A kernel of the library, not hipMemsetAsync: inside a
 // captured HIP graph (ROCm 7.2) a small memset node replayed next to ordinary launches on the same stream was
 // observed to deposit another launch's kernel arguments in its destination (the per-image max then read as a
 // pointer and every prediction fell below the threshold).
-__global__ void seg_zero_kernel(uint32_t* mx, int B, unsigned long long* counts) {
+__global__ void seg_zero_kernel(uint32_t* mx, int nm, unsigned long long* counts, int nc, unsigned long long* area,
+                                int na) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < B) mx[e] = 0u;
-  if (counts && e < 4 * B) counts[e] = 0ull;
+  if (e < nm) mx[e] = 0u;
+  if (e < nc) counts[e] = 0ull;
+  if (e < na) area[e] = 0ull;
+}
+
+int seg_zero_launch(hipStream_t st, uint32_t* mx, int nm, void* counts, int nc, void* area, int na) {
+  nm = mx ? nm : 0;
+  nc = counts ? nc : 0;
+  na = area ? na : 0;
+  const int n = max(nm, max(nc, na));
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(seg_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, mx, nm, (unsigned long long*)counts, nc,
+                     (unsigned long long*)area, na);
+  return (int)hipGetLastError();
 }
 
 // N-way label fusion: one pass over the quantised masks of all N classes (seg_u8 [N][B][3][H][W], the maxima mx [N][B]
-// that seg_u8_kernel left).  Per pixel and class the score is seg_count_kernel's mean (same fp32 expressions, same
-// table) and the class is foreground when score > its threshold; label = 0 with no foreground class, else 1 + c of the
-// foreground class with the largest score (classes are visited in ascending order and only a strictly larger score
-// takes over, so the lowest c wins a tie).  With gt (0..N, anything above N dropped like the ignore index 255) the
-// workgroup keeps pred / gt / intersection histograms of N + 1 bins in LDS and issues one 64-bit atomic per non-zero
-// cell: counts [B][2][N+1] = intersections, unions (pred + gt - inter).  4 pixels per thread through 32-bit words when
-// HW % 4 == 0 and every pointer is word-aligned; a scalar path otherwise.
+// that seg_u8_kernel left).  seg_fuse (seg_fuse.h) with class c of image b as plane c, label c + 1, the threshold from
+// mx[c][b] or (batch_max) the class's whole row, and byte ground truth (0..N, anything above N dropped like the ignore
+// index 255): counts [B][2][N+1].
 __global__ __launch_bounds__(256) void seg_labels_kernel(const uint8_t* u8, const uint32_t* mx, const uint8_t* gt,
                                                          uint8_t* labels, unsigned long long* counts, int N, int HW,
                                                          float r_thr, float fixed_thr, int batch_max) {
-  __shared__ float lut[256];
-  __shared__ float thr[256];
-  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][N + 1]
-  const int b = blockIdx.y, B = gridDim.y, NL = N + 1;
-  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  __shared__ seg_fuse_lds<false> s;
+  const int b = blockIdx.y, B = gridDim.y;
   if ((int)threadIdx.x < N) {
-    float t = fixed_thr;
-    if (r_thr > 0.f) {
-      const uint32_t* mc = mx + (size_t)threadIdx.x * B;
-      uint32_t m = mc[b];
-      if (batch_max)
-        for (int i = 0; i < B; ++i) m = max(m, mc[i]);
-      t = ((float)m / 255.0f) * r_thr;
-    }
-    thr[threadIdx.x] = t;
+    s.thr[threadIdx.x] = seg_threshold(mx + (size_t)threadIdx.x * B, b, B, r_thr, fixed_thr, batch_max);
+    s.lbl[threadIdx.x] = threadIdx.x + 1;
   }
-  for (int i = threadIdx.x; i < 3 * NL; i += 256) hist[i] = 0u;
-  __syncthreads();
-  const size_t cls = (size_t)B * 3 * HW;                  // bytes between two classes
-  const uint8_t* ub = u8 + (size_t)b * 3 * HW;            // class 0 of this image
-  const uint8_t* gb = gt ? gt + (size_t)b * HW : nullptr;
-  uint8_t* lb = labels + (size_t)b * HW;
-  auto count = [&](uint32_t l, uint32_t g) {
-    if (g > (uint32_t)N) return;   // 255 = ignore; N < g < 255 has no bin: dropped from every histogram too
-    atomicAdd(&hist[NL + l], 1u);
-    atomicAdd(&hist[2 * NL + g], 1u);
-    if (l == g) atomicAdd(&hist[l], 1u);
-  };
-  if ((HW & 3) == 0 && (((uintptr_t)ub | (uintptr_t)gb | (uintptr_t)lb) & 3) == 0) {
-    const int n4 = HW >> 2;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
-      float best[4] = {-1.f, -1.f, -1.f, -1.f};
-      uint32_t lab[4] = {0u, 0u, 0u, 0u};
-      const uint8_t* uc = ub + 4 * (size_t)e;
-      for (int c = 0; c < N; ++c, uc += cls) {
-        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
-        const float t = thr[c];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
-          if (sc > t && sc > best[k]) { best[k] = sc; lab[k] = (uint32_t)(c + 1); }
-        }
-      }
-      *(uint32_t*)(lb + 4 * (size_t)e) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-      if (gb) {
-        const uint32_t wg = *(const uint32_t*)(gb + 4 * (size_t)e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) count(lab[k], (wg >> (8 * k)) & 255u);
-      }
-    }
-  } else {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
-      float best = -1.f;
-      uint32_t lab = 0u;
-      const uint8_t* uc = ub + e;
-      for (int c = 0; c < N; ++c, uc += cls) {
-        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
-        if (sc > thr[c] && sc > best) { best = sc; lab = (uint32_t)(c + 1); }
-      }
-      lb[e] = (uint8_t)lab;
-      if (gb) count(lab, gb[e]);
-    }
-  }
-  if (!gb) return;
-  __syncthreads();
-  unsigned long long* cb = counts + (size_t)b * 2 * NL;
-  for (int l = threadIdx.x; l < NL; l += 256) {
-    const unsigned in = hist[l], un = hist[NL + l] + hist[2 * NL + l] - in;
-    if (in) atomicAdd(cb + l, (unsigned long long)in);
-    if (un) atomicAdd(cb + NL + l, (unsigned long long)un);
-  }
-}
-
-// counts of dfw_seg_labels: a library kernel for the reason seg_zero_kernel gives
-__global__ void seg_labels_zero_kernel(unsigned long long* counts, int n) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) counts[e] = 0ull;
+  const seg_planes pl = {u8 + (size_t)b * 3 * HW, (size_t)B * 3 * HW, N, HW};
+  seg_fuse<false>(s, pl, labels + (size_t)b * HW, gt ? gt + (size_t)b * HW : nullptr, false, false, seg_gt_byte{N});
+  if (gt) seg_flush_counts(s.hist, counts + (size_t)b * 2 * (N + 1), N + 1);
 }
 
 __global__ void meter_update_kernel(const long long* counts, const long long* cls, unsigned long long* ib,
@@ -913,9 +826,7 @@ extern "C" int dfw_seg_postprocess_ex(const float* x, uint8_t* seg_u8, const uin
   if (gt && !(r_threshold > 0.f) && !(threshold > 0.f)) return DFW_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * Wd, per_img = 3 * HW;
-  hipLaunchKernelGGL(seg_zero_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, st, scratch, B,
-                     (unsigned long long*)(gt ? counts : nullptr));
-  DFW_CHECK_LAUNCH();
+  if (int e = seg_zero_launch(st, scratch, B, gt ? counts : nullptr, 4 * B)) return e;
   int bx = (per_img / 4 + 255) / 256;
   if (bx > 128) bx = 128;
   if (bx < 1) bx = 1;
@@ -940,11 +851,7 @@ extern "C" int dfw_seg_labels(const uint8_t* seg_u8, const uint32_t* mx, const u
   if (B > 65535 || (long long)H * Wd > (1ll << 30)) return DFW_ERANGE;
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * Wd;
-  if (gt) {
-    const int n = B * 2 * (N + 1);
-    hipLaunchKernelGGL(seg_labels_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (unsigned long long*)counts, n);
-    DFW_CHECK_LAUNCH();
-  }
+  if (int e = seg_zero_launch(st, nullptr, 0, gt ? counts : nullptr, B * 2 * (N + 1))) return e;
   int cx = (HW / 4 + 255) / 256;
   if (cx > 64) cx = 64;
   if (cx < 1) cx = 1;

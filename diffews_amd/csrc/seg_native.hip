@@ -9,22 +9,28 @@
 // Arithmetic: resample_h_kernel's (Pillow's ImagingResample, 8 bits per channel): 2^21 + sum tap * weight, arithmetic
 // shift by 22, clamp to 0..255, uint8 intermediate between the passes; planar, since a 3-channel resize is three
 // single-channel ones.  Bicubic overshoots (a 0/200 block image reaches 225), so the dynamic threshold uses the maximum
-// of the RESIZED image, taken in the vertical pass.  Threshold and counts are seg_count_kernel's expressions.
+// of the RESIZED image, taken in the vertical pass.  Threshold and count tail are seg_count_kernel's (seg_fuse.h).
 //
 // dfw_seg_labels_native is the same for N classes (seg_u8 [N][B][3][Hs][Ws], pipeline.segment_classes): the two resize
 // kernels run over N * B planes-of-3 (grid z = c * B + i, one item per image, a byte stride per class), the fourth launch
-// is seg_labels_kernel's label rule and LDS histograms at native size.
+// is seg_fuse (seg_fuse.h) on the resized bytes.
 //
 // dfw_seg_labels_cand_native is the same for the ENTRIES of seg_candidates.hip (seg_u8 [E_cap][3][Hs][Ws], one entry per
 // (query, candidate class) pair): the two resize kernels run over E planes-of-3 (grid z = e; the entry's query is looked up
 // in the device table, its position k in the query's list takes the part of the class above, so the scratch is K strides
-// with K the longest list), the fourth launch is seg_cand_kernel's rule, histograms and area at native size.
+// with K the longest list), the fourth launch is seg_fuse over the query's entries, with area.
+//
+// What the label kernels add to seg_fuse here: planes, labels and ground truth are placed by the image's item, not by
+// H * W, and the ground truth is read in place at native size -- uint8 or int32 per image, the item's ignore_value
+// dropped, ids mapped through class_ids / entry_ids where given (native_fuse).  All three entry points check the items'
+// host mirror with one validator (native_items_check) before any launch.
 //
 // Byte work bound by HBM / L2: a thread produces 4 adjacent bytes of one channel row, one 32-bit store where the
 // address is 4-byte aligned (row starts are when w % 4 == 0: every offset of the table is 16-byte aligned), byte stores
 // otherwise.
 #include "common.h"
 #include "resample_host.h"
+#include "seg_fuse.h"
 
 namespace dfw {
 
@@ -38,13 +44,6 @@ __device__ __forceinline__ void native_store4(uint8_t* dst, uint32_t word, int n
   } else {
     for (int j = 0; j < nx; ++j) dst[j] = (uint8_t)(word >> (8 * j));
   }
-}
-
-// Same job as misc.hip's seg_zero_kernel (a library kernel, not a memset node: see the comment there).
-__global__ void native_zero_kernel(uint32_t* mx, int n_mx, unsigned long long* counts, int n_counts) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mx && e < n_mx) mx[e] = 0u;
-  if (counts && e < n_counts) counts[e] = 0ull;
 }
 
 // horizontal: seg_u8 [B][3][Hs][Ws] -> tmp[i] = [3][Hs][w_i].  Block (64, 4): x -> 4 adjacent output columns,
@@ -205,13 +204,7 @@ __global__ __launch_bounds__(256) void native_count_kernel(const dfw_native_item
   const int b = blockIdx.y;
   const dfw_native_item it = items[b];
   const int HW = it.h * it.w;
-  uint32_t m = 0;
-  if (r_thr > 0.f) {
-    m = mx[b];
-    if (batch_max)
-      for (int i = 0; i < (int)gridDim.y; ++i) m = max(m, mx[i]);
-  }
-  const float thr = r_thr > 0.f ? ((float)m / 255.0f) * r_thr : fixed_thr;
+  const float thr = seg_threshold(mx, b, gridDim.y, r_thr, fixed_thr, batch_max);
   // kept pixels, pred1, gt1, inter0, inter1 (scalars: a histogram indexed by pr would be spilled to LDS per thread);
   // pred0 = kept - pred1, gt0 = kept - gt1
   unsigned n_kept = 0, n_p1 = 0, n_g1 = 0, n_i0 = 0, n_i1 = 0;
@@ -269,163 +262,60 @@ __global__ __launch_bounds__(256) void native_count_kernel(const dfw_native_item
   if (!counts) return;   // kernel argument: uniform
   // inter0, inter1, pred0, pred1, gt0, gt1
   unsigned c[6] = {n_i0, n_i1, n_kept - n_p1, n_p1, n_kept - n_g1, n_g1};
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    unsigned v = c[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-    c[k] = v;
-  }
-  // one set of integer atomics per workgroup
-  __shared__ unsigned wc[4][6];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) wc[threadIdx.x >> 6][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t[k] = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
-    // counts[b] = {inter0, inter1, union0, union1}; union = pred + gt - inter
-    atomicAdd((unsigned long long*)(counts + b * 4 + 0), (unsigned long long)t[0]);
-    atomicAdd((unsigned long long*)(counts + b * 4 + 1), (unsigned long long)t[1]);
-    atomicAdd((unsigned long long*)(counts + b * 4 + 2), (unsigned long long)(t[2] + t[4] - t[0]));
-    atomicAdd((unsigned long long*)(counts + b * 4 + 3), (unsigned long long)(t[3] + t[5] - t[1]));
+  seg_count_reduce(c, counts + 4 * b);
+}
+
+// What both label kernels take from the image's item: where its labels and ground truth lie (gt null: no counts), and
+// seg_fuse with the ground-truth rule that the id tables select -- class_ids, else entry_ids, else the plain ids 0..NLab.
+// The functors' id maps are built here, behind a barrier: entry_ids reads s.lbl, which the caller has just written.
+template <bool AREA>
+__device__ __forceinline__ void native_fuse(seg_fuse_lds<AREA>& s, const dfw_native_item& it, const seg_planes pl,
+                                            uint8_t* labels, const uint8_t* gt, bool area, int NLab,
+                                            const int32_t* class_ids, const int32_t* entry_ids) {
+  __shared__ int idmap[256];   // ground-truth id 0..255 -> label
+  uint8_t* lb = labels + it.pred_off;
+  const uint8_t* g8 = gt ? gt + it.gt_off : nullptr;
+  const bool wide = it.gt_elem == 4;
+  const int ign = it.ignore_value;
+  if (class_ids) {
+    const seg_gt_classes map = {ign, NLab, class_ids, idmap};
+    map.fill();
+    seg_fuse<AREA>(s, pl, lb, g8, wide, area, map);
+  } else if (entry_ids) {
+    const seg_gt_entries map = {ign, pl.K, entry_ids, s.lbl, idmap};
+    __syncthreads();
+    map.fill();
+    seg_fuse<AREA>(s, pl, lb, g8, wide, area, map);
+  } else {
+    seg_fuse<AREA>(s, pl, lb, g8, wide, area, seg_gt_plain{ign, NLab});
   }
 }
 
-// label + counts per image over h_i * w_i, N classes: seg_labels_kernel's rule (misc.hip) on the RESIZED bytes -- class c of
-// image b at res + c * res_cls + u8_off -- with the thresholds from mx [N][B], the maxima of the resized planes.  The ground
-// truth is read in place at native size (uint8 or int32 per image): a pixel whose id is the item's ignore_value is dropped;
-// without class_ids the id is the label and ids outside 0..N are dropped; with class_ids the label is 1 + the lowest c
-// with class_ids[c] == id and every other id is background (ids 0..255 through an LDS table built once per workgroup).
-// Histograms of N + 1 bins in LDS, one 64-bit atomic per non-zero cell: counts [B][2][N+1].
+// label + counts per image over h_i * w_i, N classes: seg_fuse on the RESIZED bytes -- class c of image b at
+// res + c * res_cls + u8_off, label c + 1 -- with the thresholds from mx [N][B], the maxima of the resized planes, and the
+// ground truth read in place at native size (uint8 or int32 per image): counts [B][2][N+1].
 __global__ __launch_bounds__(256) void native_labels_kernel(const dfw_native_item* __restrict__ items,
                                                             const uint8_t* __restrict__ res, size_t res_cls,
                                                             const uint8_t* gt, const uint32_t* mx,
                                                             const int32_t* class_ids, uint8_t* labels,
                                                             unsigned long long* counts, int N, float r_thr,
                                                             float fixed_thr, int batch_max) {
-  __shared__ float lut[256];
-  __shared__ float thr[256];
-  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][N + 1]
-  __shared__ int idmap[256];            // class_ids: ground-truth id 0..255 -> label
-  const int b = blockIdx.y, B = gridDim.y, NL = N + 1;
+  __shared__ seg_fuse_lds<false> s;
+  const int b = blockIdx.y, B = gridDim.y;
   const dfw_native_item it = items[b];
-  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
   if ((int)threadIdx.x < N) {
-    float t = fixed_thr;
-    if (r_thr > 0.f) {
-      const uint32_t* mc = mx + (size_t)threadIdx.x * B;
-      uint32_t m = mc[b];
-      if (batch_max)
-        for (int i = 0; i < B; ++i) m = max(m, mc[i]);
-      t = ((float)m / 255.0f) * r_thr;
-    }
-    thr[threadIdx.x] = t;
+    s.thr[threadIdx.x] = seg_threshold(mx + (size_t)threadIdx.x * B, b, B, r_thr, fixed_thr, batch_max);
+    s.lbl[threadIdx.x] = threadIdx.x + 1;
   }
-  if (class_ids) {
-    int l = 0;
-    for (int c = N - 1; c >= 0; --c)
-      if (class_ids[c] == (int)threadIdx.x) l = c + 1;   // descending: the lowest c stays
-    idmap[threadIdx.x] = l;
-  }
-  for (int i = threadIdx.x; i < 3 * NL; i += 256) hist[i] = 0u;
-  __syncthreads();
-  const int HW = it.h * it.w;
-  const uint8_t* ub = res + it.u8_off;            // class 0 of this image
-  uint8_t* lb = labels + it.pred_off;
-  const uint8_t* g8 = counts ? gt + it.gt_off : nullptr;
-  const int32_t* g32 = (const int32_t*)g8;
-  const bool wide = it.gt_elem == 4;
-  const int ign = it.ignore_value;
-  auto count = [&](uint32_t l, int id) {
-    if (ign >= 0 && id == ign) return;            // ignore value: dropped from every histogram
-    int g;
-    if (!class_ids) {
-      if (id < 0 || id > N) return;               // no bin: dropped as well (dfw_seg_labels' rule)
-      g = id;
-    } else if ((unsigned)id < 256u) {
-      g = idmap[id];
-    } else {
-      g = 0;
-      for (int c = N - 1; c >= 0; --c)
-        if (class_ids[c] == id) g = c + 1;
-    }
-    atomicAdd(&hist[NL + l], 1u);
-    atomicAdd(&hist[2 * NL + g], 1u);
-    if ((int)l == g) atomicAdd(&hist[l], 1u);
-  };
-  if ((HW & 3) == 0 && (res_cls & 3) == 0 && (((uintptr_t)ub | (uintptr_t)lb | (uintptr_t)g8) & 3) == 0) {
-    const int n4 = HW >> 2;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
-      const size_t o = 4 * (size_t)e;
-      float best[4] = {-1.f, -1.f, -1.f, -1.f};
-      uint32_t lab[4] = {0u, 0u, 0u, 0u};
-      const uint8_t* uc = ub + o;
-      for (int c = 0; c < N; ++c, uc += res_cls) {
-        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
-        const float t = thr[c];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
-          if (sc > t && sc > best[k]) { best[k] = sc; lab[k] = (uint32_t)(c + 1); }
-        }
-      }
-      *(uint32_t*)(lb + o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-      if (g8) {
-        if (wide) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) count(lab[k], g32[o + k]);
-        } else {
-          const uint32_t wg = *(const uint32_t*)(g8 + o);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) count(lab[k], (int)((wg >> (8 * k)) & 255u));
-        }
-      }
-    }
-  } else {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
-      float best = -1.f;
-      uint32_t lab = 0u;
-      const uint8_t* uc = ub + e;
-      for (int c = 0; c < N; ++c, uc += res_cls) {
-        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
-        if (sc > thr[c] && sc > best) { best = sc; lab = (uint32_t)(c + 1); }
-      }
-      lb[e] = (uint8_t)lab;
-      if (g8) count(lab, wide ? g32[e] : (int)g8[e]);
-    }
-  }
-  if (!counts) return;   // kernel argument: uniform
-  __syncthreads();
-  unsigned long long* cb = counts + (size_t)b * 2 * NL;
-  for (int l = threadIdx.x; l < NL; l += 256) {
-    const unsigned in = hist[l], un = hist[NL + l] + hist[2 * NL + l] - in;
-    if (in) atomicAdd(cb + l, (unsigned long long)in);
-    if (un) atomicAdd(cb + NL + l, (unsigned long long)un);
-  }
+  const seg_planes pl = {res + it.u8_off, res_cls, N, it.h * it.w};
+  native_fuse<false>(s, it, pl, labels, counts ? gt : nullptr, false, N, class_ids, nullptr);
+  if (counts) seg_flush_counts(s.hist, counts + (size_t)b * 2 * (N + 1), N + 1);
 }
 
-// ---- candidate classes per query at native size (dfw_seg_labels_cand_native) ----
-constexpr int kNativeCandMax = 254;   // entries of one query, as seg_candidates.hip's kCandMax
-
-__global__ void native_cand_zero_kernel(uint32_t* mx, int n_mx, unsigned long long* counts, int n_counts,
-                                        unsigned long long* area, int n_area) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (mx && e < n_mx) mx[e] = 0u;
-  if (counts && e < n_counts) counts[e] = 0ull;
-  if (area && e < n_area) area[e] = 0ull;
-}
-
-// label + counts + area per query over h_q * w_q: native_labels_kernel's structure with seg_cand_kernel's per-query entry
-// range.  Entry e = lo + k of query q lies at res + k * res_cls + u8_off (the resized bytes), its threshold comes from
-// mx[e], the maximum of ITS resized planes, and its label byte from the table.  The range is clamped as seg_cand_kernel
-// clamps it and to Kcap, the longest list the workspace was validated for.  Ground truth in place at native size: the
-// item's ignore_value dropped; no id table: id = label, ids outside 0..NLab dropped; class_ids [NLab]: 1 + the lowest c with
-// class_ids[c] == id; entry_ids [E_cap]: lab[e] of the query's earliest entry with entry_ids[e] == id; every other id is
-// background.  Ids 0..255 go through an LDS table built once per workgroup.  Histograms indexed by label byte.
+// label + counts + area per query over h_q * w_q (dfw_seg_labels_cand_native): seg_cand_kernel's prologue at native size.
+// Entry e = lo + k of query q lies at res + k * res_cls + u8_off (the resized bytes), its threshold comes from mx[e], the
+// maximum of ITS resized planes, and its label byte from the table.  The range is clamped as seg_cand_kernel clamps it and
+// to Kcap, the longest list the workspace was validated for.  entry_ids [E_cap] names the ground-truth id of each entry.
 __global__ __launch_bounds__(256) void native_labels_cand_kernel(const dfw_native_item* __restrict__ items,
                                                                  const uint8_t* __restrict__ res, size_t res_cls,
                                                                  const uint8_t* gt, const uint32_t* mx,
@@ -434,152 +324,25 @@ __global__ __launch_bounds__(256) void native_labels_cand_kernel(const dfw_nativ
                                                                  unsigned long long* counts, unsigned long long* area,
                                                                  int E_cap, int Kcap, int NLab, float r_thr,
                                                                  float fixed_thr) {
-  __shared__ float lut[256];
-  __shared__ float thr[256];
-  __shared__ uint32_t lbl[256];
-  __shared__ unsigned hist[3 * 256];    // [inter | pred | gt][label byte]
-  __shared__ unsigned ahist[2 * 256];   // [foreground | won][entry of this query]
-  __shared__ int idmap[256];            // ground-truth id 0..255 -> label
+  __shared__ seg_fuse_lds<true> s;
   const int q = blockIdx.y, B = gridDim.y;
   const dfw_native_item it = items[q];
   // the query's range: two loads at a uniform address, clamped before anything is indexed with them
   int lo = tab[q], hi = tab[q + 1];
   lo = min(max(lo, 0), E_cap);
   hi = min(max(hi, lo), E_cap);
-  hi = min(hi, lo + min(Kcap, kNativeCandMax));
+  hi = min(hi, lo + min(Kcap, kSegCandMax));
   const int K = hi - lo;
   const int32_t* labt = tab + B + 1;
-  lut[threadIdx.x] = (float)threadIdx.x / 255.0f;
   if ((int)threadIdx.x < K) {
-    float t = fixed_thr;
-    if (r_thr > 0.f) t = ((float)mx[lo + threadIdx.x] / 255.0f) * r_thr;
-    thr[threadIdx.x] = t;
-    lbl[threadIdx.x] = (uint32_t)labt[lo + threadIdx.x] & 255u;
+    s.thr[threadIdx.x] = seg_threshold(mx + lo + threadIdx.x, 0, 1, r_thr, fixed_thr, 0);
+    s.lbl[threadIdx.x] = (uint32_t)labt[lo + threadIdx.x] & 255u;
   }
-  if (class_ids) {
-    int l = 0;
-    for (int c = NLab - 1; c >= 0; --c)
-      if (class_ids[c] == (int)threadIdx.x) l = c + 1;   // descending: the lowest c stays
-    idmap[threadIdx.x] = l;
-  } else if (entry_ids) {
-    int l = 0;
-    for (int k = K - 1; k >= 0; --k)
-      if (entry_ids[lo + k] == (int)threadIdx.x) l = labt[lo + k] & 255;   // descending: the earliest entry stays
-    idmap[threadIdx.x] = l;
-  }
-  for (int i = threadIdx.x; i < 3 * 256; i += 256) hist[i] = 0u;
-  for (int i = threadIdx.x; i < 2 * 256; i += 256) ahist[i] = 0u;
-  __syncthreads();
-  const int HW = it.h * it.w;
-  const uint8_t* ub = res + it.u8_off;            // position 0 of this query
-  uint8_t* lb = labels + it.pred_off;
-  const uint8_t* g8 = counts ? gt + it.gt_off : nullptr;
-  const int32_t* g32 = (const int32_t*)g8;
-  const bool wide = it.gt_elem == 4;
-  const int ign = it.ignore_value;
-  auto count = [&](uint32_t l, int id) {
-    if (ign >= 0 && id == ign) return;            // ignore value: dropped from every histogram
-    int g;
-    if (class_ids) {
-      if ((unsigned)id < 256u) {
-        g = idmap[id];
-      } else {
-        g = 0;
-        for (int c = NLab - 1; c >= 0; --c)
-          if (class_ids[c] == id) g = c + 1;
-      }
-    } else if (entry_ids) {
-      if ((unsigned)id < 256u) {
-        g = idmap[id];
-      } else {
-        g = 0;
-        for (int k = K - 1; k >= 0; --k)
-          if (entry_ids[lo + k] == id) g = (int)lbl[k];
-      }
-    } else {
-      if (id < 0 || id > NLab) return;            // no bin: dropped as well (dfw_seg_labels_cand's rule)
-      g = id;
-    }
-    atomicAdd(&hist[256 + l], 1u);
-    atomicAdd(&hist[512 + g], 1u);
-    if ((int)l == g) atomicAdd(&hist[l], 1u);
-  };
-  if ((HW & 3) == 0 && (res_cls & 3) == 0 && (((uintptr_t)ub | (uintptr_t)lb | (uintptr_t)g8) & 3) == 0) {
-    const int n4 = HW >> 2;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
-      const size_t o = 4 * (size_t)e;
-      float best[4] = {-1.f, -1.f, -1.f, -1.f};
-      uint32_t lab[4] = {0u, 0u, 0u, 0u};
-      int win[4] = {-1, -1, -1, -1};
-      const uint8_t* uc = ub + o;
-      for (int c = 0; c < K; ++c, uc += res_cls) {
-        const uint32_t w0 = *(const uint32_t*)uc, w1 = *(const uint32_t*)(uc + HW), w2 = *(const uint32_t*)(uc + 2 * (size_t)HW);
-        const float t = thr[c];
-        const uint32_t l = lbl[c];
-        unsigned nfg = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float sc = ((lut[(w0 >> (8 * k)) & 255u] + lut[(w1 >> (8 * k)) & 255u]) + lut[(w2 >> (8 * k)) & 255u]) / 3.0f;
-          if (sc > t) {
-            ++nfg;
-            if (sc > best[k]) { best[k] = sc; lab[k] = l; win[k] = c; }
-          }
-        }
-        if (area && nfg) atomicAdd(&ahist[c], nfg);
-      }
-      *(uint32_t*)(lb + o) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-      if (area) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (win[k] >= 0) atomicAdd(&ahist[256 + win[k]], 1u);
-      }
-      if (g8) {
-        if (wide) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) count(lab[k], g32[o + k]);
-        } else {
-          const uint32_t wg = *(const uint32_t*)(g8 + o);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) count(lab[k], (int)((wg >> (8 * k)) & 255u));
-        }
-      }
-    }
-  } else {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < HW; e += gridDim.x * 256) {
-      float best = -1.f;
-      uint32_t lab = 0u;
-      int win = -1;
-      const uint8_t* uc = ub + e;
-      for (int c = 0; c < K; ++c, uc += res_cls) {
-        const float sc = ((lut[uc[0]] + lut[uc[HW]]) + lut[uc[2 * (size_t)HW]]) / 3.0f;
-        if (sc > thr[c]) {
-          if (area) atomicAdd(&ahist[c], 1u);
-          if (sc > best) { best = sc; lab = lbl[c]; win = c; }
-        }
-      }
-      lb[e] = (uint8_t)lab;
-      if (area && win >= 0) atomicAdd(&ahist[256 + win], 1u);
-      if (g8) count(lab, wide ? g32[e] : (int)g8[e]);
-    }
-  }
-  if (!counts && !area) return;   // kernel arguments: uniform
-  __syncthreads();
-  if (counts) {
-    const int NB = NLab + 1;
-    unsigned long long* cb = counts + (size_t)q * 2 * NB;
-    for (int l = threadIdx.x; l < NB; l += 256) {
-      const unsigned in = hist[l], un = hist[256 + l] + hist[512 + l] - in;
-      if (in) atomicAdd(cb + l, (unsigned long long)in);
-      if (un) atomicAdd(cb + NB + l, (unsigned long long)un);
-    }
-  }
-  if (area) {
-    for (int c = threadIdx.x; c < K; c += 256) {
-      const unsigned fg = ahist[c], won = ahist[256 + c];
-      if (fg) atomicAdd(area + 2 * (size_t)(lo + c), (unsigned long long)fg);
-      if (won) atomicAdd(area + 2 * (size_t)(lo + c) + 1, (unsigned long long)won);
-    }
-  }
+  const seg_planes pl = {res + it.u8_off, res_cls, K, it.h * it.w};
+  native_fuse<true>(s, it, pl, labels, counts ? gt : nullptr, area != nullptr, NLab, class_ids,
+                    entry_ids ? entry_ids + lo : nullptr);
+  if (counts) seg_flush_counts(s.hist, counts + (size_t)q * 2 * (NLab + 1), NLab + 1);
+  if (area) seg_flush_area(s.ahist, area + 2 * (size_t)lo, K);
 }
 
 }  // namespace dfw
@@ -601,6 +364,72 @@ extern "C" int dfw_resample_coeffs_ex(int32_t in_size, int32_t out_size, int32_t
   return resample_coeffs_host(in_size, out_size, fn, support, bounds, coeffs);
 }
 
+// What the items of one call are checked against: how many bytes each buffer holds, and which buffers the call uses.
+struct native_caps {
+  size_t weights_bytes, tmp_cap;   // tmp_cap: the horizontal intermediates' part of tmp
+  bool need_res;                   // the resized bytes are written
+  size_t res_cap;
+  bool need_pred;                  // pred / labels are written
+  size_t pred_bytes;
+  bool counts;                     // the ground truth is read
+  size_t gt_bytes;
+};
+// What the launches are sized by, and the extent of one plane-of-3 in tmp / in the resized bytes.
+struct native_extents {
+  int max_h = 0, max_w = 0;
+  long long max_hw = 0;
+  uint64_t tmp_ext = 0, res_ext = 0;
+};
+
+// The host mirror of the items, checked before any launch.  Returns the error.
+static int native_items_check(const void* items_host, int B, int Hs, int Ws, const native_caps& c, native_extents* x) {
+  const dfw_native_item* it = (const dfw_native_item*)items_host;
+  for (int i = 0; i < B; ++i) {
+    const dfw_native_item& t = it[i];
+    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
+    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
+    if (c.counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
+    if (t.xk != dfw_resample_ksize_ex(Ws, t.w, DFW_FILTER_BICUBIC) || t.yk != dfw_resample_ksize_ex(Hs, t.h, DFW_FILTER_BICUBIC))
+      return DFW_ESHAPE;
+    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
+    const uint64_t hw = (uint64_t)t.h * t.w;
+    if (!extent_fits(t.xb_off, 8ull * t.w, c.weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, c.weights_bytes) ||
+        !extent_fits(t.yb_off, 8ull * t.h, c.weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, c.weights_bytes))
+      return DFW_EWORKSPACE;
+    if (!extent_fits(t.tmp_off, 3ull * Hs * t.w, c.tmp_cap)) return DFW_EWORKSPACE;
+    if (c.need_res && !extent_fits(t.u8_off, 3ull * hw, c.res_cap)) return DFW_EWORKSPACE;
+    if (c.need_pred && !extent_fits(t.pred_off, hw, c.pred_bytes)) return DFW_EWORKSPACE;
+    if (c.counts) {
+      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
+      if (!extent_fits(t.gt_off, hw * t.gt_elem, c.gt_bytes)) return DFW_EWORKSPACE;
+    }
+    const uint64_t te = (uint64_t)t.tmp_off + 3ull * Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
+    x->tmp_ext = te > x->tmp_ext ? te : x->tmp_ext;
+    x->res_ext = re > x->res_ext ? re : x->res_ext;
+    x->max_h = t.h > x->max_h ? t.h : x->max_h;
+    x->max_w = t.w > x->max_w ? t.w : x->max_w;
+    x->max_hw = (long long)hw > x->max_hw ? (long long)hw : x->max_hw;
+  }
+  return 0;
+}
+
+// `planes` planes-of-3 per item (classes, or positions of the longest candidate list), plane p lying p strides after
+// plane 0: a stride holds one plane, and the last plane ends inside its buffer.
+static int native_strides_check(int planes, size_t tmp_stride, size_t res_stride, const native_caps& c,
+                                const native_extents& x) {
+  const uint64_t more = planes > 1 ? (uint64_t)(planes - 1) : 0;
+  if (tmp_stride < x.tmp_ext || res_stride < x.res_ext) return DFW_EWORKSPACE;
+  if (more && (tmp_stride > (c.tmp_cap - x.tmp_ext) / more || res_stride > (c.res_cap - x.res_ext) / more))
+    return DFW_EWORKSPACE;
+  return 0;
+}
+
+// grid x of the count / label kernels: 4 pixels a thread, at most 64 workgroups an image
+static int native_count_blocks(long long max_hw) {
+  const long long cx = (max_hw / 4 + 255) / 256;
+  return cx > 64 ? 64 : (cx < 1 ? 1 : (int)cx);
+}
+
 extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream) {
   if (!a || !a->seg_u8 || !a->items || !a->items_host || !a->weights || !a->tmp) return DFW_EINVAL;
   if (a->B <= 0 || a->Hs <= 0 || a->Ws <= 0) return DFW_EINVAL;
@@ -611,60 +440,30 @@ extern "C" int dfw_seg_native(const dfw_seg_native_args* a, dfw_stream_t stream)
   // as dfw_seg_postprocess_ex: with neither flag > 0 the reference leaves the mask un-thresholded
   if (count_stage && !(a->r_threshold > 0.f) && !(a->threshold > 0.f)) return DFW_EINVAL;
   if (a->B > 65535 || a->Hs > 65535 || a->Ws > 65535) return DFW_ERANGE;
-  const bool need_res = a->out_u8 || count_stage;
+  // the resized bytes go to out_u8, or (where a later stage needs them) behind the horizontal intermediates in tmp
+  const bool need_res = a->out_u8 || count_stage, in_tmp = !a->out_u8 && need_res;
   uint8_t* res = a->out_u8 ? a->out_u8 : (need_res ? a->tmp + a->tmp_res_off : nullptr);
-  if (!a->out_u8 && need_res && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
-  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - (need_res ? a->tmp_res_off : 0);
-  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
-  int max_h = 0, max_w = 0;
-  long long max_hw = 0;
-  for (int i = 0; i < a->B; ++i) {
-    const dfw_native_item& t = it[i];
-    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
-    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
-    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
-    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
-        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
-      return DFW_ESHAPE;
-    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
-    const uint64_t hw = (uint64_t)t.h * t.w;
-    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
-        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
-      return DFW_EWORKSPACE;
-    const size_t tmp_cap = (!a->out_u8 && need_res) ? a->tmp_res_off : a->tmp_bytes;   // the horizontal intermediates' part
-    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
-    if (need_res && !extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
-    if (a->pred && !extent_fits(t.pred_off, hw, a->pred_bytes)) return DFW_EWORKSPACE;
-    if (a->counts) {
-      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
-      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
-    }
-    max_h = t.h > max_h ? t.h : max_h;
-    max_w = t.w > max_w ? t.w : max_w;
-    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
-  }
+  if (in_tmp && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
+  const native_caps caps = {a->weights_bytes, in_tmp ? a->tmp_res_off : a->tmp_bytes,
+                            need_res, a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - (in_tmp ? a->tmp_res_off : 0),
+                            a->pred != nullptr, a->pred_bytes, a->counts != nullptr, a->gt_bytes};
+  native_extents x;
+  if (int e = native_items_check(a->items_host, a->B, a->Hs, a->Ws, caps, &x)) return e;
   hipStream_t st = (hipStream_t)stream;
   const dfw_native_item* items = (const dfw_native_item*)a->items;
   const int B = a->B;
-  if (a->mx || a->counts) {
-    hipLaunchKernelGGL(native_zero_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, st, a->mx, B,
-                       (unsigned long long*)a->counts, 4 * B);
-    DFW_CHECK_LAUNCH();
-  }
+  if (int e = seg_zero_launch(st, a->mx, B, a->counts, 4 * B)) return e;
   const dim3 blk(64, 4);
-  hipLaunchKernelGGL(native_h_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, B), blk, 0, st, a->seg_u8, items,
+  hipLaunchKernelGGL(native_h_kernel, dim3((x.max_w + 255) / 256, (3 * a->Hs + 3) / 4, B), blk, 0, st, a->seg_u8, items,
                      a->weights, a->tmp, a->Hs, a->Ws, B, (size_t)0);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(native_v_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, B), blk, 0, st, items, a->weights,
+  hipLaunchKernelGGL(native_v_kernel, dim3((x.max_w + 255) / 256, (3 * x.max_h + 3) / 4, B), blk, 0, st, items, a->weights,
                      (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, (size_t)0, (size_t)0);
   DFW_CHECK_LAUNCH();
   if (count_stage) {
-    int cx = (int)((max_hw / 4 + 255) / 256);
-    if (cx > 64) cx = 64;
-    if (cx < 1) cx = 1;
-    hipLaunchKernelGGL(native_count_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->gt,
-                       (const uint32_t*)a->mx, a->pred, (long long*)a->counts, a->r_threshold, a->threshold,
-                       a->batch_max ? 1 : 0);
+    hipLaunchKernelGGL(native_count_kernel, dim3(native_count_blocks(x.max_hw), B), dim3(256), 0, st, items,
+                       (const uint8_t*)res, a->gt, (const uint32_t*)a->mx, a->pred, (long long*)a->counts, a->r_threshold,
+                       a->threshold, a->batch_max ? 1 : 0);
     DFW_CHECK_LAUNCH();
   }
   return 0;
@@ -682,66 +481,26 @@ extern "C" int dfw_seg_labels_native(const dfw_seg_labels_native_args* a, dfw_st
   // behind the horizontal intermediates at tmp + tmp_res_off
   if (!a->out_u8 && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
   uint8_t* res = a->out_u8 ? a->out_u8 : a->tmp + a->tmp_res_off;
-  const size_t tmp_cap = a->out_u8 ? a->tmp_bytes : a->tmp_res_off;
-  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off;
-  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
-  int max_h = 0, max_w = 0;
-  long long max_hw = 0;
-  uint64_t tmp_ext = 0, res_ext = 0;    // extent of one class plane in tmp / in the resized bytes
-  for (int i = 0; i < a->B; ++i) {
-    const dfw_native_item& t = it[i];
-    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
-    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
-    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
-    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
-        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
-      return DFW_ESHAPE;
-    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
-    const uint64_t hw = (uint64_t)t.h * t.w;
-    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
-        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
-      return DFW_EWORKSPACE;
-    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
-    if (!extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
-    if (!extent_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
-    if (a->counts) {
-      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
-      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
-    }
-    const uint64_t te = (uint64_t)t.tmp_off + 3ull * a->Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
-    tmp_ext = te > tmp_ext ? te : tmp_ext;
-    res_ext = re > res_ext ? re : res_ext;
-    max_h = t.h > max_h ? t.h : max_h;
-    max_w = t.w > max_w ? t.w : max_w;
-    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
-  }
-  // class c lies c strides after class 0: a stride holds one plane, and the last class ends inside its buffer
-  const uint64_t more = (uint64_t)(a->N - 1);
-  if (a->tmp_cls_stride < tmp_ext || a->u8_cls_stride < res_ext) return DFW_EWORKSPACE;
-  if (more && (a->tmp_cls_stride > (tmp_cap - tmp_ext) / more || a->u8_cls_stride > (res_cap - res_ext) / more))
-    return DFW_EWORKSPACE;
+  const native_caps caps = {a->weights_bytes, a->out_u8 ? a->tmp_bytes : a->tmp_res_off,
+                            true, a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off,
+                            true, a->labels_bytes, a->counts != nullptr, a->gt_bytes};
+  native_extents x;
+  if (int e = native_items_check(a->items_host, a->B, a->Hs, a->Ws, caps, &x)) return e;
+  if (int e = native_strides_check(a->N, a->tmp_cls_stride, a->u8_cls_stride, caps, x)) return e;
   hipStream_t st = (hipStream_t)stream;
   const dfw_native_item* items = (const dfw_native_item*)a->items;
-  const int N = a->N, B = a->B, n_mx = N * B, n_counts = a->counts ? B * 2 * (N + 1) : 0;
-  if (a->mx || a->counts) {
-    const int n = n_mx > n_counts ? n_mx : n_counts;
-    hipLaunchKernelGGL(native_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a->mx, n_mx,
-                       (unsigned long long*)a->counts, n_counts);
-    DFW_CHECK_LAUNCH();
-  }
+  const int N = a->N, B = a->B;
+  if (int e = seg_zero_launch(st, a->mx, N * B, a->counts, B * 2 * (N + 1))) return e;
   const dim3 blk(64, 4);
-  hipLaunchKernelGGL(native_h_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, N * B), blk, 0, st, a->seg_u8, items,
+  hipLaunchKernelGGL(native_h_kernel, dim3((x.max_w + 255) / 256, (3 * a->Hs + 3) / 4, N * B), blk, 0, st, a->seg_u8, items,
                      a->weights, a->tmp, a->Hs, a->Ws, B, a->tmp_cls_stride);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(native_v_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, N * B), blk, 0, st, items, a->weights,
-                     (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, a->tmp_cls_stride, a->u8_cls_stride);
+  hipLaunchKernelGGL(native_v_kernel, dim3((x.max_w + 255) / 256, (3 * x.max_h + 3) / 4, N * B), blk, 0, st, items,
+                     a->weights, (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, a->tmp_cls_stride, a->u8_cls_stride);
   DFW_CHECK_LAUNCH();
-  int cx = (int)((max_hw / 4 + 255) / 256);
-  if (cx > 64) cx = 64;
-  if (cx < 1) cx = 1;
-  hipLaunchKernelGGL(native_labels_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->u8_cls_stride,
-                     a->gt, (const uint32_t*)a->mx, a->class_ids, a->labels, (unsigned long long*)a->counts, N,
-                     a->r_threshold, a->threshold, a->batch_max ? 1 : 0);
+  hipLaunchKernelGGL(native_labels_kernel, dim3(native_count_blocks(x.max_hw), B), dim3(256), 0, st, items,
+                     (const uint8_t*)res, a->u8_cls_stride, a->gt, (const uint32_t*)a->mx, a->class_ids, a->labels,
+                     (unsigned long long*)a->counts, N, a->r_threshold, a->threshold, a->batch_max ? 1 : 0);
   DFW_CHECK_LAUNCH();
   return 0;
 }
@@ -756,88 +515,35 @@ extern "C" int dfw_seg_labels_cand_native(const dfw_seg_labels_cand_native_args*
   if (!(a->r_threshold > 0.f) && !(a->threshold > 0.f)) return DFW_EINVAL;
   // before the table is read: it is B + 1 + E_cap words
   if (a->B > 65535 || a->Hs > 65535 || a->Ws > 65535 || a->E_cap > (1 << 24)) return DFW_ERANGE;
-  // the table's host mirror, as dfw_seg_labels_cand validates it; K = the longest list
-  const int32_t* th = a->tab_host;
-  if (th[0] != 0) return DFW_EINVAL;
-  int K = 0;
-  for (int q = 0; q < a->B; ++q) {
-    const int32_t lo = th[q], hi = th[q + 1];
-    if (hi < lo || hi > a->E_cap || hi - lo > kNativeCandMax) return DFW_EINVAL;
-    K = hi - lo > K ? hi - lo : K;
-  }
-  const int E = th[a->B];
-  for (int e = 0; e < E; ++e) {
-    const int32_t l = th[a->B + 1 + e];
-    if (l < 1 || l > a->nlabels) return DFW_EINVAL;
-  }
-  if (E > 65535) return DFW_ERANGE;                                          // grid z = E
+  int K, E;   // the longest list: the planes of the workspace; the entries: grid z
+  if (int e = cand_table_check(a->tab_host, a->B, a->E_cap, a->nlabels, &K, &E)) return e;
+  if (E > 65535) return DFW_ERANGE;
   if (!a->out_u8 && a->tmp_res_off > a->tmp_bytes) return DFW_EWORKSPACE;
   uint8_t* res = a->out_u8 ? a->out_u8 : a->tmp + a->tmp_res_off;
-  const size_t tmp_cap = a->out_u8 ? a->tmp_bytes : a->tmp_res_off;
-  const size_t res_cap = a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off;
-  const dfw_native_item* it = (const dfw_native_item*)a->items_host;
-  int max_h = 0, max_w = 0;
-  long long max_hw = 0;
-  uint64_t tmp_ext = 0, res_ext = 0;    // extent of one list position in tmp / in the resized bytes
-  for (int i = 0; i < a->B; ++i) {
-    const dfw_native_item& t = it[i];
-    if (t.h <= 0 || t.w <= 0) return DFW_EINVAL;
-    if (t.h > 65535 || t.w > 65535) return DFW_ERANGE;
-    if (a->counts && t.gt_elem != 1 && t.gt_elem != 4) return DFW_EINVAL;
-    if (t.xk != dfw_resample_ksize_ex(a->Ws, t.w, DFW_FILTER_BICUBIC) ||
-        t.yk != dfw_resample_ksize_ex(a->Hs, t.h, DFW_FILTER_BICUBIC))
-      return DFW_ESHAPE;
-    if (((t.xb_off | t.xc_off | t.yb_off | t.yc_off) & 3) != 0) return DFW_ESHAPE;
-    const uint64_t hw = (uint64_t)t.h * t.w;
-    if (!extent_fits(t.xb_off, 8ull * t.w, a->weights_bytes) || !extent_fits(t.xc_off, 4ull * t.w * t.xk, a->weights_bytes) ||
-        !extent_fits(t.yb_off, 8ull * t.h, a->weights_bytes) || !extent_fits(t.yc_off, 4ull * t.h * t.yk, a->weights_bytes))
-      return DFW_EWORKSPACE;
-    if (!extent_fits(t.tmp_off, 3ull * a->Hs * t.w, tmp_cap)) return DFW_EWORKSPACE;
-    if (!extent_fits(t.u8_off, 3ull * hw, res_cap)) return DFW_EWORKSPACE;
-    if (!extent_fits(t.pred_off, hw, a->labels_bytes)) return DFW_EWORKSPACE;
-    if (a->counts) {
-      if (t.gt_elem == 4 && (t.gt_off & 3) != 0) return DFW_ESHAPE;
-      if (!extent_fits(t.gt_off, hw * t.gt_elem, a->gt_bytes)) return DFW_EWORKSPACE;
-    }
-    const uint64_t te = (uint64_t)t.tmp_off + 3ull * a->Hs * t.w, re = (uint64_t)t.u8_off + 3ull * hw;
-    tmp_ext = te > tmp_ext ? te : tmp_ext;
-    res_ext = re > res_ext ? re : res_ext;
-    max_h = t.h > max_h ? t.h : max_h;
-    max_w = t.w > max_w ? t.w : max_w;
-    max_hw = (long long)hw > max_hw ? (long long)hw : max_hw;
-  }
-  // position k lies k strides after position 0: a stride holds one position, and position K - 1 ends inside its buffer
-  const uint64_t more = K > 1 ? (uint64_t)(K - 1) : 0;
-  if (a->tmp_cls_stride < tmp_ext || a->u8_cls_stride < res_ext) return DFW_EWORKSPACE;
-  if (more && (a->tmp_cls_stride > (tmp_cap - tmp_ext) / more || a->u8_cls_stride > (res_cap - res_ext) / more))
-    return DFW_EWORKSPACE;
+  const native_caps caps = {a->weights_bytes, a->out_u8 ? a->tmp_bytes : a->tmp_res_off,
+                            true, a->out_u8 ? a->out_u8_bytes : a->tmp_bytes - a->tmp_res_off,
+                            true, a->labels_bytes, a->counts != nullptr, a->gt_bytes};
+  native_extents x;
+  if (int e = native_items_check(a->items_host, a->B, a->Hs, a->Ws, caps, &x)) return e;
+  if (int e = native_strides_check(K, a->tmp_cls_stride, a->u8_cls_stride, caps, x)) return e;
   hipStream_t st = (hipStream_t)stream;
   const dfw_native_item* items = (const dfw_native_item*)a->items;
-  const int B = a->B, n_mx = a->mx ? a->E_cap : 0, n_counts = a->counts ? B * 2 * (a->nlabels + 1) : 0;
-  const int n_area = a->area ? 2 * a->E_cap : 0;
-  if (n_mx || n_counts || n_area) {
-    int n = n_mx > n_counts ? n_mx : n_counts;
-    n = n_area > n ? n_area : n;
-    hipLaunchKernelGGL(native_cand_zero_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a->mx, n_mx,
-                       (unsigned long long*)a->counts, n_counts, (unsigned long long*)a->area, n_area);
-    DFW_CHECK_LAUNCH();
-  }
+  const int B = a->B;
+  if (int e = seg_zero_launch(st, a->mx, a->E_cap, a->counts, B * 2 * (a->nlabels + 1), a->area, 2 * a->E_cap)) return e;
   if (E > 0) {   // K >= 1
     const dim3 blk(64, 4);
-    hipLaunchKernelGGL(native_h_cand_kernel, dim3((max_w + 255) / 256, (3 * a->Hs + 3) / 4, E), blk, 0, st, a->seg_u8, items,
-                       a->tab, a->weights, a->tmp, a->Hs, a->Ws, B, K, a->tmp_cls_stride);
+    hipLaunchKernelGGL(native_h_cand_kernel, dim3((x.max_w + 255) / 256, (3 * a->Hs + 3) / 4, E), blk, 0, st, a->seg_u8,
+                       items, a->tab, a->weights, a->tmp, a->Hs, a->Ws, B, K, a->tmp_cls_stride);
     DFW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(native_v_cand_kernel, dim3((max_w + 255) / 256, (3 * max_h + 3) / 4, E), blk, 0, st, items, a->tab,
-                       a->weights, (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, K, a->tmp_cls_stride, a->u8_cls_stride);
+    hipLaunchKernelGGL(native_v_cand_kernel, dim3((x.max_w + 255) / 256, (3 * x.max_h + 3) / 4, E), blk, 0, st, items,
+                       a->tab, a->weights, (const uint8_t*)a->tmp, res, a->mx, a->Hs, B, K, a->tmp_cls_stride,
+                       a->u8_cls_stride);
     DFW_CHECK_LAUNCH();
   }
-  int cx = (int)((max_hw / 4 + 255) / 256);
-  if (cx > 64) cx = 64;
-  if (cx < 1) cx = 1;
-  hipLaunchKernelGGL(native_labels_cand_kernel, dim3(cx, B), dim3(256), 0, st, items, (const uint8_t*)res, a->u8_cls_stride,
-                     a->gt, (const uint32_t*)a->mx, a->tab, a->class_ids, a->entry_ids, a->labels,
-                     (unsigned long long*)a->counts, (unsigned long long*)a->area, a->E_cap, K, a->nlabels, a->r_threshold,
-                     a->threshold);
+  hipLaunchKernelGGL(native_labels_cand_kernel, dim3(native_count_blocks(x.max_hw), B), dim3(256), 0, st, items,
+                     (const uint8_t*)res, a->u8_cls_stride, a->gt, (const uint32_t*)a->mx, a->tab, a->class_ids,
+                     a->entry_ids, a->labels, (unsigned long long*)a->counts, (unsigned long long*)a->area, a->E_cap, K,
+                     a->nlabels, a->r_threshold, a->threshold);
   DFW_CHECK_LAUNCH();
   return 0;
 }

@@ -12,8 +12,7 @@
 //                       ramp); the byte is (2 A + W) / (2 W), round-half-up, in 32 bits (the host proves 2 A + W fits before
 //                       it launches).  No float operation and no atomic on the image: the result depends on no order.
 //                       The maximum goes the way seg_u8_kernel's does (wave reduce, one atomicMax per workgroup) into
-//                       mx[n], zeroed by tiles_zero_kernel (a library kernel, not a memset node: see seg_zero_kernel in
-//                       misc.hip).
+//                       mx[n], zeroed by seg_zero_launch (common.h).
 //
 // The window plan (dfw_tile_plan: sizes, ramp, at most 64 origins per axis) travels BY VALUE in the kernel arguments, as
 // dfw_fsa_attention_ragged's table does: no device allocation, no copy, and a capture keeps the values.  Both kernels are
@@ -23,11 +22,6 @@
 #include "common.h"
 
 namespace dfw {
-
-__global__ void tiles_zero_kernel(uint32_t* mx, int n) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) mx[e] = 0u;
-}
 
 // Block (64, 4): x -> 4 adjacent columns of the window, y -> row of the window, grid z -> window first + z.
 __global__ __launch_bounds__(256) void tiles_cut_kernel(const dfw_tile_plan p, const uint8_t* __restrict__ img,
@@ -171,7 +165,7 @@ static bool tiles_plan_ok(const dfw_tile_plan* p, int* cover_y, int* cover_x) {
 //
 // Per pixel the divisor 2 W is the same for all classes and channels, so the byte (2 A + W) / (2 W) is taken with one
 // reciprocal per pixel: q' = umulhi(n, floor((2^32 - 1) / d)) is at most 2 below floor(n / d) for n < 2^32, d >= 2, and
-// two compare-and-adds on the remainder make it exact.  Scores, thresholds and the tie rule are seg_labels_kernel's fp32
+// two compare-and-adds on the remainder make it exact.  Scores, thresholds and the tie rule are seg_fuse's (seg_fuse.h) fp32
 // expressions; maxima, counts and area go through LDS bins and one global atomic per touched bin and workgroup.
 constexpr int kCandSlots = 4096;   // = 64 * 64, the most windows a valid plan puts over one pixel
 
@@ -179,15 +173,6 @@ struct tiles_cells {
   int32_t ncy, ncx;                    // cells per axis
   int32_t by[2 * DFW_TILE_MAX_ORIGINS + 1], bx[2 * DFW_TILE_MAX_ORIGINS + 1];   // cell i of an axis is [b[i], b[i + 1])
 };
-
-// mx, counts and area of dfw_tiles_labels_cand: a library kernel, not a memset node (see seg_zero_kernel in misc.hip)
-__global__ void tiles_cand_zero_kernel(uint32_t* mx, int nm, unsigned long long* counts, int nc, unsigned long long* area,
-                                       int na) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < nm) mx[e] = 0u;
-  if (counts && e < nc) counts[e] = 0ull;
-  if (area && e < na) area[e] = 0ull;
-}
 
 // LABELS = false: the maximum pass (mx only), run first when the threshold is dynamic.  LABELS = true: labels, counts /
 // area where asked for, and with the fixed threshold also mx.
@@ -438,8 +423,7 @@ extern "C" int dfw_tiles_merge(const dfw_tile_plan* plan, const uint8_t* win, in
   const uint64_t wsum = (uint64_t)cy * cx * (uint64_t)plan->ramp * (uint64_t)plan->ramp;
   if (wsum > 0xffffffffull / 511ull) return DFW_ERANGE;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(tiles_zero_kernel, dim3((N + 255) / 256), dim3(256), 0, st, mx, N);
-  DFW_CHECK_LAUNCH();
+  if (int e = seg_zero_launch(st, mx, N, nullptr, 0)) return e;
   const dim3 grid((plan->img_w + 255) / 256, (3 * plan->img_h + 3) / 4, N);
   hipLaunchKernelGGL(tiles_merge_kernel, grid, dim3(64, 4), 0, st, *plan, win, out, mx);
   DFW_CHECK_LAUNCH();
@@ -483,11 +467,7 @@ extern "C" int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* e
   if (Z > (tall + 3) / 4) Z = (tall + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
   const bool want_counts = gt && counts;
-  const int nc = want_counts ? 2 * (N + 1) : 0, na = area ? 2 * N : 0;
-  const int nz = nc > N ? nc : N;   // na <= nc or na = 2 N <= 2 * (N + 1)
-  hipLaunchKernelGGL(tiles_cand_zero_kernel, dim3(((nz > na ? nz : na) + 255) / 256), dim3(256), 0, st, mx, N,
-                     (unsigned long long*)(want_counts ? counts : nullptr), nc, (unsigned long long*)area, na);
-  DFW_CHECK_LAUNCH();
+  if (int e = seg_zero_launch(st, mx, N, want_counts ? counts : nullptr, 2 * (N + 1), area, 2 * N)) return e;
   const dim3 grid(cells.ncx, cells.ncy, Z);
   const int cap = ent ? E_cap : 0;   // without entries the kernel sees every list empty, whatever the device table holds
   if (r_threshold > 0.f && E > 0) {
