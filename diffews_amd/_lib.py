@@ -110,6 +110,12 @@ class SegLabelsCandNativeArgs(C.Structure):
                 ("entry_ids", _vp), ("r_threshold", _f32), ("threshold", _f32)]
 
 
+class SegComponentsArgs(C.Structure):
+    _fields_ = [("labels", _vp), ("ids", _vp), ("filtered", _vp), ("n", _vp), ("stats", _vp), ("gt", _vp), ("counts", _vp),
+                ("ws", _vp), ("ws_bytes", _sz), ("B", _i32), ("H", _i32), ("W", _i32), ("connectivity", _i32),
+                ("min_area", _i32), ("cap", _i32), ("nlabels", _i32)]
+
+
 class InputImageItem(C.Structure):
     _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
                 ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
@@ -289,6 +295,9 @@ SYMBOLS = {
     "dfw_tiles_merge": (_i32, [C.POINTER(TilePlan), _vp, _i32, _vp, _vp, _vp]),
     "dfw_tiles_labels_cand": (_i32, [C.POINTER(TilePlan), _vp, _vp, C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32,
                                      _f32, _vp]),
+    "dfw_seg_components": (_i32, [C.POINTER(SegComponentsArgs), _vp]),
+    "dfw_seg_components_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dfw_seg_components_tile": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
 }
 
 _lib = None

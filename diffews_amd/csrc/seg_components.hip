@@ -1,0 +1,566 @@
+// Connected components of a label map (objects.label_objects): labels uint8 [B][H][W] -> ids int32 [B][H][W] numbered
+// 1..n_b per image in row-major order of each component's first pixel, with per-object label / area / box rows, an
+// optional minimum-area filter, the filtered label bytes, and seg_fuse.h's counts of the FILTERED bytes against a ground
+// truth.  All integers: the result depends on no order of execution.
+//
+// Everything is a union-find over the pixel indices p = y * W + x of one image with the invariant parent[i] <= i, so the
+// root of a set is its smallest index -- the component's first pixel.  The workspace is parent [B][HW] | area [B][HW] |
+// blk [B][nblk][2], every word of it written before it is read (the caller initialises nothing).  Launches, a number fixed
+// by the arguments (8, or 7 when the image is one tile), with no host readback in between:
+//
+//   0  seg_zero_launch       stats and counts (a library kernel, no memset node)
+//   1  cc_tile_kernel        one workgroup per kCcTH x kCcTW tile: union-find of the tile in LDS.  Every pixel gets
+//                            parent = its tile-local root (the tile-local component's smallest index, as a GLOBAL index; -1
+//                            for background) and area = the tile-local component's pixel count at that local root, 0
+//                            elsewhere.  Only local roots are ever linked from here on: a pixel is two hops from its root.
+//   2  cc_merge_kernel       one thread per pixel on a tile's left column or top row: unions across the border with global
+//                            atomicMin.  A pair that the pixel before it on the border already joins is skipped.
+//   3  cc_flatten_kernel     every local root: parent = find (now the component's first pixel), and ONE atomicAdd of its
+//                            tile-local count onto area[root] -- one atomic per (tile, local component), never per pixel
+//   4  cc_count_kernel       per block of kCcTile consecutive pixels: roots, and roots with area >= min_area
+//   5  cc_scan_kernel        one workgroup per image: exclusive scan of the block sums in place, n[b] = (kept, all)
+//   6  cc_number_kernel      per block: the kept roots get id = offset + rank + 1, written over area[root] (0 for a removed
+//                            root: the filter needs no cap); rows id <= cap of stats get label, area, the first pixel and
+//                            that pixel as the initial box
+//   7  cc_apply_kernel       one workgroup per tile: ids, filtered, the count histograms (seg_fuse.h's rule), and the box:
+//                            x0 / y1 / x1 per tile-local component by LDS atomics, then one global atomicMin / atomicMax per
+//                            (tile, local component) and field, only for ids <= cap (y0 is the first pixel's row)
+//
+// Termination: no thread waits for another thread or workgroup.  Every loop is a find, which reads strictly decreasing
+// indices (it stops at any word that is not smaller than the index it was read at, so even a damaged workspace cannot send
+// it round or outside), or a union's retry, where a failed atomicMin replaces the larger root by a strictly smaller index.
+// A find may read a stale parent (another CU's L1, another XCD's L2): that is an older ancestor of the same set, and the
+// atomicMin on the word itself returns the truth, so a stale read costs a round, never a wrong link.
+#include "common.h"
+#include "seg_fuse.h"
+
+namespace dfw {
+
+constexpr int kCcTH = 32, kCcTW = 64, kCcTile = kCcTH * kCcTW;   // 2048 pixels, 8 per thread of 256
+constexpr int kCcWords = kCcTile / 4;
+
+// ---- union-find in LDS ----
+__device__ __forceinline__ int lds_find(const volatile int* par, int i) {
+  for (;;) {
+    const int p = par[i];
+    if ((unsigned)p >= (unsigned)i) return i;
+    i = p;
+  }
+}
+__device__ __forceinline__ void lds_union(int* par, int a, int b) {
+  for (;;) {
+    a = lds_find(par, a);
+    b = lds_find(par, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(&par[a], b);
+    if (old == a) return;
+    a = old;                             // somebody linked a first: old < a, go on from there
+  }
+}
+
+// ---- union-find in global memory ----
+__device__ __forceinline__ int g_find(const int32_t* par, int i) {
+  for (;;) {
+    const int p = __hip_atomic_load(par + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((unsigned)p >= (unsigned)i) return i;
+    i = p;
+  }
+}
+__device__ __forceinline__ void g_union(int32_t* par, int a, int b) {
+  for (;;) {
+    a = g_find(par, a);
+    b = g_find(par, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(&par[a], b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// Exclusive scan of one int per thread over the workgroup of 256; *total = the sum.  Two barriers.
+__device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  if (lane == 63) wsum[wv] = inc;
+  __syncthreads();
+  int off = 0;
+  for (int w = 0; w < wv; ++w) off += wsum[w];
+  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  __syncthreads();
+  return off + inc - v;
+}
+
+// id of the component of foreground pixel p once cc_number_kernel has run: a root holds it in area, a local root (area > 0)
+// points at its root, every other pixel at its local root.
+__device__ __forceinline__ int cc_id(const int32_t* parent, const int32_t* area, int p, int pa, int ar) {
+  if (pa == p) return ar;
+  if (ar != 0) return area[pa];
+  return area[parent[pa]];
+}
+
+__global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* labels, int32_t* parent, int32_t* area, int H, int W,
+                                                      int conn8) {
+  __shared__ uint32_t lab4[kCcWords];
+  __shared__ int par[kCcTile];
+  __shared__ int cnt[kCcTile];
+  const uint8_t* lab = (const uint8_t*)lab4;
+  const int ty0 = blockIdx.y * kCcTH, tx0 = blockIdx.x * kCcTW;
+  const size_t img = (size_t)blockIdx.z * H * W;
+  const uint8_t* L = labels + img;
+  int32_t* P = parent + img;
+  int32_t* A = area + img;
+  const bool vec = (W & 3) == 0 && ((uintptr_t)labels & 3) == 0 && (((uintptr_t)parent | (uintptr_t)area) & 15) == 0;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int w = threadIdx.x + 256 * k, y = ty0 + (w >> 4), x = tx0 + (w & 15) * 4;
+    uint32_t v = 0u;
+    if (y < H) {
+      const size_t o = (size_t)y * W + x;
+      if (vec) {
+        if (x < W) v = *(const uint32_t*)(L + o);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (x + j < W) v |= (uint32_t)L[o + j] << (8 * j);
+      }
+    }
+    lab4[w] = v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      par[4 * w + j] = 4 * w + j;
+      cnt[4 * w + j] = 0;
+    }
+  }
+  __syncthreads();
+  // a pixel joins its left and upper neighbour; with 8 neighbours the two upper diagonals only where the upper one is
+  // another byte (else they reach this pixel through it)
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int w = threadIdx.x + 256 * k, ly = w >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int l = 4 * w + j, lx = l & (kCcTW - 1);
+      const uint8_t c = lab[l];
+      if (c == 0) continue;
+      if (lx > 0 && lab[l - 1] == c) lds_union(par, l, l - 1);
+      if (ly > 0) {
+        if (lab[l - kCcTW] == c) {
+          lds_union(par, l, l - kCcTW);
+        } else if (conn8) {
+          if (lx > 0 && lab[l - kCcTW - 1] == c) lds_union(par, l, l - kCcTW - 1);
+          if (lx < kCcTW - 1 && lab[l - kCcTW + 1] == c) lds_union(par, l, l - kCcTW + 1);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  int root[2][4];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int w = threadIdx.x + 256 * k;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) root[k][j] = lab[4 * w + j] ? lds_find(par, 4 * w + j) : -1;
+    // one LDS atomic per run of equal roots among the four
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (root[k][j] < 0 || (j > 0 && root[k][j - 1] == root[k][j])) continue;
+      int n = 1;
+      bool run = true;
+#pragma unroll
+      for (int i = 1; i < 4; ++i)
+        if (j + i < 4) {
+          run = run && root[k][j + i] == root[k][j];
+          n += run;
+        }
+      atomicAdd(&cnt[root[k][j]], n);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int w = threadIdx.x + 256 * k, y = ty0 + (w >> 4), x = tx0 + (w & 15) * 4;
+    if (y >= H || x >= W) continue;
+    int gp[4], ga[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = root[k][j];
+      gp[j] = r < 0 ? -1 : (ty0 + (r >> 6)) * W + tx0 + (r & (kCcTW - 1));
+      ga[j] = r == 4 * w + j ? cnt[r] : 0;
+    }
+    const size_t o = (size_t)y * W + x;
+    if (vec) {
+      *(i32x4*)(P + o) = i32x4{gp[0], gp[1], gp[2], gp[3]};
+      *(i32x4*)(A + o) = i32x4{ga[0], ga[1], ga[2], ga[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x + j < W) {
+          P[o + j] = gp[j];
+          A[o + j] = ga[j];
+        }
+    }
+  }
+}
+
+// Items of an image: (ntx - 1) * H pixels on the left column of a tile (not the image's), then (nty - 1) * W on a top row.
+__global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t* labels, int32_t* parent, int H, int W, int ntx, int nty,
+                                                       int conn8) {
+  const size_t img = (size_t)blockIdx.y * H * W;
+  const uint8_t* L = labels + img;
+  int32_t* P = parent + img;
+  const long long nv = (long long)(ntx - 1) * H, total = nv + (long long)(nty - 1) * W;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+    if (t < nv) {
+      const int c = (int)(t / H), y = (int)(t - (long long)c * H), x = (c + 1) * kCcTW;
+      const int a = y * W + x;
+      const uint8_t la = L[a];
+      if (la == 0) continue;
+      if (L[a - 1] == la) {
+        // the pixel above joins the same two tile-local components
+        const bool dup = (y % kCcTH) != 0 && L[a - W] == la && L[a - W - 1] == la;
+        if (!dup) g_union(P, a, a - 1);
+      } else if (conn8) {
+        if (y > 0 && L[a - W - 1] == la) g_union(P, a, a - W - 1);
+        if (y + 1 < H && L[a + W - 1] == la) g_union(P, a, a + W - 1);
+      }
+    } else {
+      const long long u = t - nv;
+      const int r = (int)(u / W), x = (int)(u - (long long)r * W), y = (r + 1) * kCcTH;
+      const int a = y * W + x, up = a - W;
+      const uint8_t la = L[a];
+      if (la == 0) continue;
+      if (L[up] == la) {
+        const bool dup = (x % kCcTW) != 0 && L[a - 1] == la && L[up - 1] == la;
+        if (!dup) g_union(P, a, up);
+      } else if (conn8) {
+        if (x > 0 && L[up - 1] == la) g_union(P, a, up - 1);
+        if (x + 1 < W && L[up + 1] == la) g_union(P, a, up + 1);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_flatten_kernel(int32_t* parent, int32_t* area, int HW) {
+  const size_t img = (size_t)blockIdx.y * HW;
+  int32_t* P = parent + img;
+  int32_t* A = area + img;
+  auto one = [&](int p, int a) {
+    if (a <= 0) return;                  // not a local root
+    const int r = g_find(P, p);
+    if (r == p) return;
+    P[p] = r;
+    atomicAdd(&A[r], a);
+  };
+  if ((HW & 3) == 0 && ((uintptr_t)area & 15) == 0) {
+    const int n4 = HW >> 2;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
+      const i32x4 a = *(const i32x4*)(A + 4 * (size_t)e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) one(4 * e + j, a[j]);
+    }
+  } else {
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) one(p, A[p]);
+  }
+}
+
+// The 8 consecutive pixels of this thread in block blockIdx.x of the image: which are roots (bit j of *roots) and their
+// areas.
+__device__ __forceinline__ void cc_block_roots(const int32_t* P, const int32_t* A, int HW, int p0, unsigned* roots,
+                                               int (&ar)[8]) {
+  *roots = 0u;
+  if (p0 + 8 <= HW && (((uintptr_t)(P + p0) | (uintptr_t)(A + p0)) & 15) == 0) {
+    const i32x4 q0 = *(const i32x4*)(P + p0), q1 = *(const i32x4*)(P + p0 + 4);
+    const int q[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (q[j] == p0 + j) *roots |= 1u << j;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (p0 + j < HW && P[p0 + j] == p0 + j) *roots |= 1u << j;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ar[j] = (*roots >> j) & 1u ? A[p0 + j] : 0;
+}
+
+__global__ __launch_bounds__(256) void cc_count_kernel(const int32_t* parent, const int32_t* area, int32_t* blk, int HW,
+                                                       int min_area) {
+  __shared__ int wk[4], wt[4];
+  const size_t img = (size_t)blockIdx.y * HW;
+  const int p0 = blockIdx.x * kCcTile + threadIdx.x * 8;
+  unsigned roots;
+  int ar[8];
+  cc_block_roots(parent + img, area + img, HW, p0, &roots, ar);
+  int kept = 0, all = __popc(roots);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) kept += ((roots >> j) & 1u) && ar[j] >= min_area;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kept += __shfl_xor(kept, o, 64);
+    all += __shfl_xor(all, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wk[threadIdx.x >> 6] = kept;
+    wt[threadIdx.x >> 6] = all;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t* o = blk + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    o[0] = wk[0] + wk[1] + wk[2] + wk[3];
+    o[1] = wt[0] + wt[1] + wt[2] + wt[3];
+  }
+}
+
+// blk [b][nblk][2] = (kept, all) per block -> (kept before this block, all); n [b] = (kept, all) of the image
+__global__ __launch_bounds__(256) void cc_scan_kernel(int32_t* blk, int32_t* n, int nblk) {
+  __shared__ int wsum[4];
+  int32_t* o = blk + 2 * (size_t)blockIdx.x * nblk;
+  int ck = 0, ct = 0;
+  for (int base = 0; base < nblk; base += 256) {
+    const int i = base + threadIdx.x;
+    const int k = i < nblk ? o[2 * i] : 0, t = i < nblk ? o[2 * i + 1] : 0;
+    int sk, st;
+    const int ek = block_scan(k, wsum, &sk);
+    block_scan(t, wsum, &st);
+    if (i < nblk) o[2 * i] = ck + ek;
+    ck += sk;
+    ct += st;
+  }
+  if (threadIdx.x == 0) {
+    n[2 * blockIdx.x] = ck;
+    n[2 * blockIdx.x + 1] = ct;
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_number_kernel(const uint8_t* labels, const int32_t* parent, int32_t* area,
+                                                        const int32_t* blk, int32_t* stats, int HW, int W, int min_area,
+                                                        int cap) {
+  __shared__ int wsum[4];
+  const size_t img = (size_t)blockIdx.y * HW;
+  int32_t* A = area + img;
+  const int p0 = blockIdx.x * kCcTile + threadIdx.x * 8;
+  unsigned roots;
+  int ar[8];
+  cc_block_roots(parent + img, A, HW, p0, &roots, ar);
+  int kept = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) kept += ((roots >> j) & 1u) && ar[j] >= min_area;
+  int total;
+  int id = blk[2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x)] + block_scan(kept, wsum, &total);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (!((roots >> j) & 1u)) continue;
+    const int p = p0 + j;
+    if (ar[j] < min_area) {
+      A[p] = 0;
+      continue;
+    }
+    A[p] = ++id;
+    if (stats && id <= cap) {
+      int32_t* row = stats + ((size_t)blockIdx.y * cap + (id - 1)) * 8;
+      const int y = p / W, x = p - y * W;
+      row[0] = labels[img + p];
+      row[1] = ar[j];
+      row[2] = y;
+      row[3] = x;
+      row[4] = y + 1;
+      row[5] = x + 1;
+      row[6] = p;
+      row[7] = 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_apply_kernel(const uint8_t* labels, const int32_t* parent, const int32_t* area,
+                                                       const uint8_t* gt, int32_t* ids, uint8_t* filtered, int32_t* stats,
+                                                       unsigned long long* counts, int H, int W, int cap, int NLab) {
+  __shared__ unsigned hist[3 * 256];     // seg_fuse_lds' [inter | pred | gt][label byte]
+  __shared__ int bx0[kCcTile], by1[kCcTile], bx1[kCcTile];   // per tile-local root, tile coordinates; bx1 == 0: unused
+  const int ty0 = blockIdx.y * kCcTH, tx0 = blockIdx.x * kCcTW;
+  const size_t img = (size_t)blockIdx.z * H * W;
+  const uint8_t* L = labels + img;
+  const int32_t* P = parent + img;
+  const int32_t* A = area + img;
+  const uint8_t* G = gt ? gt + img : nullptr;
+  int32_t* I = ids + img;
+  uint8_t* F = filtered ? filtered + img : nullptr;
+  int32_t* S = stats ? stats + (size_t)blockIdx.z * cap * 8 : nullptr;
+  const bool vec = (W & 3) == 0 && (((uintptr_t)labels | (uintptr_t)filtered | (uintptr_t)gt) & 3) == 0 &&
+                   (((uintptr_t)parent | (uintptr_t)area | (uintptr_t)ids) & 15) == 0;
+  const seg_gt_byte map{NLab};
+  for (int i = threadIdx.x; i < 3 * 256; i += 256) hist[i] = 0u;
+  if (S)
+    for (int i = threadIdx.x; i < kCcTile; i += 256) {
+      bx0[i] = kCcTW;
+      by1[i] = 0;
+      bx1[i] = 0;
+    }
+  __syncthreads();
+  const volatile int* vx0 = bx0;
+  const volatile int* vy1 = by1;
+  const volatile int* vx1 = bx1;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int w = threadIdx.x + 256 * k, ly = w >> 4, lx0 = (w & 15) * 4, y = ty0 + ly, x = tx0 + lx0;
+    if (y >= H || x >= W) continue;
+    const size_t o = (size_t)y * W + x;
+    const int nj = vec ? 4 : min(4, W - x);
+    uint32_t c4 = 0u, g4 = 0u;
+    int pa[4] = {-1, -1, -1, -1}, ar[4] = {0, 0, 0, 0};
+    if (vec) {
+      c4 = *(const uint32_t*)(L + o);
+      if (G) g4 = *(const uint32_t*)(G + o);
+      const i32x4 q = *(const i32x4*)(P + o), a = *(const i32x4*)(A + o);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        pa[j] = q[j];
+        ar[j] = a[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nj) {
+          c4 |= (uint32_t)L[o + j] << (8 * j);
+          if (G) g4 |= (uint32_t)G[o + j] << (8 * j);
+          pa[j] = P[o + j];
+          ar[j] = A[o + j];
+        }
+    }
+    int id[4];
+    uint32_t f4 = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t c = (c4 >> (8 * j)) & 255u;
+      const int p = (int)o + j;
+      id[j] = (j < nj && c != 0u) ? cc_id(P, A, p, pa[j], ar[j]) : 0;
+      const uint32_t f = id[j] ? c : 0u;
+      f4 |= f << (8 * j);
+      if (j < nj && G) {
+        const int g = map((int)((g4 >> (8 * j)) & 255u));
+        if (g >= 0) {
+          atomicAdd(&hist[256 + f], 1u);
+          atomicAdd(&hist[512 + g], 1u);
+          if ((int)f == g) atomicAdd(&hist[f], 1u);
+        }
+      }
+      if (S && id[j] >= 1 && id[j] <= cap) {
+        // the slot of this pixel's tile-local root: the pixel itself when it is one, else its parent (inside the tile)
+        int key = 4 * w + j;
+        if (pa[j] != p && ar[j] == 0) {
+          const int qy = pa[j] / W, qx = pa[j] - qy * W;
+          key = (qy - ty0) * kCcTW + (qx - tx0);
+        }
+        if ((unsigned)key < (unsigned)kCcTile) {
+          const int lx = lx0 + j;
+          if (lx < vx0[key]) atomicMin(&bx0[key], lx);
+          if (ly + 1 > vy1[key]) atomicMax(&by1[key], ly + 1);
+          if (lx + 1 > vx1[key]) atomicMax(&bx1[key], lx + 1);
+        }
+      }
+    }
+    if (vec) {
+      *(i32x4*)(I + o) = i32x4{id[0], id[1], id[2], id[3]};
+      if (F) *(uint32_t*)(F + o) = f4;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nj) {
+          I[o + j] = id[j];
+          if (F) F[o + j] = (uint8_t)(f4 >> (8 * j));
+        }
+    }
+  }
+  __syncthreads();
+  if (G) seg_flush_counts(hist, counts + (size_t)blockIdx.z * 2 * (NLab + 1), NLab + 1);
+  if (S)
+    for (int l = threadIdx.x; l < kCcTile; l += 256) {
+      if (bx1[l] == 0) continue;
+      const int p = (ty0 + (l >> 6)) * W + tx0 + (l & (kCcTW - 1));
+      const int id = cc_id(P, A, p, P[p], A[p]);
+      if (id < 1 || id > cap) continue;
+      int32_t* row = S + (size_t)(id - 1) * 8;
+      atomicMin(row + 3, tx0 + bx0[l]);
+      atomicMax(row + 4, ty0 + by1[l]);
+      atomicMax(row + 5, tx0 + bx1[l]);
+    }
+}
+
+static size_t cc_blocks(long long HW) { return (size_t)((HW + kCcTile - 1) / kCcTile); }
+
+}  // namespace dfw
+
+using namespace dfw;
+
+extern "C" size_t dfw_seg_components_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+  if (B < 1 || H < 1 || W < 1) return 0;
+  const long long HW = (long long)H * W;
+  return (size_t)B * ((size_t)HW * 8 + cc_blocks(HW) * 8);
+}
+
+extern "C" int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w) {
+  if (!tile_h || !tile_w) return DFW_EINVAL;
+  *tile_h = kCcTH;
+  *tile_w = kCcTW;
+  return 0;
+}
+
+extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream) {
+  if (!a || !a->labels || !a->ids || !a->n || !a->ws) return DFW_EINVAL;
+  if (a->B < 1 || a->H < 1 || a->W < 1) return DFW_EINVAL;
+  if (a->connectivity != 4 && a->connectivity != 8) return DFW_EINVAL;
+  if (a->min_area < 0) return DFW_EINVAL;
+  if (a->stats && a->cap < 1) return DFW_EINVAL;
+  if (a->counts && !a->gt) return DFW_EINVAL;
+  if (a->gt && (a->nlabels < 1 || a->nlabels > 254)) return DFW_EINVAL;
+  if (a->filtered == a->labels) return DFW_EINVAL;
+  if (a->H > 65535 || a->W > 65535 || (long long)a->H * a->W > (1ll << 30) || a->B > 65535) return DFW_ERANGE;
+  if (a->stats && (long long)a->B * a->cap * 8 > 0x7fffffffll) return DFW_ERANGE;   // seg_zero_launch counts in int
+  if (a->ws_bytes < dfw_seg_components_workspace_bytes(a->B, a->H, a->W)) return DFW_EWORKSPACE;
+  // int32 words (the workspace, ids, n, stats) and 64-bit count cells at their natural alignment
+  if ((((uintptr_t)a->ws | (uintptr_t)a->ids | (uintptr_t)a->n | (uintptr_t)a->stats) & 3) || ((uintptr_t)a->counts & 7))
+    return DFW_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const int B = a->B, H = a->H, W = a->W, HW = H * W, conn8 = a->connectivity == 8;
+  const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH, nblk = (int)cc_blocks(HW);
+  int32_t* parent = (int32_t*)a->ws;
+  int32_t* area = parent + (size_t)B * HW;
+  int32_t* blk = area + (size_t)B * HW;
+  const bool want_counts = a->gt && a->counts;
+  if (int e = seg_zero_launch(st, (uint32_t*)a->stats, a->stats ? B * a->cap * 8 : 0, want_counts ? a->counts : nullptr,
+                              want_counts ? B * 2 * (a->nlabels + 1) : 0))
+    return e;
+  hipLaunchKernelGGL(cc_tile_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, parent, area, H, W, conn8);
+  DFW_CHECK_LAUNCH();
+  const long long items = (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
+  if (items > 0) {
+    const int gx = (int)((items + 255) / 256 > 4096 ? 4096 : (items + 255) / 256);
+    hipLaunchKernelGGL(cc_merge_kernel, dim3(gx, B), dim3(256), 0, st, a->labels, parent, H, W, ntx, nty, conn8);
+    DFW_CHECK_LAUNCH();
+  }
+  {
+    const int per = (HW + 3) / 4;
+    const int gx = (per + 255) / 256 > 4096 ? 4096 : (per + 255) / 256;
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(gx, B), dim3(256), 0, st, parent, area, HW);
+    DFW_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(cc_count_kernel, dim3(nblk, B), dim3(256), 0, st, (const int32_t*)parent, (const int32_t*)area, blk, HW,
+                     a->min_area);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(cc_scan_kernel, dim3(B), dim3(256), 0, st, blk, a->n, nblk);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(cc_number_kernel, dim3(nblk, B), dim3(256), 0, st, a->labels, (const int32_t*)parent, area,
+                     (const int32_t*)blk, a->stats, HW, W, a->min_area, a->cap);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(cc_apply_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, (const int32_t*)parent,
+                     (const int32_t*)area, want_counts ? a->gt : nullptr, a->ids, a->filtered, a->stats,
+                     (unsigned long long*)a->counts, H, W, a->cap, a->nlabels);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}

@@ -1037,3 +1037,49 @@ def tiles_labels_cand(plan, ent, tab, tab_host, N, gt=None, r_threshold=0.25, th
                                           mx.data_ptr(), _p(counts), _p(area), E_cap, N, float(r_threshold),
                                           float(threshold), _stream()), "dfw_tiles_labels_cand")
     return labels, counts, mx, area
+
+
+def seg_components_workspace(B, H, W):
+    """Bytes of seg_components' workspace for a [B, H, W] label map."""
+    return int(L.lib().dfw_seg_components_workspace_bytes(int(B), int(H), int(W)))
+
+
+def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, counts=None, connectivity=8, min_area=0,
+                   nlabels=None):
+    """Connected components of a label map, on caller-owned buffers only (objects.ComponentBuffers holds a set): labels
+    uint8 [B, H, W], 0 = background, equal non-zero bytes connect over `connectivity` (4 | 8) neighbours; a component with
+    fewer than min_area pixels is removed.  Writes ids int32 [B, H, W] (0 = background or removed, else 1..n_b in row-major
+    order of each component's first pixel, restarting per image), n int32 [B, 2] = (kept, found before the filter) and,
+    where given, filtered uint8 [B, H, W] (the labels without the removed components; not `labels` itself), stats int32
+    [B, cap, 8] = (label, area, y0, x0, y1, x1 half-open, first pixel y * W + x, 0) per kept component, rows from
+    min(n_b, cap) on zero -- only stats truncates -- and counts int64 [B, 2, nlabels + 1], seg_labels' counts of the FILTERED
+    bytes against gt uint8 [B, H, W] (nlabels: the number of classes; a byte above it has no bin).  ws: a uint8 buffer of at
+    least seg_components_workspace(B, H, W) bytes, which needs no initialisation.  A fixed number of launches (at most 8),
+    no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
+    B, H, W = labels.shape
+    dev = labels.device
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_components: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegComponentsArgs()
+    a.labels, a.ids, a.n = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W)), own("n", n, torch.int32, (B, 2))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    if filtered is not None:
+        a.filtered = own("filtered", filtered, torch.uint8, (B, H, W))
+    if stats is not None:
+        if stats.dim() != 3:
+            raise ValueError("seg_components: stats must be int32 [B, cap, 8]")
+        a.stats, a.cap = own("stats", stats, torch.int32, (B, stats.shape[1], 8)), stats.shape[1]
+    if counts is not None and gt is None:
+        raise ValueError("seg_components: counts need a ground truth")
+    if gt is not None:
+        if nlabels is None:
+            raise ValueError("seg_components: a ground truth needs nlabels, the number of classes")
+        a.gt, a.nlabels = own("gt", gt, torch.uint8, (B, H, W)), int(nlabels)
+        if counts is not None:
+            a.counts = own("counts", counts, torch.int64, (B, 2, int(nlabels) + 1))
+    a.B, a.H, a.W, a.connectivity, a.min_area = B, H, W, int(connectivity), int(min_area)
+    L.check(L.lib().dfw_seg_components(C.byref(a), _stream()), "dfw_seg_components")

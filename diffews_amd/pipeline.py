@@ -1000,6 +1000,18 @@ class MarigoldPipelineRGBLatentNoise:
         coarse = r["labels"][0].cpu()                                          # the one host synchronisation
         return dict(overlap=overlap, ramp=ramp), plan.candidates_from_labels(coarse.numpy(), min_pixels, margin)
 
+    @torch.no_grad()
+    def objects(self, result, gt=None, key="labels", **kw):
+        """The objects of a route's result: objects.label_objects on result["native"][key] when the route ran at native
+        size (a list of [h_i, w_i] maps, one call per item), otherwise on result[key].  key: "labels" for the N-way,
+        candidate and tiled routes, "pred" for the binary routes (their 0 / 1 mask is a one-class label map).  gt and the
+        keywords (connectivity, min_area, max_components, nlabels, buffers) are label_objects'.  Returns its dict."""
+        from .objects import label_objects
+        src = result.get("native") or result
+        if src.get(key) is None:
+            raise KeyError(f"the result holds no {key!r} map (binary routes: key='pred')")
+        return label_objects(src[key], gt, **kw)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

@@ -776,6 +776,53 @@ int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* ent, const i
                           const uint8_t* gt, uint8_t* labels, uint32_t* mx, int64_t* counts, int64_t* area, int32_t E_cap,
                           int32_t N, float r_threshold, float threshold, dfw_stream_t stream);
 
+/*
+ * Connected components of a label map (version >= 114): the last stage behind every route that ends in `labels`.  Two
+ * pixels belong to one component when they carry the same NON-ZERO byte and a 4- or 8-connected path of that byte joins
+ * them; different bytes never merge.  A component whose area is below min_area is removed (0 and 1 keep everything).  The
+ * kept components of an image are numbered 1..n_b in row-major order of their FIRST pixel, the smallest y * W + x;
+ * numbering restarts for every image.  All integers: the result depends on no order of execution.
+ *
+ *   ids       0 for background and for removed components, else the component's number
+ *   filtered  the label bytes with the removed components set to 0 (labels itself with min_area <= 1)
+ *   n         per image (components kept, components before the filter)
+ *   stats     row id - 1 of an image = {label byte, area, y0, x0, y1, x1 (the box, half-open), first pixel y * W + x, 0};
+ *             rows from min(n_b, cap) on are zero.  ONLY stats truncates -- ids, filtered, n and counts are complete
+ *             whatever cap is -- and the caller sees it as n[b][0] > cap
+ *   counts    dfw_seg_labels' counting rule applied to the FILTERED byte: row 0 filtered == gt == l, row 1 pred_l + gt_l -
+ *             inter_l; gt 0..nlabels, 255 and anything above nlabels dropped; a filtered byte above nlabels has no bin.
+ *             With min_area <= 1 on labels that dfw_seg_labels made, these are that call's counts bit for bit
+ *   ws        dfw_seg_components_workspace_bytes(B, H, W) bytes: 8 per pixel plus 8 per dfw_seg_components_tile() pixels of
+ *             an image, rounded up.  The call writes every word it reads: the caller initialises nothing
+ *
+ * A fixed number of launches (8, or 7 for an image of one tile), chosen by the arguments and never by the image; no host
+ * readback, no loop until convergence, no memset node (stats and counts are zeroed by a library kernel), no thread that
+ * waits for another: the call can be captured and is correct at any residency.  Union-find with parent[i] <= i: tiles in
+ * LDS, borders by global atomicMin, then a flatten pass after which a component's root is its first pixel.  Area and box
+ * reach global memory as one atomic per (tile, tile-local component) and field, never one per pixel.
+ *
+ * Validated on the host before the first launch.  DFW_EINVAL: null labels / ids / n / ws; B, H or W < 1; connectivity not 4
+ * or 8; min_area < 0; stats with cap < 1; counts without gt; gt with nlabels outside 1..254; filtered == labels.
+ * DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535 (also B * cap * 8 above 2^31 - 1 with stats).
+ * DFW_EWORKSPACE: ws_bytes below the query.  DFW_ESHAPE: ws / ids / n / stats not 4-byte aligned, counts not 8-byte.
+ */
+typedef struct {
+  const uint8_t* labels;   /* [B][H][W] contiguous; 0 = background, any other byte is a class; equal bytes connect */
+  int32_t* ids;            /* out [B][H][W]: 0 = background or removed, else 1..n_b */
+  uint8_t* filtered;       /* out, optional [B][H][W]: labels with removed components set to 0; must not alias labels */
+  int32_t* n;              /* out [B][2]: (components kept, components before the filter) */
+  int32_t* stats;          /* out, optional [B][cap][8]: label, area, y0, x0, y1, x1 (half-open), first pixel y*W+x, 0 */
+  const uint8_t* gt;       /* optional [B][H][W], as dfw_seg_labels takes it */
+  int64_t* counts;         /* optional [B][2][nlabels+1], needs gt: intersections / unions of the FILTERED labels */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, connectivity, min_area, cap, nlabels;   /* connectivity 4 | 8; min_area >= 0 */
+} dfw_seg_components_args;
+int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream);
+size_t dfw_seg_components_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* the tile of the LDS pass (rows, columns): the shapes at which the kernels change path, for tests and docs */
+int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
