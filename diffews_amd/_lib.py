@@ -116,6 +116,11 @@ class SegComponentsArgs(C.Structure):
                 ("min_area", _i32), ("cap", _i32), ("nlabels", _i32)]
 
 
+class SegRleArgs(C.Structure):
+    _fields_ = [("ids", _vp), ("runs", _vp), ("run_off", _vp), ("nruns", _vp), ("ws", _vp), ("ws_bytes", _sz), ("B", _i32),
+                ("H", _i32), ("W", _i32), ("cap", _i32), ("max_runs", _i32), ("order", _i32)]
+
+
 class InputImageItem(C.Structure):
     _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
                 ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
@@ -298,6 +303,9 @@ SYMBOLS = {
     "dfw_seg_components": (_i32, [C.POINTER(SegComponentsArgs), _vp]),
     "dfw_seg_components_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dfw_seg_components_tile": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
+    "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
 }
 
 _lib = None

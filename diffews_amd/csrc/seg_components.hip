@@ -33,6 +33,7 @@
 // atomicMin on the word itself returns the truth, so a stale read costs a round, never a wrong link.
 #include "common.h"
 #include "seg_fuse.h"
+#include "seg_scan.h"
 
 namespace dfw {
 
@@ -77,24 +78,6 @@ __device__ __forceinline__ void g_union(int32_t* par, int a, int b) {
     if (old == a) return;
     a = old;
   }
-}
-
-// Exclusive scan of one int per thread over the workgroup of 256; *total = the sum.  Two barriers.
-__device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  int off = 0;
-  for (int w = 0; w < wv; ++w) off += wsum[w];
-  *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-  __syncthreads();
-  return off + inc - v;
 }
 
 // id of the component of foreground pixel p once cc_number_kernel has run: a root holds it in area, a local root (area > 0)

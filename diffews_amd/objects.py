@@ -4,8 +4,12 @@ minimum-area filter, and the filtered labels re-counted against a ground truth (
 Every segmentation route ends in a label map -- `labels` of segment_classes / segment_candidates / segment_tiled, `pred`
 of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own sizes -- and label_objects turns it into
 "which objects, how many, how big, where" without bringing the map to the host.  Nothing here synchronises except
-objects_to_host, which copies the two small tables (n and stats) once.
+objects_to_host, which copies the two small tables (n and stats) once, and runs_to_host.
+
+object_runs adds each object's SHAPE: the run-length encoding of the id map (ops.seg_rle), in row or column (COCO) order,
+still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the host and into the usual forms.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -109,3 +113,137 @@ def objects_to_host(r):
     objs = [[(s[0], s[1], (s[2], s[3], s[4], s[5]), s[6]) for s in stats[b][:min(n[b][0], cap)]] for b in range(B)]
     truncated = any(n[b][0] > cap for b in range(B))
     return (objs[0] if single else objs), truncated
+
+
+# ------------------------------------------------------------------------------------------------ run-length encodings
+
+class RunBuffers:
+    """Everything one object_runs call of a shape writes, allocated once: runs int32 [B, max_runs, 2], run_off int32
+    [B, max_components + 1], nruns int32 [B, 2] and the workspace.  max_runs defaults to min(H * W, 1 << 20) rows per
+    image -- 8 MB at the most, a choice and not a measurement: a scene of a few thousand compact objects at 4096 x 4096
+    stays far below it, a map of single pixels overflows it and object_runs reports that as found > kept."""
+
+    def __init__(self, B, H, W, max_components=1024, max_runs=None, order="column", device="cuda"):
+        self.shape, self.max_components, self.order = (int(B), int(H), int(W)), int(max_components), order
+        self.max_runs = min(int(H) * int(W), 1 << 20) if max_runs is None else int(max_runs)
+        if self.max_components < 1 or self.max_runs < 1:
+            raise ValueError("max_components and max_runs must be at least 1")
+        nbytes = ops.seg_rle_workspace(B, H, W, self.max_components, self.max_runs, order)   # refuses a bad order
+        dev = torch.device(device)
+        self.runs = torch.empty(B, self.max_runs, 2, dtype=torch.int32, device=dev)
+        self.device = self.runs.device
+        self.run_off = torch.empty(B, self.max_components + 1, dtype=torch.int32, device=dev)
+        self.nruns = torch.empty(B, 2, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _runs_one(ids, cap, order, max_runs, buffers):
+    squeeze = ids.dim() == 2
+    if squeeze:
+        ids = ids[None]
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
+        raise ValueError("object_runs takes an int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
+    ids = ids.contiguous()
+    B, H, W = ids.shape
+    if buffers is None:
+        buffers = RunBuffers(B, H, W, cap, max_runs, order, ids.device)
+    elif (buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.max_components != cap
+          or buffers.order != order or (max_runs is not None and buffers.max_runs != int(max_runs))):
+        raise ValueError(f"buffers were made for {buffers.shape}, {buffers.max_components} objects, {buffers.max_runs} runs, "
+                         f"order {buffers.order!r} on {buffers.device}; the ids are {(B, H, W)} with {cap} objects, order "
+                         f"{order!r} on {ids.device}")
+    ops.seg_rle(ids, buffers.runs, buffers.run_off, buffers.nruns, buffers.ws, cap, order)
+    r = dict(runs=buffers.runs, run_off=buffers.run_off, nruns=buffers.nruns, order=order, shape=(H, W))
+    if squeeze:
+        r.update(runs=r["runs"][0], run_off=r["run_off"][0], nruns=r["nruns"][0])
+    return r
+
+
+def object_runs(o, order="column", max_runs=None, buffers=None, max_components=None):
+    """The run-length encoding of every object of an id map.  o: a label_objects result -- the ids are o["ids"] and the
+    objects encoded are 1..cap, cap = the rows of o["stats"] -- or an int32 device tensor [H, W] / [B, H, W] of ids (or a
+    list of [h_i, w_i] maps) together with max_components=.  order: "column" (position x * H + y, COCO's) or "row"
+    (y * W + x); a run is a maximal interval of positions of one object and does not stop at a line's end.
+
+    Returns dict(runs, run_off, nruns, order, shape), the tensors on the device:
+      nruns    int32 [.., 2] = (runs kept, runs found); kept = min(found, max_runs), the first runs in ascending start
+      runs     int32 [.., max_runs, 2] = (start, length), grouped by object ascending and ascending in start within an
+               object; rows from kept on hold whatever the buffer held
+      run_off  int32 [.., cap + 1]: object k's runs are rows run_off[k-1] .. run_off[k]
+      shape    (H, W) of the map
+    A list is handled with ONE CALL PER ITEM and every value of the result is then a list, as in label_objects; `buffers` is
+    then a list of RunBuffers or None.  buffers: a RunBuffers of this shape, object count and order, reused call after call
+    (the result aliases it); max_runs: rows per image for fresh buffers (RunBuffers' default otherwise).  A fixed number of
+    launches per call and no host synchronisation."""
+    if isinstance(o, dict):
+        if max_components is not None:
+            raise ValueError("object_runs: max_components comes from the result's stats table")
+        ids, stats = o["ids"], o["stats"]
+        caps = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
+    else:
+        if max_components is None:
+            raise ValueError("object_runs: an id tensor needs max_components, the highest id to encode")
+        ids = o
+        caps = [int(max_components)] * len(ids) if isinstance(ids, (list, tuple)) else int(max_components)
+    if isinstance(ids, (list, tuple)):
+        bufs = buffers if buffers is not None else [None] * len(ids)
+        if len(bufs) != len(ids):
+            raise ValueError("object_runs: one buffers entry per id map")
+        per = [_runs_one(i, c, order, max_runs, b) for i, c, b in zip(ids, caps, bufs)]
+        return {k: [p[k] for p in per] for k in ("runs", "run_off", "nruns", "order", "shape")}
+    return _runs_one(ids, caps, order, max_runs, buffers)
+
+
+def runs_to_host(rr):
+    """object_runs' result -> (per image a list over the objects 1..min(n, cap) of int32 numpy arrays [k, 2] = (start,
+    length) in ascending start, truncated) with TWO synchronising copies (per item for a list result): the small tables
+    nruns and run_off first, then runs[:kept] of every image and nothing behind it.  n = the highest object with a run.
+    truncated: found > kept somewhere -- the buffers had fewer rows than the image has runs, and the lists hold only the
+    runs that start first.  A [H, W] result gives one image's list."""
+    if isinstance(rr["nruns"], (list, tuple)):
+        per = [runs_to_host({k: v[i] for k, v in rr.items()}) for i in range(len(rr["nruns"]))]
+        return [p[0] for p in per], any(p[1] for p in per)
+    nruns, run_off, runs = rr["nruns"], rr["run_off"], rr["runs"]
+    single = nruns.dim() == 1
+    if single:
+        nruns, run_off, runs = nruns[None], run_off[None], runs[None]
+    B, cap = run_off.shape[0], run_off.shape[1] - 1
+    both = torch.cat([nruns.reshape(-1), run_off.reshape(-1)]).cpu().numpy()       # copy one: the tables
+    nruns, run_off = both[:2 * B].reshape(B, 2), both[2 * B:].reshape(B, cap + 1)
+    kept = nruns[:, 0].tolist()
+    flat = torch.cat([runs[b, :kept[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 2)   # copy two
+    out, at = [], 0
+    for b in range(B):
+        rows, off = flat[at:at + kept[b]], run_off[b]
+        at += kept[b]
+        n = int(np.searchsorted(off, kept[b], side="left")) if kept[b] else 0   # the first k with run_off[k] == kept
+        out.append([rows[off[k - 1]:off[k]] for k in range(1, min(n, cap) + 1)])
+    truncated = bool((nruns[:, 1] > nruns[:, 0]).any())
+    return (out[0] if single else out), truncated
+
+
+def runs_to_coco(runs_k, h, w, order="column"):
+    """One object's runs [k, 2] (column order, ascending start) -> {"size": [h, w], "counts": [...]}, the uncompressed COCO
+    RLE: alternating lengths of zeros and ones over the column-major positions, zeros first.  Runs in row order are
+    refused: COCO has no such form."""
+    if order != "column":
+        raise ValueError("a COCO RLE runs down the columns: encode with order='column'")
+    counts, at = [], 0
+    for s, l in np.asarray(runs_k, dtype=np.int64).reshape(-1, 2).tolist():
+        counts += [s - at, l]
+        at = s + l
+    if at < h * w:
+        counts.append(h * w - at)
+    return {"size": [int(h), int(w)], "counts": counts}
+
+
+def runs_to_mask(runs_k, h, w, order):
+    """One object's runs [k, 2] -> numpy bool [h, w]."""
+    if order not in ("row", "column"):
+        raise ValueError(f"order must be 'row' or 'column', not {order!r}")
+    r = np.asarray(runs_k, dtype=np.int64).reshape(-1, 2)
+    edge = np.zeros(h * w + 1, np.int64)
+    np.add.at(edge, r[:, 0], 1)
+    np.add.at(edge, r[:, 0] + r[:, 1], -1)
+    flat = np.cumsum(edge[:-1]) > 0
+    return flat.reshape(h, w) if order == "row" else flat.reshape(w, h).T.copy()

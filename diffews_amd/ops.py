@@ -1083,3 +1083,47 @@ def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, count
             a.counts = own("counts", counts, torch.int64, (B, 2, int(nlabels) + 1))
     a.B, a.H, a.W, a.connectivity, a.min_area = B, H, W, int(connectivity), int(min_area)
     L.check(L.lib().dfw_seg_components(C.byref(a), _stream()), "dfw_seg_components")
+
+
+_RLE_ORDERS = {"row": 0, "column": 1}
+
+
+def _rle_order(order):
+    if order not in _RLE_ORDERS:
+        raise ValueError(f"order must be 'row' or 'column', not {order!r}")
+    return _RLE_ORDERS[order]
+
+
+def seg_rle_workspace(B, H, W, cap, max_runs, order="column"):
+    """Bytes of seg_rle's workspace for a [B, H, W] id map, objects 1..cap, max_runs rows per image."""
+    return int(L.lib().dfw_seg_rle_workspace_bytes(int(B), int(H), int(W), int(cap), int(max_runs), _rle_order(order)))
+
+
+def seg_rle(ids, runs, run_off, nruns, ws, cap, order="column"):
+    """Run-length encoding of the objects 1..cap of an id map, on caller-owned buffers only (objects.RunBuffers holds a
+    set): ids int32 [B, H, W], normally seg_components' (any int32 map is accepted; ids outside 1..cap count as 0).  A
+    pixel's position is y * W + x (order "row") or x * H + y ("column", COCO's order); a run is a maximal interval of
+    positions with one equal non-zero id and does not stop at a line's end.  Writes nruns int32 [B, 2] = (kept, found),
+    kept = min(found, max_runs) runs in ascending start; runs int32 [B, max_runs, 2] = (start, length) grouped by id ascending
+    and ascending in start within an id, rows from kept on left as they were; run_off int32 [B, cap + 1]: object k's rows are
+    run_off[k-1] .. run_off[k].  ws: a uint8 buffer of at least seg_rle_workspace(B, H, W, cap, max_runs, order) bytes, which
+    needs no initialisation.  A number of launches fixed by the arguments, no host synchronisation, no memset node: the call
+    can be captured.  Returns None."""
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("seg_rle: ids must be a contiguous int32 device tensor [B, H, W]")
+    B, H, W = ids.shape
+    dev, cap = ids.device, int(cap)
+    if runs.dim() != 3:
+        raise ValueError("seg_rle: runs must be int32 [B, max_runs, 2]")
+    max_runs = runs.shape[1]
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_rle: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegRleArgs()
+    a.ids, a.runs = ids.data_ptr(), own("runs", runs, torch.int32, (B, max_runs, 2))
+    a.run_off, a.nruns = own("run_off", run_off, torch.int32, (B, cap + 1)), own("nruns", nruns, torch.int32, (B, 2))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.B, a.H, a.W, a.cap, a.max_runs, a.order = B, H, W, cap, max_runs, _rle_order(order)
+    L.check(L.lib().dfw_seg_rle(C.byref(a), _stream()), "dfw_seg_rle")

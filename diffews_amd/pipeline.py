@@ -1012,6 +1012,12 @@ class MarigoldPipelineRGBLatentNoise:
             raise KeyError(f"the result holds no {key!r} map (binary routes: key='pred')")
         return label_objects(src[key], gt, **kw)
 
+    def object_runs(self, o, **kw):
+        """The run-length encoding of every object of pipe.objects' result: objects.object_runs(o, **kw) -- order
+        ("column", COCO's, or "row"), max_runs, buffers.  Returns its dict; objects.runs_to_host brings it to the host."""
+        from .objects import object_runs
+        return object_runs(o, **kw)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

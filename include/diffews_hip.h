@@ -823,6 +823,54 @@ size_t dfw_seg_components_workspace_bytes(int32_t B, int32_t H, int32_t W);
 /* the tile of the LDS pass (rows, columns): the shapes at which the kernels change path, for tests and docs */
 int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w);
 
+/*
+ * Run-length encoding of labelled objects (version >= 115): the shape of every object of an id map, normally the one
+ * dfw_seg_components wrote (any int32 map is accepted).  A pixel's position is q = y * W + x with order = 0 (rows) or
+ * q = x * H + y with order = 1 (columns, COCO's order); its value v(q) is its id when 1 <= id <= cap and 0 otherwise (ids
+ * above cap are not encoded, as stats does not list them; negative ids count as 0).  A run is a maximal interval
+ * [s, s + l) of positions with one equal non-zero value.  Runs do NOT stop at the end of a row or column: this flattened
+ * order is COCO's, so order = 1 maps onto an uncompressed COCO RLE one-to-one.  `found` is the number of runs of an image;
+ * the first kept = min(found, max_runs) runs IN ASCENDING s are encoded, the rest dropped: found > kept tells the caller
+ * that the encoding is incomplete.  All integers: the result depends on no order of execution.
+ *
+ *   runs      the encoded runs as (s, l), grouped by id ascending and ascending in s within an id; rows from kept on are
+ *             not written
+ *   run_off   object k's runs are rows run_off[k-1] .. run_off[k]; run_off[0] = 0, run_off[cap] = kept
+ *   nruns     per image (kept, found)
+ *   ws        dfw_seg_rle_workspace_bytes(..) bytes.  The call writes every word it reads: the caller initialises nothing
+ *
+ * Ids [[1,1,0],[2,1,1]], cap = 2: rows give runs (0,2) (4,2) | (3,1), run_off = [0,2,3]; columns read the values as
+ * 1,2,1,1,0,1 and give (0,1) (2,2) (5,1) | (1,1), run_off = [0,3,4] -- object 1's COCO counts are [0,1,1,2,1,1].
+ *
+ * A fixed number of launches, 5 + order + 3 * (the bytes cap needs: 1 below 256, 2 below 65536, ..), chosen by the
+ * arguments and never by the image; no host readback, no memset node (run_off is zeroed by a library kernel), no thread
+ * that waits for another: every cross-workgroup prefix is a scan in a launch of its own, so the call can be captured and
+ * is correct at any residency.  Starts are counted per block of positions, scanned, and compacted into (id, s, end)
+ * records; a stable LSD radix sort on the id, one byte a pass, groups them, its in-chunk ranks taken in a fixed order (no
+ * atomic decides a position).  Nothing is written outside runs[.., :kept], run_off, nruns and ws; ids is read only.
+ *
+ * Validated on the host before the first launch.  DFW_EINVAL: null args / ids / runs / run_off / nruns / ws; B, H, W, cap
+ * or max_runs < 1; order not 0 or 1; runs, run_off or nruns overlapping ids.  DFW_ERANGE: H or W above 65535, H * W above
+ * 2^30, B above 65535, B * max_runs * 2 or B * (cap + 1) above 2^31 - 1.  DFW_EWORKSPACE: ws_bytes below the query.
+ * DFW_ESHAPE: ids / runs / run_off / nruns / ws not 4-byte aligned.  Sizes are judged before the workspace, the workspace
+ * before overlap (an extent is only known to be the caller's once both have passed).
+ */
+typedef struct {
+  const int32_t* ids;      /* [B][H][W] contiguous, read only */
+  int32_t* runs;           /* out [B][max_runs][2]: (s, l); rows [kept, max_runs) are left as they were */
+  int32_t* run_off;        /* out [B][cap + 1] */
+  int32_t* nruns;          /* out [B][2]: (kept, found) */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, cap, max_runs, order;   /* order 0 = rows, 1 = columns */
+} dfw_seg_rle_args;
+int dfw_seg_rle(const dfw_seg_rle_args* a, dfw_stream_t stream);
+/* 0 for arguments dfw_seg_rle answers DFW_EINVAL for; monotone in every argument */
+size_t dfw_seg_rle_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_runs, int32_t order);
+/* positions one scan block covers, run records one sort chunk covers: the sizes at which the kernels change path, for
+ * tests and docs */
+int dfw_seg_rle_block(int32_t* pixels, int32_t* records);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
