@@ -121,6 +121,13 @@ class SegRleArgs(C.Structure):
                 ("H", _i32), ("W", _i32), ("cap", _i32), ("max_runs", _i32), ("order", _i32)]
 
 
+class SegMatchArgs(C.Structure):
+    _fields_ = [("pids", _vp), ("gids", _vp), ("pstats", _vp), ("gstats", _vp), ("skip", _vp), ("pairs", _vp),
+                ("pair_off", _vp), ("area", _vp), ("match", _vp), ("gmatch", _vp), ("pq", _vp), ("n", _vp), ("ws", _vp),
+                ("ws_bytes", _sz), ("B", _i32), ("H", _i32), ("W", _i32), ("capP", _i32), ("capG", _i32), ("nlabels", _i32),
+                ("max_records", _i32), ("max_pairs", _i32), ("num", _i32), ("den", _i32)]
+
+
 class InputImageItem(C.Structure):
     _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
                 ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
@@ -306,6 +313,9 @@ SYMBOLS = {
     "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
     "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_match": (_i32, [C.POINTER(SegMatchArgs), _vp]),
+    "dfw_seg_match_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "dfw_seg_match_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
 }
 
 _lib = None

@@ -1,0 +1,505 @@
+// Matching of predicted objects to ground-truth objects (objects.match_objects): two id maps int32 [B][H][W] -> per image
+// the overlap of every (predicted, ground-truth) pair that shares a pixel, the areas, the one-to-one matching on IoU and the
+// panoptic-quality counts per class.  All integers: the result depends on no order of execution.
+//
+// p(q) = pid when 1 <= pid <= capP, else 0; g(q) likewise with capG.  A pixel has w(q) = (p, g) unless skip[q] == 255, then
+// w(q) = (0, 0).  Position is q = y * W + x.  A record is a maximal interval of positions with one equal w != (0, 0); as in
+// seg_rle it does not stop at a row's end.  key = p * (capG + 1) + g.  A pair is a distinct key over the kept records, inter
+// the sum of the record lengths of that key.  Pairs with g = 0 or p = 0 are kept: row sums are areaP[p], the counted pixels
+// of p, column sums areaG[g]; neither depends on stats, both respect skip.  union = areaP[p] + areaG[g] - inter.  p and g
+// (both > 0) MATCH when their classes are equal, the class is in 1..nlabels and inter * den > num * union in 64-bit
+// integers, strictly; the threshold num / den is at least 1/2, so each object has at most one partner and no assignment
+// problem arises.  An object with area 0 (all its pixels skipped, or its id above cap) is absent: neither FP nor FN.
+//
+// Truncation: of the records the first max_records in ascending start are kept, of the pairs the first max_pairs in
+// ascending key; every output is what the definition gives on the kept records and pairs, and n = (pairs kept, pairs found,
+// records kept, records found) shows it.
+//
+// pids = [[1,1,0],[2,1,1]], gids = [[1,1,1],[0,2,2]], caps 2 and 2, threshold 1/2: records (1,1)x2 (0,1)x1 (2,0)x1 (1,2)x2;
+// pairs (0,1,1) (1,1,2) (1,2,2) (2,0,1); pair_off = [0,1,3,4]; areaP = [1,4,1], areaG = [1,3,2]; IoU(1,1) = 2/5, IoU(1,2) =
+// 2/4, which is not above 1/2: no match, pq[1] = (0, 2, 2, 0).
+//
+// The workspace is, for all B images, blk [nblk] | key, start, end [max_records] | key, length [max_records] | tab
+// [256][nchunk] | heads, lengths [nhead] | first, last [max_pairs], every word of it written before it is read (the caller
+// initialises nothing).  nblk = (HW + 1) / kMatchPix rounded up: position HW, behind the image, has key 0 and is always
+// covered, which closes a record that reaches the image's end; nchunk = max_records / kMatchRec rounded up, nhead =
+// (max_records + 1) / kMatchRec rounded up, for the same reason one step later.  Launches, a number fixed by the arguments,
+//
+//     14 + 3 * passes,   passes = the bytes (capP + 1) * (capG + 1) - 1 needs (1..4),
+//
+// with no host readback in between:
+//
+//   0-3   seg_zero_launch        pair_off and pq | area | match | gmatch (a library kernel, no memset node)
+//   4     match_count_kernel     per block of kMatchPix positions: the record starts, key(q) != key(q-1) and key(q) != 0
+//                                (16-byte loads of both maps, 8-byte loads of skip; the block's first position reads its
+//                                predecessor across the border)
+//   5     match_scan_kernel      one workgroup per image: exclusive scan of the block sums in place, n[2..3]
+//   6     match_emit_kernel      a start writes start[c] = q, key[c] = key(q); an end writes end[c-1] = q (rle_emit_kernel's
+//                                trick: one compaction gives every record, those over many blocks included)
+//   7+    per key byte, lowest first -- a stable LSD radix sort of the kept records on the key:
+//           match_hist_kernel    per chunk of kMatchRec records the digit histogram -> tab [digit][chunk]
+//           match_scan_kernel    exclusive scan of tab in place, digit-major
+//           match_scatter_kernel record i goes to tab[digit][chunk] + its rank among the chunk's earlier records of that
+//                                digit (chunk_rank of seg_scan.h: rle_scatter_kernel's ranking).  The first pass turns
+//                                (start, end) into a length
+//   then  match_heads_kernel     per chunk of sorted records: the heads, key[i] != key[i-1], and the sum of the lengths
+//         match_scan_kernel      both, in one launch: n[0..1]
+//         match_pairs_kernel     a head of rank c writes pairs[c] = (p, g, .), first[c] = the lengths before it, and counts
+//                                itself into pair_off[p]; a head, or the position behind the last record, writes last[c-1]
+//         match_inter_kernel     one thread per kept pair: inter = last - first into pairs, and into areaP[p] and areaG[g]
+//                                (integer atomics: sums, never positions)
+//         match_scan_kernel      pair_off: the exclusive scan of the counts is the offset table
+//         match_rule_kernel      one thread per kept pair applies the match rule: match[p], gmatch[g] (the partner is
+//                                unique: no race), TP and S into pq (integer atomics)
+//         match_rest_kernel      one thread per object: present and without a partner -> FP or FN of its class
+//
+// Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
+// cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
+#include "common.h"
+#include "seg_scan.h"
+
+namespace dfw {
+
+constexpr int kMatchPix = 2048;   // positions per scan block, 8 per thread of 256
+constexpr int kMatchRec = 2048;   // records per sort chunk, 8 rounds of 256 (and 8 per thread in the head kernels)
+
+struct match_maps {
+  const int32_t* P;
+  const int32_t* G;
+  const uint8_t* S;   // optional
+  int capP, capG;
+};
+
+__device__ __forceinline__ int match_key(int pid, int gid, int sk, const match_maps& m) {
+  const int p = (pid >= 1 && pid <= m.capP) ? pid : 0, g = (gid >= 1 && gid <= m.capG) ? gid : 0;
+  return sk == 255 ? 0 : p * (m.capG + 1) + g;
+}
+
+// v[0] = key(p0 - 1), v[1 + j] = key(p0 + j) of image-local positions; positions outside [0, HW) have key 0.  m points at
+// the image.
+__device__ __forceinline__ void match_load9(const match_maps& m, int HW, int p0, int (&v)[9]) {
+  v[0] = (p0 >= 1 && p0 - 1 < HW) ? match_key(m.P[p0 - 1], m.G[p0 - 1], m.S ? m.S[p0 - 1] : 0, m) : 0;
+  if (p0 + 8 <= HW && (((uintptr_t)(m.P + p0) | (uintptr_t)(m.G + p0)) & 15) == 0 &&
+      (!m.S || ((uintptr_t)(m.S + p0) & 7) == 0)) {
+    const i32x4 a0 = *(const i32x4*)(m.P + p0), a1 = *(const i32x4*)(m.P + p0 + 4);
+    const i32x4 b0 = *(const i32x4*)(m.G + p0), b1 = *(const i32x4*)(m.G + p0 + 4);
+    const unsigned long long s = m.S ? *(const unsigned long long*)(m.S + p0) : 0ull;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[1 + j] = match_key(a0[j], b0[j], (int)((s >> (8 * j)) & 255), m);
+      v[5 + j] = match_key(a1[j], b1[j], (int)((s >> (8 * j + 32)) & 255), m);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      v[1 + j] = p0 + j < HW ? match_key(m.P[p0 + j], m.G[p0 + j], m.S ? m.S[p0 + j] : 0, m) : 0;
+  }
+}
+
+__device__ __forceinline__ match_maps match_image(match_maps m, int b, int HW) {
+  m.P += (size_t)b * HW;
+  m.G += (size_t)b * HW;
+  if (m.S) m.S += (size_t)b * HW;
+  return m;
+}
+
+__global__ __launch_bounds__(256) void match_count_kernel(match_maps maps, int32_t* blk, int HW) {
+  __shared__ int ws[4];
+  int v[9];
+  match_load9(match_image(maps, blockIdx.y, HW), HW, blockIdx.x * kMatchPix + threadIdx.x * 8, v);
+  int n = 0;
+#pragma unroll
+  for (int j = 1; j < 9; ++j) n += v[j] != v[j - 1] && v[j] != 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) blk[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// a [plane][image][n], plane = blockIdx.y, image = blockIdx.x: exclusive scan in place, 4 consecutive words per thread and
+// round.  nout (optional, plane 0 only) [image][4]: nout[0..1] = (min(sum, limit), sum).
+__global__ __launch_bounds__(256) void match_scan_kernel(int32_t* a, int n, int32_t* nout, int limit) {
+  __shared__ int wsum[4];
+  int32_t* o = a + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * n;
+  int carry = 0;
+  for (int base = 0; base < n; base += 1024) {
+    const int i0 = base + 4 * threadIdx.x;
+    int v[4], s = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = i0 + j < n ? o[i0 + j] : 0;
+      s += v[j];
+    }
+    int total;
+    int e = carry + block_scan(s, wsum, &total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (i0 + j < n) o[i0 + j] = e;
+      e += v[j];
+    }
+    carry += total;
+  }
+  if (nout && blockIdx.y == 0 && threadIdx.x == 0) {
+    nout[4 * blockIdx.x] = min(carry, limit);
+    nout[4 * blockIdx.x + 1] = carry;
+  }
+}
+
+__global__ __launch_bounds__(256) void match_emit_kernel(match_maps maps, const int32_t* blk, int32_t* key, int32_t* start,
+                                                         int32_t* end, int HW, int max_records) {
+  __shared__ int wsum[4];
+  const int b = blockIdx.y, p0 = blockIdx.x * kMatchPix + threadIdx.x * 8;
+  int v[9];
+  match_load9(match_image(maps, b, HW), HW, p0, v);
+  int n = 0;
+#pragma unroll
+  for (int j = 1; j < 9; ++j) n += v[j] != v[j - 1] && v[j] != 0;
+  int total;
+  int c = blk[(size_t)b * gridDim.x + blockIdx.x] + block_scan(n, wsum, &total);   // starts before p0
+  const size_t r0 = (size_t)b * max_records;
+#pragma unroll
+  for (int j = 1; j < 9; ++j) {
+    if (v[j] == v[j - 1]) continue;
+    const int q = p0 + j - 1;
+    if (v[j - 1] != 0 && (unsigned)(c - 1) < (unsigned)max_records) end[r0 + c - 1] = q;   // c >= 1: it started before q
+    if (v[j] != 0) {
+      if (c < max_records) {
+        start[r0 + c] = q;
+        key[r0 + c] = v[j];
+      }
+      ++c;
+    }
+  }
+}
+
+// n [image][4]: n[2] = the records kept.
+__global__ __launch_bounds__(256) void match_hist_kernel(const int32_t* key, int32_t* tab, const int32_t* n, int max_records,
+                                                         int shift) {
+  __shared__ int hist[256];
+  const int b = blockIdx.y, nchunk = gridDim.x, kept = min(n[4 * b + 2], max_records);
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kMatchRec / 256; ++r) {
+    const int i = blockIdx.x * kMatchRec + r * 256 + threadIdx.x;
+    if (i < kept) atomicAdd(&hist[(key[(size_t)b * max_records + i] >> shift) & 255], 1);
+  }
+  __syncthreads();
+  tab[((size_t)b * 256 + threadIdx.x) * nchunk + blockIdx.x] = hist[threadIdx.x];
+}
+
+// src = (key, s, x): with `first`, s and x are the record's start and end; afterwards sx is its length and ss unused.
+__global__ __launch_bounds__(256) void match_scatter_kernel(const int32_t* skey, const int32_t* ss, const int32_t* sx,
+                                                            int32_t* dkey, int32_t* dl, const int32_t* tab, const int32_t* n,
+                                                            int max_records, int shift, int first) {
+  __shared__ int run[256];
+  __shared__ int wcnt[4][256];
+  const int b = blockIdx.y, nchunk = gridDim.x, kept = min(n[4 * b + 2], max_records);
+  if (blockIdx.x * kMatchRec >= kept) return;                          // the whole workgroup
+  const size_t r0 = (size_t)b * max_records;
+  run[threadIdx.x] = tab[((size_t)b * 256 + threadIdx.x) * nchunk + blockIdx.x];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) wcnt[w][threadIdx.x] = 0;
+  __syncthreads();
+  for (int r = 0; r < kMatchRec / 256; ++r) {
+    const int i = blockIdx.x * kMatchRec + r * 256 + threadIdx.x;
+    const bool on = i < kept;
+    const int k = on ? skey[r0 + i] : 0;
+    const int pos = chunk_rank(on, (k >> shift) & 255, run, wcnt);
+    if (on && (unsigned)pos < (unsigned)kept) {                        // always, with the table the two launches before made
+      dkey[r0 + pos] = k;
+      dl[r0 + pos] = first ? sx[r0 + i] - ss[r0 + i] : sx[r0 + i];
+    }
+  }
+}
+
+// k[0] = key[i0 - 1] (-1 in front of the first record: never a key), k[1 + j] = key[i0 + j], l[j] = len[i0 + j], for the
+// records below kept; behind them the key is -1 and the length 0, so that position `kept` reads as a head that only ends.
+__device__ __forceinline__ void match_load_sorted(const int32_t* key, const int32_t* len, int i0, int kept, int (&k)[9],
+                                                  int (&l)[8]) {
+  k[0] = (i0 >= 1 && i0 - 1 < kept) ? key[i0 - 1] : -1;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const bool on = i0 + j < kept;
+    k[1 + j] = on ? key[i0 + j] : -1;
+    l[j] = on ? len[i0 + j] : 0;
+  }
+}
+
+// hd [2][image][nhead]: the heads and the sum of the lengths of each chunk of kMatchRec sorted records.
+__global__ __launch_bounds__(256) void match_heads_kernel(const int32_t* key, const int32_t* len, int32_t* hd,
+                                                          const int32_t* n, int max_records) {
+  __shared__ int ws[2][4];
+  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kMatchRec + threadIdx.x * 8;
+  const size_t r0 = (size_t)b * max_records;
+  int k[9], l[8], h = 0, s = 0;
+  match_load_sorted(key + r0, len + r0, i0, kept, k, l);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    h += i0 + j < kept && k[1 + j] != k[j];
+    s += l[j];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    h += __shfl_xor(h, o, 64);
+    s += __shfl_xor(s, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    ws[0][threadIdx.x >> 6] = h;
+    ws[1][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    hd[((size_t)threadIdx.x * B + b) * gridDim.x + blockIdx.x] =
+        ws[threadIdx.x][0] + ws[threadIdx.x][1] + ws[threadIdx.x][2] + ws[threadIdx.x][3];
+}
+
+__global__ __launch_bounds__(256) void match_pairs_kernel(const int32_t* key, const int32_t* len, const int32_t* hd,
+                                                          int32_t* pairs, int32_t* pfirst, int32_t* plast, int32_t* pair_off,
+                                                          const int32_t* n, int max_records, int max_pairs, int capP,
+                                                          int capG) {
+  __shared__ int wsum[4];
+  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kMatchRec + threadIdx.x * 8;
+  const size_t r0 = (size_t)b * max_records, q0 = (size_t)b * max_pairs;
+  int k[9], l[8], h = 0, s = 0;
+  match_load_sorted(key + r0, len + r0, i0, kept, k, l);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    h += i0 + j < kept && k[1 + j] != k[j];
+    s += l[j];
+  }
+  int total;
+  int c = hd[(size_t)b * gridDim.x + blockIdx.x] + block_scan(h, wsum, &total);                  // heads before i0
+  int at = hd[((size_t)B + b) * gridDim.x + blockIdx.x] + block_scan(s, wsum, &total);           // lengths before i0
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int i = i0 + j;
+    if (i <= kept && k[1 + j] != k[j]) {                               // a head, or the position behind the last record
+      if ((unsigned)(c - 1) < (unsigned)max_pairs) plast[q0 + c - 1] = at;
+      if (i < kept) {
+        if (c < max_pairs) {
+          const int p = k[1 + j] / (capG + 1), g = k[1 + j] - p * (capG + 1);
+          pairs[3 * (q0 + c)] = p;
+          pairs[3 * (q0 + c) + 1] = g;
+          pfirst[q0 + c] = at;
+          atomicAdd(&pair_off[(size_t)b * (capP + 2) + p], 1);
+        }
+        ++c;
+      }
+    }
+    at += l[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void match_inter_kernel(int32_t* pairs, const int32_t* pfirst, const int32_t* plast,
+                                                          int32_t* area, const int32_t* n, int max_pairs, int capP, int capG) {
+  const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= min(n[4 * b], max_pairs)) return;
+  const size_t q = (size_t)b * max_pairs + c;
+  const int inter = plast[q] - pfirst[q], p = pairs[3 * q], g = pairs[3 * q + 1];
+  pairs[3 * q + 2] = inter;
+  int32_t* ar = area + (size_t)b * (capP + capG + 2);
+  atomicAdd(&ar[p], inter);
+  atomicAdd(&ar[capP + 1 + g], inter);
+}
+
+struct match_rule {
+  const int32_t* pstats;   // optional [B][capP][8]
+  const int32_t* gstats;   // optional [B][capG][8]
+  int capP, capG, nlabels, num, den;
+};
+
+// The class of object k (1..cap) of image b: column 0 of its stats row, 1 without a table.
+__device__ __forceinline__ int match_class(const int32_t* stats, int b, int cap, int k) {
+  return stats ? stats[((size_t)b * cap + k - 1) * 8] : 1;
+}
+
+__global__ __launch_bounds__(256) void match_rule_kernel(const int32_t* pairs, const int32_t* area, match_rule r,
+                                                         int32_t* match, int32_t* gmatch, unsigned long long* pq,
+                                                         const int32_t* n, int max_pairs) {
+  const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= min(n[4 * b], max_pairs)) return;
+  const size_t q = (size_t)b * max_pairs + c;
+  const int p = pairs[3 * q], g = pairs[3 * q + 1], inter = pairs[3 * q + 2];
+  if (p == 0 || g == 0) return;
+  const int cls = match_class(r.pstats, b, r.capP, p);
+  if (cls != match_class(r.gstats, b, r.capG, g) || cls < 1 || cls > r.nlabels) return;
+  const int32_t* ar = area + (size_t)b * (r.capP + r.capG + 2);
+  const long long uni = (long long)ar[p] + ar[r.capP + 1 + g] - inter;
+  if ((long long)inter * r.den <= (long long)r.num * uni) return;
+  int32_t* m = match + ((size_t)b * r.capP + p - 1) * 3;
+  m[0] = g;
+  m[1] = inter;
+  m[2] = (int)uni;
+  gmatch[(size_t)b * r.capG + g - 1] = p;
+  unsigned long long* row = pq + ((size_t)b * (r.nlabels + 1) + cls) * 4;
+  atomicAdd(&row[0], 1ull);
+  atomicAdd(&row[3], ((unsigned long long)inter << 32) / (unsigned long long)uni);
+}
+
+__global__ __launch_bounds__(256) void match_rest_kernel(const int32_t* area, match_rule r, const int32_t* match,
+                                                         const int32_t* gmatch, unsigned long long* pq) {
+  const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= r.capP + r.capG) return;
+  const int32_t* ar = area + (size_t)b * (r.capP + r.capG + 2);
+  const bool pred = t < r.capP;
+  const int k = pred ? t + 1 : t - r.capP + 1;
+  const int a = pred ? ar[k] : ar[r.capP + 1 + k];
+  const int partner = pred ? match[((size_t)b * r.capP + k - 1) * 3] : gmatch[(size_t)b * r.capG + k - 1];
+  if (a == 0 || partner != 0) return;
+  const int cls = pred ? match_class(r.pstats, b, r.capP, k) : match_class(r.gstats, b, r.capG, k);
+  if (cls < 1 || cls > r.nlabels) return;
+  atomicAdd(&pq[((size_t)b * (r.nlabels + 1) + cls) * 4 + (pred ? 1 : 2)], 1ull);
+}
+
+static int match_passes(long long keys) {   // keys - 1 is the highest key
+  return keys <= (1ll << 8) ? 1 : keys <= (1ll << 16) ? 2 : keys <= (1ll << 24) ? 3 : 4;
+}
+
+struct match_layout {
+  size_t blk, rec[2], tab, hd, pfirst, plast, words;   // offsets in words, for all B images
+  int nblk, nchunk, nhead;
+};
+static match_layout match_plan(long long B, long long HW, long long max_records, long long max_pairs) {
+  match_layout l;
+  l.nblk = (int)((HW + 1 + kMatchPix - 1) / kMatchPix);
+  l.nchunk = (int)((max_records + kMatchRec - 1) / kMatchRec);
+  l.nhead = (int)((max_records + 1 + kMatchRec - 1) / kMatchRec);
+  size_t w = 0;
+  l.blk = w, w += (size_t)B * l.nblk;
+  l.rec[0] = w, w += 3 * (size_t)B * max_records;
+  l.rec[1] = w, w += 2 * (size_t)B * max_records;
+  l.tab = w, w += (size_t)B * 256 * l.nchunk;
+  l.hd = w, w += 2 * (size_t)B * l.nhead;
+  l.pfirst = w, w += (size_t)B * max_pairs;
+  l.plast = w, w += (size_t)B * max_pairs;
+  l.words = w;
+  return l;
+}
+
+// The sizes dfw_seg_match refuses, and its workspace query with it: DFW_EINVAL before DFW_ERANGE.
+static int match_size_error(long long B, long long H, long long W, long long capP, long long capG, long long max_records,
+                            long long max_pairs) {
+  if (B < 1 || H < 1 || W < 1 || capP < 1 || capG < 1 || max_records < 1 || max_pairs < 1) return DFW_EINVAL;
+  // grid y carries B; H * W <= 2^30 keeps every position, HW itself, the padded block count and every sum of lengths in an
+  // int, and inter * den below 2^46
+  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  if ((capP + 1) * (capG + 1) - 1 > 0x7fffffffll) return DFW_ERANGE;   // the highest key is an int; capP + capG + 2 too, then
+  // word counts the kernels and seg_zero_launch hold in an int: rows of pairs and match, the tables, the records
+  if (B * max_pairs * 3 > 0x7fffffffll || B * max_records > 0x7fffffffll || B * capP * 3 > 0x7fffffffll ||
+      B * (capP + capG + 2) > 0x7fffffffll)
+    return DFW_ERANGE;
+  return 0;
+}
+
+static bool match_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return p && q && a < b + qn && b < a + pn;
+}
+
+}  // namespace dfw
+
+using namespace dfw;
+
+extern "C" size_t dfw_seg_match_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t capG,
+                                                int32_t max_records, int32_t max_pairs) {
+  if (match_size_error(B, H, W, capP, capG, max_records, max_pairs)) return 0;
+  return match_plan(B, (long long)H * W, max_records, max_pairs).words * 4;
+}
+
+extern "C" int dfw_seg_match_block(int32_t* pixels, int32_t* records) {
+  if (!pixels || !records) return DFW_EINVAL;
+  *pixels = kMatchPix;
+  *records = kMatchRec;
+  return 0;
+}
+
+extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
+  if (!a || !a->pids || !a->gids || !a->pairs || !a->pair_off || !a->area || !a->match || !a->gmatch || !a->pq || !a->n ||
+      !a->ws)
+    return DFW_EINVAL;
+  if (a->num < 1 || a->num > a->den || a->den > 65535 || 2 * (long long)a->num < a->den) return DFW_EINVAL;
+  if (a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
+  if (int e = match_size_error(a->B, a->H, a->W, a->capP, a->capG, a->max_records, a->max_pairs)) return e;
+  if (a->ws_bytes < dfw_seg_match_workspace_bytes(a->B, a->H, a->W, a->capP, a->capG, a->max_records, a->max_pairs))
+    return DFW_EWORKSPACE;
+  const size_t HWs = (size_t)a->H * a->W, Bs = (size_t)a->B, cP = (size_t)a->capP, cG = (size_t)a->capG;
+  const void* in[5] = {a->pids, a->gids, a->pstats, a->gstats, a->skip};
+  const size_t inb[5] = {Bs * HWs * 4, Bs * HWs * 4, Bs * cP * 32, Bs * cG * 32, Bs * HWs};
+  const void* out[7] = {a->pairs, a->pair_off, a->area, a->match, a->gmatch, a->pq, a->n};
+  const size_t outb[7] = {Bs * a->max_pairs * 12, Bs * (cP + 2) * 4, Bs * (cP + cG + 2) * 4, Bs * cP * 12, Bs * cG * 4,
+                          Bs * ((size_t)a->nlabels + 1) * 32, Bs * 16};
+  for (int i = 0; i < 5; ++i)
+    for (int o = 0; o < 7; ++o)
+      if (match_overlap(in[i], inb[i], out[o], outb[o])) return DFW_EINVAL;
+  if (((uintptr_t)a->pids | (uintptr_t)a->gids | (uintptr_t)a->pstats | (uintptr_t)a->gstats | (uintptr_t)a->pairs |
+       (uintptr_t)a->pair_off | (uintptr_t)a->area | (uintptr_t)a->match | (uintptr_t)a->gmatch | (uintptr_t)a->n |
+       (uintptr_t)a->ws) & 3)
+    return DFW_ESHAPE;
+  if ((uintptr_t)a->pq & 7) return DFW_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const int nB = a->B, iHW = a->H * a->W, capP = a->capP, capG = a->capG, M = a->max_records, MP = a->max_pairs;
+  const match_layout l = match_plan(nB, iHW, M, MP);
+  const int passes = match_passes(((long long)capP + 1) * ((long long)capG + 1));
+  int32_t* ws = (int32_t*)a->ws;
+  int32_t* blk = ws + l.blk;
+  int32_t* tab = ws + l.tab;
+  int32_t* hd = ws + l.hd;
+  int32_t* rec[2][3];
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 3; ++j) rec[i][j] = ws + l.rec[i] + (size_t)j * nB * M;   // rec[1][2] is never used
+  const match_maps maps = {a->pids, a->gids, a->skip, capP, capG};
+  const match_rule rule = {a->pstats, a->gstats, capP, capG, a->nlabels, a->num, a->den};
+  if (int e = seg_zero_launch(st, (uint32_t*)a->pair_off, nB * (capP + 2), a->pq, nB * (a->nlabels + 1) * 4)) return e;
+  if (int e = seg_zero_launch(st, (uint32_t*)a->area, nB * (capP + capG + 2), nullptr, 0)) return e;
+  if (int e = seg_zero_launch(st, (uint32_t*)a->match, nB * capP * 3, nullptr, 0)) return e;
+  if (int e = seg_zero_launch(st, (uint32_t*)a->gmatch, nB * capG, nullptr, 0)) return e;
+  hipLaunchKernelGGL(match_count_kernel, dim3(l.nblk, nB), dim3(256), 0, st, maps, blk, iHW);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, blk, l.nblk, a->n + 2, M);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_emit_kernel, dim3(l.nblk, nB), dim3(256), 0, st, maps, (const int32_t*)blk, rec[0][0], rec[0][1],
+                     rec[0][2], iHW, M);
+  DFW_CHECK_LAUNCH();
+  int cur = 0;
+  for (int p = 0; p < passes; ++p) {
+    int32_t** src = rec[cur];
+    int32_t** dst = rec[cur ^ 1];
+    hipLaunchKernelGGL(match_hist_kernel, dim3(l.nchunk, nB), dim3(256), 0, st, (const int32_t*)src[0], tab,
+                       (const int32_t*)a->n, M, 8 * p);
+    DFW_CHECK_LAUNCH();
+    hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, tab, 256 * l.nchunk, (int32_t*)nullptr, 0);
+    DFW_CHECK_LAUNCH();
+    // the first pass reads (key, start, end) and every pass writes (key, length) into arrays 0 and 1 of the other buffer
+    hipLaunchKernelGGL(match_scatter_kernel, dim3(l.nchunk, nB), dim3(256), 0, st, (const int32_t*)src[0],
+                       (const int32_t*)src[1], (const int32_t*)(p == 0 ? src[2] : src[1]), dst[0], dst[1],
+                       (const int32_t*)tab, (const int32_t*)a->n, M, 8 * p, p == 0);
+    DFW_CHECK_LAUNCH();
+    cur ^= 1;
+  }
+  const int32_t* skey = rec[cur][0];
+  const int32_t* slen = rec[cur][1];
+  int32_t* pfirst = ws + l.pfirst;
+  int32_t* plast = ws + l.plast;
+  hipLaunchKernelGGL(match_heads_kernel, dim3(l.nhead, nB), dim3(256), 0, st, skey, slen, hd, (const int32_t*)a->n, M);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 2), dim3(256), 0, st, hd, l.nhead, a->n, MP);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_pairs_kernel, dim3(l.nhead, nB), dim3(256), 0, st, skey, slen, (const int32_t*)hd, a->pairs, pfirst,
+                     plast, a->pair_off, (const int32_t*)a->n, M, MP, capP, capG);
+  DFW_CHECK_LAUNCH();
+  const dim3 pgrid((MP + 255) / 256, nB);
+  hipLaunchKernelGGL(match_inter_kernel, pgrid, dim3(256), 0, st, a->pairs, (const int32_t*)pfirst, (const int32_t*)plast,
+                     a->area, (const int32_t*)a->n, MP, capP, capG);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, a->pair_off, capP + 2, (int32_t*)nullptr, 0);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_rule_kernel, pgrid, dim3(256), 0, st, (const int32_t*)a->pairs, (const int32_t*)a->area, rule,
+                     a->match, a->gmatch, (unsigned long long*)a->pq, (const int32_t*)a->n, MP);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(match_rest_kernel, dim3((capP + capG + 255) / 256, nB), dim3(256), 0, st, (const int32_t*)a->area, rule,
+                     (const int32_t*)a->match, (const int32_t*)a->gmatch, (unsigned long long*)a->pq);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}

@@ -1,4 +1,5 @@
-// The workgroup scan the integer stages of the segmentation output side share (seg_components.hip, seg_rle.hip).
+// The workgroup scan the integer stages of the segmentation output side share (seg_components.hip, seg_rle.hip,
+// seg_match.hip), and the in-chunk ranking of their radix sort.
 #pragma once
 #include "common.h"
 
@@ -20,6 +21,40 @@ __device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
   *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
   __syncthreads();
   return off + inc - v;
+}
+
+// One round of 256 records of a sort chunk in a stable radix scatter: the destination of this thread's record, whose
+// digit is d (`on`: the thread holds a record).  run [256] holds, per digit, where the next record of that digit goes --
+// the scanned table entry of the chunk, advanced here by the round's counts -- and wcnt [4][256], all zero on entry and
+// again on return, the counts of the four waves.  Ranks come from ballots inside a wave, per-wave counts across the waves
+// and `run` across the rounds: a fixed order, no atomic decides a position.  Three barriers; every thread of the
+// workgroup calls it.  This is rle_scatter_kernel's ranking (seg_rle.hip), statement for statement; seg_match.hip calls
+// it, and seg_rle.hip keeps its own inline copy, because calling this function there changes that kernel's compiled code
+// (two more SGPRs, another schedule) and its code is to stay as measured.
+__device__ __forceinline__ int chunk_rank(bool on, int d, int (&run)[256], int (&wcnt)[4][256]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // the lanes of this wave that hold a record of the same digit
+  unsigned long long m = __ballot(on);
+#pragma unroll
+  for (int bit = 0; bit < 8; ++bit) {
+    const bool set = (d >> bit) & 1;
+    const unsigned long long bal = __ballot(set);
+    m &= set ? bal : ~bal;
+  }
+  const int rank = __popcll(m & ((1ull << lane) - 1ull));
+  if (on && rank == 0) wcnt[wv][d] = __popcll(m);
+  __syncthreads();
+  int pos = 0;
+  if (on) {
+    pos = run[d] + rank;
+    for (int w = 0; w < wv; ++w) pos += wcnt[w][d];
+  }
+  __syncthreads();
+  run[threadIdx.x] += wcnt[0][threadIdx.x] + wcnt[1][threadIdx.x] + wcnt[2][threadIdx.x] + wcnt[3][threadIdx.x];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) wcnt[w][threadIdx.x] = 0;
+  __syncthreads();
+  return pos;
 }
 
 }  // namespace dfw

@@ -133,3 +133,27 @@ def nway_iou(counts):
     fg = seen[1:]
     miou = float(iou[1:][fg].mean()) if bool(fg.any()) else 0.0
     return iou, miou
+
+
+def panoptic_quality(pq):
+    """pq int64 [B, N+1, 4] (ops.seg_match / objects.match_objects: per image and class (TP, FP, FN, S), S the sum over the
+    matched pairs of floor(IoU * 2^32); class 0 unused), a list of such tables, or their running sum [N+1, 4] -> dict(pq,
+    sq, rq: float64 [N+1] per class; mean_pq, mean_sq, mean_rq: floats).  The counts are summed over the images (exact,
+    int64), then per class SQ = S / 2^32 / TP (the mean IoU of the matched pairs, 0 without one), RQ = TP / (TP + FP / 2 +
+    FN / 2), PQ = SQ * RQ; the means run over the classes 1..N with TP + FP + FN > 0 (a class neither predicted nor present
+    says nothing; 0.0 when there is none).  Fractions in 0..1, not percent: PQ's usual scale."""
+    if isinstance(pq, (list, tuple)):
+        pq = torch.stack([p.reshape(-1, *p.shape[-2:]).sum(0) for p in pq])
+    c = pq.to(torch.int64)
+    if c.dim() == 3:
+        c = c.sum(0)
+    if c.dim() != 2 or c.shape[0] < 2 or c.shape[1] != 4:
+        raise ValueError(f"pq must be [B, N+1, 4] or [N+1, 4] with N >= 1, got {tuple(pq.shape)}")
+    tp, fp, fn, s = (c[:, i].double() for i in range(4))
+    seen = (tp + fp + fn) > 0
+    seen[0] = False
+    sq = torch.where(tp > 0, s / 4294967296.0 / tp.clamp(min=1.0), torch.zeros_like(s))
+    rq = torch.where(seen, tp / (tp + 0.5 * fp + 0.5 * fn).clamp(min=0.5), torch.zeros_like(s))
+    q = sq * rq
+    mean = lambda v: float(v[seen].mean()) if bool(seen.any()) else 0.0  # noqa: E731
+    return dict(pq=q, sq=sq, rq=rq, mean_pq=mean(q), mean_sq=mean(sq), mean_rq=mean(rq))

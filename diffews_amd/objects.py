@@ -4,10 +4,14 @@ minimum-area filter, and the filtered labels re-counted against a ground truth (
 Every segmentation route ends in a label map -- `labels` of segment_classes / segment_candidates / segment_tiled, `pred`
 of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own sizes -- and label_objects turns it into
 "which objects, how many, how big, where" without bringing the map to the host.  Nothing here synchronises except
-objects_to_host, which copies the two small tables (n and stats) once, and runs_to_host.
+objects_to_host, which copies the two small tables (n and stats) once, runs_to_host and matches_to_host.
 
 object_runs adds each object's SHAPE: the run-length encoding of the id map (ops.seg_rle), in row or column (COCO) order,
 still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the host and into the usual forms.
+
+match_objects says whether the objects are RIGHT: the objects of a prediction against those of a ground truth (ops.seg_match)
+-- the shared pixels of every pair, the areas, a one-to-one matching on IoU and (TP, FP, FN, sum of IoU) per class, which
+metrics.panoptic_quality turns into PQ, SQ and RQ; matches_to_host brings the tables to the host.
 """
 import numpy as np
 import torch
@@ -247,3 +251,165 @@ def runs_to_mask(runs_k, h, w, order):
     np.add.at(edge, r[:, 0] + r[:, 1], -1)
     flat = np.cumsum(edge[:-1]) > 0
     return flat.reshape(h, w) if order == "row" else flat.reshape(w, h).T.copy()
+
+
+# ------------------------------------------------------------------------------------------------ object matching
+
+class MatchBuffers:
+    """Everything one match_objects call of a shape writes, allocated once: pairs int32 [B, max_pairs, 3], pair_off int32
+    [B, cap_p + 2], area int32 [B, cap_p + cap_g + 2], match int32 [B, cap_p, 3], gmatch int32 [B, cap_g], pq int64
+    [B, nlabels + 1, 4], n int32 [B, 4] and the workspace.  max_records defaults to min(H * W, 1 << 20) records per image
+    and max_pairs to min(max_records, 1 << 18) rows -- choices and not measurements: a scene of a few thousand compact
+    objects at 4096 x 4096 stays far below both, maps of single pixels overflow them, and match_objects reports that as
+    n[.., 0] < n[.., 1] or n[.., 2] < n[.., 3]."""
+
+    def __init__(self, B, H, W, cap_p, cap_g, nlabels, max_records=None, max_pairs=None, device="cuda"):
+        self.shape, self.cap_p, self.cap_g, self.nlabels = (int(B), int(H), int(W)), int(cap_p), int(cap_g), int(nlabels)
+        self.max_records = min(int(H) * int(W), 1 << 20) if max_records is None else int(max_records)
+        self.max_pairs = min(self.max_records, 1 << 18) if max_pairs is None else int(max_pairs)
+        if min(self.cap_p, self.cap_g, self.nlabels, self.max_records, self.max_pairs) < 1:
+            raise ValueError("cap_p, cap_g, nlabels, max_records and max_pairs must be at least 1")
+        nbytes = ops.seg_match_workspace(B, H, W, self.cap_p, self.cap_g, self.max_records, self.max_pairs)
+        if nbytes == 0:
+            raise ValueError(f"seg_match refuses these sizes: {self.shape}, caps {self.cap_p} x {self.cap_g}, "
+                             f"{self.max_records} records, {self.max_pairs} pairs")
+        dev, i32 = torch.device(device), torch.int32
+        self.pairs = torch.empty(B, self.max_pairs, 3, dtype=i32, device=dev)
+        self.device = self.pairs.device
+        self.pair_off = torch.empty(B, self.cap_p + 2, dtype=i32, device=dev)
+        self.area = torch.empty(B, self.cap_p + self.cap_g + 2, dtype=i32, device=dev)
+        self.match = torch.empty(B, self.cap_p, 3, dtype=i32, device=dev)
+        self.gmatch = torch.empty(B, self.cap_g, dtype=i32, device=dev)
+        self.pq = torch.empty(B, self.nlabels + 1, 4, dtype=torch.int64, device=dev)
+        self.n = torch.empty(B, 4, dtype=i32, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+_MATCH_KEYS = ("pairs", "pair_off", "area", "match", "gmatch", "pq", "n")
+
+
+def _side(o, what):
+    """A label_objects result or an (ids, stats-or-None[, cap]) tuple -> (ids, stats, cap); lists stay lists."""
+    if isinstance(o, dict):
+        ids, stats = o["ids"], o["stats"]
+        if stats is None:
+            raise ValueError(f"match_objects: the {what} result holds no stats table; pass (ids, None, cap)")
+        cap = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
+        return ids, stats, cap
+    if not isinstance(o, (list, tuple)) or len(o) not in (2, 3):
+        raise ValueError(f"match_objects: {what} must be a label_objects result or a tuple (ids, stats or None[, cap])")
+    ids, stats = o[0], o[1]
+    many = isinstance(ids, (list, tuple))
+    if len(o) == 3:
+        cap = [int(o[2])] * len(ids) if many else int(o[2])
+    elif stats is None:
+        raise ValueError(f"match_objects: {what} ids without a stats table need an explicit cap: (ids, None, cap)")
+    else:
+        cap = [s.shape[-2] for s in stats] if many else stats.shape[-2]
+    if many and stats is None:
+        stats = [None] * len(ids)
+    return ids, stats, cap
+
+
+def _match_one(pids, pstats, cap_p, gids, gstats, cap_g, skip, iou, nlabels, buffers):
+    squeeze = pids.dim() == 2
+    if squeeze:
+        lift = lambda t: None if t is None else t[None]  # noqa: E731
+        pids, gids, pstats, gstats, skip = pids[None], lift(gids), lift(pstats), lift(gstats), lift(skip)
+    if pids.dim() != 3 or pids.dtype != torch.int32 or not pids.is_cuda:
+        raise ValueError("match_objects takes int32 device id maps [H, W] or [B, H, W], or lists of [h, w] maps")
+    if gids is None or gids.dtype != torch.int32 or gids.shape != pids.shape:
+        raise ValueError("match_objects: the ground truth's ids must be int32 and shaped like the prediction's")
+    if skip is not None and (skip.dtype != torch.uint8 or skip.shape != pids.shape):
+        raise ValueError("match_objects: skip must be uint8 and shaped like the ids")
+    B, H, W = pids.shape
+    if buffers is None:
+        if nlabels is None:
+            raise ValueError("match_objects needs nlabels, the number of classes (or buffers made for it)")
+        buffers = MatchBuffers(B, H, W, cap_p, cap_g, nlabels, device=pids.device)
+    elif (buffers.shape != (B, H, W) or buffers.device != pids.device or (buffers.cap_p, buffers.cap_g) != (cap_p, cap_g)
+          or (nlabels is not None and buffers.nlabels != int(nlabels))):
+        raise ValueError(f"buffers were made for {buffers.shape}, caps {buffers.cap_p} x {buffers.cap_g}, {buffers.nlabels} "
+                         f"classes on {buffers.device}; the ids are {(B, H, W)} with caps {cap_p} x {cap_g}"
+                         f"{'' if nlabels is None else f', {nlabels} classes'} on {pids.device}")
+    cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    ops.seg_match(pids.contiguous(), gids.contiguous(), buffers.pairs, buffers.pair_off, buffers.area, buffers.match,
+                  buffers.gmatch, buffers.pq, buffers.n, buffers.ws, buffers.max_records, pstats=cont(pstats),
+                  gstats=cont(gstats), skip=cont(skip), iou=iou)
+    r = {k: getattr(buffers, k) for k in _MATCH_KEYS}
+    if squeeze:
+        r = {k: v[0] for k, v in r.items()}
+    return r
+
+
+def match_objects(o_pred, o_gt, skip=None, iou=(1, 2), nlabels=None, buffers=None):
+    """The objects of a prediction matched one-to-one to those of a ground truth, and the panoptic-quality counts per
+    class.  o_pred, o_gt: two label_objects results -- the ids are o["ids"], the classes column 0 of o["stats"], the caps
+    its rows -- or tuples (ids, stats) / (ids, None, cap): int32 device ids [H, W] / [B, H, W] (or lists of [h_i, w_i]
+    maps); without a stats table every object of that side has class 1.  Ids outside 1..cap count as background.  skip
+    (optional): uint8, shaped like the ids; a pixel whose byte is 255 is not counted -- pass the ground-truth label map and
+    its ignore value does the rest.  iou = (num, den): objects of one class in 1..nlabels match when inter * den > num *
+    union in integers, strictly; num / den must be at least 1/2, so every object has at most one partner.
+
+    Returns dict(pairs, pair_off, area, match, gmatch, pq, n), all on the device:
+      n         int32 [.., 4] = (pairs kept, pairs found, records kept, records found); a record is a maximal interval of
+                positions y * W + x with one (p, g) other than (0, 0).  kept < found: the buffers were too small, and every
+                table below describes only the first records / the first pairs
+      pairs     int32 [.., max_pairs, 3] = (p, g, inter) of every pair that shares a counted pixel, p = 0 or g = 0 for
+                background, ascending in (p, g); rows from kept on hold whatever the buffer held
+      pair_off  int32 [.., cap_p + 2]: the rows of p are pair_off[p] .. pair_off[p + 1]; the last entry is kept
+      area      int32 [.., cap_p + cap_g + 2]: the counted pixels of p = 0..cap_p, then of g = 0..cap_g
+      match     int32 [.., cap_p, 3] = (g, inter, union) of object p's partner in row p - 1, zeros without one
+      gmatch    int32 [.., cap_g]: the partner p of object g, or 0
+      pq        int64 [.., nlabels + 1, 4] = (TP, FP, FN, S) per class, S = the sum of floor(inter * 2^32 / union) over the
+                TPs; an object without a counted pixel is neither FP nor FN; metrics.panoptic_quality reads this table
+    A [H, W] input gives the same without the batch axis.  A list is handled with ONE CALL PER ITEM and every value of the
+    result is then a list, as in label_objects; `skip` is a list too and `buffers` a list of MatchBuffers or None.
+    buffers: a MatchBuffers of this shape, caps and class count, reused call after call (the result aliases it); without
+    it fresh buffers of MatchBuffers' default sizes are allocated, which needs nlabels.  A fixed number of launches per
+    call and no host synchronisation."""
+    pids, pstats, cap_p = _side(o_pred, "prediction")
+    gids, gstats, cap_g = _side(o_gt, "ground truth")
+    if isinstance(pids, (list, tuple)):
+        k = len(pids)
+        if not isinstance(gids, (list, tuple)) or len(gids) != k:
+            raise ValueError("match_objects: one ground-truth id map per predicted id map")
+        skips = skip if skip is not None else [None] * k
+        bufs = buffers if buffers is not None else [None] * k
+        if len(skips) != k or len(bufs) != k:
+            raise ValueError("match_objects: one skip / buffers entry per id map")
+        per = [_match_one(pids[i], pstats[i], cap_p[i], gids[i], gstats[i], cap_g[i], skips[i], iou, nlabels, bufs[i])
+               for i in range(k)]
+        return {key: [p[key] for p in per] for key in _MATCH_KEYS}
+    if isinstance(gids, (list, tuple)):
+        raise ValueError("match_objects: one ground-truth id map per predicted id map")
+    return _match_one(pids, pstats, cap_p, gids, gstats, cap_g, skip, iou, nlabels, buffers)
+
+
+def matches_to_host(m):
+    """match_objects' result -> (dict of numpy arrays, truncated) with TWO synchronising copies (per item for a list
+    result): the tables n, pair_off, area, match, gmatch and pq first, then pairs[:kept] of every image and nothing behind
+    it.  The dict holds the tables under their names and pairs as, per image, an int32 array [kept, 3]; truncated: pairs or
+    records kept < found somewhere -- the tables then describe only what was kept.  A [H, W] result gives one image's
+    arrays."""
+    if isinstance(m["n"], (list, tuple)):
+        per = [matches_to_host({k: v[i] for k, v in m.items()}) for i in range(len(m["n"]))]
+        return {k: [p[0][k] for p in per] for k in _MATCH_KEYS}, any(p[1] for p in per)
+    single = m["n"].dim() == 1
+    t = {k: (v[None] if single else v) for k, v in m.items()}
+    B = t["n"].shape[0]
+    names = ("n", "pair_off", "area", "match", "gmatch")
+    both = torch.cat([t[k].reshape(-1) for k in names] + [t["pq"].reshape(-1).view(torch.int32)]).cpu().numpy()   # copy one
+    out, at = {}, 0
+    for k in names:
+        out[k] = both[at:at + t[k].numel()].reshape(t[k].shape)
+        at += t[k].numel()
+    out["pq"] = both[at:].view(np.int64).reshape(t["pq"].shape)
+    kept = out["n"][:, 0].tolist()
+    flat = torch.cat([t["pairs"][b, :kept[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 3)   # copy two
+    offs = np.concatenate([[0], np.cumsum(kept)])
+    out["pairs"] = [flat[offs[b]:offs[b + 1]] for b in range(B)]
+    truncated = bool((out["n"][:, 0] < out["n"][:, 1]).any() or (out["n"][:, 2] < out["n"][:, 3]).any())
+    if single:
+        out = {k: v[0] for k, v in out.items()}
+    return out, truncated

@@ -1127,3 +1127,61 @@ def seg_rle(ids, runs, run_off, nruns, ws, cap, order="column"):
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
     a.B, a.H, a.W, a.cap, a.max_runs, a.order = B, H, W, cap, max_runs, _rle_order(order)
     L.check(L.lib().dfw_seg_rle(C.byref(a), _stream()), "dfw_seg_rle")
+
+
+def seg_match_workspace(B, H, W, cap_p, cap_g, max_records, max_pairs):
+    """Bytes of seg_match's workspace for [B, H, W] id maps, objects 1..cap_p against 1..cap_g, max_records records and
+    max_pairs pair rows per image; 0 for sizes seg_match refuses."""
+    return int(L.lib().dfw_seg_match_workspace_bytes(int(B), int(H), int(W), int(cap_p), int(cap_g), int(max_records),
+                                                     int(max_pairs)))
+
+
+def seg_match(pids, gids, pairs, pair_off, area, match, gmatch, pq, n, ws, max_records, pstats=None, gstats=None, skip=None,
+              iou=(1, 2)):
+    """Predicted objects matched to ground-truth objects, on caller-owned buffers only (objects.MatchBuffers holds a set):
+    pids and gids int32 [B, H, W], normally seg_components' ids of the prediction and of the ground truth (any int32 maps
+    are accepted; ids outside 1..cap count as 0).  pstats / gstats (optional) int32 [B, cap, 8], seg_components' tables:
+    column 0 is an object's class, 1 for every object of a side without a table.  skip (optional) uint8 [B, H, W]: a pixel
+    whose byte is 255 is not counted.  iou = (num, den): objects of one class in 1..nlabels match when inter * den > num *
+    union, strictly; the threshold is at least 1/2, so every object has at most one partner.
+
+    Writes n int32 [B, 4] = (pairs kept, pairs found, records kept, records found); pairs int32 [B, max_pairs, 3] = (p, g,
+    inter) ascending in (p, g), rows from kept on left as they were; pair_off int32 [B, cap_p + 2]: the rows of p are
+    pair_off[p] .. pair_off[p + 1]; area int32 [B, cap_p + cap_g + 2] = areaP[0..cap_p], areaG[0..cap_g]; match int32
+    [B, cap_p, 3] = (g, inter, union) of each predicted object's partner or zeros; gmatch int32 [B, cap_g], the partner p or
+    0; pq int64 [B, nlabels + 1, 4] = (TP, FP, FN, S) per class, S the sum of floor(inter * 2^32 / union) over the TPs.
+    cap_p, cap_g, nlabels and max_pairs are the buffers' shapes; max_records, the records kept per image (a record is a
+    maximal interval of positions with one equal (p, g) other than (0, 0)), is given.  ws: a uint8 buffer of at least
+    seg_match_workspace(B, H, W, cap_p, cap_g, max_records, max_pairs) bytes, which needs no initialisation.  A number of
+    launches fixed by the arguments, no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    if pids.dim() != 3 or pids.dtype != torch.int32 or not pids.is_contiguous():
+        raise ValueError("seg_match: pids must be a contiguous int32 device tensor [B, H, W]")
+    B, H, W = pids.shape
+    dev = pids.device
+    if match.dim() != 3 or gmatch.dim() != 2 or pairs.dim() != 3 or pq.dim() != 3:
+        raise ValueError("seg_match: match must be int32 [B, cap_p, 3], gmatch int32 [B, cap_g], pairs int32 [B, max_pairs, 3] "
+                         "and pq int64 [B, nlabels + 1, 4]")
+    cap_p, cap_g, max_pairs, nlabels = match.shape[1], gmatch.shape[1], pairs.shape[1], pq.shape[1] - 1
+    num, den = (int(v) for v in iou)
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_match: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegMatchArgs()
+    a.pids, a.gids = pids.data_ptr(), own("gids", gids, torch.int32, (B, H, W))
+    if pstats is not None:
+        a.pstats = own("pstats", pstats, torch.int32, (B, cap_p, 8))
+    if gstats is not None:
+        a.gstats = own("gstats", gstats, torch.int32, (B, cap_g, 8))
+    if skip is not None:
+        a.skip = own("skip", skip, torch.uint8, (B, H, W))
+    a.pairs, a.pair_off = own("pairs", pairs, torch.int32, (B, max_pairs, 3)), own("pair_off", pair_off, torch.int32, (B, cap_p + 2))
+    a.area, a.match = own("area", area, torch.int32, (B, cap_p + cap_g + 2)), own("match", match, torch.int32, (B, cap_p, 3))
+    a.gmatch, a.pq = own("gmatch", gmatch, torch.int32, (B, cap_g)), own("pq", pq, torch.int64, (B, nlabels + 1, 4))
+    a.n, a.ws, a.ws_bytes = own("n", n, torch.int32, (B, 4)), own("ws", ws, torch.uint8, None), ws.numel()
+    a.B, a.H, a.W, a.capP, a.capG, a.nlabels = B, H, W, cap_p, cap_g, nlabels
+    a.max_records, a.max_pairs, a.num, a.den = int(max_records), max_pairs, num, den
+    if not pids.is_cuda:
+        raise ValueError("seg_match: pids and every buffer must be device tensors")
+    L.check(L.lib().dfw_seg_match(C.byref(a), _stream()), "dfw_seg_match")

@@ -1018,6 +1018,13 @@ class MarigoldPipelineRGBLatentNoise:
         from .objects import object_runs
         return object_runs(o, **kw)
 
+    def match_objects(self, o_pred, o_gt, **kw):
+        """The objects of a prediction matched to those of a ground truth: objects.match_objects(o_pred, o_gt, **kw) on two
+        pipe.objects / label_objects results -- skip, iou, nlabels, buffers.  Returns its dict; objects.matches_to_host
+        brings it to the host and metrics.panoptic_quality turns its pq table into PQ, SQ and RQ."""
+        from .objects import match_objects
+        return match_objects(o_pred, o_gt, **kw)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

@@ -871,6 +871,86 @@ size_t dfw_seg_rle_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap,
  * tests and docs */
 int dfw_seg_rle_block(int32_t* pixels, int32_t* records);
 
+/*
+ * Matching of predicted objects to ground-truth objects (version >= 116): the object-level score behind two id maps,
+ * normally dfw_seg_components' ids of the prediction and of the ground truth (any int32 maps are accepted).  All integers:
+ * the result depends on no order of execution.
+ *
+ *   p(q) = pid when 1 <= pid <= capP, else 0; g(q) likewise with capG.
+ *   A pixel has w(q) = (p, g) unless it is skipped (skip[q] == 255); a skipped pixel has w(q) = (0, 0).
+ *   Position is q = y * W + x.
+ *   A RECORD is a maximal interval of positions with one equal w != (0, 0).  As in dfw_seg_rle, it does not stop at a
+ *   row's end.
+ *   key = p * (capG + 1) + g.
+ *   A PAIR is a distinct key over the kept records; inter is the sum of the record lengths of that key.
+ *   Pairs with g = 0 or p = 0 are kept.  Row sums are therefore areaP[p], the counted pixels of p; column sums are
+ *   areaG[g].  Neither depends on stats, and both respect skip.
+ *   union = areaP[p] + areaG[g] - inter.
+ *   p and g (both > 0) MATCH when their classes are equal, the class is in 1..nlabels, and inter * den > num * union in
+ *   64-bit integers.  The threshold is num / den with 1 <= num <= den <= 65535 and 2 * num >= den; the comparison is
+ *   strictly greater.  Because ids partition the pixels, each object has at most one partner at any threshold >= 1/2, so
+ *   no assignment problem arises.  An object's class is column 0 of its row of pstats / gstats (as dfw_seg_components
+ *   writes them; nothing else is read), and 1 for every object of a side without a table.
+ *   An object with area == 0 (all its pixels skipped, or its id above cap) is absent: neither FP nor FN.
+ *
+ *   pairs     (p, g, inter), ascending in (p, g); rows from `kept` on are not written
+ *   pair_off  the rows of p are pair_off[p] .. pair_off[p + 1], for p = 0..capP; the last entry is the number of pairs kept
+ *   area      areaP[0..capP], then areaG[0..capG]
+ *   match     row p - 1 = (g, inter, union) of object p's partner; zeros without one
+ *   gmatch    entry g - 1 = the partner p, or 0
+ *   pq        per class (TP, FP, FN, S), S = the sum over the TPs of floor(inter * 2^32 / union) (inter <= 2^30: the
+ *             product fits; the sum is an integer atomic, so it is order-free); row 0 stays zero
+ *   n         per image (pairs kept, pairs found, records kept, records found)
+ *   ws        dfw_seg_match_workspace_bytes(..) bytes.  The call writes every word it reads: the caller initialises nothing
+ *
+ * Truncation is deterministic and visible: of the records the first max_records in ascending start are kept, of the pairs
+ * the first max_pairs in ascending key; every output is what the definition gives on the kept records and pairs, and the
+ * caller sees n[0] < n[1] or n[2] < n[3] and knows the result is incomplete.
+ *
+ * pids = [[1,1,0],[2,1,1]], gids = [[1,1,1],[0,2,2]], caps 2 and 2, threshold 1/2: records (1,1)x2, (0,1)x1, (2,0)x1,
+ * (1,2)x2; pairs (0,1,1), (1,1,2), (1,2,2), (2,0,1); pair_off = [0,1,3,4]; areaP = [1,4,1], areaG = [1,3,2]; IoU(1,1) =
+ * 2/5 and IoU(1,2) = 2/4, which is not above 1/2: no match, pq[1] = (0, 2, 2, 0).
+ *
+ * A fixed number of launches, 14 + 3 * (the bytes (capP + 1) * (capG + 1) - 1 needs, 1..4), chosen by the arguments and
+ * never by the image; no host readback, no memset node (the tables are zeroed by a library kernel), no thread that waits
+ * for another: every cross-workgroup prefix is a scan in a launch of its own, so the call can be captured and is correct
+ * at any residency.  Record starts are counted per block of positions, scanned and compacted into (key, start, end); a
+ * stable LSD radix sort on the key, one byte a pass, groups them (the in-chunk ranking is dfw_seg_rle's: no atomic decides
+ * a position); the heads of the sorted records are counted, scanned and compacted into the pair rows.  Atomics only add
+ * counts and sums.  Nothing is written outside pairs[.., :kept], the other outputs and ws; the inputs are read only.
+ *
+ * Validated on the host before the first launch.  DFW_EINVAL: null args / pids / gids / an output / ws; B, H, W, capP, capG,
+ * max_records or max_pairs < 1; a threshold that breaks the rule above; nlabels outside 1..254 (with or without stats: pq
+ * has nlabels + 1 rows); an output overlapping an input.  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535,
+ * a highest key (capP + 1) * (capG + 1) - 1 above 2^31 - 1, word counts of an output or of a workspace array beyond an
+ * int.  DFW_EWORKSPACE: ws_bytes below the query.  DFW_ESHAPE: pids / gids / pstats / gstats / an int32 output / ws not
+ * 4-byte aligned, pq not 8-byte aligned.  Sizes are judged before the workspace, the workspace before overlap.
+ */
+typedef struct {
+  const int32_t* pids;     /* [B][H][W] contiguous, read only: the prediction's ids */
+  const int32_t* gids;     /* [B][H][W] contiguous, read only: the ground truth's ids */
+  const int32_t* pstats;   /* optional [B][capP][8]: column 0 is the class of object row + 1 */
+  const int32_t* gstats;   /* optional [B][capG][8] */
+  const uint8_t* skip;     /* optional [B][H][W]: a pixel whose byte is 255 is not counted */
+  int32_t* pairs;          /* out [B][max_pairs][3]: (p, g, inter); rows [kept, max_pairs) are left as they were */
+  int32_t* pair_off;       /* out [B][capP + 2] */
+  int32_t* area;           /* out [B][capP + capG + 2] */
+  int32_t* match;          /* out [B][capP][3]: (g, inter, union) */
+  int32_t* gmatch;         /* out [B][capG] */
+  int64_t* pq;             /* out [B][nlabels + 1][4]: (TP, FP, FN, S) */
+  int32_t* n;              /* out [B][4]: (pairs kept, pairs found, records kept, records found) */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, capP, capG, nlabels, max_records, max_pairs, num, den;   /* the IoU threshold is num / den */
+} dfw_seg_match_args;
+int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream);
+/* 0 for sizes dfw_seg_match refuses (DFW_EINVAL or DFW_ERANGE); monotone in every argument over the sizes it accepts */
+size_t dfw_seg_match_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t capG, int32_t max_records,
+                                     int32_t max_pairs);
+/* positions one scan block covers, records one sort chunk covers: the sizes at which the kernels change path, for tests
+ * and docs */
+int dfw_seg_match_block(int32_t* pixels, int32_t* records);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
