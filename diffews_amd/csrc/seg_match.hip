@@ -21,198 +21,84 @@
 //
 // The workspace is, for all B images, blk [nblk] | key, start, end [max_records] | key, length [max_records] | tab
 // [256][nchunk] | heads, lengths [nhead] | first, last [max_pairs], every word of it written before it is read (the caller
-// initialises nothing).  nblk = (HW + 1) / kMatchPix rounded up: position HW, behind the image, has key 0 and is always
-// covered, which closes a record that reaches the image's end; nchunk = max_records / kMatchRec rounded up, nhead =
-// (max_records + 1) / kMatchRec rounded up, for the same reason one step later.  Launches, a number fixed by the arguments,
+// initialises nothing).  nblk = seg_blocks(HW), nchunk = seg_chunks(max_records), nhead = (max_records + 1) / kSegRec
+// rounded up: the position behind the last record is covered, as the one behind the image is one step earlier.  The
+// compaction and the sort are the shared ones of seg_sort.h, which explains them; this file supplies the source
+// (match_maps: the key of two id maps and skip), the payload (match_pay) and the tail on the sorted records.  Launches, a
+// number fixed by the arguments,
 //
 //     14 + 3 * passes,   passes = the bytes (capP + 1) * (capG + 1) - 1 needs (1..4),
 //
 // with no host readback in between:
 //
-//   0-3   seg_zero_launch        pair_off and pq | area | match | gmatch (a library kernel, no memset node)
-//   4     match_count_kernel     per block of kMatchPix positions: the record starts, key(q) != key(q-1) and key(q) != 0
-//                                (16-byte loads of both maps, 8-byte loads of skip; the block's first position reads its
-//                                predecessor across the border)
-//   5     match_scan_kernel      one workgroup per image: exclusive scan of the block sums in place, n[2..3]
-//   6     match_emit_kernel      a start writes start[c] = q, key[c] = key(q); an end writes end[c-1] = q (rle_emit_kernel's
-//                                trick: one compaction gives every record, those over many blocks included)
-//   7+    per key byte, lowest first -- a stable LSD radix sort of the kept records on the key:
-//           match_hist_kernel    per chunk of kMatchRec records the digit histogram -> tab [digit][chunk]
-//           match_scan_kernel    exclusive scan of tab in place, digit-major
-//           match_scatter_kernel record i goes to tab[digit][chunk] + its rank among the chunk's earlier records of that
-//                                digit (chunk_rank of seg_scan.h: rle_scatter_kernel's ranking).  The first pass turns
-//                                (start, end) into a length
+//   0-3   seg_zero_launch               pair_off and pq | area | match | gmatch (a library kernel, no memset node)
+//   4     seg_count_kernel<match_maps>  the record starts per block of kSegPix positions (16-byte loads of both maps,
+//                                       8-byte loads of skip)
+//   5     seg_scan_launch               exclusive scan of the block sums in place, n[2..3]
+//   6     seg_emit_kernel<match_maps>   (key, start, end) of every kept record
+//   7+    seg_sort                      per key byte hist, scan, seg_scatter_kernel<match_pay>.  The first pass turns (start,
+//                                       end) into a length
 //   then  match_heads_kernel     per chunk of sorted records: the heads, key[i] != key[i-1], and the sum of the lengths
-//         match_scan_kernel      both, in one launch: n[0..1]
+//         seg_scan_launch        both, in one launch: n[0..1]
 //         match_pairs_kernel     a head of rank c writes pairs[c] = (p, g, .), first[c] = the lengths before it, and counts
 //                                itself into pair_off[p]; a head, or the position behind the last record, writes last[c-1]
 //         match_inter_kernel     one thread per kept pair: inter = last - first into pairs, and into areaP[p] and areaG[g]
 //                                (integer atomics: sums, never positions)
-//         match_scan_kernel      pair_off: the exclusive scan of the counts is the offset table
+//         seg_scan_launch        pair_off: the exclusive scan of the counts is the offset table
 //         match_rule_kernel      one thread per kept pair applies the match rule: match[p], gmatch[g] (the partner is
 //                                unique: no race), TP and S into pq (integer atomics)
 //         match_rest_kernel      one thread per object: present and without a partner -> FP or FN of its class
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
 // cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
-#include "common.h"
-#include "seg_scan.h"
+#include "seg_sort.h"
 
 namespace dfw {
 
-constexpr int kMatchPix = 2048;   // positions per scan block, 8 per thread of 256
-constexpr int kMatchRec = 2048;   // records per sort chunk, 8 rounds of 256 (and 8 per thread in the head kernels)
-
+// The two id maps and skip (optional), [B][HW]: the key of a position.
 struct match_maps {
   const int32_t* P;
   const int32_t* G;
-  const uint8_t* S;   // optional
+  const uint8_t* S;
   int capP, capG;
+
+  __device__ __forceinline__ int key(int pid, int gid, int sk) const {
+    const int p = (pid >= 1 && pid <= capP) ? pid : 0, g = (gid >= 1 && gid <= capG) ? gid : 0;
+    return sk == 255 ? 0 : p * (capG + 1) + g;
+  }
+  __device__ __forceinline__ void load9(int b, int HW, int p0, int (&v)[9]) const {
+    const int32_t* p = P + (size_t)b * HW;
+    const int32_t* g = G + (size_t)b * HW;
+    const uint8_t* sk = S ? S + (size_t)b * HW : nullptr;
+    v[0] = (p0 >= 1 && p0 - 1 < HW) ? key(p[p0 - 1], g[p0 - 1], sk ? sk[p0 - 1] : 0) : 0;
+    if (p0 + 8 <= HW && (((uintptr_t)(p + p0) | (uintptr_t)(g + p0)) & 15) == 0 && (!sk || ((uintptr_t)(sk + p0) & 7) == 0)) {
+      const i32x4 a0 = *(const i32x4*)(p + p0), a1 = *(const i32x4*)(p + p0 + 4);
+      const i32x4 b0 = *(const i32x4*)(g + p0), b1 = *(const i32x4*)(g + p0 + 4);
+      const unsigned long long s = sk ? *(const unsigned long long*)(sk + p0) : 0ull;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[1 + j] = key(a0[j], b0[j], (int)((s >> (8 * j)) & 255));
+        v[5 + j] = key(a1[j], b1[j], (int)((s >> (8 * j + 32)) & 255));
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[1 + j] = p0 + j < HW ? key(p[p0 + j], g[p0 + j], sk ? sk[p0 + j] : 0) : 0;
+    }
+  }
+  __device__ __forceinline__ void kept(int, int) const {}
 };
 
-__device__ __forceinline__ int match_key(int pid, int gid, int sk, const match_maps& m) {
-  const int p = (pid >= 1 && pid <= m.capP) ? pid : 0, g = (gid >= 1 && gid <= m.capG) ? gid : 0;
-  return sk == 255 ? 0 : p * (m.capG + 1) + g;
-}
-
-// v[0] = key(p0 - 1), v[1 + j] = key(p0 + j) of image-local positions; positions outside [0, HW) have key 0.  m points at
-// the image.
-__device__ __forceinline__ void match_load9(const match_maps& m, int HW, int p0, int (&v)[9]) {
-  v[0] = (p0 >= 1 && p0 - 1 < HW) ? match_key(m.P[p0 - 1], m.G[p0 - 1], m.S ? m.S[p0 - 1] : 0, m) : 0;
-  if (p0 + 8 <= HW && (((uintptr_t)(m.P + p0) | (uintptr_t)(m.G + p0)) & 15) == 0 &&
-      (!m.S || ((uintptr_t)(m.S + p0) & 7) == 0)) {
-    const i32x4 a0 = *(const i32x4*)(m.P + p0), a1 = *(const i32x4*)(m.P + p0 + 4);
-    const i32x4 b0 = *(const i32x4*)(m.G + p0), b1 = *(const i32x4*)(m.G + p0 + 4);
-    const unsigned long long s = m.S ? *(const unsigned long long*)(m.S + p0) : 0ull;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[1 + j] = match_key(a0[j], b0[j], (int)((s >> (8 * j)) & 255), m);
-      v[5 + j] = match_key(a1[j], b1[j], (int)((s >> (8 * j + 32)) & 255), m);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[1 + j] = p0 + j < HW ? match_key(m.P[p0 + j], m.G[p0 + j], m.S ? m.S[p0 + j] : 0, m) : 0;
-  }
-}
-
-__device__ __forceinline__ match_maps match_image(match_maps m, int b, int HW) {
-  m.P += (size_t)b * HW;
-  m.G += (size_t)b * HW;
-  if (m.S) m.S += (size_t)b * HW;
-  return m;
-}
-
-__global__ __launch_bounds__(256) void match_count_kernel(match_maps maps, int32_t* blk, int HW) {
-  __shared__ int ws[4];
-  int v[9];
-  match_load9(match_image(maps, blockIdx.y, HW), HW, blockIdx.x * kMatchPix + threadIdx.x * 8, v);
-  int n = 0;
-#pragma unroll
-  for (int j = 1; j < 9; ++j) n += v[j] != v[j - 1] && v[j] != 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) blk[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// a [plane][image][n], plane = blockIdx.y, image = blockIdx.x: exclusive scan in place, 4 consecutive words per thread and
-// round.  nout (optional, plane 0 only) [image][4]: nout[0..1] = (min(sum, limit), sum).
-__global__ __launch_bounds__(256) void match_scan_kernel(int32_t* a, int n, int32_t* nout, int limit) {
-  __shared__ int wsum[4];
-  int32_t* o = a + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * n;
-  int carry = 0;
-  for (int base = 0; base < n; base += 1024) {
-    const int i0 = base + 4 * threadIdx.x;
-    int v[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = i0 + j < n ? o[i0 + j] : 0;
-      s += v[j];
-    }
-    int total;
-    int e = carry + block_scan(s, wsum, &total);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (i0 + j < n) o[i0 + j] = e;
-      e += v[j];
-    }
-    carry += total;
-  }
-  if (nout && blockIdx.y == 0 && threadIdx.x == 0) {
-    nout[4 * blockIdx.x] = min(carry, limit);
-    nout[4 * blockIdx.x + 1] = carry;
-  }
-}
-
-__global__ __launch_bounds__(256) void match_emit_kernel(match_maps maps, const int32_t* blk, int32_t* key, int32_t* start,
-                                                         int32_t* end, int HW, int max_records) {
-  __shared__ int wsum[4];
-  const int b = blockIdx.y, p0 = blockIdx.x * kMatchPix + threadIdx.x * 8;
-  int v[9];
-  match_load9(match_image(maps, b, HW), HW, p0, v);
-  int n = 0;
-#pragma unroll
-  for (int j = 1; j < 9; ++j) n += v[j] != v[j - 1] && v[j] != 0;
-  int total;
-  int c = blk[(size_t)b * gridDim.x + blockIdx.x] + block_scan(n, wsum, &total);   // starts before p0
-  const size_t r0 = (size_t)b * max_records;
-#pragma unroll
-  for (int j = 1; j < 9; ++j) {
-    if (v[j] == v[j - 1]) continue;
-    const int q = p0 + j - 1;
-    if (v[j - 1] != 0 && (unsigned)(c - 1) < (unsigned)max_records) end[r0 + c - 1] = q;   // c >= 1: it started before q
-    if (v[j] != 0) {
-      if (c < max_records) {
-        start[r0 + c] = q;
-        key[r0 + c] = v[j];
-      }
-      ++c;
-    }
-  }
-}
-
-// n [image][4]: n[2] = the records kept.
-__global__ __launch_bounds__(256) void match_hist_kernel(const int32_t* key, int32_t* tab, const int32_t* n, int max_records,
-                                                         int shift) {
-  __shared__ int hist[256];
-  const int b = blockIdx.y, nchunk = gridDim.x, kept = min(n[4 * b + 2], max_records);
-  hist[threadIdx.x] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kMatchRec / 256; ++r) {
-    const int i = blockIdx.x * kMatchRec + r * 256 + threadIdx.x;
-    if (i < kept) atomicAdd(&hist[(key[(size_t)b * max_records + i] >> shift) & 255], 1);
-  }
-  __syncthreads();
-  tab[((size_t)b * 256 + threadIdx.x) * nchunk + blockIdx.x] = hist[threadIdx.x];
-}
-
 // src = (key, s, x): with `first`, s and x are the record's start and end; afterwards sx is its length and ss unused.
-__global__ __launch_bounds__(256) void match_scatter_kernel(const int32_t* skey, const int32_t* ss, const int32_t* sx,
-                                                            int32_t* dkey, int32_t* dl, const int32_t* tab, const int32_t* n,
-                                                            int max_records, int shift, int first) {
-  __shared__ int run[256];
-  __shared__ int wcnt[4][256];
-  const int b = blockIdx.y, nchunk = gridDim.x, kept = min(n[4 * b + 2], max_records);
-  if (blockIdx.x * kMatchRec >= kept) return;                          // the whole workgroup
-  const size_t r0 = (size_t)b * max_records;
-  run[threadIdx.x] = tab[((size_t)b * 256 + threadIdx.x) * nchunk + blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) wcnt[w][threadIdx.x] = 0;
-  __syncthreads();
-  for (int r = 0; r < kMatchRec / 256; ++r) {
-    const int i = blockIdx.x * kMatchRec + r * 256 + threadIdx.x;
-    const bool on = i < kept;
-    const int k = on ? skey[r0 + i] : 0;
-    const int pos = chunk_rank(on, (k >> shift) & 255, run, wcnt);
-    if (on && (unsigned)pos < (unsigned)kept) {                        // always, with the table the two launches before made
-      dkey[r0 + pos] = k;
-      dl[r0 + pos] = first ? sx[r0 + i] - ss[r0 + i] : sx[r0 + i];
-    }
+struct match_pay {
+  const int32_t *ss, *sx;
+  int32_t *dkey, *dl;
+  int first;
+
+  __device__ __forceinline__ void move(size_t i, size_t pos, int key) const {
+    dkey[pos] = key;
+    dl[pos] = first ? sx[i] - ss[i] : sx[i];
   }
-}
+};
 
 // k[0] = key[i0 - 1] (-1 in front of the first record: never a key), k[1 + j] = key[i0 + j], l[j] = len[i0 + j], for the
 // records below kept; behind them the key is -1 and the length 0, so that position `kept` reads as a head that only ends.
@@ -227,19 +113,25 @@ __device__ __forceinline__ void match_load_sorted(const int32_t* key, const int3
   }
 }
 
-// hd [2][image][nhead]: the heads and the sum of the lengths of each chunk of kMatchRec sorted records.
-__global__ __launch_bounds__(256) void match_heads_kernel(const int32_t* key, const int32_t* len, int32_t* hd,
-                                                          const int32_t* n, int max_records) {
-  __shared__ int ws[2][4];
-  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kMatchRec + threadIdx.x * 8;
-  const size_t r0 = (size_t)b * max_records;
-  int k[9], l[8], h = 0, s = 0;
-  match_load_sorted(key + r0, len + r0, i0, kept, k, l);
+// h = the heads among a thread's eight sorted records, s = the sum of their lengths.
+__device__ __forceinline__ void match_heads(const int (&k)[9], const int (&l)[8], int i0, int kept, int& h, int& s) {
+  h = s = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     h += i0 + j < kept && k[1 + j] != k[j];
     s += l[j];
   }
+}
+
+// hd [2][image][nhead]: the heads and the sum of the lengths of each chunk of kSegRec sorted records.
+__global__ __launch_bounds__(256) void match_heads_kernel(const int32_t* key, const int32_t* len, int32_t* hd,
+                                                          const int32_t* n, int max_records) {
+  __shared__ int ws[2][4];
+  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kSegRec + threadIdx.x * 8;
+  const size_t r0 = (size_t)b * max_records;
+  int k[9], l[8], h, s;
+  match_load_sorted(key + r0, len + r0, i0, kept, k, l);
+  match_heads(k, l, i0, kept, h, s);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     h += __shfl_xor(h, o, 64);
@@ -260,15 +152,11 @@ __global__ __launch_bounds__(256) void match_pairs_kernel(const int32_t* key, co
                                                           const int32_t* n, int max_records, int max_pairs, int capP,
                                                           int capG) {
   __shared__ int wsum[4];
-  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kMatchRec + threadIdx.x * 8;
+  const int b = blockIdx.y, B = gridDim.y, kept = min(n[4 * b + 2], max_records), i0 = blockIdx.x * kSegRec + threadIdx.x * 8;
   const size_t r0 = (size_t)b * max_records, q0 = (size_t)b * max_pairs;
-  int k[9], l[8], h = 0, s = 0;
+  int k[9], l[8], h, s;
   match_load_sorted(key + r0, len + r0, i0, kept, k, l);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    h += i0 + j < kept && k[1 + j] != k[j];
-    s += l[j];
-  }
+  match_heads(k, l, i0, kept, h, s);
   int total;
   int c = hd[(size_t)b * gridDim.x + blockIdx.x] + block_scan(h, wsum, &total);                  // heads before i0
   int at = hd[((size_t)B + b) * gridDim.x + blockIdx.x] + block_scan(s, wsum, &total);           // lengths before i0
@@ -353,24 +241,19 @@ __global__ __launch_bounds__(256) void match_rest_kernel(const int32_t* area, ma
   atomicAdd(&pq[((size_t)b * (r.nlabels + 1) + cls) * 4 + (pred ? 1 : 2)], 1ull);
 }
 
-static int match_passes(long long keys) {   // keys - 1 is the highest key
-  return keys <= (1ll << 8) ? 1 : keys <= (1ll << 16) ? 2 : keys <= (1ll << 24) ? 3 : 4;
-}
-
 struct match_layout {
   size_t blk, rec[2], tab, hd, pfirst, plast, words;   // offsets in words, for all B images
-  int nblk, nchunk, nhead;
+  int nblk, nhead;
 };
 static match_layout match_plan(long long B, long long HW, long long max_records, long long max_pairs) {
   match_layout l;
-  l.nblk = (int)((HW + 1 + kMatchPix - 1) / kMatchPix);
-  l.nchunk = (int)((max_records + kMatchRec - 1) / kMatchRec);
-  l.nhead = (int)((max_records + 1 + kMatchRec - 1) / kMatchRec);
+  l.nblk = seg_blocks(HW);
+  l.nhead = seg_chunks(max_records + 1);
   size_t w = 0;
   l.blk = w, w += (size_t)B * l.nblk;
   l.rec[0] = w, w += 3 * (size_t)B * max_records;
   l.rec[1] = w, w += 2 * (size_t)B * max_records;
-  l.tab = w, w += (size_t)B * 256 * l.nchunk;
+  l.tab = w, w += (size_t)B * 256 * seg_chunks(max_records);
   l.hd = w, w += 2 * (size_t)B * l.nhead;
   l.pfirst = w, w += (size_t)B * max_pairs;
   l.plast = w, w += (size_t)B * max_pairs;
@@ -393,11 +276,6 @@ static int match_size_error(long long B, long long H, long long W, long long cap
   return 0;
 }
 
-static bool match_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + qn && b < a + pn;
-}
-
 }  // namespace dfw
 
 using namespace dfw;
@@ -410,8 +288,8 @@ extern "C" size_t dfw_seg_match_workspace_bytes(int32_t B, int32_t H, int32_t W,
 
 extern "C" int dfw_seg_match_block(int32_t* pixels, int32_t* records) {
   if (!pixels || !records) return DFW_EINVAL;
-  *pixels = kMatchPix;
-  *records = kMatchRec;
+  *pixels = kSegPix;
+  *records = kSegRec;
   return 0;
 }
 
@@ -432,7 +310,7 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
                           Bs * ((size_t)a->nlabels + 1) * 32, Bs * 16};
   for (int i = 0; i < 5; ++i)
     for (int o = 0; o < 7; ++o)
-      if (match_overlap(in[i], inb[i], out[o], outb[o])) return DFW_EINVAL;
+      if (seg_overlap(in[i], inb[i], out[o], outb[o])) return DFW_EINVAL;
   if (((uintptr_t)a->pids | (uintptr_t)a->gids | (uintptr_t)a->pstats | (uintptr_t)a->gstats | (uintptr_t)a->pairs |
        (uintptr_t)a->pair_off | (uintptr_t)a->area | (uintptr_t)a->match | (uintptr_t)a->gmatch | (uintptr_t)a->n |
        (uintptr_t)a->ws) & 3)
@@ -441,10 +319,9 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   const int nB = a->B, iHW = a->H * a->W, capP = a->capP, capG = a->capG, M = a->max_records, MP = a->max_pairs;
   const match_layout l = match_plan(nB, iHW, M, MP);
-  const int passes = match_passes(((long long)capP + 1) * ((long long)capG + 1));
+  const int passes = seg_key_passes(((long long)capP + 1) * ((long long)capG + 1));
   int32_t* ws = (int32_t*)a->ws;
   int32_t* blk = ws + l.blk;
-  int32_t* tab = ws + l.tab;
   int32_t* hd = ws + l.hd;
   int32_t* rec[2][3];
   for (int i = 0; i < 2; ++i)
@@ -455,37 +332,28 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   if (int e = seg_zero_launch(st, (uint32_t*)a->area, nB * (capP + capG + 2), nullptr, 0)) return e;
   if (int e = seg_zero_launch(st, (uint32_t*)a->match, nB * capP * 3, nullptr, 0)) return e;
   if (int e = seg_zero_launch(st, (uint32_t*)a->gmatch, nB * capG, nullptr, 0)) return e;
-  hipLaunchKernelGGL(match_count_kernel, dim3(l.nblk, nB), dim3(256), 0, st, maps, blk, iHW);
+  hipLaunchKernelGGL(seg_count_kernel<match_maps>, dim3(l.nblk, nB), dim3(256), 0, st, maps, blk, iHW);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, blk, l.nblk, a->n + 2, M);
+  if (int e = seg_scan_launch(st, blk, 1, nB, l.nblk, a->n + 2, 4, M)) return e;
+  hipLaunchKernelGGL(seg_emit_kernel<match_maps>, dim3(l.nblk, nB), dim3(256), 0, st, maps, (const int32_t*)blk, rec[0][0],
+                     rec[0][1], rec[0][2], iHW, M);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(match_emit_kernel, dim3(l.nblk, nB), dim3(256), 0, st, maps, (const int32_t*)blk, rec[0][0], rec[0][1],
-                     rec[0][2], iHW, M);
-  DFW_CHECK_LAUNCH();
-  int cur = 0;
-  for (int p = 0; p < passes; ++p) {
-    int32_t** src = rec[cur];
-    int32_t** dst = rec[cur ^ 1];
-    hipLaunchKernelGGL(match_hist_kernel, dim3(l.nchunk, nB), dim3(256), 0, st, (const int32_t*)src[0], tab,
-                       (const int32_t*)a->n, M, 8 * p);
-    DFW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, tab, 256 * l.nchunk, (int32_t*)nullptr, 0);
-    DFW_CHECK_LAUNCH();
-    // the first pass reads (key, start, end) and every pass writes (key, length) into arrays 0 and 1 of the other buffer
-    hipLaunchKernelGGL(match_scatter_kernel, dim3(l.nchunk, nB), dim3(256), 0, st, (const int32_t*)src[0],
-                       (const int32_t*)src[1], (const int32_t*)(p == 0 ? src[2] : src[1]), dst[0], dst[1],
-                       (const int32_t*)tab, (const int32_t*)a->n, M, 8 * p, p == 0);
-    DFW_CHECK_LAUNCH();
-    cur ^= 1;
-  }
+  const int32_t* const key[2] = {rec[0][0], rec[1][0]};
+  int cur;
+  // the first pass reads (key, start, end) and every pass writes (key, length) into arrays 0 and 1 of the other buffer
+  if (int e = seg_sort(st, key, ws + l.tab, a->n + 2, 4, nB, M, passes, &cur, [&](int p) {
+        int32_t** s = rec[p & 1];
+        int32_t** d = rec[(p & 1) ^ 1];
+        return match_pay{s[1], p == 0 ? s[2] : s[1], d[0], d[1], p == 0};
+      }))
+    return e;
   const int32_t* skey = rec[cur][0];
   const int32_t* slen = rec[cur][1];
   int32_t* pfirst = ws + l.pfirst;
   int32_t* plast = ws + l.plast;
   hipLaunchKernelGGL(match_heads_kernel, dim3(l.nhead, nB), dim3(256), 0, st, skey, slen, hd, (const int32_t*)a->n, M);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 2), dim3(256), 0, st, hd, l.nhead, a->n, MP);
-  DFW_CHECK_LAUNCH();
+  if (int e = seg_scan_launch(st, hd, 2, nB, l.nhead, a->n, 4, MP)) return e;
   hipLaunchKernelGGL(match_pairs_kernel, dim3(l.nhead, nB), dim3(256), 0, st, skey, slen, (const int32_t*)hd, a->pairs, pfirst,
                      plast, a->pair_off, (const int32_t*)a->n, M, MP, capP, capG);
   DFW_CHECK_LAUNCH();
@@ -493,8 +361,7 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   hipLaunchKernelGGL(match_inter_kernel, pgrid, dim3(256), 0, st, a->pairs, (const int32_t*)pfirst, (const int32_t*)plast,
                      a->area, (const int32_t*)a->n, MP, capP, capG);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(match_scan_kernel, dim3(nB, 1), dim3(256), 0, st, a->pair_off, capP + 2, (int32_t*)nullptr, 0);
-  DFW_CHECK_LAUNCH();
+  if (int e = seg_scan_launch(st, a->pair_off, 1, nB, capP + 2)) return e;
   hipLaunchKernelGGL(match_rule_kernel, pgrid, dim3(256), 0, st, (const int32_t*)a->pairs, (const int32_t*)a->area, rule,
                      a->match, a->gmatch, (unsigned long long*)a->pq, (const int32_t*)a->n, MP);
   DFW_CHECK_LAUNCH();

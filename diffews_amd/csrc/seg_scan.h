@@ -1,5 +1,5 @@
-// The workgroup scan the integer stages of the segmentation output side share (seg_components.hip, seg_rle.hip,
-// seg_match.hip), and the in-chunk ranking of their radix sort.
+// The workgroup scan the integer stages of the segmentation output side share (seg_components.hip, seg_sort.h,
+// seg_match.hip), and the in-chunk ranking of the radix sort (seg_sort.h).
 #pragma once
 #include "common.h"
 
@@ -28,9 +28,7 @@ __device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
 // the scanned table entry of the chunk, advanced here by the round's counts -- and wcnt [4][256], all zero on entry and
 // again on return, the counts of the four waves.  Ranks come from ballots inside a wave, per-wave counts across the waves
 // and `run` across the rounds: a fixed order, no atomic decides a position.  Three barriers; every thread of the
-// workgroup calls it.  This is rle_scatter_kernel's ranking (seg_rle.hip), statement for statement; seg_match.hip calls
-// it, and seg_rle.hip keeps its own inline copy, because calling this function there changes that kernel's compiled code
-// (two more SGPRs, another schedule) and its code is to stay as measured.
+// workgroup calls it.  Its one caller is seg_scatter_kernel (seg_sort.h).
 __device__ __forceinline__ int chunk_rank(bool on, int d, int (&run)[256], int (&wcnt)[4][256]) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // the lanes of this wave that hold a record of the same digit

@@ -103,6 +103,15 @@ def _block(lib):
     return p.value, r.value
 
 
+def test_block_sizes_are_the_shared_ones(hip_lib):
+    """The run-length and the matching stage use one compaction and one sort (csrc/seg_sort.h, seg_sort.hip): both block
+    queries report the same (pixels, records)."""
+    p, r = C.c_int32(), C.c_int32()
+    assert hip_lib.dfw_seg_match_block(C.byref(p), C.byref(r)) == 0
+    assert (p.value, r.value) == _block(hip_lib)
+    assert "seg_sort.hip" in __import__("diffews_amd.build", fromlist=["SOURCES"]).SOURCES
+
+
 def test_workspace_query_is_monotone(hip_lib):
     q = hip_lib.dfw_seg_rle_workspace_bytes
     P, R = _block(hip_lib)
