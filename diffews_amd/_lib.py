@@ -128,6 +128,15 @@ class SegMatchArgs(C.Structure):
                 ("max_records", _i32), ("max_pairs", _i32), ("num", _i32), ("den", _i32)]
 
 
+class SegComponentsRounds(C.Structure):
+    _fields_ = [("blocks", _i32), ("merge", _i32), ("flatten", _i32), ("flatten_vector", _i32), ("scan", _i32)]
+
+
+class SegSortRounds(C.Structure):
+    _fields_ = [("blocks", _i32), ("block_scan", _i32), ("passes", _i32), ("table_scan", _i32), ("offsets_scan", _i32),
+                ("heads_scan", _i32)]
+
+
 class InputImageItem(C.Structure):
     _fields_ = [("H", _i32), ("W", _i32), ("xk", _i32), ("yk", _i32), ("src_off", _i64),
                 ("xb_off", _i64), ("xc_off", _i64), ("yb_off", _i64), ("yc_off", _i64), ("tmp_off", _i64), ("dst_off", _i64)]
@@ -310,12 +319,15 @@ SYMBOLS = {
     "dfw_seg_components": (_i32, [C.POINTER(SegComponentsArgs), _vp]),
     "dfw_seg_components_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dfw_seg_components_tile": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_components_rounds": (_i32, [_i32, _i32, _i32, _vp, C.POINTER(SegComponentsRounds)]),
     "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
     "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_rle_rounds": (_i32, [_i32] * 6 + [C.POINTER(SegSortRounds)]),
     "dfw_seg_match": (_i32, [C.POINTER(SegMatchArgs), _vp]),
     "dfw_seg_match_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_match_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_match_rounds": (_i32, [_i32] * 7 + [C.POINTER(SegSortRounds)]),
 }
 
 _lib = None

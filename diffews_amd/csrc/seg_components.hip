@@ -477,6 +477,35 @@ __global__ __launch_bounds__(256) void cc_apply_kernel(const uint8_t* labels, co
 
 static size_t cc_blocks(long long HW) { return (size_t)((HW + kCcTile - 1) / kCcTile); }
 
+// The sizes dfw_seg_components refuses, and its rounds query with it: DFW_EINVAL before DFW_ERANGE.
+static int cc_size_error(long long B, long long H, long long W) {
+  if (B < 1 || H < 1 || W < 1) return DFW_EINVAL;
+  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  return 0;
+}
+
+// One inline function per launch whose kernel loops: the grid, and with it the trips of the loop.
+constexpr int kCcGridCap = 4096;
+// cc_merge_kernel: one thread per item, grid-stride behind the cap.
+inline long long cc_merge_items(int H, int W) {
+  const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH;
+  return (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
+}
+inline int cc_merge_grid(long long items) {
+  return (int)((items + 255) / 256 > kCcGridCap ? kCcGridCap : (items + 255) / 256);
+}
+// cc_flatten_kernel: the grid is sized for four pixels a thread; the kernel takes that path when HW is a multiple of
+// four and area is 16-byte aligned, else one pixel a thread over the same grid.  cc_flatten_vector repeats the kernel's
+// own test for the query (the kernel decides on the device; the launcher never asks): keep the two in step.
+inline int cc_flatten_grid(int HW) {
+  const int per = (HW + 3) / 4;
+  return (per + 255) / 256 > kCcGridCap ? kCcGridCap : (per + 255) / 256;
+}
+inline bool cc_flatten_vector(int HW, uintptr_t area) { return (HW & 3) == 0 && (area & 15) == 0; }
+// cc_scan_kernel: 256 block sums a round, one workgroup per image.
+inline int cc_scan_rounds(int nblk) { return (nblk + 255) / 256; }
+inline int cc_grid_rounds(long long items, int gx) { return gx < 1 ? 0 : (int)((items + 256ll * gx - 1) / (256ll * gx)); }
+
 }  // namespace dfw
 
 using namespace dfw;
@@ -494,6 +523,23 @@ extern "C" int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w) {
   return 0;
 }
 
+extern "C" int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const void* ws,
+                                         dfw_seg_components_rounds_out* out) {
+  if (!out || !ws) return DFW_EINVAL;
+  if (int e = cc_size_error(B, H, W)) return e;
+  if ((uintptr_t)ws & 3) return DFW_ESHAPE;
+  const int HW = H * W, nblk = (int)cc_blocks(HW);
+  const long long items = cc_merge_items(H, W);
+  // the address of the area plane behind parent [B][HW]; ws is never dereferenced, so it is an integer here
+  const uintptr_t area = (uintptr_t)ws + (uintptr_t)B * (uintptr_t)HW * 4;
+  out->blocks = nblk;
+  out->merge = cc_grid_rounds(items, items > 0 ? cc_merge_grid(items) : 0);
+  out->flatten_vector = cc_flatten_vector(HW, area);
+  out->flatten = cc_grid_rounds(out->flatten_vector ? HW / 4 : HW, cc_flatten_grid(HW));
+  out->scan = cc_scan_rounds(nblk);
+  return 0;
+}
+
 extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream) {
   if (!a || !a->labels || !a->ids || !a->n || !a->ws) return DFW_EINVAL;
   if (a->B < 1 || a->H < 1 || a->W < 1) return DFW_EINVAL;
@@ -503,7 +549,7 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
   if (a->counts && !a->gt) return DFW_EINVAL;
   if (a->gt && (a->nlabels < 1 || a->nlabels > 254)) return DFW_EINVAL;
   if (a->filtered == a->labels) return DFW_EINVAL;
-  if (a->H > 65535 || a->W > 65535 || (long long)a->H * a->W > (1ll << 30) || a->B > 65535) return DFW_ERANGE;
+  if (int e = cc_size_error(a->B, a->H, a->W)) return e;
   if (a->stats && (long long)a->B * a->cap * 8 > 0x7fffffffll) return DFW_ERANGE;   // seg_zero_launch counts in int
   if (a->ws_bytes < dfw_seg_components_workspace_bytes(a->B, a->H, a->W)) return DFW_EWORKSPACE;
   // int32 words (the workspace, ids, n, stats) and 64-bit count cells at their natural alignment
@@ -521,18 +567,14 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
     return e;
   hipLaunchKernelGGL(cc_tile_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, parent, area, H, W, conn8);
   DFW_CHECK_LAUNCH();
-  const long long items = (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
+  const long long items = cc_merge_items(H, W);
   if (items > 0) {
-    const int gx = (int)((items + 255) / 256 > 4096 ? 4096 : (items + 255) / 256);
-    hipLaunchKernelGGL(cc_merge_kernel, dim3(gx, B), dim3(256), 0, st, a->labels, parent, H, W, ntx, nty, conn8);
+    hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_merge_grid(items), B), dim3(256), 0, st, a->labels, parent, H, W, ntx, nty,
+                       conn8);
     DFW_CHECK_LAUNCH();
   }
-  {
-    const int per = (HW + 3) / 4;
-    const int gx = (per + 255) / 256 > 4096 ? 4096 : (per + 255) / 256;
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(gx, B), dim3(256), 0, st, parent, area, HW);
-    DFW_CHECK_LAUNCH();
-  }
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_flatten_grid(HW), B), dim3(256), 0, st, parent, area, HW);
+  DFW_CHECK_LAUNCH();
   hipLaunchKernelGGL(cc_count_kernel, dim3(nblk, B), dim3(256), 0, st, (const int32_t*)parent, (const int32_t*)area, blk, HW,
                      a->min_area);
   DFW_CHECK_LAUNCH();

@@ -241,6 +241,9 @@ __global__ __launch_bounds__(256) void match_rest_kernel(const int32_t* area, ma
   atomicAdd(&pq[((size_t)b * (r.nlabels + 1) + cls) * 4 + (pred ? 1 : 2)], 1ull);
 }
 
+// Words of pair_off per image, the scan behind match_inter_kernel.
+inline int match_offsets(long long capP) { return (int)(capP + 2); }
+
 struct match_layout {
   size_t blk, rec[2], tab, hd, pfirst, plast, words;   // offsets in words, for all B images
   int nblk, nhead;
@@ -260,6 +263,9 @@ static match_layout match_plan(long long B, long long HW, long long max_records,
   l.words = w;
   return l;
 }
+
+// Digit passes of the sort: the bytes the highest key needs.
+inline int match_passes(long long capP, long long capG) { return seg_key_passes((capP + 1) * (capG + 1)); }
 
 // The sizes dfw_seg_match refuses, and its workspace query with it: DFW_EINVAL before DFW_ERANGE.
 static int match_size_error(long long B, long long H, long long W, long long capP, long long capG, long long max_records,
@@ -293,6 +299,20 @@ extern "C" int dfw_seg_match_block(int32_t* pixels, int32_t* records) {
   return 0;
 }
 
+extern "C" int dfw_seg_match_rounds(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t capG, int32_t max_records,
+                                    int32_t max_pairs, dfw_seg_sort_rounds* out) {
+  if (!out) return DFW_EINVAL;
+  if (int e = match_size_error(B, H, W, capP, capG, max_records, max_pairs)) return e;
+  const match_layout l = match_plan(B, (long long)H * W, max_records, max_pairs);
+  out->blocks = l.nblk;
+  out->block_scan = seg_scan_rounds(l.nblk);
+  out->passes = match_passes(capP, capG);
+  out->table_scan = seg_scan_rounds(seg_table_words(max_records));
+  out->offsets_scan = seg_scan_rounds(match_offsets(capP));
+  out->heads_scan = seg_scan_rounds(l.nhead);
+  return 0;
+}
+
 extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   if (!a || !a->pids || !a->gids || !a->pairs || !a->pair_off || !a->area || !a->match || !a->gmatch || !a->pq || !a->n ||
       !a->ws)
@@ -319,7 +339,7 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   const int nB = a->B, iHW = a->H * a->W, capP = a->capP, capG = a->capG, M = a->max_records, MP = a->max_pairs;
   const match_layout l = match_plan(nB, iHW, M, MP);
-  const int passes = seg_key_passes(((long long)capP + 1) * ((long long)capG + 1));
+  const int passes = match_passes(capP, capG);
   int32_t* ws = (int32_t*)a->ws;
   int32_t* blk = ws + l.blk;
   int32_t* hd = ws + l.hd;
@@ -361,7 +381,7 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   hipLaunchKernelGGL(match_inter_kernel, pgrid, dim3(256), 0, st, a->pairs, (const int32_t*)pfirst, (const int32_t*)plast,
                      a->area, (const int32_t*)a->n, MP, capP, capG);
   DFW_CHECK_LAUNCH();
-  if (int e = seg_scan_launch(st, a->pair_off, 1, nB, capP + 2)) return e;
+  if (int e = seg_scan_launch(st, a->pair_off, 1, nB, match_offsets(capP))) return e;
   hipLaunchKernelGGL(match_rule_kernel, pgrid, dim3(256), 0, st, (const int32_t*)a->pairs, (const int32_t*)a->area, rule,
                      a->match, a->gmatch, (unsigned long long*)a->pq, (const int32_t*)a->n, MP);
   DFW_CHECK_LAUNCH();

@@ -99,10 +99,27 @@ __global__ __launch_bounds__(256) void rle_transpose_kernel(const int32_t* ids, 
   }
 }
 
+// Words of run_off per image, the scan behind the emit.
+inline int rle_offsets(long long cap) { return (int)(cap + 1); }
+
 struct rle_layout {
   size_t blk, plane, rec[2], tab, words;   // offsets in words, for all B images
   int nblk, passes;
 };
+// The sizes dfw_seg_rle refuses, and its rounds query with it: DFW_EINVAL before DFW_ERANGE.
+static int rle_size_error(long long B, long long H, long long W, long long cap, long long max_runs, int order) {
+  if (B < 1 || H < 1 || W < 1 || cap < 1 || max_runs < 1) return DFW_EINVAL;
+  if (order != 0 && order != 1) return DFW_EINVAL;
+  // grid y / z carry B; H * W <= 2^30 keeps every position, HW itself and the padded block count in an int
+  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  // rows of runs are addressed in words: B * max_runs * 2 < 2^31, which also bounds max_runs below 2^30 and the digit
+  // table, 256 * nchunk <= 2^27 words an image, inside an int
+  if (B * max_runs * 2 > 0x7fffffffll) return DFW_ERANGE;
+  // seg_zero_launch counts run_off's B * (cap + 1) words in an int (so cap + 1 does not wrap either)
+  if (B * (cap + 1) > 0x7fffffffll) return DFW_ERANGE;
+  return 0;
+}
+
 static rle_layout rle_plan(long long B, long long HW, int cap, long long max_runs, int order) {
   rle_layout l;
   l.nblk = seg_blocks(HW);
@@ -134,17 +151,23 @@ extern "C" int dfw_seg_rle_block(int32_t* pixels, int32_t* records) {
   return 0;
 }
 
+extern "C" int dfw_seg_rle_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_runs, int32_t order,
+                                  dfw_seg_sort_rounds* out) {
+  if (!out) return DFW_EINVAL;
+  if (int e = rle_size_error(B, H, W, cap, max_runs, order)) return e;
+  const rle_layout l = rle_plan(B, (long long)H * W, cap, max_runs, order);
+  out->blocks = l.nblk;
+  out->block_scan = seg_scan_rounds(l.nblk);
+  out->passes = l.passes;
+  out->table_scan = seg_scan_rounds(seg_table_words(max_runs));
+  out->offsets_scan = seg_scan_rounds(rle_offsets(cap));
+  out->heads_scan = 0;
+  return 0;
+}
+
 extern "C" int dfw_seg_rle(const dfw_seg_rle_args* a, dfw_stream_t stream) {
   if (!a || !a->ids || !a->runs || !a->run_off || !a->nruns || !a->ws) return DFW_EINVAL;
-  if (a->B < 1 || a->H < 1 || a->W < 1 || a->cap < 1 || a->max_runs < 1) return DFW_EINVAL;
-  if (a->order != 0 && a->order != 1) return DFW_EINVAL;
-  // grid y / z carry B; H * W <= 2^30 keeps every position, HW itself and the padded block count in an int
-  if (a->H > 65535 || a->W > 65535 || (long long)a->H * a->W > (1ll << 30) || a->B > 65535) return DFW_ERANGE;
-  // rows of runs are addressed in words: B * max_runs * 2 < 2^31, which also bounds max_runs below 2^30 and the digit
-  // table, 256 * nchunk <= 2^27 words an image, inside an int
-  if ((long long)a->B * a->max_runs * 2 > 0x7fffffffll) return DFW_ERANGE;
-  // seg_zero_launch counts run_off's B * (cap + 1) words in an int (so cap + 1 does not wrap either)
-  if ((long long)a->B * ((long long)a->cap + 1) > 0x7fffffffll) return DFW_ERANGE;
+  if (int e = rle_size_error(a->B, a->H, a->W, a->cap, a->max_runs, a->order)) return e;
   if (a->ws_bytes < dfw_seg_rle_workspace_bytes(a->B, a->H, a->W, a->cap, a->max_runs, a->order)) return DFW_EWORKSPACE;
   const size_t idb = (size_t)a->B * a->H * a->W * 4;
   if (seg_overlap(a->ids, idb, a->runs, (size_t)a->B * a->max_runs * 8) ||
@@ -175,7 +198,7 @@ extern "C" int dfw_seg_rle(const dfw_seg_rle_args* a, dfw_stream_t stream) {
   hipLaunchKernelGGL(seg_emit_kernel<rle_src>, dim3(l.nblk, B), dim3(256), 0, st, src, (const int32_t*)blk, rec[0][0],
                      rec[0][1], rec[0][2], iHW, M);
   DFW_CHECK_LAUNCH();
-  if (int e = seg_scan_launch(st, a->run_off, 1, B, cap + 1)) return e;
+  if (int e = seg_scan_launch(st, a->run_off, 1, B, rle_offsets(cap))) return e;
   const int32_t* const key[2] = {rec[0][0], rec[1][0]};
   return seg_sort(st, key, ws + l.tab, a->nruns, 2, B, M, l.passes, nullptr, [&](int p) {   // the last pass lands in runs
     int32_t** s = rec[p & 1];

@@ -41,6 +41,11 @@ int seg_hist_launch(hipStream_t st, const int32_t* key, int32_t* tab, const int3
 
 inline int seg_blocks(long long HW) { return (int)((HW + 1 + kSegPix - 1) / kSegPix); }
 inline int seg_chunks(long long max_records) { return (int)((max_records + kSegRec - 1) / kSegRec); }
+// Trips of seg_scan_kernel's loop over the n words of one (plane, image): 256 threads scan 4 words each a round and carry
+// the sum into the next one.  The grid, (images, planes), adds nothing to it.
+inline int seg_scan_rounds(long long n) { return (int)((n + 1023) / 1024); }
+// Words of the digit table of one image that seg_sort scans per pass.
+inline int seg_table_words(long long max_records) { return 256 * seg_chunks(max_records); }
 // Digit passes for keys 0 .. keys - 1.
 inline int seg_key_passes(long long keys) {
   return keys <= (1ll << 8) ? 1 : keys <= (1ll << 16) ? 2 : keys <= (1ll << 24) ? 3 : 4;
@@ -133,7 +138,7 @@ int seg_sort(hipStream_t st, const int32_t* const (&key)[2], int32_t* tab, const
   const int nchunk = seg_chunks(max_records);
   for (int p = 0; p < passes; ++p) {
     if (int e = seg_hist_launch(st, key[p & 1], tab, n, stride, B, max_records, 8 * p)) return e;
-    if (int e = seg_scan_launch(st, tab, 1, B, 256 * nchunk)) return e;
+    if (int e = seg_scan_launch(st, tab, 1, B, seg_table_words(max_records))) return e;
     auto pl = pay(p);
     hipLaunchKernelGGL(seg_scatter_kernel<decltype(pl)>, dim3(nchunk, B), dim3(256), 0, st, key[p & 1], pl,
                        (const int32_t*)tab, n, stride, max_records, 8 * p);

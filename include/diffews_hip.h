@@ -822,6 +822,18 @@ int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream);
 size_t dfw_seg_components_workspace_bytes(int32_t B, int32_t H, int32_t W);
 /* the tile of the LDS pass (rows, columns): the shapes at which the kernels change path, for tests and docs */
 int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w);
+/* How often each loop of dfw_seg_components that carries a value from one round to the next would run for these
+ * arguments (version >= 117; host only, launches nothing, like dfw_gemm_kernel_name): computed by the expressions the
+ * launcher sizes its grids with, for tests and docs.  ws is only looked at for its alignment, which chooses the flatten
+ * path.  Errors as dfw_seg_components gives them for the same B, H, W and ws. */
+typedef struct {
+  int32_t blocks;           /* scan blocks of dfw_seg_components_tile() pixels per image */
+  int32_t merge;            /* grid-stride trips of the border-union kernel (0: one tile, no launch) */
+  int32_t flatten;          /* grid-stride trips of the flatten kernel on the path it takes */
+  int32_t flatten_vector;   /* 1: four pixels a thread (H * W a multiple of 4 and a 16-byte aligned area plane), else 0 */
+  int32_t scan;             /* rounds of 256 block sums of the one-workgroup scan */
+} dfw_seg_components_rounds_out;
+int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const void* ws, dfw_seg_components_rounds_out* out);
 
 /*
  * Run-length encoding of labelled objects (version >= 115): the shape of every object of an id map, normally the one
@@ -870,6 +882,20 @@ size_t dfw_seg_rle_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap,
 /* positions one scan block covers, run records one sort chunk covers: the sizes at which the kernels change path, for
  * tests and docs */
 int dfw_seg_rle_block(int32_t* pixels, int32_t* records);
+/* How often each one-workgroup scan of dfw_seg_rle / dfw_seg_match would go round, 1024 words a round with the sum
+ * carried into the next (version >= 117; host only, launches nothing): computed by the expressions the launchers use,
+ * for tests and docs.  Errors: DFW_EINVAL for a null out, then the size errors of dfw_seg_rle / dfw_seg_match
+ * themselves, in their order (DFW_EINVAL before DFW_ERANGE); pointers, workspace and overlap are not part of it. */
+typedef struct {
+  int32_t blocks;         /* scan blocks of `pixels` positions per image, position H * W included */
+  int32_t block_scan;     /* the scan of the block sums: (kept, found) */
+  int32_t passes;         /* digit passes of the sort, each with one table scan */
+  int32_t table_scan;     /* the scan of the digit table, 256 words per chunk of `records` */
+  int32_t offsets_scan;   /* the scan of run_off (cap + 1 words) or pair_off (capP + 2 words) */
+  int32_t heads_scan;     /* dfw_seg_match only: the scan of the heads and lengths per chunk; 0 for dfw_seg_rle */
+} dfw_seg_sort_rounds;
+int dfw_seg_rle_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_runs, int32_t order,
+                       dfw_seg_sort_rounds* out);
 
 /*
  * Matching of predicted objects to ground-truth objects (version >= 116): the object-level score behind two id maps,
@@ -950,6 +976,9 @@ size_t dfw_seg_match_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t ca
 /* positions one scan block covers, records one sort chunk covers: the sizes at which the kernels change path, for tests
  * and docs */
 int dfw_seg_match_block(int32_t* pixels, int32_t* records);
+/* dfw_seg_rle_rounds for dfw_seg_match (version >= 117) */
+int dfw_seg_match_rounds(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t capG, int32_t max_records, int32_t max_pairs,
+                         dfw_seg_sort_rounds* out);
 
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =

@@ -36,6 +36,23 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert h.dfw_gemm(ctypes.byref(a), None) == -2            # DFW_ESHAPE: K not a multiple of 64
     f = _lib.FsaArgs()
     assert h.dfw_fsa_attention(ctypes.byref(f), None) == -1
+    # the rounds queries of the object stages launch nothing either
+    assert h.dfw_version() >= 117
+    i32 = ctypes.c_int32
+    assert _lib.SYMBOLS["dfw_seg_components_rounds"] == (i32, [i32] * 3 + [ctypes.c_void_p, ctypes.POINTER(_lib.SegComponentsRounds)])
+    assert _lib.SYMBOLS["dfw_seg_rle_rounds"] == (i32, [i32] * 6 + [ctypes.POINTER(_lib.SegSortRounds)])
+    assert _lib.SYMBOLS["dfw_seg_match_rounds"] == (i32, [i32] * 7 + [ctypes.POINTER(_lib.SegSortRounds)])
+    c, r = _lib.SegComponentsRounds(), _lib.SegSortRounds()
+    assert h.dfw_seg_components_rounds(1, 32, 64, 16, None) == -1 and h.dfw_seg_components_rounds(1, 32, 64, None, ctypes.byref(c)) == -1
+    assert h.dfw_seg_components_rounds(1, 0, 64, 16, ctypes.byref(c)) == -1
+    assert h.dfw_seg_components_rounds(1, 32, 64, 16, ctypes.byref(c)) == 0
+    assert (c.blocks, c.merge, c.flatten, c.flatten_vector, c.scan) == (1, 0, 1, 1, 1)
+    assert h.dfw_seg_rle_rounds(1, 32, 64, 255, 2048, 1, None) == -1 and h.dfw_seg_rle_rounds(1, 32, 64, 0, 2048, 1, ctypes.byref(r)) == -1
+    assert h.dfw_seg_rle_rounds(1, 32, 64, 255, 2048, 1, ctypes.byref(r)) == 0
+    assert (r.blocks, r.block_scan, r.passes, r.table_scan, r.offsets_scan, r.heads_scan) == (2, 1, 1, 1, 1, 0)
+    assert h.dfw_seg_match_rounds(1, 32, 64, 255, 255, 2048, 0, ctypes.byref(r)) == -1
+    assert h.dfw_seg_match_rounds(1, 32, 64, 255, 255, 8193, 64, ctypes.byref(r)) == 0
+    assert (r.blocks, r.block_scan, r.passes, r.table_scan, r.offsets_scan, r.heads_scan) == (2, 1, 2, 2, 1, 1)
 
 
 def test_struct_layouts_match_header():
@@ -48,7 +65,8 @@ def test_struct_layouts_match_header():
                        ("dfw_groupnorm_bwd_args", _lib.GroupNormBwdArgs), ("dfw_layernorm_bwd_args", _lib.LayerNormBwdArgs),
                        ("dfw_fsa_bwd_args", _lib.FsaBwdArgs), ("dfw_xattn_bwd_args", _lib.XattnBwdArgs),
                        ("dfw_attn_bwd_args", _lib.AttnBwdArgs), ("dfw_adamw_args", _lib.AdamWArgs), ("dfw_image_args", _lib.ImageArgs),
-                       ("dfw_vattn_args", _lib.VattnArgs), ("dfw_config", _lib.Config)):
+                       ("dfw_vattn_args", _lib.VattnArgs), ("dfw_config", _lib.Config),
+                       ("dfw_seg_components_rounds_out", _lib.SegComponentsRounds), ("dfw_seg_sort_rounds", _lib.SegSortRounds)):
         body = re.search(r"typedef struct \{([^{}]*)\}\s*" + cname + ";", hdr).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []
@@ -67,7 +85,7 @@ def test_sizeof_structs_against_compiler(tmp_path):
     names = ["dfw_gemm_args", "dfw_fsa_args", "dfw_xattn_args", "dfw_groupnorm_args", "dfw_layernorm_args",
              "dfw_conv_small_args", "dfw_gemm_tn_args", "dfw_groupnorm_bwd_args", "dfw_layernorm_bwd_args",
              "dfw_fsa_bwd_args", "dfw_xattn_bwd_args", "dfw_attn_bwd_args", "dfw_adamw_args", "dfw_image_args", "dfw_vattn_args",
-             "dfw_config"]
+             "dfw_config", "dfw_seg_components_rounds_out", "dfw_seg_sort_rounds"]
     src.write_text('#include <stdio.h>\n#include "diffews_hip.h"\nint main(){' +
                    "".join(f'printf("%zu ", sizeof({n}));' for n in names) + 'return 0;}\n')
     exe = tmp_path / "sz"
@@ -77,7 +95,7 @@ def test_sizeof_structs_against_compiler(tmp_path):
                                                 _lib.LayerNormArgs, _lib.ConvSmallArgs, _lib.GemmTnArgs,
                                                 _lib.GroupNormBwdArgs, _lib.LayerNormBwdArgs, _lib.FsaBwdArgs,
                                                 _lib.XattnBwdArgs, _lib.AttnBwdArgs, _lib.AdamWArgs, _lib.ImageArgs, _lib.VattnArgs,
-                                                _lib.Config)]
+                                                _lib.Config, _lib.SegComponentsRounds, _lib.SegSortRounds)]
 
 
 def test_library_reads_nothing_from_the_environment():
