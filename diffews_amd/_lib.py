@@ -128,6 +128,12 @@ class SegMatchArgs(C.Structure):
                 ("max_records", _i32), ("max_pairs", _i32), ("num", _i32), ("den", _i32)]
 
 
+class SegScoresArgs(C.Structure):
+    _fields_ = [("ids", _vp), ("labels", _vp), ("seg_u8", _vp), ("planes", _vp), ("planes_host", _vp), ("scores", _vp),
+                ("ws", _vp), ("ws_bytes", _sz), ("B", _i32), ("H", _i32), ("W", _i32), ("cap", _i32), ("nlabels", _i32),
+                ("P", _i32)]
+
+
 class SegComponentsRounds(C.Structure):
     _fields_ = [("blocks", _i32), ("merge", _i32), ("flatten", _i32), ("flatten_vector", _i32), ("scan", _i32)]
 
@@ -328,6 +334,9 @@ SYMBOLS = {
     "dfw_seg_match_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_match_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "dfw_seg_match_rounds": (_i32, [_i32] * 7 + [C.POINTER(SegSortRounds)]),
+    "dfw_seg_scores": (_i32, [C.POINTER(SegScoresArgs), _vp]),
+    "dfw_seg_scores_workspace_bytes": (_sz, [_i32, _i32]),
+    "dfw_seg_scores_block": (_i32, [C.POINTER(_i32)]),
 }
 
 _lib = None

@@ -157,3 +157,61 @@ def panoptic_quality(pq):
     q = sq * rq
     mean = lambda v: float(v[seen].mean()) if bool(seen.any()) else 0.0  # noqa: E731
     return dict(pq=q, sq=sq, rq=rq, mean_pq=mean(q), mean_sq=mean(sq), mean_rq=mean(rq))
+
+
+_COCO_THRESHOLDS = tuple((n, 20) for n in range(10, 20))      # IoU 0.50, 0.55, .., 0.95
+
+
+def _detection_rows(dets):
+    """An array [k, 5], or lists of them nested in any depth, -> one int64 array in order."""
+    import numpy as np
+    if isinstance(dets, (list, tuple)):
+        parts = [_detection_rows(d) for d in dets]
+        return np.concatenate(parts) if parts else np.zeros((0, 5), np.int64)
+    return np.asarray(dets, dtype=np.int64).reshape(-1, 5)
+
+
+def average_precision(dets, npos, thresholds=_COCO_THRESHOLDS):
+    """Average precision per class over a whole dataset.  dets: objects.detections_to_host's rows (class, sum, n, inter,
+    union) -- an int64 array [k, 5], or lists of them (over images, over calls, nested), concatenated in order; npos int64
+    [nlabels + 1], the ground-truth objects per class (the sum of detections_to_host's npos over the dataset; class 0
+    unused).  thresholds: IoU thresholds as integer pairs (num, den), COCO's 0.50:0.05:0.95 by default; each needs
+    2 * num >= den (the match table holds one partner, found above 1/2), ValueError otherwise.
+
+    Per class with npos > 0 and per threshold: the class' detections are sorted by their score sum / n (the float64
+    quotient of two exact integers; sum / (765 n) ranks the same) descending and stably, so ties keep image and then
+    object order; a detection is a TP when it has a partner and inter * den > num * union in integers -- STRICTLY above,
+    the matching rule of objects.match_objects, where COCO counts IoU >= threshold; precision TP / rank is made
+    non-increasing from the right; it is sampled at the recalls k / 100, k = 0..100, at the first rank whose recall reaches
+    the sample (searchsorted, side="left"), 0 beyond the last recall; AP is the mean of the 101 samples (their exactly
+    rounded sum over 101).  A class without a detection has AP 0.  No area ranges and no maxDets.
+
+    Returns dict(ap float64 [nlabels + 1, T], NaN for classes without positives; map = the nanmean over all of it, as the exactly
+    rounded sum over the count (NaN when no class has a positive); ap50 = the column of (10, 20), or None without that threshold; thresholds)."""
+    import math
+    import numpy as np
+    thresholds = tuple((int(a), int(b)) for a, b in thresholds)
+    for num, den in thresholds:
+        if num < 1 or den < num or 2 * num < den:
+            raise ValueError(f"average_precision: the threshold {num}/{den} is not in [1/2, 1]")
+    rows = _detection_rows(dets)
+    npos = np.asarray(npos, dtype=np.int64).reshape(-1)
+    ap = np.full((npos.shape[0], len(thresholds)), np.nan)
+    samples = np.arange(101) / 100.0
+    for c in range(1, npos.shape[0]):
+        if npos[c] <= 0:
+            continue
+        d = rows[rows[:, 0] == c]
+        score = d[:, 1].astype(np.float64) / d[:, 2].astype(np.float64)
+        d = d[np.argsort(-score, kind="stable")]
+        rank = np.arange(1, d.shape[0] + 1, dtype=np.float64)
+        for t, (num, den) in enumerate(thresholds):
+            tp = np.cumsum((d[:, 4] > 0) & (d[:, 3] * den > num * d[:, 4])).astype(np.float64)
+            recall, prec = tp / float(npos[c]), tp / rank
+            prec = np.maximum.accumulate(prec[::-1])[::-1]
+            at = np.searchsorted(recall, samples, side="left")
+            q = np.where(at < d.shape[0], prec[np.minimum(at, max(d.shape[0] - 1, 0))], 0.0) if d.shape[0] else np.zeros(101)
+            ap[c, t] = math.fsum(q.tolist()) / 101.0
+    vals = ap[~np.isnan(ap)].tolist()
+    ap50 = ap[:, thresholds.index((10, 20))] if (10, 20) in thresholds else None
+    return dict(ap=ap, map=math.fsum(vals) / len(vals) if vals else float("nan"), ap50=ap50, thresholds=thresholds)

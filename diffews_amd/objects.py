@@ -4,7 +4,8 @@ minimum-area filter, and the filtered labels re-counted against a ground truth (
 Every segmentation route ends in a label map -- `labels` of segment_classes / segment_candidates / segment_tiled, `pred`
 of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own sizes -- and label_objects turns it into
 "which objects, how many, how big, where" without bringing the map to the host.  Nothing here synchronises except
-objects_to_host, which copies the two small tables (n and stats) once, runs_to_host and matches_to_host.
+objects_to_host, which copies the two small tables (n and stats) once, runs_to_host, matches_to_host, scores_to_host and
+detections_to_host.
 
 object_runs adds each object's SHAPE: the run-length encoding of the id map (ops.seg_rle), in row or column (COCO) order,
 still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the host and into the usual forms.
@@ -12,6 +13,12 @@ still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the 
 match_objects says whether the objects are RIGHT: the objects of a prediction against those of a ground truth (ops.seg_match)
 -- the shared pixels of every pair, the areas, a one-to-one matching on IoU and (TP, FP, FN, sum of IoU) per class, which
 metrics.panoptic_quality turns into PQ, SQ and RQ; matches_to_host brings the tables to the host.
+
+object_scores says how SURE the model is of each object: the decoder's uint8 mask planes reduced over the id map
+(ops.seg_scores) into (sum, counted pixels, min, max) per object, exact integers; planes_for_classes / planes_for_binary /
+planes_for_candidates build the table that says which planes a label of an image reads.  scores_to_host brings the table
+to the host, coco_results turns the three host tables into COCO result records, and detections_to_host gathers what
+metrics.average_precision ranks.
 """
 import numpy as np
 import torch
@@ -413,3 +420,222 @@ def matches_to_host(m):
     if single:
         out = {k: v[0] for k, v in out.items()}
     return out, truncated
+
+
+# ------------------------------------------------------------------------------------------------ per-object confidence
+
+def planes_for_classes(N, B):
+    """The plane table of N-way class-major planes [N, B, 3, H, W] (segment_classes; dense segment_tiled with B = 1): int32
+    [B, N + 1], label l of image b reads plane group (l - 1) * B + b; entry 0 is unused (-1)."""
+    N, B = int(N), int(B)
+    if N < 1 or B < 1:
+        raise ValueError("planes_for_classes: N and B must be at least 1")
+    t = torch.full((B, N + 1), -1, dtype=torch.int32)
+    t[:, 1:] = (torch.arange(N, dtype=torch.int32) * B)[None, :] + torch.arange(B, dtype=torch.int32)[:, None]
+    return t
+
+
+def planes_for_binary(B):
+    """The plane table of the binary routes' planes [B, 3, H, W]: int32 [B, 2], label 1 of image b reads plane group b."""
+    return planes_for_classes(1, B)
+
+
+def planes_for_candidates(candidates, nlabels, labels="global"):
+    """The plane table of entry-major candidate planes [E, 3, H, W] (segment_candidates), from the lists that call takes:
+    `candidates` is one sequence of set indices per query.  Entries are numbered as the route numbers them -- queries in
+    order, each list in ascending set index (the route sorts it) -- and entry e of query i is read by label 1 + set index
+    (labels="global", the route's "set") or 1 + position in the query's sorted list (labels="local").  Returns int32
+    [b, nlabels + 1], -1 for a label the query does not list; a query may have no candidate.  ValueError for a label above
+    nlabels, a set named twice by one query or another `labels`."""
+    if labels not in ("global", "set", "local"):
+        raise ValueError(f"planes_for_candidates: labels is 'global' or 'local', not {labels!r}")
+    nlabels = int(nlabels)
+    if nlabels < 1:
+        raise ValueError("planes_for_candidates: nlabels must be at least 1")
+    lists = [sorted(int(c) for c in (cs.tolist() if isinstance(cs, torch.Tensor) else cs)) for cs in candidates]
+    t = torch.full((len(lists), nlabels + 1), -1, dtype=torch.int32)
+    e = 0
+    for i, cs in enumerate(lists):
+        if len(set(cs)) != len(cs) or (cs and cs[0] < 0):
+            raise ValueError(f"planes_for_candidates: query {i} names a set twice or a negative one ({cs})")
+        for pos, c in enumerate(cs):
+            lab = 1 + (pos if labels == "local" else c)
+            if lab > nlabels:
+                raise ValueError(f"planes_for_candidates: query {i} needs label {lab}, the table ends at {nlabels}")
+            t[i, lab] = e
+            e += 1
+    return t
+
+
+class ScoreBuffers:
+    """Everything one object_scores call of a size writes, allocated once: scores int64 [B, cap, 4], the workspace, and the
+    plane table twice -- planes_host, a pinned int32 [B, nlabels + 1] mirror, and planes, its device copy.  The shape of
+    the maps is not part of it: the buffers depend on B, cap and nlabels only."""
+
+    def __init__(self, B, cap, nlabels, device="cuda"):
+        self.B, self.cap, self.nlabels = int(B), int(cap), int(nlabels)
+        if min(self.B, self.cap) < 1 or not 1 <= self.nlabels <= 254:
+            raise ValueError("ScoreBuffers: B and cap must be at least 1 and nlabels in 1..254")
+        nbytes = ops.seg_scores_workspace(self.B, self.cap)
+        if nbytes == 0:
+            raise ValueError(f"seg_scores refuses these sizes: {self.B} images, {self.cap} objects")
+        dev = torch.device(device)
+        self.scores = torch.empty(self.B, self.cap, 4, dtype=torch.int64, device=dev)
+        self.device = self.scores.device
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.planes = torch.empty(self.B, self.nlabels + 1, dtype=torch.int32, device=dev)
+        self.planes_host = torch.empty(self.B, self.nlabels + 1, dtype=torch.int32).pin_memory()
+        self._copied = None     # the event behind the last copy out of planes_host
+
+    def stage(self, table):
+        """table -> planes_host -> planes, the copy on the current stream.  Only the previous copy out of the mirror is
+        waited for, on the host, before the mirror is overwritten; nothing else synchronises."""
+        if self._copied is not None:
+            self._copied.synchronize()
+        self.planes_host.copy_(table)
+        self.planes.copy_(self.planes_host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record(torch.cuda.current_stream(self.device))
+
+
+def _plane_table(planes, what="planes"):
+    t = torch.as_tensor(planes)
+    if t.is_cuda or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError(f"object_scores: {what} must be an integer HOST tensor or a nested list [B, nlabels + 1]")
+    return t.to(torch.int32)
+
+
+def _scores_one(ids, labels, cap, seg_u8, table, buffers):
+    squeeze = ids.dim() == 2
+    if squeeze:
+        ids, labels = ids[None], (labels[None] if labels.dim() == 2 else labels)
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
+        raise ValueError("object_scores takes int32 device ids [H, W] or [B, H, W], or a list of [h, w] maps")
+    if labels.dtype != torch.uint8 or labels.shape != ids.shape:
+        raise ValueError("object_scores: the labels must be uint8 and shaped like the ids")
+    B, H, W = ids.shape
+    if (not isinstance(seg_u8, torch.Tensor) or seg_u8.dtype != torch.uint8 or seg_u8.dim() < 3
+            or tuple(seg_u8.shape[-3:]) != (3, H, W) or not seg_u8.is_contiguous() or seg_u8.device != ids.device):
+        raise ValueError(f"object_scores: seg_u8 must be a contiguous uint8 tensor [..., 3, {H}, {W}] on {ids.device}")
+    if table.dim() != 2 or table.shape[0] != B or not 2 <= table.shape[1] <= 255:
+        raise ValueError(f"object_scores: the plane table must be [B, nlabels + 1] = [{B}, 2..255], got {tuple(table.shape)}")
+    nlabels = table.shape[1] - 1
+    if buffers is None:
+        buffers = ScoreBuffers(B, cap, nlabels, ids.device)
+    elif (buffers.B, buffers.cap, buffers.nlabels) != (B, cap, nlabels) or buffers.device != ids.device:
+        raise ValueError(f"buffers were made for {buffers.B} images, {buffers.cap} objects, {buffers.nlabels} labels on "
+                         f"{buffers.device}; the call has {B} images, {cap} objects, {nlabels} labels on {ids.device}")
+    buffers.stage(table)
+    ops.seg_scores(ids.contiguous(), labels.contiguous(), seg_u8.view(-1, 3, H, W), buffers.planes, buffers.planes_host,
+                   buffers.scores, buffers.ws)
+    r = dict(scores=buffers.scores, planes=buffers.planes)
+    if squeeze:
+        r = {k: v[0] for k, v in r.items()}
+    return r
+
+
+def object_scores(o, seg_u8, planes, buffers=None):
+    """How sure the decoder is of every object: its mask planes reduced over the objects of a label map.  o: a label_objects
+    result -- its ids, its (filtered) labels and the rows of its stats table (cap) are used.  seg_u8: any contiguous uint8
+    device tensor whose last three axes are [3, H, W], viewed as P plane groups [P, 3, H, W].  planes: an int32 host tensor
+    or nested list [B, nlabels + 1], the plane group that label l of image b reads, -1 for none (planes_for_classes /
+    planes_for_binary / planes_for_candidates build it); it is staged in a pinned mirror and a device copy held by the
+    buffers, and copied again on every call.
+
+    A pixel is counted when its id lies in 1..cap, its label l in 1..nlabels and planes[b][l] in 0..P-1; its value is the
+    sum of the three bytes of that plane group at the pixel, 0..765.  Returns dict(scores, planes) on the device: scores
+    int64 [.., cap, 4] = (sum, counted pixels, min, max) of object id in row id - 1 -- zeros for an object without a
+    counted pixel -- and planes, the device table the call read.  A [H, W] result gives the same without the batch axis.
+    A list result (native sizes) is handled with ONE CALL PER ITEM: seg_u8 is then a list of [.., 3, h_i, w_i] tensors,
+    planes one [1, nlabels + 1] table for every item or a list of them, buffers a list of ScoreBuffers or None, and every
+    value of the result is a list.  buffers: a ScoreBuffers of this B, cap and nlabels, reused call after call (the result
+    aliases it).  Three launches and one small copy per call, no host synchronisation."""
+    ids, labels, stats = o["ids"], o["labels"], o["stats"]
+    if isinstance(ids, (list, tuple)):
+        k = len(ids)
+        if not isinstance(seg_u8, (list, tuple)) or len(seg_u8) != k:
+            raise ValueError("object_scores: one seg_u8 tensor per id map")
+        if isinstance(planes, (list, tuple)) and len(planes) == k and all(_plane_table(p).dim() == 2 for p in planes):
+            tabs = [_plane_table(p) for p in planes]
+        else:
+            tabs = [_plane_table(planes)] * k
+        bufs = buffers if buffers is not None else [None] * k
+        if len(bufs) != k:
+            raise ValueError("object_scores: one buffers entry per id map")
+        per = [_scores_one(ids[i], labels[i], stats[i].shape[-2], seg_u8[i], tabs[i], bufs[i]) for i in range(k)]
+        return {key: [p[key] for p in per] for key in ("scores", "planes")}
+    return _scores_one(ids, labels, stats.shape[-2], seg_u8, _plane_table(planes), buffers)
+
+
+def scores_to_host(s):
+    """object_scores' result -> dict(sum, n, min, max, mean) of numpy arrays [B, cap] ([cap] for a [H, W] result; a list of
+    such dicts for a list result), with ONE synchronising copy (per item for a list result).  sum, n, min and max are the
+    int64 columns of the table; mean = sum / (765 * n) as float64, the object's confidence in 0..1, and 0 where n == 0."""
+    if isinstance(s["scores"], (list, tuple)):
+        return [scores_to_host({"scores": t}) for t in s["scores"]]
+    t = s["scores"].cpu().numpy()                                    # the one copy
+    out = dict(sum=t[..., 0], n=t[..., 1], min=t[..., 2], max=t[..., 3])
+    out["mean"] = _mean_score(out["sum"], out["n"])
+    return out
+
+
+def _mean_score(total, n):
+    total, n = np.asarray(total, dtype=np.int64), np.asarray(n, dtype=np.int64)
+    return np.where(n > 0, total.astype(np.float64) / np.maximum(765 * n, 1).astype(np.float64), 0.0)
+
+
+def coco_results(o_host, runs_host, scores_host, image_id, category_ids, h, w):
+    """COCO result records of ONE image from its three host tables: o_host, the image's list from objects_to_host;
+    runs_host, the image's list from runs_to_host (column order); scores_host, the image's dict from scores_to_host.
+    Returns, for the objects 1..min(n, cap) in id order, a list of {"image_id", "category_id" = category_ids[label - 1],
+    "segmentation" = runs_to_coco(runs, h, w), "bbox" = [x, y, width, height] from the half-open box, "area", "score" = the
+    mean above}.  Host only: no copy of its own."""
+    out = []
+    for k, (label, area, (y0, x0, y1, x1), _first) in enumerate(o_host):
+        runs = runs_host[k] if k < len(runs_host) else np.zeros((0, 2), np.int32)
+        total, n = int(scores_host["sum"][k]), int(scores_host["n"][k])
+        out.append({"image_id": image_id, "category_id": category_ids[label - 1],
+                    "segmentation": runs_to_coco(runs, h, w), "bbox": [int(x0), int(y0), int(x1 - x0), int(y1 - y0)],
+                    "area": int(area), "score": float(_mean_score(total, n))})
+    return out
+
+
+def detections_to_host(o, s, m):
+    """What metrics.average_precision ranks, from a label_objects result o, its object_scores s and its match_objects m
+    against the ground truth, with ONE synchronising copy (per item for list results) of n, column 0 of stats, scores, and
+    m's match, area and pq.  m must have been made with iou=(1, 2): its match table then holds every partner above 1/2, so
+    every stricter threshold is decided from (inter, union) alone.
+
+    Returns (dets, npos).  dets: per image an int64 array [k, 5] = (class, sum, n, inter, union) of every object p in id
+    order that has n > 0 counted score pixels and a counted pixel in m (area[p] > 0), inter and union 0 without a partner;
+    one array for a [H, W] result, a list over the images otherwise.  npos: int64 [nlabels + 1] = TP + FN of m's pq, summed
+    over the images: the ground-truth objects of every class."""
+    if isinstance(o["n"], (list, tuple)):
+        per = [detections_to_host({k: v[i] for k, v in o.items()}, {k: v[i] for k, v in s.items()},
+                                  {k: v[i] for k, v in m.items()}) for i in range(len(o["n"]))]
+        return [p[0] for p in per], np.sum([p[1] for p in per], axis=0)
+    single = o["n"].dim() == 1
+    lift = (lambda t: t[None]) if single else (lambda t: t)
+    n, stats, scores, match, area, pq = (lift(t) for t in (o["n"], o["stats"], s["scores"], m["match"], m["area"], m["pq"]))
+    B, cap = stats.shape[:2]
+    if scores.shape[:2] != (B, cap) or match.shape[:2] != (B, cap):
+        raise ValueError("detections_to_host: o, s and m must describe the same images and the same number of objects")
+    parts = [n.reshape(-1), stats[:, :, 0].reshape(-1), match.reshape(-1), area[:, 1:cap + 1].reshape(-1),
+             scores.reshape(-1).view(torch.int32), pq.reshape(-1).view(torch.int32)]
+    both = torch.cat(parts).cpu().numpy()                           # the one copy
+    cut = np.cumsum([p.numel() for p in parts])
+    n, cls, match, area = both[:cut[0]].reshape(B, 2), both[cut[0]:cut[1]].reshape(B, cap), \
+        both[cut[1]:cut[2]].reshape(B, cap, 3), both[cut[2]:cut[3]].reshape(B, cap)
+    scores = both[cut[3]:cut[4]].view(np.int64).reshape(B, cap, 4)
+    pq = both[cut[4]:].view(np.int64).reshape(B, -1, 4)
+    dets = []
+    for b in range(B):
+        k = min(int(n[b, 0]), cap)
+        keep = (scores[b, :k, 1] > 0) & (area[b, :k] > 0)
+        paired = match[b, :k, 0] > 0
+        rows = np.stack([cls[b, :k].astype(np.int64), scores[b, :k, 0], scores[b, :k, 1],
+                         np.where(paired, match[b, :k, 1], 0).astype(np.int64),
+                         np.where(paired, match[b, :k, 2], 0).astype(np.int64)], axis=1)
+        dets.append(rows[keep])
+    npos = (pq[:, :, 0] + pq[:, :, 2]).sum(axis=0)
+    return (dets[0] if single else dets), npos

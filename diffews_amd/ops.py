@@ -1185,3 +1185,49 @@ def seg_match(pids, gids, pairs, pair_off, area, match, gmatch, pq, n, ws, max_r
     if not pids.is_cuda:
         raise ValueError("seg_match: pids and every buffer must be device tensors")
     L.check(L.lib().dfw_seg_match(C.byref(a), _stream()), "dfw_seg_match")
+
+
+def seg_scores_workspace(B, cap):
+    """Bytes of seg_scores' workspace for B images and objects 1..cap; 0 for sizes seg_scores refuses."""
+    return int(L.lib().dfw_seg_scores_workspace_bytes(int(B), int(cap)))
+
+
+def seg_scores_block():
+    """Positions one workgroup of seg_scores covers: the size at which its kernel changes path."""
+    p = C.c_int32()
+    L.check(L.lib().dfw_seg_scores_block(C.byref(p)), "dfw_seg_scores_block")
+    return p.value
+
+
+def seg_scores(ids, labels, seg_u8, planes, planes_host, scores, ws):
+    """Per-object confidence, on caller-owned buffers only (objects.ScoreBuffers holds a set): ids int32 [B, H, W] and
+    labels uint8 [B, H, W], normally seg_components' ids and filtered map; seg_u8 uint8 [P, 3, H, W], P plane groups of
+    three channels; planes int32 [B, nlabels + 1] on the device, the plane group of every label of every image (-1: none;
+    entry 0 is never read), and planes_host, its host mirror (a CPU tensor, pinned or not), which is what the call
+    validates -- the kernel reads the device table when it runs and treats an entry outside 0..P-1 as "not counted".  A
+    pixel is counted when 1 <= id <= cap, its label l lies in 1..nlabels and planes[b, l] in 0..P-1; its value is the sum
+    of the three bytes of that plane group at the pixel, 0..765.  Writes scores int64 [B, cap, 4] = (sum, counted pixels,
+    min, max) of object id in row id - 1, zeros for a row without a counted pixel; cap and nlabels are the buffers' shapes.
+    ws: a uint8 buffer of at least seg_scores_workspace(B, cap) bytes, which needs no initialisation.  Three launches, no
+    host synchronisation, no memset node: the call can be captured.  Returns None."""
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("seg_scores: ids must be a contiguous int32 device tensor [B, H, W]")
+    B, H, W = ids.shape
+    dev = ids.device
+    if scores.dim() != 3 or planes.dim() != 2 or seg_u8.dim() != 4:
+        raise ValueError("seg_scores: scores must be int64 [B, cap, 4], planes int32 [B, nlabels + 1] and seg_u8 uint8 "
+                         "[P, 3, H, W]")
+    cap, nl1, P = scores.shape[1], planes.shape[1], seg_u8.shape[0]
+
+    def own(name, t, dtype, shape, device=dev):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != device or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_scores: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
+        return t.data_ptr()
+    a = L.SegScoresArgs()
+    a.ids, a.labels = ids.data_ptr(), own("labels", labels, torch.uint8, (B, H, W))
+    a.seg_u8, a.planes = own("seg_u8", seg_u8, torch.uint8, (P, 3, H, W)), own("planes", planes, torch.int32, (B, nl1))
+    a.planes_host = own("planes_host", planes_host, torch.int32, (B, nl1), torch.device("cpu"))
+    a.scores = own("scores", scores, torch.int64, (B, cap, 4))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.B, a.H, a.W, a.cap, a.nlabels, a.P = B, H, W, cap, nl1 - 1, P
+    L.check(L.lib().dfw_seg_scores(C.byref(a), _stream()), "dfw_seg_scores")

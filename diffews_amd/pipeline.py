@@ -1025,6 +1025,52 @@ class MarigoldPipelineRGBLatentNoise:
         from .objects import match_objects
         return match_objects(o_pred, o_gt, **kw)
 
+    def object_scores(self, result, o, candidates=None, labels="global", key=None, buffers=None):
+        """How sure the model is of every object of pipe.objects' result o: objects.object_scores on the mask planes the
+        route's `result` kept and the plane table that belongs to them --
+          segment_queries / run_episodes / segment_routed   seg_u8 [b, 3, H, W], objects.planes_for_binary(b)
+          segment_classes                                   seg_u8 [N, b, 3, H, W], objects.planes_for_classes(N, b)
+          segment_candidates                                seg_u8 [E, 3, H, W], objects.planes_for_candidates of
+                                                            `candidates` (the lists the route was given) and `labels`
+                                                            ("global": label = 1 + set index, the route's "set"; "local")
+          dense segment_tiled                               seg_u8 [N, 3, h, w], objects.planes_for_classes(N, 1)
+          the binary native route                           result["native"]["seg_u8"], a list of [3, h_i, w_i], one call
+                                                            per item with objects.planes_for_binary(1)
+        key (optional): the map o was made from, as given to pipe.objects; KeyError when the result holds none.
+        ValueError, naming the reason, for the routes that keep no planes at the label map's size: the N-way and candidate
+        native routes (their planes stay at the processing size) and segment_tiled with candidates (the merged image is
+        never built); and for a candidate result without `candidates`.  Returns objects.object_scores' dict;
+        objects.scores_to_host brings it to the host."""
+        from . import objects as ob
+        nat = result.get("native")
+        src = nat or result
+        if key is not None and src.get(key) is None:
+            raise KeyError(f"the result holds no {key!r} map (binary routes: key='pred')")
+        if nat:
+            if nat.get("labels") is not None:
+                raise ValueError("object_scores: the N-way and candidate native routes keep their planes at the processing "
+                                 "size only; there are no planes at the native label maps' sizes to score")
+            if nat.get("seg_u8") is None:
+                raise ValueError("object_scores: the native result holds no seg_u8 planes (ops.seg_native want_u8=False)")
+            return ob.object_scores(o, [p.contiguous() for p in nat["seg_u8"]], ob.planes_for_binary(1), buffers)
+        seg_u8 = result.get("seg_u8")
+        if "plan" in result:
+            if seg_u8 is None:
+                raise ValueError("object_scores: segment_tiled with candidates never builds the merged planes; there is "
+                                 "nothing at the label map's size to score")
+            return ob.object_scores(o, seg_u8, ob.planes_for_classes(seg_u8.shape[0], 1), buffers)
+        if seg_u8 is None:
+            raise ValueError("object_scores: the result holds no seg_u8 planes")
+        if "entries" in result:
+            if candidates is None:
+                raise ValueError("object_scores: a segment_candidates result needs candidates=, the lists the route was given")
+            lists = [sorted(int(c) for c in (cs.tolist() if isinstance(cs, torch.Tensor) else cs)) for cs in candidates]
+            nlabels = max([len(cs) if labels == "local" else 1 + max(cs, default=0) for cs in lists] + [1])
+            return ob.object_scores(o, seg_u8, ob.planes_for_candidates(lists, nlabels, labels), buffers)
+        if seg_u8.dim() == 5:
+            return ob.object_scores(o, seg_u8, ob.planes_for_classes(seg_u8.shape[0], seg_u8.shape[1]), buffers)
+        return ob.object_scores(o, seg_u8, ob.planes_for_binary(seg_u8.shape[0]), buffers)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

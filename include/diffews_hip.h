@@ -980,6 +980,69 @@ int dfw_seg_match_block(int32_t* pixels, int32_t* records);
 int dfw_seg_match_rounds(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t capG, int32_t max_records, int32_t max_pairs,
                          dfw_seg_sort_rounds* out);
 
+/*
+ * Per-object confidence (version >= 118): how sure the decoder is of every object of an id map -- the uint8 mask planes
+ * the label rule was computed from, reduced over the ids.  A segmented reduction, per object and exact.  All integers:
+ * the result depends on no order of execution.
+ *
+ *   Position is q = y * W + x.
+ *   A pixel is COUNTED when 1 <= id <= cap, l = labels[q] lies in 1..nlabels and g = planes[b][l] lies in 0..P-1.
+ *   A counted pixel's value is s = u0 + u1 + u2, the three bytes of plane group g at q: 0..765, the numerator of
+ *   dfw_seg_labels' score_c.
+ *   Row id - 1 of scores[b] is (sum of s, counted pixels, min s, max s) over the object's counted pixels; a row without a
+ *   counted pixel is (0, 0, 0, 0).  Every row 0..cap-1 is written.  Ids above cap are not scored, as stats does not list
+ *   them; negative ids count as 0.
+ *
+ *   ids          normally dfw_seg_components' ids (any int32 map is accepted)
+ *   labels       normally dfw_seg_components' filtered map: the class byte of every pixel
+ *   seg_u8       P plane groups of three channels, each [H][W].  Which group a class of an image reads is the table's
+ *                business, so one layout serves every route: N-way class-major planes [N][B] give planes[b][l] =
+ *                (l - 1) * B + b, the binary routes planes[b][1] = b, entry-major candidate planes planes[b][lab[e]] = e
+ *   planes       device, [B][nlabels + 1]: the plane group of label l of image b, -1 for none; entry 0 is never read.  The
+ *                kernel reads it when it RUNS and clamps what it reads: an entry outside 0..P-1 means "not counted", so a
+ *                table overwritten later gives other numbers, never a read outside seg_u8
+ *   planes_host  its host mirror: what this call validates
+ *   ws           dfw_seg_scores_workspace_bytes(B, cap) bytes.  The call writes every word it reads: the caller
+ *                initialises nothing
+ *
+ * ids [[1,1,2]], labels [[2,2,1]], cap = 2, nlabels = 2, planes = [[*, -1, 0]], group 0 = channels [[10,20,9]],
+ * [[1,2,9]], [[0,3,9]]: the two pixels of object 1 carry label 2 -> group 0 and s = 11 and 25, so row 0 = (36, 2, 11, 25);
+ * object 2's pixel carries label 1, which has no plane: row 1 = (0, 0, 0, 0).
+ *
+ * Three launches whatever the image holds: a library kernel zeroes the accumulators (no memset node), the reduction, and
+ * a finish kernel that writes every row.  No host readback, no thread that waits for another: the call can be captured
+ * and is correct at any residency.  The reduction never issues an atomic per pixel: a workgroup covers a block of
+ * dfw_seg_scores_block() consecutive positions, each thread folds its equal neighbouring ids, a segmented scan folds the
+ * runs across the lanes of a wave and LDS across the waves, and every maximal piece of one id inside the block issues ONE
+ * set of integer atomics (64-bit add of the sum, 32-bit add / max / max of the rest; the minimum is kept as the maximum
+ * of 765 - s, so zero is every field's identity).  Nothing is written outside scores and ws; the inputs are read only.
+ *
+ * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / ids / labels / seg_u8 / planes /
+ * planes_host / scores / ws; B, H, W, cap or P < 1; nlabels outside 1..254.  DFW_ERANGE: H or W above 65535, H * W above
+ * 2^30, B above 65535; P * 3 * H * W above 2^63 - 1 (seg_u8 is addressed in size_t, so no int32 arguments reach this);
+ * B * cap * 5 above 2^31 - 1 (the accumulators' words and the rows of scores are counted in an int; the B * cap * 4 words
+ * of scores are addressed in size_t).  DFW_EINVAL: a planes_host entry 1..nlabels above P - 1 or below -1.
+ * DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: scores or ws overlapping an input or each other.  DFW_ESHAPE:
+ * ids / planes / ws not 4-byte aligned, scores not 8-byte aligned.  Sizes are judged before the table, the table before
+ * the workspace, the workspace before overlap.
+ */
+typedef struct {
+  const int32_t* ids;           /* [B][H][W] contiguous, read only */
+  const uint8_t* labels;        /* [B][H][W] contiguous, read only */
+  const uint8_t* seg_u8;        /* [P][3][H][W] contiguous, read only */
+  const int32_t* planes;        /* device [B][nlabels + 1]: plane group per label, -1 for none; entry 0 unused */
+  const int32_t* planes_host;   /* host mirror of planes */
+  int64_t* scores;              /* out [B][cap][4]: (sum, counted pixels, min, max) */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, cap, nlabels, P;
+} dfw_seg_scores_args;
+int dfw_seg_scores(const dfw_seg_scores_args* a, dfw_stream_t stream);
+/* 0 for sizes dfw_seg_scores refuses (B or cap < 1, B above 65535, B * cap * 5 above 2^31 - 1); monotone otherwise */
+size_t dfw_seg_scores_workspace_bytes(int32_t B, int32_t cap);
+/* positions one workgroup covers: the size at which the kernel changes path, for tests and docs */
+int dfw_seg_scores_block(int32_t* pixels);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
