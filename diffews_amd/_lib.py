@@ -134,6 +134,16 @@ class SegScoresArgs(C.Structure):
                 ("P", _i32)]
 
 
+class SegBoundaryArgs(C.Structure):
+    _fields_ = [("map", _vp), ("dist", _vp), ("band", _vp), ("ws", _vp), ("ws_bytes", _sz), ("elem", _i32), ("B", _i32),
+                ("H", _i32), ("W", _i32), ("dmax", _i32), ("d", _i32)]
+
+
+class SegBoundaryCountsArgs(C.Structure):
+    _fields_ = [("pred", _vp), ("pdist", _vp), ("gt", _vp), ("gdist", _vp), ("counts", _vp), ("B", _i32), ("H", _i32),
+                ("W", _i32), ("d", _i32), ("nlabels", _i32)]
+
+
 class SegComponentsRounds(C.Structure):
     _fields_ = [("blocks", _i32), ("merge", _i32), ("flatten", _i32), ("flatten_vector", _i32), ("scan", _i32)]
 
@@ -337,6 +347,10 @@ SYMBOLS = {
     "dfw_seg_scores": (_i32, [C.POINTER(SegScoresArgs), _vp]),
     "dfw_seg_scores_workspace_bytes": (_sz, [_i32, _i32]),
     "dfw_seg_scores_block": (_i32, [C.POINTER(_i32)]),
+    "dfw_seg_boundary": (_i32, [C.POINTER(SegBoundaryArgs), _vp]),
+    "dfw_seg_boundary_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "dfw_seg_boundary_block": (_i32, [C.POINTER(_i32)] * 3),
+    "dfw_seg_boundary_counts": (_i32, [C.POINTER(SegBoundaryCountsArgs), _vp]),
 }
 
 _lib = None

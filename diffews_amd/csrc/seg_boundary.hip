@@ -1,0 +1,364 @@
+// Boundary bands (objects.boundary_bands): the capped chessboard distance of every pixel of a label map (uint8) or an id
+// map (int32) to its own contour, and the per-class counts of two such bands.  map [B][H][W] -> dist uint8 [B][H][W]:
+// 0 where map == 0, else min(D, dmax + 1), D the smallest max(|dy|, |dx|) to a position that lies outside the image or
+// holds another value; optionally band [B][H][W] of the map's type, the value where 1 <= dist <= d and 0 elsewhere.
+// Values are compared for equality only.  All integers: the result depends on no order of execution.
+//
+// The exact two-pass form.  h(y, x) = min(x - run_start + 1, run_end - x) is the distance along the row to the nearest
+// position that is outside the row or holds another value; then
+//   D(y, x) = min(y + 1, H - y, min over dy of c(dy)),  c(dy) = max(|dy|, h(y + dy, x)) while map[y + dy][x] == v,
+//                                                       c(dy) = |dy| at the first row where it differs,
+// and nothing beyond that row, or beyond |dy| >= the best so far, can be smaller.  h is capped at dmax + 1 as well, which
+// changes no capped D: min(max(a, min(h, c)), c) == min(max(a, h), c).
+//
+// Launches, two whatever the image holds, no host readback in between:
+//
+//   0  boundary_row_kernel<T>     per block of kBndPos consecutive positions y * W + x of one image: the window of
+//                                 kBndPos + 2 * kBndHalo positions goes to LDS (16-byte / 4-byte loads of four elements where
+//                                 the address allows and the four lie inside the image, else by element; outside the image
+//                                 reads nothing).  A position is a BREAK when it lies outside the image, starts a row or
+//                                 holds another value than its predecessor.  Each thread owns 10 positions of the window;
+//                                 the last break at or before a position is an inclusive max-scan of break positions and
+//                                 the next break behind it an exclusive min-scan from the right (wave64 shuffles, the four
+//                                 waves through LDS).  The halo of kBndHalo >= 254 + 1 positions a side makes every capped
+//                                 distance of the block's own positions final.  h goes to the workspace, one byte a pixel,
+//                                 as 8-byte stores where the address allows.
+//   1  boundary_col_kernel<T, V>  per tile of kBndRows x kBndCols pixels: a thread owns V pixels side by side (V = 4
+//                                 through one 32-bit word of h and of a uint8 map, or 16 bytes of an int32 map, when W % 4
+//                                 == 0 and every pointer is aligned for it; V = 1 otherwise) and walks dy = 1, 2, ... up
+//                                 and down the column while dy < the largest best-so-far of its pixels.  The walk stays
+//                                 inside the image by itself: best <= min(y + 1, H - y) from the start.  dist and band
+//                                 come out of the same pass.
+//
+// Why plain column reads through the caches and not an LDS tile with halo: the walk of a pixel ends after D steps, so only
+// the pixels deep inside an object go the whole dmax rows; at dmax = 116 a tile needs a 232-row halo, i.e. (16 + 232) x 64
+// x (1 + 4) bytes = 79 KB for an id map, above the 64 KB of static LDS, and a taller tile only moves the ratio from 15x to
+// 5x re-read.  A row of a tile is 64 consecutive bytes of h (one cache line) and the 15 neighbouring tile rows read the
+// same lines, so the re-reads are L1 / L2 hits; profiles/object_boundaries_timing.md holds the measured cost.
+//
+// dfw_seg_boundary_counts: per pixel, dropped when gt > nlabels (seg_gt_byte's rule); l = pred if 1 <= pdist <= d else 0,
+// g = gt if 1 <= gdist <= d else 0; pred[l]++, gt[g]++, inter[l]++ when l == g, in LDS histograms per workgroup of
+// kBndCountPix positions, flushed by seg_flush_counts (seg_fuse.h) into counts [B][2][nlabels + 1] = (intersections,
+// unions).  Pixels in neither band, the bulk of an image, are counted in a register and reach the histogram once per wave.
+// Two launches: a library kernel zeroes counts (no memset node), then the count.
+//
+// Termination: in dfw_seg_boundary no thread waits for another thread or workgroup and no atomics are used; every loop
+// but the column walk has a trip count fixed at compile time, and the walk ends after at most dmax steps.  The counts use
+// LDS and global integer atomics (order-free) and wait for nothing.  Any grid is correct at any residency.
+#include "seg_fuse.h"
+#include "seg_sort.h"
+
+namespace dfw {
+
+constexpr int kBndPos = 2048;                          // positions a workgroup of the row pass covers
+constexpr int kBndHalo = 256;                          // >= dmax + 1 for every dmax <= 254, a multiple of 16
+constexpr int kBndWin = kBndPos + 2 * kBndHalo;        // 2560 = 256 threads x 10
+constexpr int kBndOwn = kBndWin / 256;
+constexpr int kBndRows = 16, kBndCols = 64;            // the tile of the column pass
+constexpr int kBndCountPix = 4096;                     // positions a workgroup of the counts covers, 16 per thread
+static_assert(kBndOwn * 256 == kBndWin && kBndHalo >= 255 && kBndPos == 256 * 8, "the row pass's layout");
+
+using u32x2 = unsigned __attribute__((ext_vector_type(2)));
+
+// V neighbouring elements -> ints
+template <typename T, int V> __device__ __forceinline__ void bnd_load(const T* p, int (&o)[V]) {
+  if constexpr (V == 1) {
+    o[0] = (int)p[0];
+  } else if constexpr (sizeof(T) == 1) {
+    const uint32_t w = *(const uint32_t*)p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (int)((w >> (8 * k)) & 255u);
+  } else {
+    const i32x4 w = *(const i32x4*)p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = w[k];
+  }
+}
+template <typename T, int V> __device__ __forceinline__ void bnd_store(T* p, const int (&o)[V]) {
+  if constexpr (V == 1) {
+    p[0] = (T)o[0];
+  } else if constexpr (sizeof(T) == 1) {
+    *(uint32_t*)p = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
+  } else {
+    i32x4 w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = o[k];
+    *(i32x4*)p = w;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void boundary_row_kernel(const T* map, uint8_t* hrow, int HW, int W, int cap) {
+  __shared__ __attribute__((aligned(16))) int val[kBndWin];
+  __shared__ __attribute__((aligned(8))) uint8_t hb[kBndPos];
+  __shared__ int wlast[4], wfirst[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int p0 = blockIdx.x * kBndPos, w0 = p0 - kBndHalo;   // the window's first position, negative in block 0
+  const T* mp = map + (size_t)blockIdx.y * HW;
+#pragma unroll
+  for (int r = 0; r < (kBndWin / 4 + 255) / 256; ++r) {
+    const int c = r * 256 + t;
+    if (c < kBndWin / 4) {
+      const int q = w0 + 4 * c;
+      int v[4];
+      if (q >= 0 && q + 4 <= HW && ((uintptr_t)(mp + q) & (4 * sizeof(T) - 1)) == 0) {
+        bnd_load<T, 4>(mp + q, v);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (q + k >= 0 && q + k < HW) ? (int)mp[q + k] : 0;
+      }
+      i32x4 w;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = v[k];
+      *(i32x4*)(val + 4 * c) = w;
+    }
+  }
+  __syncthreads();
+  const int i0 = kBndOwn * t, q0 = w0 + i0;
+  int v[kBndOwn + 1];
+  v[0] = t ? val[i0 - 1] : 0;
+#pragma unroll
+  for (int j = 0; j < kBndOwn; ++j) v[j + 1] = val[i0 + j];
+  // breaks: the window's first position is one as well, which no position of the block itself can see (kBndHalo > cap)
+  int x = q0 >= 0 ? q0 % W : 0;
+  int last = -1, first = kBndWin, L[kBndOwn];
+  unsigned brk = 0u;
+#pragma unroll
+  for (int j = 0; j < kBndOwn; ++j) {
+    const int q = q0 + j;
+    if (q < 0 || q >= HW || x == 0 || v[j + 1] != v[j] || i0 + j == 0) {
+      brk |= 1u << j;
+      last = i0 + j;
+      if (first == kBndWin) first = i0 + j;
+    }
+    L[j] = last;
+    if (q >= 0 && ++x == W) x = 0;
+  }
+  int ls = last, fs = first;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int a = __shfl_up(ls, o, 64), c = __shfl_down(fs, o, 64);
+    if (lane >= o) ls = max(ls, a);
+    if (lane + o < 64) fs = min(fs, c);
+  }
+  if (lane == 63) wlast[wave] = ls;
+  if (lane == 0) wfirst[wave] = fs;
+  int before = __shfl_up(ls, 1, 64), behind = __shfl_down(fs, 1, 64);
+  if (lane == 0) before = -1;
+  if (lane == 63) behind = kBndWin;
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (u < wave) before = max(before, wlast[u]);
+    if (u > wave) behind = min(behind, wfirst[u]);
+  }
+  int nb = behind;
+#pragma unroll
+  for (int j = kBndOwn - 1; j >= 0; --j) {
+    const int i = i0 + j;
+    const int h = min(min(i - max(L[j], before) + 1, nb - i), cap);
+    if (i >= kBndHalo && i < kBndHalo + kBndPos) hb[i - kBndHalo] = (uint8_t)h;
+    if (brk & (1u << j)) nb = i;
+  }
+  __syncthreads();
+  const int p = p0 + 8 * t;
+  uint8_t* hp = hrow + (size_t)blockIdx.y * HW;
+  if (p + 8 <= HW && ((uintptr_t)(hp + p) & 7) == 0) {
+    *(u32x2*)(hp + p) = *(const u32x2*)(hb + 8 * t);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (p + k < HW) hp[p + k] = hb[8 * t + k];
+  }
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void boundary_col_kernel(const T* map, const uint8_t* hrow, uint8_t* dist, T* band, int H,
+                                                           int W, int cap, int d) {
+  constexpr int TX = kBndCols / V, TY = 256 / TX;   // threads along a tile row, rows a round
+  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+  const int x = blockIdx.x * kBndCols + tx * V;
+  if (x >= W) return;                               // V == 4 only with W % 4 == 0: x < W covers x + 3
+  const size_t img = (size_t)blockIdx.z * H * W;
+#pragma unroll
+  for (int r = 0; r < kBndRows / TY; ++r) {
+    const int y = blockIdx.y * kBndRows + r * TY + ty;
+    if (y >= H) return;
+    const size_t o = img + (size_t)y * W + x;
+    int v[V], best[V];
+    bnd_load<T, V>(map + o, v);
+    bnd_load<uint8_t, V>(hrow + o, best);
+    const int edge = min(min(y + 1, H - y), cap);
+    int far = 0;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      best[k] = v[k] ? min(best[k], edge) : 0;
+      far = max(far, best[k]);
+    }
+    // dy < far <= min(y + 1, H - y): rows y - dy and y + dy exist.  A pixel with best <= dy takes nothing from this round:
+    // both candidates are >= dy
+    for (int dy = 1; dy < far; ++dy) {
+      const size_t s = (size_t)dy * W;
+      int mu[V], hu[V], md[V], hd[V];
+      bnd_load<T, V>(map + o - s, mu);
+      bnd_load<uint8_t, V>(hrow + o - s, hu);
+      bnd_load<T, V>(map + o + s, md);
+      bnd_load<uint8_t, V>(hrow + o + s, hd);
+      far = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const int cu = mu[k] == v[k] ? max(dy, hu[k]) : dy, cd = md[k] == v[k] ? max(dy, hd[k]) : dy;
+        best[k] = min(best[k], min(cu, cd));
+        far = max(far, best[k]);
+      }
+    }
+    bnd_store<uint8_t, V>(dist + o, best);
+    if (band) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) v[k] = best[k] <= d ? v[k] : 0;   // best == 0 only where v == 0
+      bnd_store<T, V>(band + o, v);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void boundary_zero_kernel(unsigned long long* words, int n) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n) words[e] = 0ull;
+}
+
+__global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pred, const uint8_t* pdist, const uint8_t* gt,
+                                                              const uint8_t* gdist, unsigned long long* counts, int HW,
+                                                              int d, int nlabels) {
+  __shared__ unsigned hist[3 * 256];   // [inter | pred | gt][label byte]
+  const int t = threadIdx.x;
+  for (int i = t; i < 3 * 256; i += 256) hist[i] = 0u;
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.y * HW;
+  pred += base, pdist += base, gt += base, gdist += base;
+  const seg_gt_byte bin = {nlabels};
+  unsigned none = 0u;                  // kept pixels in neither band: bin 0 of all three
+  auto count = [&](int p, int pd, int g, int gd) {
+    if (bin(g) < 0) return;
+    const int l = (unsigned)(pd - 1) < (unsigned)d ? p : 0, gg = (unsigned)(gd - 1) < (unsigned)d ? g : 0;
+    if ((l | gg) == 0) {
+      ++none;
+      return;
+    }
+    atomicAdd(&hist[256 + l], 1u);
+    atomicAdd(&hist[512 + gg], 1u);
+    if (l == gg) atomicAdd(&hist[l], 1u);
+  };
+  const int p0 = blockIdx.x * kBndCountPix;
+  if ((HW & 3) == 0 && (((uintptr_t)pred | (uintptr_t)pdist | (uintptr_t)gt | (uintptr_t)gdist) & 3) == 0) {
+#pragma unroll
+    for (int r = 0; r < kBndCountPix / 1024; ++r) {
+      const int q = p0 + 4 * (r * 256 + t);
+      if (q < HW) {
+        const uint32_t wp = *(const uint32_t*)(pred + q), wpd = *(const uint32_t*)(pdist + q);
+        const uint32_t wg = *(const uint32_t*)(gt + q), wgd = *(const uint32_t*)(gdist + q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          count((wp >> (8 * k)) & 255u, (wpd >> (8 * k)) & 255u, (wg >> (8 * k)) & 255u, (wgd >> (8 * k)) & 255u);
+      }
+    }
+  } else {
+#pragma unroll 4
+    for (int r = 0; r < kBndCountPix / 256; ++r) {
+      const int q = p0 + r * 256 + t;
+      if (q < HW) count(pred[q], pdist[q], gt[q], gdist[q]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) none += (unsigned)__shfl_xor((int)none, o, 64);
+  if ((t & 63) == 0 && none) {
+    atomicAdd(&hist[0], none);
+    atomicAdd(&hist[256], none);
+    atomicAdd(&hist[512], none);
+  }
+  __syncthreads();
+  const int NB = nlabels + 1;
+  seg_flush_counts(hist, counts + (size_t)blockIdx.y * 2 * NB, NB);
+}
+
+// The sizes both entry points refuse: DFW_EINVAL before DFW_ERANGE.
+static int boundary_size_error(long long B, long long H, long long W) {
+  if (B < 1 || H < 1 || W < 1) return DFW_EINVAL;
+  // grid z carries B and grid y the rows' tiles; H * W <= 2^30 keeps every position of an image, and the row pass's window
+  // behind it, in an int
+  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  return 0;
+}
+
+template <typename T>
+static void boundary_launch(hipStream_t st, const dfw_seg_boundary_args* a, bool vec) {
+  const int HW = a->H * a->W, cap = a->dmax + 1;
+  hipLaunchKernelGGL(boundary_row_kernel<T>, dim3((HW + kBndPos - 1) / kBndPos, a->B), dim3(256), 0, st, (const T*)a->map,
+                     (uint8_t*)a->ws, HW, a->W, cap);
+  const dim3 grid((a->W + kBndCols - 1) / kBndCols, (a->H + kBndRows - 1) / kBndRows, a->B);
+  if (vec)
+    hipLaunchKernelGGL((boundary_col_kernel<T, 4>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws, a->dist,
+                       (T*)a->band, a->H, a->W, cap, a->d);
+  else
+    hipLaunchKernelGGL((boundary_col_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws, a->dist,
+                       (T*)a->band, a->H, a->W, cap, a->d);
+}
+
+}  // namespace dfw
+
+using namespace dfw;
+
+extern "C" size_t dfw_seg_boundary_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t elem) {
+  if ((elem != 1 && elem != 4) || boundary_size_error(B, H, W)) return 0;
+  return ((size_t)B * H * W + 15) & ~(size_t)15;   // h, one byte a pixel
+}
+
+extern "C" int dfw_seg_boundary_block(int32_t* rows, int32_t* cols, int32_t* positions) {
+  if (!rows || !cols || !positions) return DFW_EINVAL;
+  *rows = kBndRows, *cols = kBndCols, *positions = kBndPos;
+  return 0;
+}
+
+extern "C" int dfw_seg_boundary(const dfw_seg_boundary_args* a, dfw_stream_t stream) {
+  if (!a || !a->map || !a->dist || !a->ws) return DFW_EINVAL;
+  if (a->elem != 1 && a->elem != 4) return DFW_EINVAL;
+  if (a->dmax < 1 || a->dmax > 254) return DFW_EINVAL;
+  if (a->band && (a->d < 1 || a->d > a->dmax)) return DFW_EINVAL;
+  if (int e = boundary_size_error(a->B, a->H, a->W)) return e;
+  const size_t wsb = dfw_seg_boundary_workspace_bytes(a->B, a->H, a->W, a->elem);
+  if (a->ws_bytes < wsb) return DFW_EWORKSPACE;
+  const size_t n = (size_t)a->B * a->H * a->W, el = (size_t)a->elem;
+  if (seg_overlap(a->map, n * el, a->dist, n) || seg_overlap(a->map, n * el, a->band, n * el) ||
+      seg_overlap(a->map, n * el, a->ws, wsb) || seg_overlap(a->dist, n, a->band, n * el) ||
+      seg_overlap(a->dist, n, a->ws, wsb) || seg_overlap(a->band, n * el, a->ws, wsb))
+    return DFW_EINVAL;
+  if (a->elem == 4 && (((uintptr_t)a->map | (uintptr_t)a->band) & 3)) return DFW_ESHAPE;
+  if ((uintptr_t)a->ws & 3) return DFW_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  // four pixels a thread in the column pass: whole words of every map, in every row of every image
+  const uintptr_t al = 4 * el - 1;
+  const bool vec = a->W % 4 == 0 && (((uintptr_t)a->map | (uintptr_t)a->band) & al) == 0 && ((uintptr_t)a->dist & 3) == 0;
+  if (a->elem == 1) boundary_launch<uint8_t>(st, a, vec);
+  else boundary_launch<int32_t>(st, a, vec);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t stream) {
+  if (!a || !a->pred || !a->pdist || !a->gt || !a->gdist || !a->counts) return DFW_EINVAL;
+  if (a->d < 1 || a->d > 254) return DFW_EINVAL;
+  if (a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
+  if (int e = boundary_size_error(a->B, a->H, a->W)) return e;
+  const size_t n = (size_t)a->B * a->H * a->W, cb = (size_t)a->B * 2 * (a->nlabels + 1) * 8;
+  const void* const in[4] = {a->pred, a->pdist, a->gt, a->gdist};
+  for (int i = 0; i < 4; ++i)
+    if (seg_overlap(in[i], n, a->counts, cb)) return DFW_EINVAL;
+  if ((uintptr_t)a->counts & 7) return DFW_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const int HW = a->H * a->W, words = a->B * 2 * (a->nlabels + 1);
+  hipLaunchKernelGGL(boundary_zero_kernel, dim3((words + 255) / 256), dim3(256), 0, st, (unsigned long long*)a->counts, words);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(boundary_counts_kernel, dim3((HW + kBndCountPix - 1) / kBndCountPix, a->B), dim3(256), 0, st, a->pred,
+                     a->pdist, a->gt, a->gdist, (unsigned long long*)a->counts, HW, a->d, a->nlabels);
+  DFW_CHECK_LAUNCH();
+  return 0;
+}

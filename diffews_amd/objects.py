@@ -19,6 +19,16 @@ object_scores says how SURE the model is of each object: the decoder's uint8 mas
 planes_for_candidates build the table that says which planes a label of an image reads.  scores_to_host brings the table
 to the host, coco_results turns the three host tables into COCO result records, and detections_to_host gathers what
 metrics.average_precision ranks.
+
+boundary_bands says how good the CONTOURS are: the capped chessboard distance of every pixel of a label map or an id map
+to its own contour (ops.seg_boundary) and the band of pixels within d of it, d = 2 % of the image diagonal by default --
+the band of Boundary IoU (Cheng et al., CVPR 2021).  object_boundaries runs it on the labels and the ids of a label_objects
+result; boundary_counts counts two label bands against each other per class, in the counts layout metrics.nway_iou /
+metrics.boundary_iou read.  Per-object Boundary IoU needs no stage of its own: the band of an id map is an id map, so
+    pb, gb = object_boundaries(o_pred), object_boundaries(o_gt)
+    m = match_objects((pb["ids"]["band"], o_pred["stats"]), (gb["ids"]["band"], o_gt["stats"]), skip=gt_labels, nlabels=N)
+gives in m["pairs"] the shared band pixels of every (pred, gt) pair, in m["area"] the band areas, and in m["match"] / m["pq"]
+the matching and the panoptic counts at Boundary IoU above `iou`.
 """
 import numpy as np
 import torch
@@ -639,3 +649,145 @@ def detections_to_host(o, s, m):
         dets.append(rows[keep])
     npos = (pq[:, :, 0] + pq[:, :, 2]).sum(axis=0)
     return (dets[0] if single else dets), npos
+
+
+# ------------------------------------------------------------------------------------------------ boundary bands
+
+_BOUNDARY_DMAX = 254
+
+
+class BoundaryBuffers:
+    """Everything one boundary_bands call of a shape writes, allocated once: dist uint8 [B, H, W], band [B, H, W] of the
+    map's dtype (torch.uint8 for label maps, torch.int32 for id maps) and the workspace.  dmax is the search radius of the
+    calls that use the buffers without naming one."""
+
+    def __init__(self, B, H, W, dmax, dtype=torch.uint8, device="cuda"):
+        self.shape, self.dmax, self.dtype = (int(B), int(H), int(W)), int(dmax), dtype
+        if dtype not in (torch.uint8, torch.int32):
+            raise ValueError("BoundaryBuffers: dtype must be torch.uint8 (label maps) or torch.int32 (id maps)")
+        if not 1 <= self.dmax <= _BOUNDARY_DMAX:
+            raise ValueError(f"BoundaryBuffers: dmax must lie in 1..{_BOUNDARY_DMAX}, got {self.dmax}")
+        nbytes = ops.seg_boundary_workspace(*self.shape, 1 if dtype == torch.uint8 else 4)
+        if nbytes == 0:
+            raise ValueError(f"seg_boundary refuses these sizes: {self.shape}")
+        dev = torch.device(device)
+        self.dist = torch.empty(self.shape, dtype=torch.uint8, device=dev)
+        self.device = self.dist.device
+        self.band = torch.empty(self.shape, dtype=dtype, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _bands_one(m, d, ratio, dmax, buffers):
+    squeeze = m.dim() == 2
+    if squeeze:
+        m = m[None]
+    if m.dim() != 3 or m.dtype not in (torch.uint8, torch.int32) or not m.is_cuda:
+        raise ValueError("boundary_bands takes a uint8 or int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
+    B, H, W = m.shape
+    if d is None:
+        from .metrics import boundary_width
+        d = boundary_width(H, W, ratio)
+    d = int(d)
+    if dmax is None:
+        dmax = d if buffers is None else buffers.dmax
+    dmax = int(dmax)
+    if d > _BOUNDARY_DMAX or dmax > _BOUNDARY_DMAX:
+        raise ValueError(f"boundary_bands: a band of {max(d, dmax)} pixels is above the limit of {_BOUNDARY_DMAX} (dist is a "
+                         f"byte): at ratio 0.02 that is an image diagonal of about 12 700 pixels")
+    if d < 1 or dmax < d:
+        raise ValueError(f"boundary_bands: the width must lie in 1..dmax, got d = {d}, dmax = {dmax}")
+    if buffers is None:
+        buffers = BoundaryBuffers(B, H, W, dmax, m.dtype, m.device)
+    elif buffers.shape != (B, H, W) or buffers.device != m.device or buffers.dtype != m.dtype:
+        raise ValueError(f"buffers were made for {buffers.shape} of {buffers.dtype} on {buffers.device}, the map is "
+                         f"{(B, H, W)} of {m.dtype} on {m.device}")
+    ops.seg_boundary(m.contiguous(), buffers.dist, buffers.ws, dmax, band=buffers.band, d=d)
+    dist, band = buffers.dist, buffers.band
+    if squeeze:
+        dist, band = dist[0], band[0]
+    return dict(dist=dist, band=band, d=d, dmax=dmax)
+
+
+def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None):
+    """Distance to the contour and the boundary band of a label map or an id map.  m: a uint8 or int32 device tensor [H, W]
+    or [B, H, W] (0 = background; every other value, 255 and negative ints included, is an object value, compared for
+    equality only), or a LIST of [h_i, w_i] maps.  d: the band's width in pixels, by default metrics.boundary_width(H, W,
+    ratio) = 2 % of the image diagonal; dmax: the search radius, d by default (or the buffers' dmax), at most 254 -- a
+    larger d is a ValueError.
+
+    Returns dict(dist, band, d, dmax) on the device: dist uint8, 0 on background, else min(D, dmax + 1) with D the
+    chessboard distance to the nearest position outside the image or of another value (1 on the contour), so one dist
+    answers every width up to dmax; band, of m's dtype, the value where 1 <= dist <= d and 0 elsewhere -- for the mask of
+    one value exactly mask - eroded of the published mask_to_boundary.  A [H, W] input gives the same without the batch
+    axis.  A list is handled with ONE CALL PER ITEM, d comes from each item's own size, and every value of the result is a
+    list; buffers is then a list of BoundaryBuffers or None.  buffers: a BoundaryBuffers of this shape and dtype, reused
+    call after call (the result aliases it).  Two launches per call and no host synchronisation."""
+    if isinstance(m, (list, tuple)):
+        ds = d if isinstance(d, (list, tuple)) else [d] * len(m)
+        bufs = buffers if buffers is not None else [None] * len(m)
+        if len(ds) != len(m) or len(bufs) != len(m):
+            raise ValueError("boundary_bands: one d / buffers entry per map")
+        per = [_bands_one(x, di, ratio, dmax, b) for x, di, b in zip(m, ds, bufs)]
+        return {k: [p[k] for p in per] for k in ("dist", "band", "d", "dmax")}
+    return _bands_one(m, d, ratio, dmax, buffers)
+
+
+def object_boundaries(o, d=None, ratio=0.02, dmax=None, buffers=None):
+    """boundary_bands of both maps of a label_objects result o: its (filtered) labels, whose band feeds boundary_counts,
+    and its ids, whose band is an id map that match_objects takes (per-object Boundary IoU, see the module docstring).
+    buffers: dict(labels=BoundaryBuffers of uint8, ids=BoundaryBuffers of int32) -- of lists of them for a list result --
+    or None.  Returns dict(labels, ids, d): two boundary_bands results and the width they share (a list for a list)."""
+    buffers = buffers or {}
+    lab = boundary_bands(o["labels"], d, ratio, dmax, buffers.get("labels"))
+    ids = boundary_bands(o["ids"], lab["d"], ratio, dmax, buffers.get("ids"))
+    return dict(labels=lab, ids=ids, d=lab["d"])
+
+
+def _bcounts_one(bp, bg, pred, gt, nlabels, d, counts):
+    squeeze = pred.dim() == 2
+    pdist, gdist = bp["dist"], bg["dist"]
+    if squeeze:
+        pred, gt, pdist, gdist = pred[None], (gt[None] if gt.dim() == 2 else gt), pdist[None], gdist[None]
+    if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_cuda:
+        raise ValueError("boundary_counts takes uint8 device label maps [H, W] or [B, H, W], or lists of [h, w] maps")
+    if gt.dtype != torch.uint8 or gt.shape != pred.shape:
+        raise ValueError("boundary_counts: gt must be uint8 and shaped like pred")
+    if pdist.shape != pred.shape or gdist.shape != pred.shape:
+        raise ValueError("boundary_counts: the dist maps must be shaped like pred")
+    nlabels = int(nlabels)
+    if not 1 <= nlabels <= 254:
+        raise ValueError("boundary_counts: nlabels must lie in 1..254")
+    d = int(bp["d"] if d is None else d)
+    if d < 1 or d > min(bp.get("dmax", d), bg.get("dmax", d)):
+        raise ValueError(f"boundary_counts: d = {d} is outside 1..dmax of the dist maps")
+    B = pred.shape[0]
+    if counts is None:
+        counts = torch.empty(B, 2, nlabels + 1, dtype=torch.int64, device=pred.device)
+    elif squeeze and counts.dim() == 2:
+        counts = counts[None]
+    ops.seg_boundary_counts(pred.contiguous(), pdist.contiguous(), gt.contiguous(), gdist.contiguous(), counts, d)
+    return counts[0] if squeeze else counts
+
+
+def boundary_counts(bp, bg, pred, gt, nlabels, d=None, counts=None):
+    """Per-class counts of the boundary band of a prediction against that of a ground truth.  bp, bg: boundary_bands
+    results of the two uint8 label maps pred and gt (device tensors [H, W] / [B, H, W], or lists of [h_i, w_i] maps; the
+    four then are lists, handled with one call per item).  d: the width, bp's by default; any width up to the dmax both
+    dist maps were made with.  A pixel with gt > nlabels (255 included) is dropped; otherwise it counts for its predicted
+    class when it lies in the prediction's band and for its true class when it lies in the ground truth's band, for bin 0
+    otherwise.  The ground truth's distance was taken on the map as given: 255 is a value like any other there, so a class
+    pixel beside an ignore region lies in the band -- the published method has no ignore label, and treating the unknown
+    as "other" needs no second rule.
+
+    Returns counts int64 [.., 2, nlabels + 1] = (intersections, unions) on the device, the layout of label_objects'
+    counts: metrics.boundary_iou(counts) is Boundary IoU per class and its mean.  counts (optional): the buffer to write,
+    reused call after call.  Two launches per call and no host synchronisation."""
+    if isinstance(pred, (list, tuple)):
+        k = len(pred)
+        cs = counts if counts is not None else [None] * k
+        ds = d if isinstance(d, (list, tuple)) else [d] * k
+        if not isinstance(gt, (list, tuple)) or len(gt) != k or len(bp["dist"]) != k or len(bg["dist"]) != k or len(cs) != k:
+            raise ValueError("boundary_counts: one gt, one dist pair and one counts entry per predicted map")
+        item = lambda r, i: {key: v[i] for key, v in r.items()}  # noqa: E731
+        return [_bcounts_one(item(bp, i), item(bg, i), pred[i], gt[i], nlabels, ds[i], cs[i]) for i in range(k)]
+    return _bcounts_one(bp, bg, pred, gt, nlabels, d, counts)

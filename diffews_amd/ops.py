@@ -1231,3 +1231,72 @@ def seg_scores(ids, labels, seg_u8, planes, planes_host, scores, ws):
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
     a.B, a.H, a.W, a.cap, a.nlabels, a.P = B, H, W, cap, nl1 - 1, P
     L.check(L.lib().dfw_seg_scores(C.byref(a), _stream()), "dfw_seg_scores")
+
+
+def seg_boundary_workspace(B, H, W, elem=1):
+    """Bytes of seg_boundary's workspace for a [B, H, W] map of elem-byte values (1 | 4); 0 for sizes it refuses."""
+    return int(L.lib().dfw_seg_boundary_workspace_bytes(int(B), int(H), int(W), int(elem)))
+
+
+def seg_boundary_block():
+    """(rows, cols, positions): the tile of seg_boundary's column pass and the positions a workgroup of its row pass
+    covers -- the sizes at which its kernels change path."""
+    r, c, p = C.c_int32(), C.c_int32(), C.c_int32()
+    L.check(L.lib().dfw_seg_boundary_block(C.byref(r), C.byref(c), C.byref(p)), "dfw_seg_boundary_block")
+    return r.value, c.value, p.value
+
+
+def seg_boundary(map, dist, ws, dmax, band=None, d=None):
+    """Capped chessboard distance to the contour, on caller-owned buffers only (objects.BoundaryBuffers holds a set): map
+    uint8 or int32 [B, H, W], values compared for equality only, 0 = background, every other value (255, values above 255
+    and negative ints included) an object value.  Writes dist uint8 [B, H, W]: 0 where map == 0, else min(D, dmax + 1), D
+    the smallest max(|dy|, |dx|) to a position outside the image or of another value (1 on the image's edge and next to
+    another value); 1 <= dmax <= 254 and dmax + 1 means "deeper than dmax".  band (optional, map's dtype) receives the value
+    where 1 <= dist <= d and 0 elsewhere, 1 <= d <= dmax, from the same launch.  ws: a uint8 buffer of at least
+    seg_boundary_workspace(B, H, W, map.element_size()) bytes, which needs no initialisation.  Two launches, no host
+    synchronisation, no memset node, no atomics: the call can be captured.  Returns None."""
+    if map.dim() != 3 or map.dtype not in (torch.uint8, torch.int32) or not map.is_contiguous() or not map.is_cuda:
+        raise ValueError("seg_boundary: map must be a contiguous uint8 or int32 device tensor [B, H, W]")
+    B, H, W = map.shape
+    dev = map.device
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_boundary: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegBoundaryArgs()
+    a.map, a.dist = map.data_ptr(), own("dist", dist, torch.uint8, (B, H, W))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    if (band is None) != (d is None):
+        raise ValueError("seg_boundary: band and d go together")
+    if band is not None:
+        a.band, a.d = own("band", band, map.dtype, (B, H, W)), int(d)
+    a.elem, a.B, a.H, a.W, a.dmax = map.element_size(), B, H, W, int(dmax)
+    L.check(L.lib().dfw_seg_boundary(C.byref(a), _stream()), "dfw_seg_boundary")
+
+
+def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
+    """Per-class counts of two boundary bands, on caller-owned buffers only: pred and gt uint8 [B, H, W] label maps, pdist
+    and gdist their seg_boundary dist maps, d the band's width (at most the dmax the maps were made with).  Per pixel:
+    dropped when gt > nlabels (255 included); l = pred if 1 <= pdist <= d else 0, g = gt if 1 <= gdist <= d else 0;
+    predicted[l]++ when l <= nlabels, truth[g]++, intersection[l]++ when l == g.  Writes counts int64 [B, 2, nlabels + 1] =
+    (intersections, unions), seg_labels' layout: metrics.boundary_iou(counts) is Boundary IoU per class.  nlabels is the
+    buffer's shape.  gdist is the distance of gt as given, so a class pixel beside a 255 region lies in the band.  Two
+    launches, no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_contiguous() or not pred.is_cuda:
+        raise ValueError("seg_boundary_counts: pred must be a contiguous uint8 device tensor [B, H, W]")
+    B, H, W = pred.shape
+    dev = pred.device
+    if counts.dim() != 3:
+        raise ValueError("seg_boundary_counts: counts must be int64 [B, 2, nlabels + 1]")
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+            raise ValueError(f"seg_boundary_counts: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegBoundaryCountsArgs()
+    a.pred, a.pdist = pred.data_ptr(), own("pdist", pdist, torch.uint8, (B, H, W))
+    a.gt, a.gdist = own("gt", gt, torch.uint8, (B, H, W)), own("gdist", gdist, torch.uint8, (B, H, W))
+    a.counts = own("counts", counts, torch.int64, (B, 2, counts.shape[2]))
+    a.B, a.H, a.W, a.d, a.nlabels = B, H, W, int(d), counts.shape[2] - 1
+    L.check(L.lib().dfw_seg_boundary_counts(C.byref(a), _stream()), "dfw_seg_boundary_counts")

@@ -1071,6 +1071,28 @@ class MarigoldPipelineRGBLatentNoise:
             return ob.object_scores(o, seg_u8, ob.planes_for_classes(seg_u8.shape[0], seg_u8.shape[1]), buffers)
         return ob.object_scores(o, seg_u8, ob.planes_for_binary(seg_u8.shape[0]), buffers)
 
+    def object_boundaries(self, o, **kw):
+        """The boundary bands of pipe.objects' result: objects.object_boundaries(o, **kw) -- d, ratio, dmax, buffers.
+        Returns dict(labels, ids, d); the band of the ids goes to pipe.match_objects for per-object Boundary IoU."""
+        from .objects import object_boundaries
+        return object_boundaries(o, **kw)
+
+    def boundary_counts(self, result, gt, nlabels, key="labels", **kw):
+        """Boundary IoU counts of a route's label map against a ground truth: objects.boundary_bands on
+        result["native"][key] when the route ran at native size (lists, one call per item), otherwise on result[key],
+        and on gt, then objects.boundary_counts.  key: "labels" for the N-way, candidate and tiled routes, "pred" for the
+        binary routes, as in pipe.objects.  gt: uint8, shaped like the map (a list for a native result).  The keywords (d,
+        ratio, dmax) are boundary_bands'.  Returns counts int64 [.., 2, nlabels + 1]; metrics.boundary_iou reads them."""
+        from .objects import boundary_bands, boundary_counts
+        src = result.get("native") or result
+        if src.get(key) is None:
+            raise KeyError(f"the result holds no {key!r} map (binary routes: key='pred')")
+        pred = src[key]
+        bp = boundary_bands(pred, **kw)
+        kw["d"] = bp["d"]
+        bg = boundary_bands(gt, **kw)
+        return boundary_counts(bp, bg, pred, gt, nlabels)
+
     def _replay(self, key, step, ins):
         """HIP-graph cache of the fused step: capture once per key into static input buffers, then one
         graph launch per call (the eager path pays ~750 ctypes launches of host time per step)."""

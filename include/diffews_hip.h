@@ -1043,6 +1043,68 @@ size_t dfw_seg_scores_workspace_bytes(int32_t B, int32_t cap);
 /* positions one workgroup covers: the size at which the kernel changes path, for tests and docs */
 int dfw_seg_scores_block(int32_t* pixels);
 
+/* Boundary bands (objects.boundary_bands, Boundary IoU of Cheng et al., CVPR 2021): the capped chessboard distance of
+ * every pixel of a label map or an id map to its own contour.  All integers: the result depends on no order of execution.
+ *
+ *   map is [B][H][W] of uint8 (elem = 1) or int32 (elem = 4).  Values are compared for equality only; 0 is background and
+ *   every other value -- 255, values above 255 and negative ints included -- is an object value.
+ *   For a pixel q = (y, x) with v = map[q] != 0, D(q) is the smallest max(|dy|, |dx|) to a position that lies outside the
+ *   image or holds a value != v: D >= 1, and a pixel on the image's edge or next to another value has D = 1.  Images of a
+ *   batch never see each other.
+ *   dist[q] = 0 where map[q] == 0, else min(D(q), dmax + 1): dmax + 1 means "deeper than dmax", so one dist answers every
+ *   band width d <= dmax.
+ *   band (optional, the type of map) holds map[q] where 1 <= dist[q] <= d and 0 elsewhere.  For the binary mask map == v
+ *   this is mask - eroded of the published mask_to_boundary (zero padding, d iterations of a 3 x 3 erosion).
+ *
+ * map [[7,7,7,7,7],[7,7,7,7,7],[7,7,7,7,7]] with dmax = 2: dist [[1,1,1,1,1],[1,2,2,2,1],[1,1,1,1,1]], and with d = 1 band
+ * is the map with its three middle pixels of the middle row set to 0.
+ *
+ * Two launches whatever the image holds (a row pass into ws, one byte a pixel, and a column pass that writes dist and
+ * band), no memset node, no host readback, no atomics and no thread that waits for another: the call can be captured and
+ * is correct at any residency.  The column pass takes four pixels a thread when W % 4 == 0 and map, band and dist are
+ * aligned to four elements; one pixel a thread otherwise.  Nothing is written outside dist, band and ws; map is read only.
+ *
+ * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / map / dist / ws; elem not 1 or
+ * 4; dmax outside 1..254; d outside 1..dmax when band is given; B, H or W < 1.  DFW_ERANGE: H, W or B above 65535, H * W
+ * above 2^30.  DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: dist, band or ws overlapping map or each other.
+ * DFW_ESHAPE: an int32 map or band not 4-byte aligned, ws not 4-byte aligned.
+ */
+typedef struct {
+  const void* map;              /* [B][H][W] of uint8 or int32, contiguous, read only */
+  uint8_t* dist;                /* out [B][H][W] */
+  void* band;                   /* out [B][H][W] of map's type, or null */
+  void* ws;
+  size_t ws_bytes;
+  int32_t elem, B, H, W, dmax, d;
+} dfw_seg_boundary_args;
+int dfw_seg_boundary(const dfw_seg_boundary_args* a, dfw_stream_t stream);
+/* 0 for sizes dfw_seg_boundary refuses (B, H or W < 1 or above 65535, H * W above 2^30, elem not 1 or 4) */
+size_t dfw_seg_boundary_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t elem);
+/* the tile of the column pass (rows x cols) and the positions a workgroup of the row pass covers, for tests and docs */
+int dfw_seg_boundary_block(int32_t* rows, int32_t* cols, int32_t* positions);
+
+/* Per-class counts of two boundary bands, in dfw_seg_labels' counts layout.  Per pixel: dropped when gt > nlabels (255
+ * included); else l = pred if 1 <= pdist <= d, else 0, and g = gt if 1 <= gdist <= d, else 0; predicted[l]++ when l <=
+ * nlabels, truth[g]++, intersection[l]++ when l == g.  counts [B][2][nlabels + 1] = (intersections, unions = predicted +
+ * truth - intersection) per image; bin 0 holds the pixels in neither band.  gdist is the distance of gt as given: 255 is a
+ * value like any other there, so a class pixel beside an ignore region lies in the band.  Counts for several d come from
+ * one pair of dist maps by calling again.  Two launches: a library kernel zeroes counts (no memset node), then LDS
+ * histograms per workgroup flushed with 64-bit integer atomics; capturable, order-free.
+ *
+ * Validated in this order.  DFW_EINVAL: null args / pred / pdist / gt / gdist / counts; d outside 1..254; nlabels outside
+ * 1..254; B, H or W < 1.  DFW_ERANGE: as dfw_seg_boundary.  DFW_EINVAL: counts overlapping an input.  DFW_ESHAPE: counts
+ * not 8-byte aligned.
+ */
+typedef struct {
+  const uint8_t* pred;          /* [B][H][W] label bytes, read only */
+  const uint8_t* pdist;         /* [B][H][W] dfw_seg_boundary's dist of pred */
+  const uint8_t* gt;            /* [B][H][W] */
+  const uint8_t* gdist;         /* [B][H][W] dist of gt */
+  int64_t* counts;              /* out [B][2][nlabels + 1] */
+  int32_t B, H, W, d, nlabels;
+} dfw_seg_boundary_counts_args;
+int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t stream);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
