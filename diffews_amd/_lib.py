@@ -116,6 +116,12 @@ class SegComponentsArgs(C.Structure):
                 ("min_area", _i32), ("cap", _i32), ("nlabels", _i32)]
 
 
+class SegHolesArgs(C.Structure):
+    _fields_ = [("labels", _vp), ("ids", _vp), ("stats", _vp), ("gt", _vp), ("ids_out", _vp), ("labels_out", _vp),
+                ("holes", _vp), ("stats_out", _vp), ("counts", _vp), ("ws", _vp), ("ws_bytes", _sz), ("B", _i32), ("H", _i32),
+                ("W", _i32), ("connectivity", _i32), ("max_area", _i32), ("cap", _i32), ("nlabels", _i32)]
+
+
 class SegRleArgs(C.Structure):
     _fields_ = [("ids", _vp), ("runs", _vp), ("run_off", _vp), ("nruns", _vp), ("ws", _vp), ("ws_bytes", _sz), ("B", _i32),
                 ("H", _i32), ("W", _i32), ("cap", _i32), ("max_runs", _i32), ("order", _i32)]
@@ -336,6 +342,8 @@ SYMBOLS = {
     "dfw_seg_components_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dfw_seg_components_tile": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "dfw_seg_components_rounds": (_i32, [_i32, _i32, _i32, _vp, C.POINTER(SegComponentsRounds)]),
+    "dfw_seg_holes": (_i32, [C.POINTER(SegHolesArgs), _vp]),
+    "dfw_seg_holes_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
     "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),

@@ -26,59 +26,13 @@
 //                            x0 / y1 / x1 per tile-local component by LDS atomics, then one global atomicMin / atomicMax per
 //                            (tile, local component) and field, only for ids <= cap (y0 is the first pixel's row)
 //
-// Termination: no thread waits for another thread or workgroup.  Every loop is a find, which reads strictly decreasing
-// indices (it stops at any word that is not smaller than the index it was read at, so even a damaged workspace cannot send
-// it round or outside), or a union's retry, where a failed atomicMin replaces the larger root by a strictly smaller index.
-// A find may read a stale parent (another CU's L1, another XCD's L2): that is an older ancestor of the same set, and the
-// atomicMin on the word itself returns the truth, so a stale read costs a round, never a wrong link.
+// Launches 1 to 3, the grids' sizing and the argument why every loop ends are seg_unionfind.h's, shared with seg_holes.hip.
 #include "common.h"
 #include "seg_fuse.h"
 #include "seg_scan.h"
+#include "seg_unionfind.h"
 
 namespace dfw {
-
-constexpr int kCcTH = 32, kCcTW = 64, kCcTile = kCcTH * kCcTW;   // 2048 pixels, 8 per thread of 256
-constexpr int kCcWords = kCcTile / 4;
-
-// ---- union-find in LDS ----
-__device__ __forceinline__ int lds_find(const volatile int* par, int i) {
-  for (;;) {
-    const int p = par[i];
-    if ((unsigned)p >= (unsigned)i) return i;
-    i = p;
-  }
-}
-__device__ __forceinline__ void lds_union(int* par, int a, int b) {
-  for (;;) {
-    a = lds_find(par, a);
-    b = lds_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&par[a], b);
-    if (old == a) return;
-    a = old;                             // somebody linked a first: old < a, go on from there
-  }
-}
-
-// ---- union-find in global memory ----
-__device__ __forceinline__ int g_find(const int32_t* par, int i) {
-  for (;;) {
-    const int p = __hip_atomic_load(par + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned)p >= (unsigned)i) return i;
-    i = p;
-  }
-}
-__device__ __forceinline__ void g_union(int32_t* par, int a, int b) {
-  for (;;) {
-    a = g_find(par, a);
-    b = g_find(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(&par[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 // id of the component of foreground pixel p once cc_number_kernel has run: a root holds it in area, a local root (area > 0)
 // points at its root, every other pixel at its local root.
@@ -88,169 +42,19 @@ __device__ __forceinline__ int cc_id(const int32_t* parent, const int32_t* area,
   return area[parent[pa]];
 }
 
+// The three union-find passes (seg_unionfind.h) on the label bytes themselves: equal non-zero bytes join.
 __global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* labels, int32_t* parent, int32_t* area, int H, int W,
                                                       int conn8) {
-  __shared__ uint32_t lab4[kCcWords];
-  __shared__ int par[kCcTile];
-  __shared__ int cnt[kCcTile];
-  const uint8_t* lab = (const uint8_t*)lab4;
-  const int ty0 = blockIdx.y * kCcTH, tx0 = blockIdx.x * kCcTW;
-  const size_t img = (size_t)blockIdx.z * H * W;
-  const uint8_t* L = labels + img;
-  int32_t* P = parent + img;
-  int32_t* A = area + img;
-  const bool vec = (W & 3) == 0 && ((uintptr_t)labels & 3) == 0 && (((uintptr_t)parent | (uintptr_t)area) & 15) == 0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int w = threadIdx.x + 256 * k, y = ty0 + (w >> 4), x = tx0 + (w & 15) * 4;
-    uint32_t v = 0u;
-    if (y < H) {
-      const size_t o = (size_t)y * W + x;
-      if (vec) {
-        if (x < W) v = *(const uint32_t*)(L + o);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (x + j < W) v |= (uint32_t)L[o + j] << (8 * j);
-      }
-    }
-    lab4[w] = v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      par[4 * w + j] = 4 * w + j;
-      cnt[4 * w + j] = 0;
-    }
-  }
-  __syncthreads();
-  // a pixel joins its left and upper neighbour; with 8 neighbours the two upper diagonals only where the upper one is
-  // another byte (else they reach this pixel through it)
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int w = threadIdx.x + 256 * k, ly = w >> 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int l = 4 * w + j, lx = l & (kCcTW - 1);
-      const uint8_t c = lab[l];
-      if (c == 0) continue;
-      if (lx > 0 && lab[l - 1] == c) lds_union(par, l, l - 1);
-      if (ly > 0) {
-        if (lab[l - kCcTW] == c) {
-          lds_union(par, l, l - kCcTW);
-        } else if (conn8) {
-          if (lx > 0 && lab[l - kCcTW - 1] == c) lds_union(par, l, l - kCcTW - 1);
-          if (lx < kCcTW - 1 && lab[l - kCcTW + 1] == c) lds_union(par, l, l - kCcTW + 1);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  int root[2][4];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int w = threadIdx.x + 256 * k;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) root[k][j] = lab[4 * w + j] ? lds_find(par, 4 * w + j) : -1;
-    // one LDS atomic per run of equal roots among the four
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (root[k][j] < 0 || (j > 0 && root[k][j - 1] == root[k][j])) continue;
-      int n = 1;
-      bool run = true;
-#pragma unroll
-      for (int i = 1; i < 4; ++i)
-        if (j + i < 4) {
-          run = run && root[k][j + i] == root[k][j];
-          n += run;
-        }
-      atomicAdd(&cnt[root[k][j]], n);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int w = threadIdx.x + 256 * k, y = ty0 + (w >> 4), x = tx0 + (w & 15) * 4;
-    if (y >= H || x >= W) continue;
-    int gp[4], ga[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = root[k][j];
-      gp[j] = r < 0 ? -1 : (ty0 + (r >> 6)) * W + tx0 + (r & (kCcTW - 1));
-      ga[j] = r == 4 * w + j ? cnt[r] : 0;
-    }
-    const size_t o = (size_t)y * W + x;
-    if (vec) {
-      *(i32x4*)(P + o) = i32x4{gp[0], gp[1], gp[2], gp[3]};
-      *(i32x4*)(A + o) = i32x4{ga[0], ga[1], ga[2], ga[3]};
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (x + j < W) {
-          P[o + j] = gp[j];
-          A[o + j] = ga[j];
-        }
-    }
-  }
+  cc_tile_body<cc_key_label>(labels, parent, area, H, W, conn8);
 }
 
-// Items of an image: (ntx - 1) * H pixels on the left column of a tile (not the image's), then (nty - 1) * W on a top row.
 __global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t* labels, int32_t* parent, int H, int W, int ntx, int nty,
                                                        int conn8) {
-  const size_t img = (size_t)blockIdx.y * H * W;
-  const uint8_t* L = labels + img;
-  int32_t* P = parent + img;
-  const long long nv = (long long)(ntx - 1) * H, total = nv + (long long)(nty - 1) * W;
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-    if (t < nv) {
-      const int c = (int)(t / H), y = (int)(t - (long long)c * H), x = (c + 1) * kCcTW;
-      const int a = y * W + x;
-      const uint8_t la = L[a];
-      if (la == 0) continue;
-      if (L[a - 1] == la) {
-        // the pixel above joins the same two tile-local components
-        const bool dup = (y % kCcTH) != 0 && L[a - W] == la && L[a - W - 1] == la;
-        if (!dup) g_union(P, a, a - 1);
-      } else if (conn8) {
-        if (y > 0 && L[a - W - 1] == la) g_union(P, a, a - W - 1);
-        if (y + 1 < H && L[a + W - 1] == la) g_union(P, a, a + W - 1);
-      }
-    } else {
-      const long long u = t - nv;
-      const int r = (int)(u / W), x = (int)(u - (long long)r * W), y = (r + 1) * kCcTH;
-      const int a = y * W + x, up = a - W;
-      const uint8_t la = L[a];
-      if (la == 0) continue;
-      if (L[up] == la) {
-        const bool dup = (x % kCcTW) != 0 && L[a - 1] == la && L[up - 1] == la;
-        if (!dup) g_union(P, a, up);
-      } else if (conn8) {
-        if (x > 0 && L[up - 1] == la) g_union(P, a, up - 1);
-        if (x + 1 < W && L[up + 1] == la) g_union(P, a, up + 1);
-      }
-    }
-  }
+  cc_merge_body<cc_key_label>(labels, parent, H, W, ntx, nty, conn8);
 }
 
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int32_t* parent, int32_t* area, int HW) {
-  const size_t img = (size_t)blockIdx.y * HW;
-  int32_t* P = parent + img;
-  int32_t* A = area + img;
-  auto one = [&](int p, int a) {
-    if (a <= 0) return;                  // not a local root
-    const int r = g_find(P, p);
-    if (r == p) return;
-    P[p] = r;
-    atomicAdd(&A[r], a);
-  };
-  if ((HW & 3) == 0 && ((uintptr_t)area & 15) == 0) {
-    const int n4 = HW >> 2;
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) {
-      const i32x4 a = *(const i32x4*)(A + 4 * (size_t)e);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) one(4 * e + j, a[j]);
-    }
-  } else {
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) one(p, A[p]);
-  }
+  cc_flatten_body(parent, area, HW);
 }
 
 // The 8 consecutive pixels of this thread in block blockIdx.x of the image: which are roots (bit j of *roots) and their
@@ -475,33 +279,6 @@ __global__ __launch_bounds__(256) void cc_apply_kernel(const uint8_t* labels, co
     }
 }
 
-static size_t cc_blocks(long long HW) { return (size_t)((HW + kCcTile - 1) / kCcTile); }
-
-// The sizes dfw_seg_components refuses, and its rounds query with it: DFW_EINVAL before DFW_ERANGE.
-static int cc_size_error(long long B, long long H, long long W) {
-  if (B < 1 || H < 1 || W < 1) return DFW_EINVAL;
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
-  return 0;
-}
-
-// One inline function per launch whose kernel loops: the grid, and with it the trips of the loop.
-constexpr int kCcGridCap = 4096;
-// cc_merge_kernel: one thread per item, grid-stride behind the cap.
-inline long long cc_merge_items(int H, int W) {
-  const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH;
-  return (long long)(ntx - 1) * H + (long long)(nty - 1) * W;
-}
-inline int cc_merge_grid(long long items) {
-  return (int)((items + 255) / 256 > kCcGridCap ? kCcGridCap : (items + 255) / 256);
-}
-// cc_flatten_kernel: the grid is sized for four pixels a thread; the kernel takes that path when HW is a multiple of
-// four and area is 16-byte aligned, else one pixel a thread over the same grid.  cc_flatten_vector repeats the kernel's
-// own test for the query (the kernel decides on the device; the launcher never asks): keep the two in step.
-inline int cc_flatten_grid(int HW) {
-  const int per = (HW + 3) / 4;
-  return (per + 255) / 256 > kCcGridCap ? kCcGridCap : (per + 255) / 256;
-}
-inline bool cc_flatten_vector(int HW, uintptr_t area) { return (HW & 3) == 0 && (area & 15) == 0; }
 // cc_scan_kernel: 256 block sums a round, one workgroup per image.
 inline int cc_scan_rounds(int nblk) { return (nblk + 255) / 256; }
 inline int cc_grid_rounds(long long items, int gx) { return gx < 1 ? 0 : (int)((items + 256ll * gx - 1) / (256ll * gx)); }

@@ -7,6 +7,10 @@ of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own s
 objects_to_host, which copies the two small tables (n and stats) once, runs_to_host, matches_to_host, scores_to_host and
 detections_to_host.
 
+fill_holes is the partner of min_area: the background regions that ONE object encloses, up to max_area pixels, take that
+object's id and label (ops.seg_holes), and the result is again a label_objects result, so every stage below takes it.  A
+region between two objects, or one with an island of another object inside, is left alone.
+
 object_runs adds each object's SHAPE: the run-length encoding of the id map (ops.seg_rle), in row or column (COCO) order,
 still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the host and into the usual forms.
 
@@ -134,6 +138,113 @@ def objects_to_host(r):
     objs = [[(s[0], s[1], (s[2], s[3], s[4], s[5]), s[6]) for s in stats[b][:min(n[b][0], cap)]] for b in range(B)]
     truncated = any(n[b][0] > cap for b in range(B))
     return (objs[0] if single else objs), truncated
+
+
+# ------------------------------------------------------------------------------------------------ holes
+
+class HoleBuffers:
+    """Everything one fill_holes call of a shape writes, allocated once: ids int32 [B, H, W], labels uint8 [B, H, W],
+    holes int32 [B, 2], stats int32 [B, max_components, 8], the workspace, and -- made on first use for a number of
+    classes -- counts int64 [B, 2, nlabels + 1].  max_components is that of the label_objects result the calls take.  A
+    later call with the same buffers overwrites them."""
+
+    def __init__(self, B, H, W, max_components=1024, device="cuda"):
+        self.shape, self.max_components = (int(B), int(H), int(W)), int(max_components)
+        if self.max_components < 1:
+            raise ValueError("max_components must be at least 1")
+        nbytes = ops.seg_holes_workspace(*self.shape)
+        if nbytes == 0:
+            raise ValueError(f"seg_holes refuses these sizes: {self.shape}")
+        dev = torch.device(device)
+        self.ids = torch.empty(self.shape, dtype=torch.int32, device=dev)
+        self.device = self.ids.device                                  # "cuda" resolved to the current device
+        self.labels = torch.empty(self.shape, dtype=torch.uint8, device=dev)
+        self.holes = torch.empty(self.shape[0], 2, dtype=torch.int32, device=dev)
+        self.stats = torch.empty(self.shape[0], self.max_components, 8, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._counts = {}
+
+    def counts(self, nlabels):
+        c = self._counts.get(nlabels)
+        if c is None:
+            c = self._counts[nlabels] = torch.empty(self.shape[0], 2, nlabels + 1, dtype=torch.int64, device=self.device)
+        return c
+
+
+def _holes_one(o, max_area, connectivity, gt, nlabels, buffers):
+    if connectivity not in (4, 8):
+        raise ValueError(f"fill_holes: connectivity must be 4 or 8, not {connectivity!r}")
+    if max_area is not None and not 0 <= int(max_area) <= 2 ** 31 - 1:
+        raise ValueError(f"fill_holes: max_area must lie in 0..2^31 - 1 (None: no limit), got {max_area}")
+    ids, labels, n, stats = o["ids"], o["labels"], o["n"], o["stats"]
+    squeeze = ids.dim() == 2
+    if squeeze:
+        ids, labels, stats, gt = ids[None], labels[None], stats[None], None if gt is None else gt[None]
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda or labels.dtype != torch.uint8 or labels.shape != ids.shape:
+        raise ValueError("fill_holes takes a label_objects result: ids int32 and labels uint8 on the device, [H, W] or "
+                         "[B, H, W], or lists of [h, w] maps")
+    B, H, W = ids.shape
+    if stats.dim() != 3 or stats.dtype != torch.int32 or stats.shape[0] != B or stats.shape[2] != 8:
+        raise ValueError("fill_holes: stats must be the int32 [.., max_components, 8] table of the label_objects result")
+    cap = stats.shape[1]
+    if buffers is None:
+        buffers = HoleBuffers(B, H, W, cap, ids.device)
+    elif buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.max_components != cap:
+        raise ValueError(f"buffers were made for {buffers.shape} with {buffers.max_components} components on {buffers.device}, "
+                         f"the objects are {(B, H, W)} with {cap} on {ids.device}")
+    counts = None
+    if gt is not None:
+        if nlabels is None:
+            raise ValueError("fill_holes: a ground truth needs nlabels, the number of classes")
+        if gt.dtype != torch.uint8 or gt.shape != ids.shape:
+            raise ValueError("fill_holes: gt must be uint8 and shaped like the labels")
+        gt, counts = gt.contiguous(), buffers.counts(int(nlabels))
+    ops.seg_holes(labels.contiguous(), ids.contiguous(), buffers.ids, buffers.labels, buffers.holes, buffers.ws,
+                  stats=stats.contiguous(), stats_out=buffers.stats, gt=gt, counts=counts, connectivity=connectivity,
+                  max_area=max_area, nlabels=nlabels)
+    r = dict(ids=buffers.ids, labels=buffers.labels, stats=buffers.stats, counts=counts, holes=buffers.holes)
+    if squeeze:
+        r = {k: (None if v is None else v[0]) for k, v in r.items()}
+    r["n"] = n
+    return r
+
+
+def fill_holes(o, max_area=None, connectivity=8, gt=None, nlabels=None, buffers=None):
+    """Fills the pinholes of the objects of a label_objects result o -- the partner of its min_area, which turns a speck
+    inside an object into background, a hole that object_runs, match_objects and boundary_bands would all see.
+
+    A region is a connected component of background pixels (labels == 0) under the DUAL of `connectivity`, which is the
+    objects' and must be the one o was made with: 4 neighbours for 8-connected objects, 8 for 4-connected ones.  It is
+    enclosed when none of its pixels lies on the first or last row or column.  Its owner is the id of the pixel to the left
+    of its first pixel (the smallest y * W + x).  It is FILLED when it is enclosed, the owner is at least 1, every
+    non-background pixel in the neighbourhood of its pixels carries the owner's id, and it has at most max_area pixels
+    (None: no limit; 0 fills nothing).  NOT filled, on purpose: a region bordered by two objects, whether or not they share
+    a class, and a hole with an island of another object inside -- label_objects(min_area=k) removes such islands first.
+    gt (optional, with nlabels): as label_objects takes it.
+
+    Returns dict(ids, labels, n, stats, counts, holes), all on the device and itself a label_objects result, which
+    objects_to_host, object_runs, match_objects, object_scores, object_boundaries and boundary_counts take unchanged:
+      ids, labels  o's maps with every pixel of a filled region set to the owner's id and label byte
+      n            o's n, passed through: filling neither adds nor removes an object
+      stats        o's stats with column 1 (area) grown by, and column 7 set to, the object's filled pixels; label, box and
+                   first pixel do not change.  Re-labelling `labels` with label_objects gives exactly these ids and, with
+                   column 7 zeroed, these stats
+      counts       int64 [.., 2, nlabels + 1] (intersections, unions) of the filled labels against gt, or None
+      holes        int32 [.., 2] = (regions filled, regions enclosed)
+    A [H, W] result gives the same without the batch axis.  A list (native-size) result is handled with ONE CALL PER ITEM;
+    gt is then a list too and buffers a list of HoleBuffers or None.  buffers: a HoleBuffers of this shape and
+    max_components, reused call after call (the result then aliases it).  At most 6 launches per call and no host
+    synchronisation."""
+    if isinstance(o["ids"], (list, tuple)):
+        k = len(o["ids"])
+        gts = gt if gt is not None else [None] * k
+        bufs = buffers if buffers is not None else [None] * k
+        if len(gts) != k or len(bufs) != k:
+            raise ValueError("fill_holes: one gt / buffers entry per item")
+        per = [_holes_one({key: o[key][i] for key in ("ids", "labels", "n", "stats")}, max_area, connectivity, g, nlabels, b)
+               for i, (g, b) in enumerate(zip(gts, bufs))]
+        return {key: [p[key] for p in per] for key in ("ids", "labels", "n", "stats", "counts", "holes")}
+    return _holes_one(o, max_area, connectivity, gt, nlabels, buffers)
 
 
 # ------------------------------------------------------------------------------------------------ run-length encodings

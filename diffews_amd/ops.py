@@ -1085,6 +1085,60 @@ def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, count
     L.check(L.lib().dfw_seg_components(C.byref(a), _stream()), "dfw_seg_components")
 
 
+def seg_holes_workspace(B, H, W):
+    """Bytes of seg_holes' workspace for [B, H, W] maps; 0 for sizes the call refuses."""
+    return int(L.lib().dfw_seg_holes_workspace_bytes(int(B), int(H), int(W)))
+
+
+def seg_holes(labels, ids, ids_out, labels_out, holes, ws, stats=None, stats_out=None, gt=None, counts=None, connectivity=8,
+              max_area=None, nlabels=None):
+    """Fills the holes of labelled objects, on caller-owned buffers only (objects.HoleBuffers holds a set): labels uint8
+    [B, H, W] and ids int32 [B, H, W], normally seg_components' filtered and ids.  A region is a connected component of
+    zero bytes under the DUAL of `connectivity` (the objects': 8 -> regions over 4 neighbours, 4 -> over 8); it is filled
+    when it touches no row or column of the image frame, the id left of its first pixel (the owner) is at least 1, every
+    non-background pixel around it carries that id, and it has at most max_area pixels (None: 2^31 - 1; 0 fills nothing).
+    Regions bordered by two objects -- of one class or two -- and holes with an island of another object inside are left
+    alone.  Writes ids_out int32 and labels_out uint8 [B, H, W] (the inputs with every filled pixel set to the owner's id
+    and label byte), holes int32 [B, 2] = (regions filled, regions enclosed) and, where given, stats_out int32 [B, cap, 8]
+    = stats with column 1 (area) grown by, and column 7 set to, each object's filled pixels, and counts int64 [B, 2,
+    nlabels + 1], seg_labels' counts of labels_out against gt uint8 [B, H, W].  No output may share memory with an input.
+    ws: a uint8 buffer of at least seg_holes_workspace(B, H, W) bytes, which needs no initialisation.  A fixed number of
+    launches (at most 6), no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
+    B, H, W = labels.shape
+    dev = labels.device
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_holes: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegHolesArgs()
+    a.labels, a.ids = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W))
+    a.ids_out, a.labels_out = own("ids_out", ids_out, torch.int32, (B, H, W)), own("labels_out", labels_out, torch.uint8, (B, H, W))
+    a.holes = own("holes", holes, torch.int32, (B, 2))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    if (stats is None) != (stats_out is None):
+        raise ValueError("seg_holes: stats and stats_out come together")
+    if stats is not None:
+        if stats.dim() != 3:
+            raise ValueError("seg_holes: stats must be int32 [B, cap, 8]")
+        cap = stats.shape[1]
+        a.stats, a.stats_out, a.cap = own("stats", stats, torch.int32, (B, cap, 8)), own("stats_out", stats_out, torch.int32, (B, cap, 8)), cap
+    if counts is not None and gt is None:
+        raise ValueError("seg_holes: counts need a ground truth")
+    if gt is not None:
+        if nlabels is None:
+            raise ValueError("seg_holes: a ground truth needs nlabels, the number of classes")
+        a.gt, a.nlabels = own("gt", gt, torch.uint8, (B, H, W)), int(nlabels)
+        if counts is not None:
+            a.counts = own("counts", counts, torch.int64, (B, 2, int(nlabels) + 1))
+    max_area = 2 ** 31 - 1 if max_area is None else int(max_area)
+    if not 0 <= max_area <= 2 ** 31 - 1:
+        raise ValueError(f"seg_holes: max_area must lie in 0..2^31 - 1, got {max_area}")
+    a.B, a.H, a.W, a.connectivity, a.max_area = B, H, W, int(connectivity), max_area
+    L.check(L.lib().dfw_seg_holes(C.byref(a), _stream()), "dfw_seg_holes")
+
+
 _RLE_ORDERS = {"row": 0, "column": 1}
 
 

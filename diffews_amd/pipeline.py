@@ -1071,6 +1071,12 @@ class MarigoldPipelineRGBLatentNoise:
             return ob.object_scores(o, seg_u8, ob.planes_for_classes(seg_u8.shape[0], seg_u8.shape[1]), buffers)
         return ob.object_scores(o, seg_u8, ob.planes_for_binary(seg_u8.shape[0]), buffers)
 
+    def fill_holes(self, o, **kw):
+        """Fills the holes of the objects of pipe.objects' result: objects.fill_holes(o, **kw) -- max_area, connectivity,
+        gt, nlabels, buffers.  Returns a result of the same form (plus `holes`), which every object stage takes."""
+        from .objects import fill_holes
+        return fill_holes(o, **kw)
+
     def object_boundaries(self, o, **kw):
         """The boundary bands of pipe.objects' result: objects.object_boundaries(o, **kw) -- d, ratio, dmax, buffers.
         Returns dict(labels, ids, d); the band of the ids goes to pipe.match_objects for per-object Boundary IoU."""

@@ -836,6 +836,67 @@ typedef struct {
 int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const void* ws, dfw_seg_components_rounds_out* out);
 
 /*
+ * Filling the holes of labelled objects (version >= 120): the partner of min_area.  labels and ids are normally the
+ * `filtered` and `ids` outputs of dfw_seg_components (any pair of maps is accepted).  All integers: the result is exact and
+ * depends on no order of execution.
+ *
+ *   background     a pixel whose labels byte is 0; every other byte, 255 included, is not
+ *   region         a connected component of background pixels under the DUAL connectivity hc: 4 when `connectivity` (that
+ *                  of the objects, as dfw_seg_components takes it) is 8, and 8 when it is 4
+ *   enclosed       no pixel of the region lies on the first or last row or on the first or last column; a map with H < 3
+ *                  or W < 3 therefore has no enclosed region
+ *   owner          the ids value of the pixel to the LEFT of the region's first pixel, the smallest y * W + x; for an
+ *                  enclosed region that pixel exists and is not background
+ *   border pixels  the non-background pixels in the hc-neighbourhood of any pixel of the region
+ *   filled         enclosed, owner >= 1, every border pixel has ids == owner, and area <= max_area (>= 0; 0 fills nothing)
+ *
+ * NOT filled, on purpose: a region bordered by two objects, whether or not the two share a class (two 4-connected objects
+ * of one class that touch diagonally included), and a hole with an island of another object inside it.  min_area removes
+ * such islands first, so a second rule is not needed.
+ *
+ *   ids_out, labels_out  the inputs, except that every pixel of a filled region takes the owner's id and the owner's label
+ *                  byte, the labels byte of the pixel to the left of the region's first pixel
+ *   holes          per image (regions filled, regions enclosed)
+ *   stats_out      optional, needs stats and cap >= 1: stats, except that in the rows of ids <= cap column 1 (area) grows
+ *                  by the object's filled pixels and column 7 (0 so far) holds that number.  Label, box and first pixel
+ *                  do not change: a hole lies inside its owner's box and behind its first pixel
+ *   counts         optional, needs gt and nlabels: dfw_seg_components' counting rule applied to labels_out
+ *   ws             dfw_seg_holes_workspace_bytes(B, H, W) bytes, 8 per pixel.  The call writes every word it reads: the
+ *                  caller initialises nothing
+ *
+ * A fixed number of launches (6, or 5 for an image of one tile), chosen by the arguments and never by the image: the three
+ * union-find passes of dfw_seg_components on the zero bytes (their grids are that call's, so dfw_seg_components_rounds
+ * describes their trips), one pass over the frame pixels that also zeroes holes and counts and copies stats, one pass that
+ * decides per region, one that writes the outputs.  No host readback, no memset or copy node, no thread that waits for
+ * another: the call can be captured.  The filled pixels reach stats_out as one atomic per (tile, tile-local region) and
+ * field, holes as one per tile and field, never one per pixel.
+ *
+ * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / labels / ids / ids_out /
+ * labels_out / holes / ws; B, H or W < 1; connectivity not 4 or 8; max_area < 0; stats_out without stats or with cap < 1;
+ * counts without gt; gt with nlabels outside 1..254.  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535 (also
+ * B * cap * 8 above 2^31 - 1 with stats_out).  DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: an output or the
+ * workspace sharing a byte with an input or with another output (stats only counts with stats_out, counts only with gt).
+ * DFW_ESHAPE: ws / ids / ids_out / holes / stats / stats_out not 4-byte aligned, counts not 8-byte.
+ */
+typedef struct {
+  const uint8_t* labels;   /* [B][H][W] contiguous; 0 = background */
+  const int32_t* ids;      /* [B][H][W] the object of every pixel, 0 = none */
+  const int32_t* stats;    /* optional [B][cap][8], dfw_seg_components' stats: read only with stats_out */
+  const uint8_t* gt;       /* optional [B][H][W], as dfw_seg_labels takes it */
+  int32_t* ids_out;        /* out [B][H][W] */
+  uint8_t* labels_out;     /* out [B][H][W] */
+  int32_t* holes;          /* out [B][2]: (regions filled, regions enclosed) */
+  int32_t* stats_out;      /* out, optional [B][cap][8], needs stats and cap >= 1 */
+  int64_t* counts;         /* out, optional [B][2][nlabels+1], needs gt: intersections / unions of labels_out */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, connectivity, max_area, cap, nlabels;   /* connectivity 4 | 8: the OBJECTS'; max_area >= 0 */
+} dfw_seg_holes_args;
+int dfw_seg_holes(const dfw_seg_holes_args* a, dfw_stream_t stream);
+/* 0 for sizes dfw_seg_holes refuses (B, H or W < 1 or above 65535, H * W above 2^30) */
+size_t dfw_seg_holes_workspace_bytes(int32_t B, int32_t H, int32_t W);
+
+/*
  * Run-length encoding of labelled objects (version >= 115): the shape of every object of an id map, normally the one
  * dfw_seg_components wrote (any int32 map is accepted).  A pixel's position is q = y * W + x with order = 0 (rows) or
  * q = x * H + y with order = 1 (columns, COCO's order); its value v(q) is its id when 1 <= id <= cap and 0 otherwise (ids
