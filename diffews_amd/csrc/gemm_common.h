@@ -1,5 +1,11 @@
 // Shared between gemm.hip (128-wide tiles) and gemm_big.hip (256-row tiles): kernel parameters,
 // the epilogue for 4 consecutive output channels, tile coordinates.
+//
+// Non-finite values: every epilogue keeps an inf / NaN of the accumulator, bias, row bias or residual non-finite through
+// scale, SiLU, GEGLU and the 16-bit store (an fp32 result above the fp16 range is stored as +-inf), because the training
+// step's overflow guard reads only the norm of the final gradient (tests/test_nonfinite_gpu.py).  The one exception is
+// DFW_ACT_CLAMP1 = fminf(fmaxf(v, -1), 1): it clamps by design (+inf -> 1, -inf -> -1, NaN -> -1, fmaxf returning its
+// other operand); it is the decoder's last conv, inference only, and never lies between a loss and a gradient.
 #pragma once
 #include "common.h"
 

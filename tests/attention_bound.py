@@ -96,10 +96,12 @@ def key_segments(k, v, b, n_plain=0, nshot=0, k_bank=None, v_bank=None):
 
 # ------------------------------------------------------------------------------------------------ forward
 
-def fwd_ref(q, K, V, dtype, c=1.0, round_p=True, tile=64, nsplit=1, xattn=False):
+def fwd_ref(q, K, V, dtype, c=1.0, round_p=True, tile=64, nsplit=1, xattn=False, nonfinite=False):
     """fp64 reference and error allowance of one (image, head) of a forward kernel.  q [n, D], K / V [nk, D] (16-bit
     values, any device; K / V in the kernel's key order).  c: factor to log2 units (1: q pre-scaled).
-    Returns (r [n, D], e [n, D], lse [n], e_lse [n]): check(y, r, e, dtype) and check(lse_y, lse, e_lse, float32)."""
+    Returns (r [n, D], e [n, D], lse [n], e_lse [n]): check(y, r, e, dtype) and check(lse_y, lse, e_lse, float32).
+    nonfinite (tests/nonfinite.py): a score of -inf is a mask -- its probability is exactly 0 and carries no error, so its
+    score allowance (inf) is left out instead of turning the row's allowance into 0 x inf."""
     q, K, V = q.to(F64), K.to(F64), V.to(F64)
     n, D = q.shape
     nk = K.shape[0]
@@ -118,6 +120,8 @@ def fwd_ref(q, K, V, dtype, c=1.0, round_p=True, tile=64, nsplit=1, xattn=False)
         ri = P @ V
         PV = P @ Va
         es = C_ACC * U24 * (math.sqrt(D) * A + m.abs() + KDEFER) + (4 + nt) * U24 * (s.abs() + m.abs() + KDEFER)
+        if nonfinite:
+            es = torch.where(s == -math.inf, torch.zeros_like(es), es)
         Pe = P * (LN2 * es + E_EXP)
         ei = Pe @ Va + Pe.sum(1, keepdim=True) * ri.abs()                      # score + exp2
         if round_p:

@@ -163,12 +163,13 @@ def check(y, r, e, out_dtype, where=None, label="", show=6):
     return worst
 
 
-def gn_chunk_check(y, part, groups, bm, bn, label=""):
+def gn_chunk_check(y, part, groups, bm, bn, label="", nonfinite=False):
     """Fused GroupNorm partial sums part [B, chunks, groups, 2] (sum, sum of squares) of the NHWC output y [B, Ho, Wo, N]
     against fp64 sums of y per (image, chunk, group).  Chunk c of an image is wave row wm = c % WGM (WGM = 8 / (bn / 64)
     wave rows of bh / WGM pixel rows each, bh = bm / 16) of the bh x 16 pixel patch c // WGM (patches row-major): the
     slot the epilogues of conv_patch / conv_patch8 / gemm8 / gemm_big write.  Tolerance: recursive fp32 summation of
-    n terms in any order, n 2^-24 sum |y| (n + 1 for the squares).  Returns the worst err / tolerance ratio."""
+    n terms in any order, n 2^-24 sum |y| (n + 1 for the squares).  Returns the worst err / tolerance ratio.
+    nonfinite: see _nonfinite_slots."""
     B, Ho, Wo, N = y.shape
     cpg, wgm, bh = N // groups, 8 // (bn // 64), bm // 16
     band = bh // wgm
@@ -183,6 +184,8 @@ def gn_chunk_check(y, part, groups, bm, bn, label=""):
     tol_q = (n + 1) * 2.0 ** -24 * q + 1e-30
     ratio = torch.maximum((got[..., 0] - s).abs() / tol_s, (got[..., 1] - q).abs() / tol_q)
     ratio = torch.where(torch.isfinite(got).all(-1), ratio, torch.full_like(ratio, math.inf))
+    if nonfinite:
+        ratio = _nonfinite_slots(ratio, s, q, got, label)
     worst = float(ratio.max())
     if not worst <= 1.0:
         b, c, g = [int(t) for t in torch.nonzero(ratio == ratio.max())[0]]
@@ -190,6 +193,19 @@ def gn_chunk_check(y, part, groups, bm, bn, label=""):
                              f"(patch {c // wgm}, wave row {c % wgm}), group {g}: got {got[b, c, g].tolist()}, "
                              f"fp64 {[float(s[b, c, g]), float(q[b, c, g])]}")
     return worst
+
+
+def _nonfinite_slots(ratio, s, q, got, label):
+    """nonfinite=True of the chunk checkers (tests/nonfinite.py): a slot whose stored values sum to a non-finite number
+    must hold a non-finite sum and a non-finite sum of squares; such slots then count as exact (ratio 0), every other
+    slot keeps its ratio.  Finite y never reaches this."""
+    expect = ~(torch.isfinite(s) & torch.isfinite(q))
+    lost = expect & torch.isfinite(got).any(-1)
+    if bool(lost.any()):
+        b, c, g = [int(t) for t in torch.nonzero(lost)[0]]
+        raise AssertionError(f"{label}: fused GroupNorm sums finite over non-finite outputs at image {b}, chunk {c}, "
+                             f"group {g}: got {got[b, c, g].tolist()}")
+    return torch.where(expect, torch.zeros_like(ratio), ratio)
 
 
 def conv_small_ref(x, w, bias, taps, in_scale=1.0, out_scale=1.0):
@@ -223,11 +239,12 @@ def conv_small_ref(x, w, bias, taps, in_scale=1.0, out_scale=1.0):
     return r, e
 
 
-def cs_chunk_check(y, part, groups, iters, label=""):
+def cs_chunk_check(y, part, groups, iters, label="", nonfinite=False):
     """Fused GroupNorm partial sums part [B, chunks, groups, 2] of conv_small8w's NHWC output y [B, H, W, N] against
     fp64 sums of the STORED y per (image, chunk, group).  Chunk c of an image is the c-th run of 16 * iters consecutive
     8-pixel groups in row-major order (one workgroup's pixels).  Tolerance as in gn_chunk_check: recursive fp32 summation
-    of n terms in any order, n 2^-24 sum |y| (n + 1 for the squares).  Returns the worst err / tolerance ratio."""
+    of n terms in any order, n 2^-24 sum |y| (n + 1 for the squares).  Returns the worst err / tolerance ratio.
+    nonfinite: see _nonfinite_slots."""
     B, H, W, N = y.shape
     per_img, per_blk = H * (W // 8), 16 * iters
     assert W % 8 == 0 and per_img % per_blk == 0 and N % groups == 0, (H, W, iters, N, groups)
@@ -242,6 +259,8 @@ def cs_chunk_check(y, part, groups, iters, label=""):
     tol_q = (n + 1) * 2.0 ** -24 * q + 1e-30
     ratio = torch.maximum((got[..., 0] - s).abs() / tol_s, (got[..., 1] - q).abs() / tol_q)
     ratio = torch.where(torch.isfinite(got).all(-1), ratio, torch.full_like(ratio, math.inf))
+    if nonfinite:
+        ratio = _nonfinite_slots(ratio, s, q, got, label)
     worst = float(ratio.max())
     if not worst <= 1.0:
         b, c, g = [int(t) for t in torch.nonzero(ratio == ratio.max())[0]]

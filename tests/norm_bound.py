@@ -335,27 +335,31 @@ def colsum_ref(x, segs, scale=1.0, old=None):
 
 # ---------------------------------------------------------------------------------------- softmax
 
-def softmax_rows_ref(x, scale, approx_exp=False):
+def softmax_rows_ref(x, scale, approx_exp=False, nonfinite=False):
     """x [rows, L] fp32 -> (r, e) of softmax(x * scale).  Each probability exp2((x - m) c), c = fl(scale log2 e): the
     difference, c and the product are rounded (3 u |(x - m) scale| on the exponent), TRANS for exp2; the row sum
     (L / 256 terms per thread -- 4 L / 1024 in the register kernel --, butterfly, 4 waves) carries the p-weighted mean of
-    those plus acc(); the divide and the final product one u each.  approx_exp: __expf (softmax_groups), same budget."""
+    those plus acc(); the divide and the final product one u each.  approx_exp: __expf (softmax_groups), same budget.
+    nonfinite (tests/nonfinite.py): a logit of -inf is a mask -- its probability is exactly 0 and carries no error, so
+    its exponent term (inf) is left out of the row's allowance instead of turning it into 0 x inf."""
     rows, L = x.shape
     s = x.to(F64) * float(scale)
     m = s.max(1, keepdim=True).values
     p = torch.softmax(s, 1)
     eps_i = 3 * U32 * (s - m).abs() + TRANS
+    if nonfinite:
+        eps_i = torch.where(s == -math.inf, torch.zeros_like(eps_i), eps_i)
     path = [cdiv(L, 256), 6, 4] if not approx_exp else [L]
     rel = eps_i + (p * eps_i).sum(1, keepdim=True) + acc(path) + 3 * U32
     return p, p * rel
 
 
-def softmax_groups_ref(x, groups, L):
+def softmax_groups_ref(x, groups, L, nonfinite=False):
     """x [rows, ld] fp32 -> (r, e) [rows, ld]: softmax over each group's L entries; columns >= groups * L are exactly 0."""
     rows, ld = x.shape
     r = torch.zeros(rows, ld, dtype=F64, device=x.device)
     e = torch.zeros_like(r)
-    p, pe = softmax_rows_ref(x[:, :groups * L].reshape(rows * groups, L), 1.0, approx_exp=True)
+    p, pe = softmax_rows_ref(x[:, :groups * L].reshape(rows * groups, L), 1.0, approx_exp=True, nonfinite=nonfinite)
     r[:, :groups * L], e[:, :groups * L] = p.reshape(rows, -1), pe.reshape(rows, -1)
     return r, e
 
