@@ -127,6 +127,11 @@ class SegRleArgs(C.Structure):
                 ("H", _i32), ("W", _i32), ("cap", _i32), ("max_runs", _i32), ("order", _i32)]
 
 
+class SegContoursArgs(C.Structure):
+    _fields_ = [("ids", _vp), ("verts", _vp), ("rings", _vp), ("ring_off", _vp), ("n", _vp), ("ws", _vp), ("ws_bytes", _sz),
+                ("B", _i32), ("H", _i32), ("W", _i32), ("cap", _i32), ("max_edges", _i32), ("connectivity", _i32)]
+
+
 class SegMatchArgs(C.Structure):
     _fields_ = [("pids", _vp), ("gids", _vp), ("pstats", _vp), ("gstats", _vp), ("skip", _vp), ("pairs", _vp),
                 ("pair_off", _vp), ("area", _vp), ("match", _vp), ("gmatch", _vp), ("pq", _vp), ("n", _vp), ("ws", _vp),
@@ -157,6 +162,11 @@ class SegComponentsRounds(C.Structure):
 class SegSortRounds(C.Structure):
     _fields_ = [("blocks", _i32), ("block_scan", _i32), ("passes", _i32), ("table_scan", _i32), ("offsets_scan", _i32),
                 ("heads_scan", _i32)]
+
+
+class SegContoursTrips(C.Structure):
+    _fields_ = [("blocks", _i32), ("block_scan", _i32), ("doubling", _i32), ("ring_blocks", _i32), ("ring_scan", _i32),
+                ("passes", _i32), ("table_scan", _i32), ("offsets_scan", _i32), ("corners_scan", _i32), ("launches", _i32)]
 
 
 class InputImageItem(C.Structure):
@@ -344,6 +354,10 @@ SYMBOLS = {
     "dfw_seg_components_rounds": (_i32, [_i32, _i32, _i32, _vp, C.POINTER(SegComponentsRounds)]),
     "dfw_seg_holes": (_i32, [C.POINTER(SegHolesArgs), _vp]),
     "dfw_seg_holes_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dfw_seg_contours": (_i32, [C.POINTER(SegContoursArgs), _vp]),
+    "dfw_seg_contours_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "dfw_seg_contours_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "dfw_seg_contours_rounds": (_i32, [_i32] * 5 + [C.POINTER(SegContoursTrips)]),
     "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
     "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),

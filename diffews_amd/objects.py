@@ -4,8 +4,8 @@ minimum-area filter, and the filtered labels re-counted against a ground truth (
 Every segmentation route ends in a label map -- `labels` of segment_classes / segment_candidates / segment_tiled, `pred`
 of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own sizes -- and label_objects turns it into
 "which objects, how many, how big, where" without bringing the map to the host.  Nothing here synchronises except
-objects_to_host, which copies the two small tables (n and stats) once, runs_to_host, matches_to_host, scores_to_host and
-detections_to_host.
+objects_to_host, which copies the two small tables (n and stats) once, runs_to_host, contours_to_host, matches_to_host,
+scores_to_host and detections_to_host.
 
 fill_holes is the partner of min_area: the background regions that ONE object encloses, up to max_area pixels, take that
 object's id and label (ops.seg_holes), and the result is again a label_objects result, so every stage below takes it.  A
@@ -13,6 +13,10 @@ region between two objects, or one with an island of another object inside, is l
 
 object_runs adds each object's SHAPE: the run-length encoding of the id map (ops.seg_rle), in row or column (COCO) order,
 still on the device; runs_to_host / runs_to_coco / runs_to_mask bring it to the host and into the usual forms.
+
+object_contours gives each object's OUTLINE: rings of corner points on the pixel lattice (ops.seg_contours), the outer ring
+and the hole rings of every object, still on the device; contours_to_host brings them to the host, rings_to_geojson /
+rings_to_coco / rings_to_mask put them into the usual forms.
 
 match_objects says whether the objects are RIGHT: the objects of a prediction against those of a ground truth (ops.seg_match)
 -- the shared pixels of every pair, the areas, a one-to-one matching on IoU and (TP, FP, FN, sum of IoU) per class, which
@@ -379,6 +383,166 @@ def runs_to_mask(runs_k, h, w, order):
     np.add.at(edge, r[:, 0] + r[:, 1], -1)
     flat = np.cumsum(edge[:-1]) > 0
     return flat.reshape(h, w) if order == "row" else flat.reshape(w, h).T.copy()
+
+
+# ------------------------------------------------------------------------------------------------ outlines
+
+class ContourBuffers:
+    """Everything one object_contours call of a shape writes, allocated once: verts int32 [B, max_edges, 2], rings int32
+    [B, max_edges / 4, 4], ring_off int32 [B, max_components + 1], n int32 [B, 4] and the workspace (4 bytes a pixel and 64
+    a row of max_edges).  max_edges defaults to max(4096, H * W // 8) rounded down to a multiple of 4 -- a choice and not a
+    measurement: compact objects have far fewer unit edges than that, a map of single pixels has 4 * H * W and
+    object_contours reports it as not complete, with the number to size for in n[.., 0]."""
+
+    def __init__(self, B, H, W, max_components=1024, max_edges=None, device="cuda"):
+        self.shape, self.max_components = (int(B), int(H), int(W)), int(max_components)
+        self.max_edges = max(4096, int(H) * int(W) // 8) // 4 * 4 if max_edges is None else int(max_edges)
+        if self.max_components < 1 or self.max_edges < 4 or self.max_edges % 4:
+            raise ValueError("max_components must be at least 1 and max_edges a multiple of 4, at least 4")
+        nbytes = ops.seg_contours_workspace(B, H, W, self.max_components, self.max_edges)
+        if nbytes == 0:
+            raise ValueError(f"seg_contours refuses these sizes: {self.shape}, {self.max_components} objects, {self.max_edges} edges")
+        dev, i32 = torch.device(device), torch.int32
+        self.verts = torch.empty(B, self.max_edges, 2, dtype=i32, device=dev)
+        self.device = self.verts.device
+        self.rings = torch.empty(B, self.max_edges // 4, 4, dtype=i32, device=dev)
+        self.ring_off = torch.empty(B, self.max_components + 1, dtype=i32, device=dev)
+        self.n = torch.empty(B, 4, dtype=i32, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+_CONTOUR_KEYS = ("verts", "rings", "ring_off", "n")
+
+
+def _contours_one(ids, cap, connectivity, max_edges, buffers):
+    squeeze = ids.dim() == 2
+    if squeeze:
+        ids = ids[None]
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
+        raise ValueError("object_contours takes an int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
+    ids = ids.contiguous()
+    B, H, W = ids.shape
+    if buffers is None:
+        buffers = ContourBuffers(B, H, W, cap, max_edges, ids.device)
+    elif (buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.max_components != cap
+          or (max_edges is not None and buffers.max_edges != int(max_edges))):
+        raise ValueError(f"buffers were made for {buffers.shape}, {buffers.max_components} objects, {buffers.max_edges} edges "
+                         f"on {buffers.device}; the ids are {(B, H, W)} with {cap} objects on {ids.device}")
+    ops.seg_contours(ids, buffers.verts, buffers.rings, buffers.ring_off, buffers.n, buffers.ws, cap, connectivity)
+    r = {k: getattr(buffers, k) for k in _CONTOUR_KEYS}
+    if squeeze:
+        r = {k: v[0] for k, v in r.items()}
+    r.update(shape=(H, W), connectivity=connectivity)
+    return r
+
+
+def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_components=None):
+    """The outline of every object of an id map as rings of corner points.  o: a label_objects or fill_holes result -- the
+    ids are o["ids"] and the objects outlined are 1..cap, cap = the rows of o["stats"] -- or an int32 device tensor [H, W] /
+    [B, H, W] of ids (or a list of [h_i, w_i] maps) together with max_components=.  connectivity: 4 | 8, the one the ids
+    were made with.
+
+    Pixel (x, y) is the unit square from (x, y) to (x + 1, y + 1), so corners are lattice points 0..W x 0..H.  A ring runs
+    clockwise on screen (y down) with the object on its right; its area is the integral of x dy: positive for an outer
+    ring, negative for a hole ring.  Only corners are kept (no collinear points), the first being the first corner from the
+    ring's smallest edge.  With connectivity 8 a ring may touch itself at a vertex where two pixels meet diagonally.
+
+    Returns dict(verts, rings, ring_off, n, shape, connectivity), the tensors on the device:
+      n         int32 [.., 4] = (unit edges found, corners, rings, complete).  complete = 0: the image has more edges than
+                max_edges and NOTHING of it was written -- corners and rings are 0, ring_off is zero; size max_edges from
+                n[.., 0] and call again
+      rings     int32 [.., max_edges / 4, 4] = (id, first, count, area) sorted by id, an object's outer ring first and
+                its hole rings behind it; rows from n[.., 2] on hold whatever the buffer held
+      ring_off  int32 [.., cap + 1]: object k's rings are rows ring_off[k-1] .. ring_off[k]
+      verts     int32 [.., max_edges, 2] = (X, Y): ring r's corners are rows first .. first + count
+      shape     (H, W) of the map
+    A list is handled with ONE CALL PER ITEM and every value of the result is then a list, as in label_objects; `buffers`
+    is then a list of ContourBuffers or None.  buffers: a ContourBuffers of this shape and object count, reused call after
+    call (the result aliases it); max_edges: rows per image for fresh buffers (ContourBuffers' default otherwise).  A fixed
+    number of launches per call and no host synchronisation."""
+    if connectivity not in (4, 8):
+        raise ValueError(f"object_contours: connectivity must be 4 or 8, not {connectivity!r}")
+    if isinstance(o, dict):
+        if max_components is not None:
+            raise ValueError("object_contours: max_components comes from the result's stats table")
+        ids, stats = o["ids"], o["stats"]
+        caps = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
+    else:
+        if max_components is None:
+            raise ValueError("object_contours: an id tensor needs max_components, the highest id to outline")
+        ids = o
+        caps = [int(max_components)] * len(ids) if isinstance(ids, (list, tuple)) else int(max_components)
+    if isinstance(ids, (list, tuple)):
+        bufs = buffers if buffers is not None else [None] * len(ids)
+        if len(bufs) != len(ids):
+            raise ValueError("object_contours: one buffers entry per id map")
+        per = [_contours_one(i, c, connectivity, max_edges, b) for i, c, b in zip(ids, caps, bufs)]
+        return {k: [p[k] for p in per] for k in _CONTOUR_KEYS + ("shape", "connectivity")}
+    return _contours_one(ids, caps, connectivity, max_edges, buffers)
+
+
+def contours_to_host(c):
+    """object_contours' result -> (per image a list over the objects 1..n of lists of (area, int32 numpy [k, 2] of (X, Y)),
+    the outer ring first; incomplete) with TWO synchronising copies (per item for a list result): the tables n, ring_off
+    and rings first, then verts[:corners] of every image and nothing behind it.  n = the highest object with a ring.
+    incomplete: some image had more edges than max_edges; its list is empty.  A [H, W] result gives one image's list."""
+    if isinstance(c["n"], (list, tuple)):
+        per = [contours_to_host({k: v[i] for k, v in c.items()}) for i in range(len(c["n"]))]
+        return [p[0] for p in per], any(p[1] for p in per)
+    n, ring_off, rings, verts = c["n"], c["ring_off"], c["rings"], c["verts"]
+    single = n.dim() == 1
+    if single:
+        n, ring_off, rings, verts = n[None], ring_off[None], rings[None], verts[None]
+    B, cap = ring_off.shape[0], ring_off.shape[1] - 1
+    both = torch.cat([n.reshape(-1), ring_off.reshape(-1), rings.reshape(-1)]).cpu().numpy()       # copy one: the tables
+    n, ring_off = both[:4 * B].reshape(B, 4), both[4 * B:4 * B + B * (cap + 1)].reshape(B, cap + 1)
+    rings = both[4 * B + B * (cap + 1):].reshape(B, -1, 4)
+    corners = n[:, 1].tolist()
+    flat = torch.cat([verts[b, :corners[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 2)   # copy two
+    out, at = [], 0
+    for b in range(B):
+        pts, off, nr = flat[at:at + corners[b]], ring_off[b], int(n[b, 2])
+        at += corners[b]
+        top = int(np.searchsorted(off, nr, side="left")) if nr else 0        # the first k with ring_off[k] == rings
+        out.append([[(int(a), pts[f:f + k]) for _, f, k, a in rings[b, off[o - 1]:off[o]].tolist()]
+                    for o in range(1, min(top, cap) + 1)])
+    incomplete = bool((n[:, 3] == 0).any())
+    return (out[0] if single else out), incomplete
+
+
+def _closed(pts):
+    p = np.asarray(pts, dtype=np.int64).reshape(-1, 2).tolist()
+    return p + p[:1]
+
+
+def rings_to_geojson(rings):
+    """One object's rings [(area, corners [k, 2])], the outer ring first (as contours_to_host lists them) -> {"type":
+    "Polygon", "coordinates": [outer, hole, ..]}, every ring closed (its first point repeated at the end), in pixel-corner
+    coordinates [x, y] with y growing downwards.  Orientation: in these coordinates the outer ring runs clockwise as seen
+    on screen and the holes counter-clockwise; with y flipped to point up, as a map projection has it, that is
+    counter-clockwise outside and clockwise inside, the right-hand rule of RFC 7946."""
+    return {"type": "Polygon", "coordinates": [_closed(p) for _, p in rings]}
+
+
+def rings_to_coco(rings):
+    """One object's rings -> its OUTER ring as a flat [x0, y0, x1, y1, ..] list, one polygon of a COCO `segmentation`.
+    COCO polygons have no holes: the hole rings are dropped, and the polygon then covers them.  For an exact mask use
+    runs_to_coco on object_runs' result."""
+    return [v for xy in np.asarray(rings[0][1], dtype=np.int64).reshape(-1, 2).tolist() for v in xy] if rings else []
+
+
+def rings_to_mask(rings, h, w):
+    """One object's rings [(area, corners [k, 2])] -> numpy bool [h, w].  Every vertical side of a ring adds, for each row
+    it spans, -1 at its column when it heads south (the object lies to its west) and +1 when it heads north; the
+    cumulative sum along x is 1 inside and 0 outside."""
+    acc = np.zeros((h, w + 1), np.int64)
+    for _, pts in rings:
+        p = np.asarray(pts, dtype=np.int64).reshape(-1, 2)
+        q = np.roll(p, -1, axis=0)
+        for (x0, y0), (x1, y1) in zip(p.tolist(), q.tolist()):
+            if x0 == x1 and y0 != y1:
+                acc[min(y0, y1):max(y0, y1), x0] += -1 if y1 > y0 else 1
+    return np.cumsum(acc, axis=1)[:, :w] > 0
 
 
 # ------------------------------------------------------------------------------------------------ object matching

@@ -1183,6 +1183,48 @@ def seg_rle(ids, runs, run_off, nruns, ws, cap, order="column"):
     L.check(L.lib().dfw_seg_rle(C.byref(a), _stream()), "dfw_seg_rle")
 
 
+def seg_contours_workspace(B, H, W, cap, max_edges):
+    """Bytes of seg_contours' workspace for a [B, H, W] id map, objects 1..cap, max_edges edges per image; 0 for arguments
+    seg_contours answers DFW_EINVAL for."""
+    return int(L.lib().dfw_seg_contours_workspace_bytes(int(B), int(H), int(W), int(cap), int(max_edges)))
+
+
+def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8):
+    """Outlines of the objects 1..cap of an id map as rings of corner points, on caller-owned buffers only
+    (objects.ContourBuffers holds a set): ids int32 [B, H, W], normally seg_components' or seg_holes' (any int32 map is
+    accepted; ids outside 1..cap count as 0); connectivity = 4 | 8, the one the ids were made with.  Pixel (x, y) is the
+    unit square from (x, y) to (x + 1, y + 1); a ring runs clockwise on screen (y down), the object on its right, so an
+    outer ring has a positive area and a hole ring a negative one (include/diffews_hip.h holds the definition).  Writes n
+    int32 [B, 4] = (edges found, corners, rings, complete); rings int32 [B, max_edges / 4, 4] = (id, first, count, area)
+    sorted by id and then by the ring's smallest edge key; ring_off int32 [B, cap + 1]: object k's rings are rows
+    ring_off[k-1] .. ring_off[k]; verts int32 [B, max_edges, 2] = (X, Y), the corners of ring r being rows first ..
+    first + count.  An image with more than max_edges edges gets n = (found, 0, 0, 0), a zero ring_off and no row: there
+    are no partial results.  Rows behind the kept ones are left as they were.  ws: a uint8 buffer of at least
+    seg_contours_workspace(B, H, W, cap, max_edges) bytes, which needs no initialisation.  A number of launches fixed by
+    the arguments, no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("seg_contours: ids must be a contiguous int32 device tensor [B, H, W]")
+    if connectivity not in (4, 8):
+        raise ValueError(f"seg_contours: connectivity must be 4 or 8, not {connectivity!r}")
+    B, H, W = ids.shape
+    dev, cap = ids.device, int(cap)
+    if verts.dim() != 3 or verts.shape[1] < 4 or verts.shape[1] % 4:
+        raise ValueError("seg_contours: verts must be int32 [B, max_edges, 2] with max_edges a multiple of 4, at least 4")
+    max_edges = verts.shape[1]
+
+    def own(name, t, dtype, shape):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"seg_contours: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    a = L.SegContoursArgs()
+    a.ids, a.verts = ids.data_ptr(), own("verts", verts, torch.int32, (B, max_edges, 2))
+    a.rings, a.ring_off = own("rings", rings, torch.int32, (B, max_edges // 4, 4)), own("ring_off", ring_off, torch.int32, (B, cap + 1))
+    a.n = own("n", n, torch.int32, (B, 4))
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.B, a.H, a.W, a.cap, a.max_edges, a.connectivity = B, H, W, cap, max_edges, int(connectivity)
+    L.check(L.lib().dfw_seg_contours(C.byref(a), _stream()), "dfw_seg_contours")
+
+
 def seg_match_workspace(B, H, W, cap_p, cap_g, max_records, max_pairs):
     """Bytes of seg_match's workspace for [B, H, W] id maps, objects 1..cap_p against 1..cap_g, max_records records and
     max_pairs pair rows per image; 0 for sizes seg_match refuses."""

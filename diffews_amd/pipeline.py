@@ -1018,6 +1018,12 @@ class MarigoldPipelineRGBLatentNoise:
         from .objects import object_runs
         return object_runs(o, **kw)
 
+    def object_contours(self, o, **kw):
+        """The outline of every object of pipe.objects' (or pipe.fill_holes') result as rings of corner points:
+        objects.object_contours(o, **kw) -- connectivity, max_edges, buffers."""
+        from .objects import object_contours
+        return object_contours(o, **kw)
+
     def match_objects(self, o_pred, o_gt, **kw):
         """The objects of a prediction matched to those of a ground truth: objects.match_objects(o_pred, o_gt, **kw) on two
         pipe.objects / label_objects results -- skip, iou, nlabels, buffers.  Returns its dict; objects.matches_to_host

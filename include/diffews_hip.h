@@ -1166,6 +1166,97 @@ typedef struct {
 } dfw_seg_boundary_counts_args;
 int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t stream);
 
+/*
+ * Outlines of labelled objects (version >= 121): every object of an id map, normally the one dfw_seg_components or
+ * dfw_seg_holes wrote (any int32 map is accepted), as rings of corner points -- what GeoJSON polygons, COCO polygon
+ * segmentations and GIS tools take.  All integers: the result depends on no order of execution.
+ *
+ *   v(y, x)    the id when 1 <= id <= cap, else 0; outside the image v is 0
+ *   pixel      (x, y) is the unit square with the corners (x, y) and (x + 1, y + 1); vertices are the lattice points
+ *              0 <= X <= W, 0 <= Y <= H
+ *   edge       a side of a pixel p with v(p) != 0 whose pixel across that side has a different v.  Edges are directed
+ *              clockwise on screen (y down), the object on the right: side 0 is the top, heading east; 1 the right, heading
+ *              south; 2 the bottom, heading west; 3 the left, heading north.  Its key is 4 * (y * W + x) + side.  Between two
+ *              different objects both pixels own an edge
+ *   successor  of edge e of pixel p, side s, id i; it depends on `connectivity`, which must be the one the ids were made
+ *              with.  A is the pixel ahead of p in the heading, L the pixel to the left of A relative to the heading.  A
+ *              left turn goes to side (s + 3) % 4 of L, straight to side s of A, a right turn to side (s + 1) % 4 of p.
+ *              Connectivity 8: left if v(L) == i, else straight if v(A) == i, else right.  Connectivity 4: right if
+ *              v(A) != i, else left if v(L) == i, else straight.  The map is a bijection on the edges, also for ids that do
+ *              not match the connectivity
+ *   ring       a cycle of the successor; it belongs to one id.  Its leader is its smallest key, the rank of an edge the
+ *              number of successor steps from the leader, its area the sum of X over its south edges minus the sum of X over
+ *              its north edges, X the edge's column: the integral of x dy, positive for an outer ring, negative for a hole
+ *   corners    of a ring: the start vertices of the edges whose predecessor has another heading, in ascending rank.  The
+ *              leader's own start need not be one (a hole two pixels wide).  With connectivity 8 a ring may visit a vertex
+ *              twice, where two pixels touch diagonally; it never crosses itself
+ *
+ *   n          per image (edges found, corners, rings, complete); complete = 1 when edges found <= max_edges.  Otherwise
+ *              n = (edges found, 0, 0, 0), ring_off is all zero and no row of rings or verts is written: there are no
+ *              partial results, a cut ring is not a ring.  The caller sizes max_edges from n[0] and calls again
+ *   rings      (id, first, count, area), sorted by id ascending, then by leader ascending; first is the row of the ring's
+ *              first corner in verts
+ *   ring_off   object k's rings are rows ring_off[k-1] .. ring_off[k]; ring_off[0] = 0
+ *   verts      (X, Y); each ring's corners are contiguous and in rank order, the rings in the order of `rings`
+ *   ws         dfw_seg_contours_workspace_bytes(..) bytes, 4 per pixel and 64 per edge of max_edges and a little more.  The
+ *              call writes every word it reads: the caller initialises nothing
+ * Rows behind the kept ones are left as they were; nothing is written outside the four outputs and ws; ids is read only.
+ *
+ * When the ids come from dfw_seg_components with the same connectivity, the first ring of an object is its only outer
+ * ring and its leader has side 0, every later ring is a hole ring (negative area, a leader of another side), and the areas
+ * of an object's rings sum to its pixel count.
+ *
+ * Connectivity 8, cap = 1.  [[1,1,1,1],[1,0,0,1],[1,1,1,1]] has 20 edges and two rings: (1, 0, 4, 12) with the corners
+ * (0,0) (4,0) (4,3) (0,3) and (1, 4, 4, -2) with the corners (1,1) (1,2) (3,2) (3,1).  The diamond [[0,1,0],[1,0,1],[0,1,0]]
+ * has 16 edges: the outer ring has 12 corners, starts at (1,0) and has area 5, the hole ring has the corners (2,1) (1,1)
+ * (1,2) (2,2) and area -1.  Under connectivity 4 with the ids 1..4 the same diamond gives four unit squares.
+ *
+ * A fixed number of launches, 14 + 2 * R + 3 * passes with R = ceil(log2(max_edges)) and passes = the bytes cap needs (1
+ * below 256, 2 below 65536, ..), chosen by the arguments and never by the image; no host readback, no memset node
+ * (ring_off is zeroed by a library kernel), no thread that waits for another: every cross-workgroup prefix is a scan in a
+ * launch of its own, the cycles are followed by pointer doubling between two buffers in turn (R rounds to find every
+ * ring's leader, R to sum corners and area to the ring's end), and the ring table is sorted by dfw_seg_rle's stable radix
+ * sort -- no atomic decides a position.  The call can be captured and is correct at any residency.
+ *
+ * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / ids / verts / rings / ring_off /
+ * n / ws; connectivity not 4 or 8; B, H, W or cap < 1; max_edges < 4 or not a multiple of 4.  DFW_ERANGE: H, W or B above
+ * 65535, 4 * H * W above 2^31 - 1 (the keys), B * max_edges * 2 or B * (cap + 1) above 2^31 - 1.  DFW_EWORKSPACE: ws_bytes
+ * below the query.  DFW_EINVAL: an output or ws sharing a byte with ids or with another output.  DFW_ESHAPE: ids or
+ * ring_off not 4-byte aligned, verts not 8-byte aligned, rings, n or ws not 16-byte aligned.
+ */
+typedef struct {
+  const int32_t* ids;      /* [B][H][W] contiguous, read only */
+  int32_t* verts;          /* out [B][max_edges][2]: (X, Y); rows behind the corners are left as they were */
+  int32_t* rings;          /* out [B][max_edges / 4][4]: (id, first, count, area); rows behind the rings are left */
+  int32_t* ring_off;       /* out [B][cap + 1] */
+  int32_t* n;              /* out [B][4]: (edges found, corners, rings, complete) */
+  void* ws;
+  size_t ws_bytes;
+  int32_t B, H, W, cap, max_edges, connectivity;   /* connectivity 4 | 8: the one the ids were made with */
+} dfw_seg_contours_args;
+int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t stream);
+/* 0 for arguments dfw_seg_contours answers DFW_EINVAL for; monotone in every argument */
+size_t dfw_seg_contours_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_edges);
+/* pixels one scan block covers, edges one block of the ring count covers: the sizes at which the kernels change path, for
+ * tests and docs */
+int dfw_seg_contours_block(int32_t* pixels, int32_t* edges);
+/* The trip counts of dfw_seg_contours (host only, launches nothing), computed by the expressions the launcher uses, for
+ * tests and docs.  Errors: DFW_EINVAL for a null out, then the size errors of dfw_seg_contours in its order; pointers,
+ * connectivity, workspace and overlap are not part of it. */
+typedef struct {
+  int32_t blocks;         /* scan blocks of `pixels` positions per image */
+  int32_t block_scan;     /* trips of the scan of the block sums, 1024 words a trip: edges found */
+  int32_t doubling;       /* R: the rounds of each of the two pointer-doubling loops */
+  int32_t ring_blocks;    /* blocks of `edges` edges per image */
+  int32_t ring_scan;      /* trips of the scan of the leaders per block: rings */
+  int32_t passes;         /* digit passes of the sort, each with one table scan */
+  int32_t table_scan;     /* trips of the scan of the digit table, 256 words per chunk of ring rows */
+  int32_t offsets_scan;   /* trips of the scan of ring_off (cap + 1 words) */
+  int32_t corners_scan;   /* trips of the scan of the corners per ring (max_edges / 4 words) */
+  int32_t launches;       /* 14 + 2 * doubling + 3 * passes */
+} dfw_seg_contours_trips;
+int dfw_seg_contours_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_edges, dfw_seg_contours_trips* out);
+
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
  * T): backward of the UNet's ops.  Data gradients of Linear / conv3x3 are dfw_gemm calls with transposed /
