@@ -20,7 +20,9 @@ three visible without a reference:
   * `check_launches(modules, call)` runs `call(run)` three times -- plain, under 0xFF, under 0x7B -- and requires
     everything it returns to be bit-equal across the three and both verifications to pass.  An element never written
     differs between the two patterns; a read of uninitialised scratch or past an input is NaN in one run and something
-    else in the other; a race shows as a difference.  There is no tolerance.
+    else in the other; a race shows as a difference.  There is no tolerance.  On a device the two pattern launches also
+    fill every CU's LDS with the same byte in front of every launching library call (tests/lds_poison.py), so the same
+    bit-equality covers LDS a kernel reads without having written it; lds=False leaves LDS alone.
 
 A torn store begins right behind the tensor's end, so the first guard bytes catch it; GUARD is a multiple of 512, so the
 view keeps the alignment the allocator gives.  A store that lands further away cannot be caught by a guard of any size.
@@ -311,11 +313,63 @@ def _sync():
         _torch.cuda.synchronize()
 
 
-def check_launches(modules, call, declared=(), patterns=PATTERNS):
+class _Differs(Exception):
+    """A result of a pattern run is not the plain run's: the message, before anyone knows which pattern caused it."""
+
+
+def _pattern_run(modules, call, p, lds_pattern, lds, ref, shapes):
+    """One guarded launch under memory pattern p, LDS filled with the byte lds_pattern in front of every library call (None:
+    LDS left alone).  Returns (names recorded, entry points poisoned); GuardError from verify(), _Differs from the comparison."""
+    g = Guard(p)
+    poisoned = set()
+    with contextlib.ExitStack() as stack:
+        if lds_pattern is not None:
+            proxy = stack.enter_context(lds(lds_pattern))
+            poisoned = proxy.poisoned
+        stack.enter_context(g.installed(*modules))
+        res = flatten(call(g))
+    _sync()
+    g.verify()
+    got = [(tuple(t.shape), t.dtype) for t in res]
+    if got != shapes:
+        raise GuardError(f"pattern 0x{p:02X}: the launch returned {got}, the plain one {shapes}")
+    for i, (t, r) in enumerate(zip(res, ref)):
+        b = bits(t)
+        if not _torch.equal(b, r):
+            ne = (b != r).nonzero()
+            esz = t.element_size()
+            buf = g.owner_of(t)
+            what = buf.describe() if buf is not None else "tensor the guard did not allocate"
+            raise _Differs(f"result {i} {shapes[i]} differs from the plain launch in {ne.numel()} byte(s), "
+                           f"first at element {int(ne[0]) // esz}, last at element {int(ne[-1]) // esz}: {what}")
+    return g.names(), set(poisoned)
+
+
+def _lds_installer(lds):
+    """lds=True: tests/lds_poison.installed, where there is a device to poison; a callable: that context manager."""
+    if lds is True:
+        if not _torch.cuda.is_available():
+            return None
+        import lds_poison
+        return lds_poison.installed
+    return lds or None
+
+
+def check_launches(modules, call, declared=(), patterns=PATTERNS, lds=True):
     """call(run) three times: run = Plain(), then a Guard per pattern installed in `modules`.  call places its inputs
     (run.place / run.inout), allocates the outputs it hands over (run.empty) and returns every tensor that is a result.
     GuardError unless the results are bit-equal across the three launches, both verifications pass and every name in
-    `declared` appears in a call chain of the recorded allocations.  Returns the names recorded."""
+    `declared` appears in a call chain of the recorded allocations -- or, for a name that begins with `dfw_`, among the
+    library entry points that were preceded by an LDS fill.  Returns the names recorded, those entry points included.
+
+    lds (default on, where there is a device): in the two pattern launches every launching entry point of the library is
+    also preceded by a fill of every CU's LDS with the same byte (tests/lds_poison.py: 0xFF is NaN in the three float types
+    and -1 in integers, 0x7B large and finite), so the bit-equality covers what a kernel reads from LDS without having
+    written it.  The plain launch stays plain.  An entry point that launches several kernels gets the fill in front of its
+    first one only.  When a result differs, the launch is repeated under the same memory pattern with LDS zero-filled: if
+    that one is bit-equal, the error says that LDS is the cause and names the entry points poisoned.  lds=False: memory
+    only; a callable `lds(pattern)`: that context manager in place of lds_poison.installed."""
+    install = _lds_installer(lds)
     run = Plain()
     res = flatten(call(run))
     _sync()
@@ -324,25 +378,25 @@ def check_launches(modules, call, declared=(), patterns=PATTERNS):
     del res
     names = set()
     for p in patterns:
-        g = Guard(p)
-        with g.installed(*modules):
-            res = flatten(call(g))
-        _sync()
-        g.verify()
-        got = [(tuple(t.shape), t.dtype) for t in res]
-        if got != shapes:
-            raise GuardError(f"pattern 0x{p:02X}: the launch returned {got}, the plain one {shapes}")
-        for i, (t, r) in enumerate(zip(res, ref)):
-            b = bits(t)
-            if not _torch.equal(b, r):
-                ne = (b != r).nonzero()
-                esz = t.element_size()
-                buf = g.owner_of(t)
-                what = buf.describe() if buf is not None else "tensor the guard did not allocate"
-                raise GuardError(f"pattern 0x{p:02X}: result {i} {shapes[i]} differs from the plain launch in {ne.numel()} byte(s), "
-                                 f"first at element {int(ne[0]) // esz}, last at element {int(ne[-1]) // esz}: {what}")
-        names |= g.names()
-        del res, g
+        try:
+            recorded, poisoned = _pattern_run(modules, call, p, p if install else None, install, ref, shapes)
+            if install and not poisoned:
+                raise GuardError(f"pattern 0x{p:02X}: no library call of this case was preceded by an LDS fill: it does not fetch "
+                                 "the handle through diffews_amd._lib.lib() (lds=False for a case that launches nothing)")
+            names |= poisoned
+        except _Differs as e:
+            if not install:
+                raise GuardError(f"pattern 0x{p:02X}: {e}") from None
+            try:
+                _, poisoned = _pattern_run(modules, call, p, 0x00, install, ref, shapes)
+            except (_Differs, GuardError):
+                raise GuardError(f"pattern 0x{p:02X} (in memory and in LDS; the difference stays with LDS zero-filled, so it is "
+                                 f"not the LDS pattern's): {e}") from None
+            raise GuardError(f"LDS pattern 0x{p:02X} (word 0x{p * 0x01010101:08X} in every CU's LDS in front of "
+                             f"{', '.join(sorted(poisoned)) or 'no entry point'}): {e}; the same launch under memory pattern "
+                             f"0x{p:02X} with LDS zero-filled is bit-equal to the plain one: a kernel of these entry points "
+                             "reads LDS it has not written, no allocation is involved") from None
+        names |= recorded
     missing = set(declared) - names
     if missing:
         raise GuardError(f"no allocation was recorded for {sorted(missing)}; recorded: {sorted(names)}")

@@ -17,6 +17,9 @@ Model level (tiny UNet / VAE of tests/test_model_gpu.py, built fresh inside ever
 pattern from an earlier one; the proxy also stands in for torch in unet, vae, pipeline and train): one run_episodes
 episode and one prepare_support + segment_queries pass with nshot 1, one segment_classes call, one UNetTrainer step
 (loss, prediction, every gradient, the updated master weights, both moments and the 16-bit shadow).
+
+LDS: in the two pattern launches check_launches also fills every CU's LDS with the pattern in front of every launching
+library call (tests/lds_poison.py); the model-level cases declare, as `dfw_` names, entry points that must have been poisoned.
 """
 import pytest
 import torch
@@ -73,24 +76,26 @@ def test_harness_reports_broken_contracts_on_the_device(env):
     """What tests/test_launch_guard_cpu.py proves on fake ops, once with the real kernels and device memory, through calls
     that break a documented contract on purpose (every access stays inside the guarded buffers): an accumulate target
     nobody initialised, a dpred destination that is not zero-initialised (backward.hip: channels C..7 are the caller's),
-    one element written behind a wrapper's output, an input overwritten after the launch."""
+    one element written behind a wrapper's output, an input overwritten after the launch.  lds=False: the messages pinned here
+    are the memory-only ones (tests/test_lds_poison_gpu.py pins those of the LDS poison)."""
     ops, ob, _ = env
     g = npg.gen(1)
     x, pred, tgt = npg.randn((64, 24), g, torch.bfloat16), npg.randn((2, 4, 16, 16), g), npg.randn((2, 4, 16, 16), g)
-    lg.check_launches([ob], lambda run: ob.colsum(run.place(x), out=run.full((1, 24), 1.5, dtype=F32, device="cuda"), accumulate=True))
+    lg.check_launches([ob], lambda run: ob.colsum(run.place(x), out=run.full((1, 24), 1.5, dtype=F32, device="cuda"), accumulate=True),
+                      lds=False)
 
     def stale(run):
         return ob.colsum(run.place(x), out=run.empty(1, 24, dtype=F32, device="cuda"), accumulate=True)
 
     with pytest.raises(lg.GuardError, match="result 0 .* differs from the plain launch .* allocated by stale"):
-        lg.check_launches([ob], stale)
+        lg.check_launches([ob], stale, lds=False)
 
     def unzeroed(run):
         return ob.mse_loss(run.place(pred), run.place(tgt), torch.bfloat16,
                            dpred_out=run.empty(2, 16, 16, 8, dtype=torch.bfloat16, device="cuda"))
 
     with pytest.raises(lg.GuardError, match=r"result 1 .* first at element 4, .* allocated by unzeroed"):
-        lg.check_launches([ob], unzeroed)
+        lg.check_launches([ob], unzeroed, lds=False)
 
     def torn(run):
         y = ob.silu(run.place(x))
@@ -99,7 +104,7 @@ def test_harness_reports_broken_contracts_on_the_device(env):
         return y
 
     with pytest.raises(lg.GuardError, match=r"store past the end \(first damaged guard byte \+0\) of the buffer of 3072 bytes allocated by silu"):
-        lg.check_launches([ob], torn)
+        lg.check_launches([ob], torn, lds=False)
 
     def clobbered(run):
         px = run.place(x)
@@ -108,7 +113,7 @@ def test_harness_reports_broken_contracts_on_the_device(env):
         return y
 
     with pytest.raises(lg.GuardError, match="input modified at byte 15[01]: buffer of 3072 bytes placed by clobbered"):
-        lg.check_launches([ob], clobbered)
+        lg.check_launches([ob], clobbered, lds=False)
 
 
 # ------------------------------------------------------------------------------------------------ dfw_gemm, dfw_gemm_tn
@@ -813,7 +818,8 @@ def test_episode_guarded(tiny, model_modules):
         bank = pipe.prepare_support(sup, msk)
         return ep, pipe.segment_queries(bank, qry, query_gt=gt, captured=False)
 
-    lg.check_launches(model_modules, call, D_FWD["conv"] + D_FWD["linear"] + D_FSA + D_GN + D_LN + D_SEG[:1])
+    lg.check_launches(model_modules, call, D_FWD["conv"] + D_FWD["linear"] + D_FSA + D_GN + D_LN + D_SEG[:1] +
+                      ("dfw_gemm", "dfw_fsa_attention", "dfw_groupnorm", "dfw_layernorm", "dfw_seg_postprocess_ex"))
 
 
 def test_segment_classes_guarded(tiny, model_modules):
@@ -829,7 +835,7 @@ def test_segment_classes_guarded(tiny, model_modules):
         pipe = tiny["build"]()
         return pipe.segment_classes(pipe.prepare_support_classes(sups, msks), qry, query_labels=labels, captured=False)
 
-    lg.check_launches(model_modules, call, D_FSA + D_SEG[1:2])
+    lg.check_launches(model_modules, call, D_FSA + D_SEG[1:2] + ("dfw_gemm", "dfw_seg_labels"))
 
 
 def test_trainer_step_guarded(tiny, model_modules):
@@ -848,4 +854,6 @@ def test_trainer_step_guarded(tiny, model_modules):
         tr.optimizer_step(1e-4, max_grad_norm=1.0)
         return loss, pred, grads, tr.P.master, tr.P.exp_avg, tr.P.exp_avg_sq, tr.P.shadow
 
-    lg.check_launches(model_modules, call, D_WS + D_FSA_BWD + D_GN_BWD + D_LN_BWD + D_FLUSH)
+    lg.check_launches(model_modules, call, D_WS + D_FSA_BWD + D_GN_BWD + D_LN_BWD + D_FLUSH +
+                      ("dfw_gemm", "dfw_gemm_tn", "dfw_fsa_attention_bwd", "dfw_groupnorm_bwd", "dfw_layernorm_bwd", "dfw_colsum_batch",
+                       "dfw_adamw"))
