@@ -45,8 +45,8 @@
 // Termination: in dfw_seg_boundary no thread waits for another thread or workgroup and no atomics are used; every loop
 // but the column walk has a trip count fixed at compile time, and the walk ends after at most dmax steps.  The counts use
 // LDS and global integer atomics (order-free) and wait for nothing.  Any grid is correct at any residency.
+#include "seg_args.h"
 #include "seg_fuse.h"
-#include "seg_sort.h"
 
 namespace dfw {
 
@@ -280,15 +280,6 @@ __global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pre
   seg_flush_counts(hist, counts + (size_t)blockIdx.y * 2 * NB, NB);
 }
 
-// The sizes both entry points refuse: DFW_EINVAL before DFW_ERANGE.
-static int boundary_size_error(long long B, long long H, long long W) {
-  if (B < 1 || H < 1 || W < 1) return DFW_EINVAL;
-  // grid z carries B and grid y the rows' tiles; H * W <= 2^30 keeps every position of an image, and the row pass's window
-  // behind it, in an int
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
-  return 0;
-}
-
 template <typename T>
 static void boundary_launch(hipStream_t st, const dfw_seg_boundary_args* a, bool vec) {
   const int HW = a->H * a->W, cap = a->dmax + 1;
@@ -308,7 +299,7 @@ static void boundary_launch(hipStream_t st, const dfw_seg_boundary_args* a, bool
 using namespace dfw;
 
 extern "C" size_t dfw_seg_boundary_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t elem) {
-  if ((elem != 1 && elem != 4) || boundary_size_error(B, H, W)) return 0;
+  if ((elem != 1 && elem != 4) || seg_map_size_error(B, H, W)) return 0;
   return ((size_t)B * H * W + 15) & ~(size_t)15;   // h, one byte a pixel
 }
 
@@ -323,16 +314,13 @@ extern "C" int dfw_seg_boundary(const dfw_seg_boundary_args* a, dfw_stream_t str
   if (a->elem != 1 && a->elem != 4) return DFW_EINVAL;
   if (a->dmax < 1 || a->dmax > 254) return DFW_EINVAL;
   if (a->band && (a->d < 1 || a->d > a->dmax)) return DFW_EINVAL;
-  if (int e = boundary_size_error(a->B, a->H, a->W)) return e;
+  if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
   const size_t wsb = dfw_seg_boundary_workspace_bytes(a->B, a->H, a->W, a->elem);
   if (a->ws_bytes < wsb) return DFW_EWORKSPACE;
   const size_t n = (size_t)a->B * a->H * a->W, el = (size_t)a->elem;
-  if (seg_overlap(a->map, n * el, a->dist, n) || seg_overlap(a->map, n * el, a->band, n * el) ||
-      seg_overlap(a->map, n * el, a->ws, wsb) || seg_overlap(a->dist, n, a->band, n * el) ||
-      seg_overlap(a->dist, n, a->ws, wsb) || seg_overlap(a->band, n * el, a->ws, wsb))
-    return DFW_EINVAL;
-  if (a->elem == 4 && (((uintptr_t)a->map | (uintptr_t)a->band) & 3)) return DFW_ESHAPE;
-  if ((uintptr_t)a->ws & 3) return DFW_ESHAPE;
+  const seg_buf bufs[] = {seg_in(a->map, n * el, el), seg_out(a->dist, n), seg_out(a->band, n * el, el),
+                          seg_out(a->ws, wsb, 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   // four pixels a thread in the column pass: whole words of every map, in every row of every image
   const uintptr_t al = 4 * el - 1;
@@ -347,12 +335,11 @@ extern "C" int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, df
   if (!a || !a->pred || !a->pdist || !a->gt || !a->gdist || !a->counts) return DFW_EINVAL;
   if (a->d < 1 || a->d > 254) return DFW_EINVAL;
   if (a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
-  if (int e = boundary_size_error(a->B, a->H, a->W)) return e;
+  if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
   const size_t n = (size_t)a->B * a->H * a->W, cb = (size_t)a->B * 2 * (a->nlabels + 1) * 8;
-  const void* const in[4] = {a->pred, a->pdist, a->gt, a->gdist};
-  for (int i = 0; i < 4; ++i)
-    if (seg_overlap(in[i], n, a->counts, cb)) return DFW_EINVAL;
-  if ((uintptr_t)a->counts & 7) return DFW_ESHAPE;
+  const seg_buf bufs[] = {seg_in(a->pred, n), seg_in(a->pdist, n), seg_in(a->gt, n), seg_in(a->gdist, n),
+                          seg_out(a->counts, cb, 8)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int HW = a->H * a->W, words = a->B * 2 * (a->nlabels + 1);
   hipLaunchKernelGGL(boundary_zero_kernel, dim3((words + 255) / 256), dim3(256), 0, st, (unsigned long long*)a->counts, words);

@@ -28,6 +28,7 @@
 //
 // Launches 1 to 3, the grids' sizing and the argument why every loop ends are seg_unionfind.h's, shared with seg_holes.hip.
 #include "common.h"
+#include "seg_args.h"
 #include "seg_fuse.h"
 #include "seg_scan.h"
 #include "seg_unionfind.h"
@@ -303,7 +304,7 @@ extern "C" int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w) {
 extern "C" int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const void* ws,
                                          dfw_seg_components_rounds_out* out) {
   if (!out || !ws) return DFW_EINVAL;
-  if (int e = cc_size_error(B, H, W)) return e;
+  if (int e = seg_map_size_error(B, H, W)) return e;
   if ((uintptr_t)ws & 3) return DFW_ESHAPE;
   const int HW = H * W, nblk = (int)cc_blocks(HW);
   const long long items = cc_merge_items(H, W);
@@ -325,15 +326,21 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
   if (a->stats && a->cap < 1) return DFW_EINVAL;
   if (a->counts && !a->gt) return DFW_EINVAL;
   if (a->gt && (a->nlabels < 1 || a->nlabels > 254)) return DFW_EINVAL;
-  if (a->filtered == a->labels) return DFW_EINVAL;
-  if (int e = cc_size_error(a->B, a->H, a->W)) return e;
+  if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
   if (a->stats && (long long)a->B * a->cap * 8 > 0x7fffffffll) return DFW_ERANGE;   // seg_zero_launch counts in int
   if (a->ws_bytes < dfw_seg_components_workspace_bytes(a->B, a->H, a->W)) return DFW_EWORKSPACE;
-  // int32 words (the workspace, ids, n, stats) and 64-bit count cells at their natural alignment
-  if ((((uintptr_t)a->ws | (uintptr_t)a->ids | (uintptr_t)a->n | (uintptr_t)a->stats) & 3) || ((uintptr_t)a->counts & 7))
-    return DFW_ESHAPE;
-  hipStream_t st = (hipStream_t)stream;
   const int B = a->B, H = a->H, W = a->W, HW = H * W, conn8 = a->connectivity == 8;
+  const size_t px = (size_t)B * HW;
+  const seg_buf bufs[] = {seg_in(a->labels, px),
+                          seg_in(a->counts ? a->gt : nullptr, px),
+                          seg_out(a->ids, px * 4, 4),
+                          seg_out(a->n, (size_t)B * 8, 4),
+                          seg_out(a->filtered, px),
+                          seg_out(a->stats, (size_t)B * a->cap * 32, 4),
+                          seg_out(a->counts, (size_t)B * 2 * (a->nlabels + 1) * 8, 8),
+                          seg_out(a->ws, dfw_seg_components_workspace_bytes(B, H, W), 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
+  hipStream_t st = (hipStream_t)stream;
   const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH, nblk = (int)cc_blocks(HW);
   int32_t* parent = (int32_t*)a->ws;
   int32_t* area = parent + (size_t)B * HW;

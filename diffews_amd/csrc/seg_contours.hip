@@ -69,6 +69,7 @@
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
 // cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
+#include "seg_args.h"
 #include "seg_sort.h"
 
 namespace dfw {
@@ -430,17 +431,13 @@ extern "C" int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t str
   if (int e = ct_size_error(a->B, a->H, a->W, a->cap, a->max_edges)) return e;
   const size_t need = dfw_seg_contours_workspace_bytes(a->B, a->H, a->W, a->cap, a->max_edges);
   if (a->ws_bytes < need) return DFW_EWORKSPACE;
-  {
-    const void* p[6] = {a->ids, a->verts, a->rings, a->ring_off, a->n, a->ws};
-    const size_t nb[6] = {(size_t)a->B * a->H * a->W * 4, (size_t)a->B * a->max_edges * 8, (size_t)a->B * (a->max_edges / 4) * 16,
-                          (size_t)a->B * ((size_t)a->cap + 1) * 4, (size_t)a->B * 16, need};
-    for (int i = 0; i < 6; ++i)
-      for (int j = i + 1; j < 6; ++j)
-        if (seg_overlap(p[i], nb[i], p[j], nb[j])) return DFW_EINVAL;
-  }
-  if (((uintptr_t)a->ids | (uintptr_t)a->ring_off) & 3) return DFW_ESHAPE;
-  if ((uintptr_t)a->verts & 7) return DFW_ESHAPE;                                      // rows of 8 bytes
-  if (((uintptr_t)a->rings | (uintptr_t)a->n | (uintptr_t)a->ws) & 15) return DFW_ESHAPE;   // rows and records of 16
+  const seg_buf bufs[] = {seg_in(a->ids, (size_t)a->B * a->H * a->W * 4, 4),
+                          seg_out(a->verts, (size_t)a->B * a->max_edges * 8, 8),               // rows of 8 bytes
+                          seg_out(a->rings, (size_t)a->B * (a->max_edges / 4) * 16, 16),       // rows and records of 16
+                          seg_out(a->ring_off, (size_t)a->B * ((size_t)a->cap + 1) * 4, 4),
+                          seg_out(a->n, (size_t)a->B * 16, 16),
+                          seg_out(a->ws, need, 16)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int B = a->B, H = a->H, W = a->W, cap = a->cap, E = a->max_edges, Q = E / 4;
   const ct_layout l = ct_plan(B, (long long)H * W, cap, E);

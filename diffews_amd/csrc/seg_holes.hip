@@ -31,6 +31,7 @@
 //
 // No kernel of 3 to 5 loops over a capped grid.  Termination of 0 to 2: seg_unionfind.h.  No thread waits for another.
 #include "common.h"
+#include "seg_args.h"
 #include "seg_fuse.h"
 #include "seg_unionfind.h"
 
@@ -296,19 +297,12 @@ __global__ __launch_bounds__(256) void sh_apply_kernel(const uint8_t* labels, co
     }
 }
 
-// byte ranges [p, p + n) that share a byte; a null pointer or an empty range shares none
-static bool sh_overlap(const void* p, size_t n, const void* q, size_t m) {
-  if (!p || !q || n == 0 || m == 0) return false;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + m && b < a + n;
-}
-
 }  // namespace dfw
 
 using namespace dfw;
 
 extern "C" size_t dfw_seg_holes_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-  if (cc_size_error(B, H, W)) return 0;
+  if (seg_map_size_error(B, H, W)) return 0;
   return (size_t)B * (size_t)H * (size_t)W * 8;
 }
 
@@ -320,30 +314,23 @@ extern "C" int dfw_seg_holes(const dfw_seg_holes_args* a, dfw_stream_t stream) {
   if (a->stats_out && (!a->stats || a->cap < 1)) return DFW_EINVAL;
   if (a->counts && !a->gt) return DFW_EINVAL;
   if (a->gt && (a->nlabels < 1 || a->nlabels > 254)) return DFW_EINVAL;
-  if (int e = cc_size_error(a->B, a->H, a->W)) return e;
+  if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
   if (a->stats_out && (long long)a->B * a->cap * 8 > 0x7fffffffll) return DFW_ERANGE;
   if (a->ws_bytes < dfw_seg_holes_workspace_bytes(a->B, a->H, a->W)) return DFW_EWORKSPACE;
   const int B = a->B, H = a->H, W = a->W, HW = H * W;
   const bool want_counts = a->gt && a->counts, want_stats = a->stats_out != nullptr;
-  {
-    // no output (the workspace is one) on an input or on another output
-    const size_t px = (size_t)B * HW, st = want_stats ? (size_t)B * a->cap * 32 : 0;
-    const size_t cn = want_counts ? (size_t)B * 2 * (a->nlabels + 1) * 8 : 0;
-    const void* in[4] = {a->labels, a->ids, want_stats ? a->stats : nullptr, a->gt};
-    const size_t inb[4] = {px, px * 4, st, a->gt ? px : 0};
-    const void* out[6] = {a->ids_out, a->labels_out, a->holes, a->stats_out, want_counts ? a->counts : nullptr, a->ws};
-    const size_t outb[6] = {px * 4, px, (size_t)B * 8, st, cn, px * 8};
-    for (int i = 0; i < 6; ++i) {
-      for (int j = 0; j < 4; ++j)
-        if (sh_overlap(out[i], outb[i], in[j], inb[j])) return DFW_EINVAL;
-      for (int j = i + 1; j < 6; ++j)
-        if (sh_overlap(out[i], outb[i], out[j], outb[j])) return DFW_EINVAL;
-    }
-  }
-  // int32 words (the workspace, both id maps, holes, both stats) and 64-bit count cells at their natural alignment
-  if ((((uintptr_t)a->ws | (uintptr_t)a->ids | (uintptr_t)a->ids_out | (uintptr_t)a->holes | (uintptr_t)a->stats_out |
-        (uintptr_t)(want_stats ? a->stats : nullptr)) & 3) || ((uintptr_t)a->counts & 7))
-    return DFW_ESHAPE;
+  const size_t px = (size_t)B * HW, sb = want_stats ? (size_t)B * a->cap * 32 : 0;   // stats only with stats_out
+  const seg_buf bufs[] = {seg_in(a->labels, px),
+                          seg_in(a->ids, px * 4, 4),
+                          seg_in(a->stats, sb, 4),
+                          seg_in(a->gt, px),
+                          seg_out(a->ids_out, px * 4, 4),
+                          seg_out(a->labels_out, px),
+                          seg_out(a->holes, (size_t)B * 8, 4),
+                          seg_out(a->stats_out, sb, 4),
+                          seg_out(a->counts, (size_t)B * 2 * (a->nlabels + 1) * 8, 8),
+                          seg_out(a->ws, px * 8, 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int hc8 = a->connectivity == 4;                  // the dual of the objects' connectivity
   const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH;

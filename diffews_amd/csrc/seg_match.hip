@@ -51,6 +51,7 @@
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
 // cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
+#include "seg_args.h"
 #include "seg_sort.h"
 
 namespace dfw {
@@ -271,9 +272,8 @@ inline int match_passes(long long capP, long long capG) { return seg_key_passes(
 static int match_size_error(long long B, long long H, long long W, long long capP, long long capG, long long max_records,
                             long long max_pairs) {
   if (B < 1 || H < 1 || W < 1 || capP < 1 || capG < 1 || max_records < 1 || max_pairs < 1) return DFW_EINVAL;
-  // grid y carries B; H * W <= 2^30 keeps every position, HW itself, the padded block count and every sum of lengths in an
-  // int, and inter * den below 2^46
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  // H * W <= 2^30 also keeps every sum of lengths in an int, and inter * den below 2^46
+  if (int e = seg_map_size_error(B, H, W)) return e;
   if ((capP + 1) * (capG + 1) - 1 > 0x7fffffffll) return DFW_ERANGE;   // the highest key is an int; capP + capG + 2 too, then
   // word counts the kernels and seg_zero_launch hold in an int: rows of pairs and match, the tables, the records
   if (B * max_pairs * 3 > 0x7fffffffll || B * max_records > 0x7fffffffll || B * capP * 3 > 0x7fffffffll ||
@@ -320,22 +320,23 @@ extern "C" int dfw_seg_match(const dfw_seg_match_args* a, dfw_stream_t stream) {
   if (a->num < 1 || a->num > a->den || a->den > 65535 || 2 * (long long)a->num < a->den) return DFW_EINVAL;
   if (a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
   if (int e = match_size_error(a->B, a->H, a->W, a->capP, a->capG, a->max_records, a->max_pairs)) return e;
-  if (a->ws_bytes < dfw_seg_match_workspace_bytes(a->B, a->H, a->W, a->capP, a->capG, a->max_records, a->max_pairs))
-    return DFW_EWORKSPACE;
-  const size_t HWs = (size_t)a->H * a->W, Bs = (size_t)a->B, cP = (size_t)a->capP, cG = (size_t)a->capG;
-  const void* in[5] = {a->pids, a->gids, a->pstats, a->gstats, a->skip};
-  const size_t inb[5] = {Bs * HWs * 4, Bs * HWs * 4, Bs * cP * 32, Bs * cG * 32, Bs * HWs};
-  const void* out[7] = {a->pairs, a->pair_off, a->area, a->match, a->gmatch, a->pq, a->n};
-  const size_t outb[7] = {Bs * a->max_pairs * 12, Bs * (cP + 2) * 4, Bs * (cP + cG + 2) * 4, Bs * cP * 12, Bs * cG * 4,
-                          Bs * ((size_t)a->nlabels + 1) * 32, Bs * 16};
-  for (int i = 0; i < 5; ++i)
-    for (int o = 0; o < 7; ++o)
-      if (seg_overlap(in[i], inb[i], out[o], outb[o])) return DFW_EINVAL;
-  if (((uintptr_t)a->pids | (uintptr_t)a->gids | (uintptr_t)a->pstats | (uintptr_t)a->gstats | (uintptr_t)a->pairs |
-       (uintptr_t)a->pair_off | (uintptr_t)a->area | (uintptr_t)a->match | (uintptr_t)a->gmatch | (uintptr_t)a->n |
-       (uintptr_t)a->ws) & 3)
-    return DFW_ESHAPE;
-  if ((uintptr_t)a->pq & 7) return DFW_ESHAPE;
+  const size_t need = dfw_seg_match_workspace_bytes(a->B, a->H, a->W, a->capP, a->capG, a->max_records, a->max_pairs);
+  if (a->ws_bytes < need) return DFW_EWORKSPACE;
+  const size_t Bs = (size_t)a->B, px = Bs * a->H * a->W, cP = (size_t)a->capP, cG = (size_t)a->capG;
+  const seg_buf bufs[] = {seg_in(a->pids, px * 4, 4),
+                          seg_in(a->gids, px * 4, 4),
+                          seg_in(a->pstats, Bs * cP * 32, 4),
+                          seg_in(a->gstats, Bs * cG * 32, 4),
+                          seg_in(a->skip, px),
+                          seg_out(a->pairs, Bs * a->max_pairs * 12, 4),
+                          seg_out(a->pair_off, Bs * (cP + 2) * 4, 4),
+                          seg_out(a->area, Bs * (cP + cG + 2) * 4, 4),
+                          seg_out(a->match, Bs * cP * 12, 4),
+                          seg_out(a->gmatch, Bs * cG * 4, 4),
+                          seg_out(a->pq, Bs * ((size_t)a->nlabels + 1) * 32, 8),
+                          seg_out(a->n, Bs * 16, 4),
+                          seg_out(a->ws, need, 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int nB = a->B, iHW = a->H * a->W, capP = a->capP, capG = a->capG, M = a->max_records, MP = a->max_pairs;
   const match_layout l = match_plan(nB, iHW, M, MP);

@@ -30,6 +30,7 @@
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
 // cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
+#include "seg_args.h"
 #include "seg_sort.h"
 
 namespace dfw {
@@ -110,8 +111,7 @@ struct rle_layout {
 static int rle_size_error(long long B, long long H, long long W, long long cap, long long max_runs, int order) {
   if (B < 1 || H < 1 || W < 1 || cap < 1 || max_runs < 1) return DFW_EINVAL;
   if (order != 0 && order != 1) return DFW_EINVAL;
-  // grid y / z carry B; H * W <= 2^30 keeps every position, HW itself and the padded block count in an int
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  if (int e = seg_map_size_error(B, H, W)) return e;
   // rows of runs are addressed in words: B * max_runs * 2 < 2^31, which also bounds max_runs below 2^30 and the digit
   // table, 256 * nchunk <= 2^27 words an image, inside an int
   if (B * max_runs * 2 > 0x7fffffffll) return DFW_ERANGE;
@@ -168,14 +168,14 @@ extern "C" int dfw_seg_rle_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, 
 extern "C" int dfw_seg_rle(const dfw_seg_rle_args* a, dfw_stream_t stream) {
   if (!a || !a->ids || !a->runs || !a->run_off || !a->nruns || !a->ws) return DFW_EINVAL;
   if (int e = rle_size_error(a->B, a->H, a->W, a->cap, a->max_runs, a->order)) return e;
-  if (a->ws_bytes < dfw_seg_rle_workspace_bytes(a->B, a->H, a->W, a->cap, a->max_runs, a->order)) return DFW_EWORKSPACE;
-  const size_t idb = (size_t)a->B * a->H * a->W * 4;
-  if (seg_overlap(a->ids, idb, a->runs, (size_t)a->B * a->max_runs * 8) ||
-      seg_overlap(a->ids, idb, a->run_off, (size_t)a->B * ((size_t)a->cap + 1) * 4) ||
-      seg_overlap(a->ids, idb, a->nruns, (size_t)a->B * 8))
-    return DFW_EINVAL;
-  if (((uintptr_t)a->ids | (uintptr_t)a->runs | (uintptr_t)a->run_off | (uintptr_t)a->nruns | (uintptr_t)a->ws) & 3)
-    return DFW_ESHAPE;
+  const size_t need = dfw_seg_rle_workspace_bytes(a->B, a->H, a->W, a->cap, a->max_runs, a->order);
+  if (a->ws_bytes < need) return DFW_EWORKSPACE;
+  const seg_buf bufs[] = {seg_in(a->ids, (size_t)a->B * a->H * a->W * 4, 4),
+                          seg_out(a->runs, (size_t)a->B * a->max_runs * 8, 4),
+                          seg_out(a->run_off, (size_t)a->B * ((size_t)a->cap + 1) * 4, 4),
+                          seg_out(a->nruns, (size_t)a->B * 8, 4),
+                          seg_out(a->ws, need, 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int B = a->B, H = a->H, W = a->W, cap = a->cap, M = a->max_runs, iHW = H * W;
   const rle_layout l = rle_plan(B, iHW, cap, M, a->order);

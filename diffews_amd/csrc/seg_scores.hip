@@ -31,6 +31,7 @@
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed at compile time.  Any
 // grid is correct at any residency.
+#include "seg_args.h"
 #include "seg_sort.h"
 
 namespace dfw {
@@ -226,8 +227,7 @@ __global__ __launch_bounds__(256) void scores_finish_kernel(const void* ws, long
 static int scores_size_error(long long B, long long H, long long W, long long cap, long long nlabels, long long P) {
   if (B < 1 || H < 1 || W < 1 || cap < 1 || P < 1) return DFW_EINVAL;
   if (nlabels < 1 || nlabels > 254) return DFW_EINVAL;
-  // grid y carries B; H * W <= 2^30 keeps every position and the padded block count in an int
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
+  if (int e = seg_map_size_error(B, H, W)) return e;
   // seg_u8 is addressed in size_t: P * 3 * H * W must stay below 2^63, which int32 arguments cannot break (2^31 * 3 *
   // 2^30); the test is here for the day a size widens
   if (P > (0x7fffffffffffffffll / 3) / (H * W)) return DFW_ERANGE;
@@ -260,13 +260,13 @@ extern "C" int dfw_seg_scores(const dfw_seg_scores_args* a, dfw_stream_t stream)
   const size_t wsb = dfw_seg_scores_workspace_bytes(a->B, a->cap);
   if (a->ws_bytes < wsb) return DFW_EWORKSPACE;
   const size_t HW = (size_t)a->H * a->W, rows = (size_t)a->B * a->cap;
-  const void* const in[4] = {a->ids, a->labels, a->seg_u8, a->planes};
-  const size_t inb[4] = {a->B * HW * 4, a->B * HW, (size_t)a->P * 3 * HW, (size_t)a->B * (a->nlabels + 1) * 4};
-  for (int i = 0; i < 4; ++i)
-    if (seg_overlap(in[i], inb[i], a->scores, rows * 32) || seg_overlap(in[i], inb[i], a->ws, wsb)) return DFW_EINVAL;
-  if (seg_overlap(a->scores, rows * 32, a->ws, wsb)) return DFW_EINVAL;
-  if (((uintptr_t)a->ids | (uintptr_t)a->planes | (uintptr_t)a->ws) & 3) return DFW_ESHAPE;
-  if ((uintptr_t)a->scores & 7) return DFW_ESHAPE;
+  const seg_buf bufs[] = {seg_in(a->ids, a->B * HW * 4, 4),
+                          seg_in(a->labels, a->B * HW),
+                          seg_in(a->seg_u8, (size_t)a->P * 3 * HW),
+                          seg_in(a->planes, (size_t)a->B * (a->nlabels + 1) * 4, 4),   // planes_host is host memory
+                          seg_out(a->scores, rows * 32, 8),
+                          seg_out(a->ws, wsb, 4)};
+  if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int iHW = a->H * a->W, irows = a->B * a->cap;
   const score_ws w = score_split(a->ws, rows);

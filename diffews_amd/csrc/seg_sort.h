@@ -50,11 +50,6 @@ inline int seg_table_words(long long max_records) { return 256 * seg_chunks(max_
 inline int seg_key_passes(long long keys) {
   return keys <= (1ll << 8) ? 1 : keys <= (1ll << 16) ? 2 : keys <= (1ll << 24) ? 3 : 4;
 }
-// Two byte ranges share a byte; a null one shares none.
-inline bool seg_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return p && q && a < b + qn && b < a + pn;
-}
 
 // The starts among a thread's eight positions: v[0] is the predecessor's key.
 __device__ __forceinline__ int seg_starts(const int (&v)[9]) {

@@ -252,13 +252,6 @@ __device__ __forceinline__ void cc_flatten_body(int32_t* parent, int32_t* area, 
 
 inline size_t cc_blocks(long long HW) { return (size_t)((HW + kCcTile - 1) / kCcTile); }
 
-// The sizes dfw_seg_components and dfw_seg_holes refuse, and the rounds query with them: DFW_EINVAL before DFW_ERANGE.
-inline int cc_size_error(long long B, long long H, long long W) {
-  if (B < 1 || H < 1 || W < 1) return DFW_EINVAL;
-  if (H > 65535 || W > 65535 || H * W > (1ll << 30) || B > 65535) return DFW_ERANGE;
-  return 0;
-}
-
 // One inline function per launch whose kernel loops: the grid, and with it the trips of the loop.
 constexpr int kCcGridCap = 4096;
 // the merge: one thread per item, grid-stride behind the cap.

@@ -44,6 +44,65 @@ import torch
 from . import ops
 
 
+# ------------------------------------------------------------------------------------------------ what the stages share
+
+def _per_item(call, k, optional, message, keys):
+    """The list dispatch of every stage: each of `optional` is a list of k per-item arguments or None (k times None then;
+    any other length is ValueError(message)); call(i, *entries of item i) runs once per item, and the per-item dicts
+    become one dict of lists over `keys`."""
+    cols = [c if c is not None else [None] * k for c in optional]
+    if any(len(c) != k for c in cols):
+        raise ValueError(message)
+    per = [call(i, *(c[i] for c in cols)) for i in range(k)]
+    return {key: [p[key] for p in per] for key in keys}
+
+
+def _lift(squeeze, *ts):
+    """[H, W] inputs as batches of one when squeeze is set; None stays None."""
+    return tuple(t[None] if squeeze and t is not None else t for t in ts)
+
+
+def _unlift(squeeze, r):
+    """... and the result without that batch axis again: every tensor of r loses it, everything else stays."""
+    return {k: (v[0] if squeeze and isinstance(v, torch.Tensor) else v) for k, v in r.items()}
+
+
+def _rows(stats):
+    """cap, the rows of a stats table -- per item for a list."""
+    return [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
+
+
+def _ids_caps(o, max_components, who, verb):
+    """A label_objects result, or an id tensor (or list of them) with max_components -> (ids, cap); cap per item for a
+    list."""
+    if isinstance(o, dict):
+        if max_components is not None:
+            raise ValueError(f"{who}: max_components comes from the result's stats table")
+        return o["ids"], _rows(o["stats"])
+    if max_components is None:
+        raise ValueError(f"{who}: an id tensor needs max_components, the highest id to {verb}")
+    return o, [int(max_components)] * len(o) if isinstance(o, (list, tuple)) else int(max_components)
+
+
+def _cached_counts(self, nlabels):
+    """The counts method of ComponentBuffers and HoleBuffers: int64 [B, 2, nlabels + 1], made on first use for a number of
+    classes and kept."""
+    c = self._counts.get(nlabels)
+    if c is None:
+        c = self._counts[nlabels] = torch.empty(self.shape[0], 2, nlabels + 1, dtype=torch.int64, device=self.device)
+    return c
+
+
+def _to_host(tensors):
+    """int32 / int64 device tensors -> numpy arrays of the same shapes and dtypes with ONE synchronising copy: flattened
+    and concatenated on the device (an int64 table as pairs of int32), copied, split again."""
+    parts = [t.reshape(-1).view(torch.int32) if t.dtype == torch.int64 else t.reshape(-1) for t in tensors]
+    flat = torch.cat(parts).cpu().numpy()
+    cut = np.cumsum([0] + [p.numel() for p in parts])
+    return [(flat[cut[i]:cut[i + 1]].view(np.int64) if t.dtype == torch.int64 else flat[cut[i]:cut[i + 1]]).reshape(t.shape)
+            for i, t in enumerate(tensors)]
+
+
 class ComponentBuffers:
     """Everything one label_objects call of a shape writes, allocated once: ids int32 [B, H, W], labels uint8 [B, H, W]
     (the filtered map), n int32 [B, 2], stats int32 [B, max_components, 8], the workspace, and -- made on first use for a
@@ -62,17 +121,12 @@ class ComponentBuffers:
         self.ws = torch.empty(ops.seg_components_workspace(B, H, W), dtype=torch.uint8, device=dev)
         self._counts = {}
 
-    def counts(self, nlabels):
-        c = self._counts.get(nlabels)
-        if c is None:
-            c = self._counts[nlabels] = torch.empty(self.shape[0], 2, nlabels + 1, dtype=torch.int64, device=self.device)
-        return c
+    counts = _cached_counts
 
 
 def _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers):
     squeeze = labels.dim() == 2
-    if squeeze:
-        labels, gt = labels[None], None if gt is None else gt[None]
+    labels, gt = _lift(squeeze, labels, gt)
     if labels.dim() != 3 or labels.dtype != torch.uint8 or not labels.is_cuda:
         raise ValueError("label_objects takes a uint8 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
     labels = labels.contiguous()
@@ -90,10 +144,7 @@ def _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers):
         gt, counts = gt.contiguous(), buffers.counts(int(nlabels))
     ops.seg_components(labels, buffers.ids, buffers.n, buffers.ws, filtered=buffers.labels, stats=buffers.stats, gt=gt,
                        counts=counts, connectivity=connectivity, min_area=min_area, nlabels=nlabels)
-    r = dict(ids=buffers.ids, labels=buffers.labels, n=buffers.n, stats=buffers.stats, counts=counts)
-    if squeeze:
-        r = {k: (None if v is None else v[0]) for k, v in r.items()}
-    return r
+    return _unlift(squeeze, dict(ids=buffers.ids, labels=buffers.labels, n=buffers.n, stats=buffers.stats, counts=counts))
 
 
 def label_objects(labels, gt=None, connectivity=8, min_area=0, max_components=1024, nlabels=None, buffers=None):
@@ -115,12 +166,9 @@ def label_objects(labels, gt=None, connectivity=8, min_area=0, max_components=10
     ComponentBuffers or None.  buffers: a ComponentBuffers of this shape, reused call after call (the result then aliases
     it); without it fresh buffers are allocated.  A fixed number of launches per call and no host synchronisation."""
     if isinstance(labels, (list, tuple)):
-        gts = gt if gt is not None else [None] * len(labels)
-        bufs = buffers if buffers is not None else [None] * len(labels)
-        if len(gts) != len(labels) or len(bufs) != len(labels):
-            raise ValueError("label_objects: one gt / buffers entry per label map")
-        per = [_one(l, g, connectivity, min_area, max_components, nlabels, b) for l, g, b in zip(labels, gts, bufs)]
-        return {k: [p[k] for p in per] for k in ("ids", "labels", "n", "stats", "counts")}
+        return _per_item(lambda i, g, b: _one(labels[i], g, connectivity, min_area, max_components, nlabels, b), len(labels),
+                         (gt, buffers), "label_objects: one gt / buffers entry per label map",
+                         ("ids", "labels", "n", "stats", "counts"))
     return _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers)
 
 
@@ -137,8 +185,7 @@ def objects_to_host(r):
     if single:
         n, stats = n[None], stats[None]
     B, cap = stats.shape[:2]
-    both = torch.cat([n.reshape(-1), stats.reshape(-1)]).cpu()       # the one copy
-    n, stats = both[:2 * B].view(B, 2).tolist(), both[2 * B:].view(B, cap, 8).tolist()
+    n, stats = (a.tolist() for a in _to_host([n, stats]))            # the one copy
     objs = [[(s[0], s[1], (s[2], s[3], s[4], s[5]), s[6]) for s in stats[b][:min(n[b][0], cap)]] for b in range(B)]
     truncated = any(n[b][0] > cap for b in range(B))
     return (objs[0] if single else objs), truncated
@@ -168,11 +215,7 @@ class HoleBuffers:
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._counts = {}
 
-    def counts(self, nlabels):
-        c = self._counts.get(nlabels)
-        if c is None:
-            c = self._counts[nlabels] = torch.empty(self.shape[0], 2, nlabels + 1, dtype=torch.int64, device=self.device)
-        return c
+    counts = _cached_counts
 
 
 def _holes_one(o, max_area, connectivity, gt, nlabels, buffers):
@@ -182,8 +225,7 @@ def _holes_one(o, max_area, connectivity, gt, nlabels, buffers):
         raise ValueError(f"fill_holes: max_area must lie in 0..2^31 - 1 (None: no limit), got {max_area}")
     ids, labels, n, stats = o["ids"], o["labels"], o["n"], o["stats"]
     squeeze = ids.dim() == 2
-    if squeeze:
-        ids, labels, stats, gt = ids[None], labels[None], stats[None], None if gt is None else gt[None]
+    ids, labels, stats, gt = _lift(squeeze, ids, labels, stats, gt)
     if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda or labels.dtype != torch.uint8 or labels.shape != ids.shape:
         raise ValueError("fill_holes takes a label_objects result: ids int32 and labels uint8 on the device, [H, W] or "
                          "[B, H, W], or lists of [h, w] maps")
@@ -206,9 +248,7 @@ def _holes_one(o, max_area, connectivity, gt, nlabels, buffers):
     ops.seg_holes(labels.contiguous(), ids.contiguous(), buffers.ids, buffers.labels, buffers.holes, buffers.ws,
                   stats=stats.contiguous(), stats_out=buffers.stats, gt=gt, counts=counts, connectivity=connectivity,
                   max_area=max_area, nlabels=nlabels)
-    r = dict(ids=buffers.ids, labels=buffers.labels, stats=buffers.stats, counts=counts, holes=buffers.holes)
-    if squeeze:
-        r = {k: (None if v is None else v[0]) for k, v in r.items()}
+    r = _unlift(squeeze, dict(ids=buffers.ids, labels=buffers.labels, stats=buffers.stats, counts=counts, holes=buffers.holes))
     r["n"] = n
     return r
 
@@ -240,14 +280,10 @@ def fill_holes(o, max_area=None, connectivity=8, gt=None, nlabels=None, buffers=
     max_components, reused call after call (the result then aliases it).  At most 6 launches per call and no host
     synchronisation."""
     if isinstance(o["ids"], (list, tuple)):
-        k = len(o["ids"])
-        gts = gt if gt is not None else [None] * k
-        bufs = buffers if buffers is not None else [None] * k
-        if len(gts) != k or len(bufs) != k:
-            raise ValueError("fill_holes: one gt / buffers entry per item")
-        per = [_holes_one({key: o[key][i] for key in ("ids", "labels", "n", "stats")}, max_area, connectivity, g, nlabels, b)
-               for i, (g, b) in enumerate(zip(gts, bufs))]
-        return {key: [p[key] for p in per] for key in ("ids", "labels", "n", "stats", "counts", "holes")}
+        item = lambda i: {key: o[key][i] for key in ("ids", "labels", "n", "stats")}  # noqa: E731
+        return _per_item(lambda i, g, b: _holes_one(item(i), max_area, connectivity, g, nlabels, b), len(o["ids"]),
+                         (gt, buffers), "fill_holes: one gt / buffers entry per item",
+                         ("ids", "labels", "n", "stats", "counts", "holes"))
     return _holes_one(o, max_area, connectivity, gt, nlabels, buffers)
 
 
@@ -275,8 +311,7 @@ class RunBuffers:
 
 def _runs_one(ids, cap, order, max_runs, buffers):
     squeeze = ids.dim() == 2
-    if squeeze:
-        ids = ids[None]
+    ids, = _lift(squeeze, ids)
     if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
         raise ValueError("object_runs takes an int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
     ids = ids.contiguous()
@@ -289,10 +324,7 @@ def _runs_one(ids, cap, order, max_runs, buffers):
                          f"order {buffers.order!r} on {buffers.device}; the ids are {(B, H, W)} with {cap} objects, order "
                          f"{order!r} on {ids.device}")
     ops.seg_rle(ids, buffers.runs, buffers.run_off, buffers.nruns, buffers.ws, cap, order)
-    r = dict(runs=buffers.runs, run_off=buffers.run_off, nruns=buffers.nruns, order=order, shape=(H, W))
-    if squeeze:
-        r.update(runs=r["runs"][0], run_off=r["run_off"][0], nruns=r["nruns"][0])
-    return r
+    return _unlift(squeeze, dict(runs=buffers.runs, run_off=buffers.run_off, nruns=buffers.nruns, order=order, shape=(H, W)))
 
 
 def object_runs(o, order="column", max_runs=None, buffers=None, max_components=None):
@@ -311,22 +343,10 @@ def object_runs(o, order="column", max_runs=None, buffers=None, max_components=N
     then a list of RunBuffers or None.  buffers: a RunBuffers of this shape, object count and order, reused call after call
     (the result aliases it); max_runs: rows per image for fresh buffers (RunBuffers' default otherwise).  A fixed number of
     launches per call and no host synchronisation."""
-    if isinstance(o, dict):
-        if max_components is not None:
-            raise ValueError("object_runs: max_components comes from the result's stats table")
-        ids, stats = o["ids"], o["stats"]
-        caps = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
-    else:
-        if max_components is None:
-            raise ValueError("object_runs: an id tensor needs max_components, the highest id to encode")
-        ids = o
-        caps = [int(max_components)] * len(ids) if isinstance(ids, (list, tuple)) else int(max_components)
+    ids, caps = _ids_caps(o, max_components, "object_runs", "encode")
     if isinstance(ids, (list, tuple)):
-        bufs = buffers if buffers is not None else [None] * len(ids)
-        if len(bufs) != len(ids):
-            raise ValueError("object_runs: one buffers entry per id map")
-        per = [_runs_one(i, c, order, max_runs, b) for i, c, b in zip(ids, caps, bufs)]
-        return {k: [p[k] for p in per] for k in ("runs", "run_off", "nruns", "order", "shape")}
+        return _per_item(lambda i, b: _runs_one(ids[i], caps[i], order, max_runs, b), len(ids), (buffers,),
+                         "object_runs: one buffers entry per id map", ("runs", "run_off", "nruns", "order", "shape"))
     return _runs_one(ids, caps, order, max_runs, buffers)
 
 
@@ -344,14 +364,12 @@ def runs_to_host(rr):
     if single:
         nruns, run_off, runs = nruns[None], run_off[None], runs[None]
     B, cap = run_off.shape[0], run_off.shape[1] - 1
-    both = torch.cat([nruns.reshape(-1), run_off.reshape(-1)]).cpu().numpy()       # copy one: the tables
-    nruns, run_off = both[:2 * B].reshape(B, 2), both[2 * B:].reshape(B, cap + 1)
+    nruns, run_off = _to_host([nruns, run_off])                               # copy one: the tables
     kept = nruns[:, 0].tolist()
-    flat = torch.cat([runs[b, :kept[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 2)   # copy two
-    out, at = [], 0
+    runs = _to_host([runs[b, :kept[b]] for b in range(B)])                    # copy two
+    out = []
     for b in range(B):
-        rows, off = flat[at:at + kept[b]], run_off[b]
-        at += kept[b]
+        rows, off = runs[b], run_off[b]
         n = int(np.searchsorted(off, kept[b], side="left")) if kept[b] else 0   # the first k with run_off[k] == kept
         out.append([rows[off[k - 1]:off[k]] for k in range(1, min(n, cap) + 1)])
     truncated = bool((nruns[:, 1] > nruns[:, 0]).any())
@@ -416,8 +434,7 @@ _CONTOUR_KEYS = ("verts", "rings", "ring_off", "n")
 
 def _contours_one(ids, cap, connectivity, max_edges, buffers):
     squeeze = ids.dim() == 2
-    if squeeze:
-        ids = ids[None]
+    ids, = _lift(squeeze, ids)
     if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
         raise ValueError("object_contours takes an int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
     ids = ids.contiguous()
@@ -429,11 +446,7 @@ def _contours_one(ids, cap, connectivity, max_edges, buffers):
         raise ValueError(f"buffers were made for {buffers.shape}, {buffers.max_components} objects, {buffers.max_edges} edges "
                          f"on {buffers.device}; the ids are {(B, H, W)} with {cap} objects on {ids.device}")
     ops.seg_contours(ids, buffers.verts, buffers.rings, buffers.ring_off, buffers.n, buffers.ws, cap, connectivity)
-    r = {k: getattr(buffers, k) for k in _CONTOUR_KEYS}
-    if squeeze:
-        r = {k: v[0] for k, v in r.items()}
-    r.update(shape=(H, W), connectivity=connectivity)
-    return r
+    return _unlift(squeeze, dict({k: getattr(buffers, k) for k in _CONTOUR_KEYS}, shape=(H, W), connectivity=connectivity))
 
 
 def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_components=None):
@@ -462,22 +475,10 @@ def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_compone
     number of launches per call and no host synchronisation."""
     if connectivity not in (4, 8):
         raise ValueError(f"object_contours: connectivity must be 4 or 8, not {connectivity!r}")
-    if isinstance(o, dict):
-        if max_components is not None:
-            raise ValueError("object_contours: max_components comes from the result's stats table")
-        ids, stats = o["ids"], o["stats"]
-        caps = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
-    else:
-        if max_components is None:
-            raise ValueError("object_contours: an id tensor needs max_components, the highest id to outline")
-        ids = o
-        caps = [int(max_components)] * len(ids) if isinstance(ids, (list, tuple)) else int(max_components)
+    ids, caps = _ids_caps(o, max_components, "object_contours", "outline")
     if isinstance(ids, (list, tuple)):
-        bufs = buffers if buffers is not None else [None] * len(ids)
-        if len(bufs) != len(ids):
-            raise ValueError("object_contours: one buffers entry per id map")
-        per = [_contours_one(i, c, connectivity, max_edges, b) for i, c, b in zip(ids, caps, bufs)]
-        return {k: [p[k] for p in per] for k in _CONTOUR_KEYS + ("shape", "connectivity")}
+        return _per_item(lambda i, b: _contours_one(ids[i], caps[i], connectivity, max_edges, b), len(ids), (buffers,),
+                         "object_contours: one buffers entry per id map", _CONTOUR_KEYS + ("shape", "connectivity"))
     return _contours_one(ids, caps, connectivity, max_edges, buffers)
 
 
@@ -494,15 +495,11 @@ def contours_to_host(c):
     if single:
         n, ring_off, rings, verts = n[None], ring_off[None], rings[None], verts[None]
     B, cap = ring_off.shape[0], ring_off.shape[1] - 1
-    both = torch.cat([n.reshape(-1), ring_off.reshape(-1), rings.reshape(-1)]).cpu().numpy()       # copy one: the tables
-    n, ring_off = both[:4 * B].reshape(B, 4), both[4 * B:4 * B + B * (cap + 1)].reshape(B, cap + 1)
-    rings = both[4 * B + B * (cap + 1):].reshape(B, -1, 4)
-    corners = n[:, 1].tolist()
-    flat = torch.cat([verts[b, :corners[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 2)   # copy two
-    out, at = [], 0
+    n, ring_off, rings = _to_host([n, ring_off, rings])                       # copy one: the tables
+    verts = _to_host([verts[b, :int(n[b, 1])] for b in range(B)])              # copy two: the corners
+    out = []
     for b in range(B):
-        pts, off, nr = flat[at:at + corners[b]], ring_off[b], int(n[b, 2])
-        at += corners[b]
+        pts, off, nr = verts[b], ring_off[b], int(n[b, 2])
         top = int(np.searchsorted(off, nr, side="left")) if nr else 0        # the first k with ring_off[k] == rings
         out.append([[(int(a), pts[f:f + k]) for _, f, k, a in rings[b, off[o - 1]:off[o]].tolist()]
                     for o in range(1, min(top, cap) + 1)])
@@ -586,8 +583,7 @@ def _side(o, what):
         ids, stats = o["ids"], o["stats"]
         if stats is None:
             raise ValueError(f"match_objects: the {what} result holds no stats table; pass (ids, None, cap)")
-        cap = [s.shape[-2] for s in stats] if isinstance(stats, (list, tuple)) else stats.shape[-2]
-        return ids, stats, cap
+        return ids, stats, _rows(stats)
     if not isinstance(o, (list, tuple)) or len(o) not in (2, 3):
         raise ValueError(f"match_objects: {what} must be a label_objects result or a tuple (ids, stats or None[, cap])")
     ids, stats = o[0], o[1]
@@ -597,7 +593,7 @@ def _side(o, what):
     elif stats is None:
         raise ValueError(f"match_objects: {what} ids without a stats table need an explicit cap: (ids, None, cap)")
     else:
-        cap = [s.shape[-2] for s in stats] if many else stats.shape[-2]
+        cap = _rows(stats)
     if many and stats is None:
         stats = [None] * len(ids)
     return ids, stats, cap
@@ -605,9 +601,7 @@ def _side(o, what):
 
 def _match_one(pids, pstats, cap_p, gids, gstats, cap_g, skip, iou, nlabels, buffers):
     squeeze = pids.dim() == 2
-    if squeeze:
-        lift = lambda t: None if t is None else t[None]  # noqa: E731
-        pids, gids, pstats, gstats, skip = pids[None], lift(gids), lift(pstats), lift(gstats), lift(skip)
+    pids, gids, pstats, gstats, skip = _lift(squeeze, pids, gids, pstats, gstats, skip)
     if pids.dim() != 3 or pids.dtype != torch.int32 or not pids.is_cuda:
         raise ValueError("match_objects takes int32 device id maps [H, W] or [B, H, W], or lists of [h, w] maps")
     if gids is None or gids.dtype != torch.int32 or gids.shape != pids.shape:
@@ -628,10 +622,7 @@ def _match_one(pids, pstats, cap_p, gids, gstats, cap_g, skip, iou, nlabels, buf
     ops.seg_match(pids.contiguous(), gids.contiguous(), buffers.pairs, buffers.pair_off, buffers.area, buffers.match,
                   buffers.gmatch, buffers.pq, buffers.n, buffers.ws, buffers.max_records, pstats=cont(pstats),
                   gstats=cont(gstats), skip=cont(skip), iou=iou)
-    r = {k: getattr(buffers, k) for k in _MATCH_KEYS}
-    if squeeze:
-        r = {k: v[0] for k, v in r.items()}
-    return r
+    return _unlift(squeeze, {k: getattr(buffers, k) for k in _MATCH_KEYS})
 
 
 def match_objects(o_pred, o_gt, skip=None, iou=(1, 2), nlabels=None, buffers=None):
@@ -666,13 +657,9 @@ def match_objects(o_pred, o_gt, skip=None, iou=(1, 2), nlabels=None, buffers=Non
         k = len(pids)
         if not isinstance(gids, (list, tuple)) or len(gids) != k:
             raise ValueError("match_objects: one ground-truth id map per predicted id map")
-        skips = skip if skip is not None else [None] * k
-        bufs = buffers if buffers is not None else [None] * k
-        if len(skips) != k or len(bufs) != k:
-            raise ValueError("match_objects: one skip / buffers entry per id map")
-        per = [_match_one(pids[i], pstats[i], cap_p[i], gids[i], gstats[i], cap_g[i], skips[i], iou, nlabels, bufs[i])
-               for i in range(k)]
-        return {key: [p[key] for p in per] for key in _MATCH_KEYS}
+        return _per_item(lambda i, s, b: _match_one(pids[i], pstats[i], cap_p[i], gids[i], gstats[i], cap_g[i], s, iou,
+                                                    nlabels, b),
+                         k, (skip, buffers), "match_objects: one skip / buffers entry per id map", _MATCH_KEYS)
     if isinstance(gids, (list, tuple)):
         raise ValueError("match_objects: one ground-truth id map per predicted id map")
     return _match_one(pids, pstats, cap_p, gids, gstats, cap_g, skip, iou, nlabels, buffers)
@@ -690,17 +677,9 @@ def matches_to_host(m):
     single = m["n"].dim() == 1
     t = {k: (v[None] if single else v) for k, v in m.items()}
     B = t["n"].shape[0]
-    names = ("n", "pair_off", "area", "match", "gmatch")
-    both = torch.cat([t[k].reshape(-1) for k in names] + [t["pq"].reshape(-1).view(torch.int32)]).cpu().numpy()   # copy one
-    out, at = {}, 0
-    for k in names:
-        out[k] = both[at:at + t[k].numel()].reshape(t[k].shape)
-        at += t[k].numel()
-    out["pq"] = both[at:].view(np.int64).reshape(t["pq"].shape)
-    kept = out["n"][:, 0].tolist()
-    flat = torch.cat([t["pairs"][b, :kept[b]].reshape(-1) for b in range(B)]).cpu().numpy().reshape(-1, 3)   # copy two
-    offs = np.concatenate([[0], np.cumsum(kept)])
-    out["pairs"] = [flat[offs[b]:offs[b + 1]] for b in range(B)]
+    names = ("n", "pair_off", "area", "match", "gmatch", "pq")
+    out = dict(zip(names, _to_host([t[k] for k in names])))                    # copy one: the tables
+    out["pairs"] = _to_host([t["pairs"][b, :int(out["n"][b, 0])] for b in range(B)])   # copy two
     truncated = bool((out["n"][:, 0] < out["n"][:, 1]).any() or (out["n"][:, 2] < out["n"][:, 3]).any())
     if single:
         out = {k: v[0] for k, v in out.items()}
@@ -813,10 +792,7 @@ def _scores_one(ids, labels, cap, seg_u8, table, buffers):
     buffers.stage(table)
     ops.seg_scores(ids.contiguous(), labels.contiguous(), seg_u8.view(-1, 3, H, W), buffers.planes, buffers.planes_host,
                    buffers.scores, buffers.ws)
-    r = dict(scores=buffers.scores, planes=buffers.planes)
-    if squeeze:
-        r = {k: v[0] for k, v in r.items()}
-    return r
+    return _unlift(squeeze, dict(scores=buffers.scores, planes=buffers.planes))
 
 
 def object_scores(o, seg_u8, planes, buffers=None):
@@ -844,11 +820,8 @@ def object_scores(o, seg_u8, planes, buffers=None):
             tabs = [_plane_table(p) for p in planes]
         else:
             tabs = [_plane_table(planes)] * k
-        bufs = buffers if buffers is not None else [None] * k
-        if len(bufs) != k:
-            raise ValueError("object_scores: one buffers entry per id map")
-        per = [_scores_one(ids[i], labels[i], stats[i].shape[-2], seg_u8[i], tabs[i], bufs[i]) for i in range(k)]
-        return {key: [p[key] for p in per] for key in ("scores", "planes")}
+        return _per_item(lambda i, b: _scores_one(ids[i], labels[i], stats[i].shape[-2], seg_u8[i], tabs[i], b), k,
+                         (buffers,), "object_scores: one buffers entry per id map", ("scores", "planes"))
     return _scores_one(ids, labels, stats.shape[-2], seg_u8, _plane_table(planes), buffers)
 
 
@@ -900,19 +873,11 @@ def detections_to_host(o, s, m):
                                   {k: v[i] for k, v in m.items()}) for i in range(len(o["n"]))]
         return [p[0] for p in per], np.sum([p[1] for p in per], axis=0)
     single = o["n"].dim() == 1
-    lift = (lambda t: t[None]) if single else (lambda t: t)
-    n, stats, scores, match, area, pq = (lift(t) for t in (o["n"], o["stats"], s["scores"], m["match"], m["area"], m["pq"]))
+    n, stats, scores, match, area, pq = _lift(single, o["n"], o["stats"], s["scores"], m["match"], m["area"], m["pq"])
     B, cap = stats.shape[:2]
     if scores.shape[:2] != (B, cap) or match.shape[:2] != (B, cap):
         raise ValueError("detections_to_host: o, s and m must describe the same images and the same number of objects")
-    parts = [n.reshape(-1), stats[:, :, 0].reshape(-1), match.reshape(-1), area[:, 1:cap + 1].reshape(-1),
-             scores.reshape(-1).view(torch.int32), pq.reshape(-1).view(torch.int32)]
-    both = torch.cat(parts).cpu().numpy()                           # the one copy
-    cut = np.cumsum([p.numel() for p in parts])
-    n, cls, match, area = both[:cut[0]].reshape(B, 2), both[cut[0]:cut[1]].reshape(B, cap), \
-        both[cut[1]:cut[2]].reshape(B, cap, 3), both[cut[2]:cut[3]].reshape(B, cap)
-    scores = both[cut[3]:cut[4]].view(np.int64).reshape(B, cap, 4)
-    pq = both[cut[4]:].view(np.int64).reshape(B, -1, 4)
+    n, cls, match, area, scores, pq = _to_host([n, stats[:, :, 0], match, area[:, 1:cap + 1], scores, pq])   # the one copy
     dets = []
     for b in range(B):
         k = min(int(n[b, 0]), cap)
@@ -954,8 +919,7 @@ class BoundaryBuffers:
 
 def _bands_one(m, d, ratio, dmax, buffers):
     squeeze = m.dim() == 2
-    if squeeze:
-        m = m[None]
+    m, = _lift(squeeze, m)
     if m.dim() != 3 or m.dtype not in (torch.uint8, torch.int32) or not m.is_cuda:
         raise ValueError("boundary_bands takes a uint8 or int32 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
     B, H, W = m.shape
@@ -977,10 +941,7 @@ def _bands_one(m, d, ratio, dmax, buffers):
         raise ValueError(f"buffers were made for {buffers.shape} of {buffers.dtype} on {buffers.device}, the map is "
                          f"{(B, H, W)} of {m.dtype} on {m.device}")
     ops.seg_boundary(m.contiguous(), buffers.dist, buffers.ws, dmax, band=buffers.band, d=d)
-    dist, band = buffers.dist, buffers.band
-    if squeeze:
-        dist, band = dist[0], band[0]
-    return dict(dist=dist, band=band, d=d, dmax=dmax)
+    return _unlift(squeeze, dict(dist=buffers.dist, band=buffers.band, d=d, dmax=dmax))
 
 
 def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None):
@@ -999,11 +960,8 @@ def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None):
     call after call (the result aliases it).  Two launches per call and no host synchronisation."""
     if isinstance(m, (list, tuple)):
         ds = d if isinstance(d, (list, tuple)) else [d] * len(m)
-        bufs = buffers if buffers is not None else [None] * len(m)
-        if len(ds) != len(m) or len(bufs) != len(m):
-            raise ValueError("boundary_bands: one d / buffers entry per map")
-        per = [_bands_one(x, di, ratio, dmax, b) for x, di, b in zip(m, ds, bufs)]
-        return {k: [p[k] for p in per] for k in ("dist", "band", "d", "dmax")}
+        return _per_item(lambda i, di, b: _bands_one(m[i], di, ratio, dmax, b), len(m), (ds, buffers),
+                         "boundary_bands: one d / buffers entry per map", ("dist", "band", "d", "dmax"))
     return _bands_one(m, d, ratio, dmax, buffers)
 
 

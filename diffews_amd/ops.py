@@ -1039,6 +1039,17 @@ def tiles_labels_cand(plan, ent, tab, tab_host, N, gt=None, r_threshold=0.25, th
     return labels, counts, mx, area
 
 
+def _owner(fn, dev):
+    """The check every seg_* wrapper runs on a caller-owned buffer: own(name, t, dtype, shape) returns t's address, or
+    raises the wrapper's ValueError unless t is a contiguous `dtype` tensor of `shape` (None: any) on `dev` -- or on
+    `device`, for the one buffer that lives elsewhere."""
+    def own(name, t, dtype, shape, device=dev):
+        if t.dtype != dtype or not t.is_contiguous() or t.device != device or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{fn}: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
+        return t.data_ptr()
+    return own
+
+
 def seg_components_workspace(B, H, W):
     """Bytes of seg_components' workspace for a [B, H, W] label map."""
     return int(L.lib().dfw_seg_components_workspace_bytes(int(B), int(H), int(W)))
@@ -1059,11 +1070,7 @@ def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, count
     assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
     B, H, W = labels.shape
     dev = labels.device
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_components: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_components", dev)
     a = L.SegComponentsArgs()
     a.labels, a.ids, a.n = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W)), own("n", n, torch.int32, (B, 2))
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
@@ -1107,11 +1114,7 @@ def seg_holes(labels, ids, ids_out, labels_out, holes, ws, stats=None, stats_out
     assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
     B, H, W = labels.shape
     dev = labels.device
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_holes: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_holes", dev)
     a = L.SegHolesArgs()
     a.labels, a.ids = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W))
     a.ids_out, a.labels_out = own("ids_out", ids_out, torch.int32, (B, H, W)), own("labels_out", labels_out, torch.uint8, (B, H, W))
@@ -1170,11 +1173,7 @@ def seg_rle(ids, runs, run_off, nruns, ws, cap, order="column"):
     if runs.dim() != 3:
         raise ValueError("seg_rle: runs must be int32 [B, max_runs, 2]")
     max_runs = runs.shape[1]
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_rle: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_rle", dev)
     a = L.SegRleArgs()
     a.ids, a.runs = ids.data_ptr(), own("runs", runs, torch.int32, (B, max_runs, 2))
     a.run_off, a.nruns = own("run_off", run_off, torch.int32, (B, cap + 1)), own("nruns", nruns, torch.int32, (B, 2))
@@ -1211,11 +1210,7 @@ def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8):
     if verts.dim() != 3 or verts.shape[1] < 4 or verts.shape[1] % 4:
         raise ValueError("seg_contours: verts must be int32 [B, max_edges, 2] with max_edges a multiple of 4, at least 4")
     max_edges = verts.shape[1]
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_contours: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_contours", dev)
     a = L.SegContoursArgs()
     a.ids, a.verts = ids.data_ptr(), own("verts", verts, torch.int32, (B, max_edges, 2))
     a.rings, a.ring_off = own("rings", rings, torch.int32, (B, max_edges // 4, 4)), own("ring_off", ring_off, torch.int32, (B, cap + 1))
@@ -1259,11 +1254,7 @@ def seg_match(pids, gids, pairs, pair_off, area, match, gmatch, pq, n, ws, max_r
                          "and pq int64 [B, nlabels + 1, 4]")
     cap_p, cap_g, max_pairs, nlabels = match.shape[1], gmatch.shape[1], pairs.shape[1], pq.shape[1] - 1
     num, den = (int(v) for v in iou)
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_match: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_match", dev)
     a = L.SegMatchArgs()
     a.pids, a.gids = pids.data_ptr(), own("gids", gids, torch.int32, (B, H, W))
     if pstats is not None:
@@ -1314,11 +1305,7 @@ def seg_scores(ids, labels, seg_u8, planes, planes_host, scores, ws):
         raise ValueError("seg_scores: scores must be int64 [B, cap, 4], planes int32 [B, nlabels + 1] and seg_u8 uint8 "
                          "[P, 3, H, W]")
     cap, nl1, P = scores.shape[1], planes.shape[1], seg_u8.shape[0]
-
-    def own(name, t, dtype, shape, device=dev):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != device or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_scores: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
-        return t.data_ptr()
+    own = _owner("seg_scores", dev)
     a = L.SegScoresArgs()
     a.ids, a.labels = ids.data_ptr(), own("labels", labels, torch.uint8, (B, H, W))
     a.seg_u8, a.planes = own("seg_u8", seg_u8, torch.uint8, (P, 3, H, W)), own("planes", planes, torch.int32, (B, nl1))
@@ -1355,11 +1342,7 @@ def seg_boundary(map, dist, ws, dmax, band=None, d=None):
         raise ValueError("seg_boundary: map must be a contiguous uint8 or int32 device tensor [B, H, W]")
     B, H, W = map.shape
     dev = map.device
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"seg_boundary: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_boundary", dev)
     a = L.SegBoundaryArgs()
     a.map, a.dist = map.data_ptr(), own("dist", dist, torch.uint8, (B, H, W))
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
@@ -1385,11 +1368,7 @@ def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
     dev = pred.device
     if counts.dim() != 3:
         raise ValueError("seg_boundary_counts: counts must be int64 [B, 2, nlabels + 1]")
-
-    def own(name, t, dtype, shape):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
-            raise ValueError(f"seg_boundary_counts: {name} must be a contiguous {dtype} tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+    own = _owner("seg_boundary_counts", dev)
     a = L.SegBoundaryCountsArgs()
     a.pred, a.pdist = pred.data_ptr(), own("pdist", pdist, torch.uint8, (B, H, W))
     a.gt, a.gdist = own("gt", gt, torch.uint8, (B, H, W)), own("gdist", gdist, torch.uint8, (B, H, W))

@@ -777,6 +777,25 @@ int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* ent, const i
                           int32_t N, float r_threshold, float threshold, dfw_stream_t stream);
 
 /*
+ * The buffers of the object stages -- dfw_seg_components, dfw_seg_holes, dfw_seg_rle, dfw_seg_match, dfw_seg_scores,
+ * dfw_seg_boundary, dfw_seg_boundary_counts and dfw_seg_contours, everything from here to the end of dfw_seg_contours --
+ * are judged by one rule (one piece of code, csrc/seg_args.h; version >= 122).  Every stage validates on the host before
+ * its first launch, in this order: null pointers and scalars (DFW_EINVAL), sizes (DFW_EINVAL before DFW_ERANGE), the
+ * workspace (DFW_EWORKSPACE: ws_bytes below the stage's query), then the buffers:
+ *   overlap    DFW_EINVAL when a buffer the call WRITES -- every output, and the workspace, taken as the bytes the query
+ *              returns and not as ws_bytes -- shares a byte with any other device buffer of the call.  Extents are the
+ *              shapes documented at the struct, half-open: buffers that touch end to start are fine, so outputs and
+ *              workspace may be carved back to back out of one allocation.  Two INPUTS may alias each other (gt ==
+ *              labels, pids == gids, pred == gt).  An optional buffer takes part only when the call uses it
+ *   alignment  only then DFW_ESHAPE when a buffer is off its alignment: 4 bytes for int32 tables and maps and for the
+ *              workspace, 8 for int64 tables, none for byte maps, unless the stage says otherwise
+ * An extent is only known to be the caller's once sizes and workspace have passed, hence the order.  Up to version 121
+ * dfw_seg_components compared only filtered == labels, dfw_seg_rle only ids against its outputs and dfw_seg_match only
+ * inputs against outputs; a call with two outputs on each other, or with the workspace on anything, was launched there
+ * and returned garbage.  From 122 on all three refuse it like the other five, which refuse exactly what they did.
+ */
+
+/*
  * Connected components of a label map (version >= 114): the last stage behind every route that ends in `labels`.  Two
  * pixels belong to one component when they carry the same NON-ZERO byte and a 4- or 8-connected path of that byte joins
  * them; different bytes never merge.  A component whose area is below min_area is removed (0 and 1 keep everything).  The
@@ -802,9 +821,9 @@ int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* ent, const i
  * reach global memory as one atomic per (tile, tile-local component) and field, never one per pixel.
  *
  * Validated on the host before the first launch.  DFW_EINVAL: null labels / ids / n / ws; B, H or W < 1; connectivity not 4
- * or 8; min_area < 0; stats with cap < 1; counts without gt; gt with nlabels outside 1..254; filtered == labels.
- * DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535 (also B * cap * 8 above 2^31 - 1 with stats).
- * DFW_EWORKSPACE: ws_bytes below the query.  DFW_ESHAPE: ws / ids / n / stats not 4-byte aligned, counts not 8-byte.
+ * or 8; min_area < 0; stats with cap < 1; counts without gt; gt with nlabels outside 1..254.  DFW_ERANGE: H or W above
+ * 65535, H * W above 2^30, B above 65535 (also B * cap * 8 above 2^31 - 1 with stats).  Then the workspace and the buffers,
+ * by the rule above: filtered on labels is one such overlap; gt counts only with counts.
  */
 typedef struct {
   const uint8_t* labels;   /* [B][H][W] contiguous; 0 = background, any other byte is a class; equal bytes connect */
@@ -874,9 +893,8 @@ int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const void* ws, d
  * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / labels / ids / ids_out /
  * labels_out / holes / ws; B, H or W < 1; connectivity not 4 or 8; max_area < 0; stats_out without stats or with cap < 1;
  * counts without gt; gt with nlabels outside 1..254.  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535 (also
- * B * cap * 8 above 2^31 - 1 with stats_out).  DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: an output or the
- * workspace sharing a byte with an input or with another output (stats only counts with stats_out, counts only with gt).
- * DFW_ESHAPE: ws / ids / ids_out / holes / stats / stats_out not 4-byte aligned, counts not 8-byte.
+ * B * cap * 8 above 2^31 - 1 with stats_out).  Then the workspace and the buffers, by the rule above: stats only counts
+ * with stats_out.
  */
 typedef struct {
   const uint8_t* labels;   /* [B][H][W] contiguous; 0 = background */
@@ -923,10 +941,9 @@ size_t dfw_seg_holes_workspace_bytes(int32_t B, int32_t H, int32_t W);
  * atomic decides a position).  Nothing is written outside runs[.., :kept], run_off, nruns and ws; ids is read only.
  *
  * Validated on the host before the first launch.  DFW_EINVAL: null args / ids / runs / run_off / nruns / ws; B, H, W, cap
- * or max_runs < 1; order not 0 or 1; runs, run_off or nruns overlapping ids.  DFW_ERANGE: H or W above 65535, H * W above
- * 2^30, B above 65535, B * max_runs * 2 or B * (cap + 1) above 2^31 - 1.  DFW_EWORKSPACE: ws_bytes below the query.
- * DFW_ESHAPE: ids / runs / run_off / nruns / ws not 4-byte aligned.  Sizes are judged before the workspace, the workspace
- * before overlap (an extent is only known to be the caller's once both have passed).
+ * or max_runs < 1; order not 0 or 1.  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535, B * max_runs * 2
+ * or B * (cap + 1) above 2^31 - 1.  Then the workspace and the buffers, by the rule above; runs, rows of two int32, needs
+ * 4-byte alignment only.
  */
 typedef struct {
   const int32_t* ids;      /* [B][H][W] contiguous, read only */
@@ -1008,10 +1025,9 @@ int dfw_seg_rle_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max
  *
  * Validated on the host before the first launch.  DFW_EINVAL: null args / pids / gids / an output / ws; B, H, W, capP, capG,
  * max_records or max_pairs < 1; a threshold that breaks the rule above; nlabels outside 1..254 (with or without stats: pq
- * has nlabels + 1 rows); an output overlapping an input.  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535,
- * a highest key (capP + 1) * (capG + 1) - 1 above 2^31 - 1, word counts of an output or of a workspace array beyond an
- * int.  DFW_EWORKSPACE: ws_bytes below the query.  DFW_ESHAPE: pids / gids / pstats / gstats / an int32 output / ws not
- * 4-byte aligned, pq not 8-byte aligned.  Sizes are judged before the workspace, the workspace before overlap.
+ * has nlabels + 1 rows).  DFW_ERANGE: H or W above 65535, H * W above 2^30, B above 65535, a highest key (capP + 1) *
+ * (capG + 1) - 1 above 2^31 - 1, word counts of an output or of a workspace array beyond an int.  Then the workspace and
+ * the buffers, by the rule above.
  */
 typedef struct {
   const int32_t* pids;     /* [B][H][W] contiguous, read only: the prediction's ids */
@@ -1083,9 +1099,8 @@ int dfw_seg_match_rounds(int32_t B, int32_t H, int32_t W, int32_t capP, int32_t 
  * 2^30, B above 65535; P * 3 * H * W above 2^63 - 1 (seg_u8 is addressed in size_t, so no int32 arguments reach this);
  * B * cap * 5 above 2^31 - 1 (the accumulators' words and the rows of scores are counted in an int; the B * cap * 4 words
  * of scores are addressed in size_t).  DFW_EINVAL: a planes_host entry 1..nlabels above P - 1 or below -1.
- * DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: scores or ws overlapping an input or each other.  DFW_ESHAPE:
- * ids / planes / ws not 4-byte aligned, scores not 8-byte aligned.  Sizes are judged before the table, the table before
- * the workspace, the workspace before overlap.
+ * Then the workspace and the buffers, by the rule above: sizes are judged before the table, the table before the
+ * workspace.  planes_host is host memory and no part of the overlap rule.
  */
 typedef struct {
   const int32_t* ids;           /* [B][H][W] contiguous, read only */
@@ -1127,8 +1142,8 @@ int dfw_seg_scores_block(int32_t* pixels);
  *
  * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / map / dist / ws; elem not 1 or
  * 4; dmax outside 1..254; d outside 1..dmax when band is given; B, H or W < 1.  DFW_ERANGE: H, W or B above 65535, H * W
- * above 2^30.  DFW_EWORKSPACE: ws_bytes below the query.  DFW_EINVAL: dist, band or ws overlapping map or each other.
- * DFW_ESHAPE: an int32 map or band not 4-byte aligned, ws not 4-byte aligned.
+ * above 2^30.  Then the workspace and the buffers, by the rule above: map and band are aligned to their element, dist
+ * needs no alignment.
  */
 typedef struct {
   const void* map;              /* [B][H][W] of uint8 or int32, contiguous, read only */
@@ -1153,8 +1168,7 @@ int dfw_seg_boundary_block(int32_t* rows, int32_t* cols, int32_t* positions);
  * histograms per workgroup flushed with 64-bit integer atomics; capturable, order-free.
  *
  * Validated in this order.  DFW_EINVAL: null args / pred / pdist / gt / gdist / counts; d outside 1..254; nlabels outside
- * 1..254; B, H or W < 1.  DFW_ERANGE: as dfw_seg_boundary.  DFW_EINVAL: counts overlapping an input.  DFW_ESHAPE: counts
- * not 8-byte aligned.
+ * 1..254; B, H or W < 1.  DFW_ERANGE: as dfw_seg_boundary.  Then the buffers, by the rule above; there is no workspace.
  */
 typedef struct {
   const uint8_t* pred;          /* [B][H][W] label bytes, read only */
@@ -1220,9 +1234,8 @@ int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t 
  *
  * Validated on the host before the first launch, in this order.  DFW_EINVAL: null args / ids / verts / rings / ring_off /
  * n / ws; connectivity not 4 or 8; B, H, W or cap < 1; max_edges < 4 or not a multiple of 4.  DFW_ERANGE: H, W or B above
- * 65535, 4 * H * W above 2^31 - 1 (the keys), B * max_edges * 2 or B * (cap + 1) above 2^31 - 1.  DFW_EWORKSPACE: ws_bytes
- * below the query.  DFW_EINVAL: an output or ws sharing a byte with ids or with another output.  DFW_ESHAPE: ids or
- * ring_off not 4-byte aligned, verts not 8-byte aligned, rings, n or ws not 16-byte aligned.
+ * 65535, 4 * H * W above 2^31 - 1 (the keys), B * max_edges * 2 or B * (cap + 1) above 2^31 - 1.  Then the workspace and
+ * the buffers, by the rule above, with alignments of its own: verts 8 bytes, rings, n and ws 16 (rows and records of 16).
  */
 typedef struct {
   const int32_t* ids;      /* [B][H][W] contiguous, read only */

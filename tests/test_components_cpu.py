@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import components_ref as cr
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -237,6 +238,13 @@ def test_every_refusal_comes_from_the_host_before_any_launch(hip_lib):
     assert hip_lib.dfw_seg_components(C.byref(a), None) == DFW_ERANGE
     # nothing was written by any of these
     assert not keep["ids"].any() and not keep["n"].any()
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    px, ws = 2 * 5 * 7, hip_lib.dfw_seg_components_workspace_bytes(2, 5, 7)
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_components(C.byref(a), None), lambda: _valid(hip_lib),
+                       dict(labels=(px, 1), gt=(px, 1)),
+                       dict(ids=(4 * px, 4), n=(2 * 8, 4), filtered=(px, 1), stats=(2 * 4 * 32, 4), counts=(2 * 2 * 4 * 8, 8),
+                            ws=(ws, 4)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def test_optional_outputs_may_be_absent(hip_lib):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import boundary_ref as br
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -214,6 +215,10 @@ def test_every_refusal_of_seg_boundary_comes_from_the_host(hip_lib):
     assert hip_lib.dfw_seg_boundary(C.byref(a), None) == DFW_EINVAL
     assert broken(band=None, d=0, ws_bytes=0) == DFW_EWORKSPACE
     assert broken(band=None, d=99, H=65536) == DFW_ERANGE
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_boundary(C.byref(a), None), lambda: _valid(hip_lib), dict(map=(4 * 2 * 5 * 7, 4)),
+                       dict(dist=(2 * 5 * 7, 1), band=(4 * 2 * 5 * 7, 4), ws=(hip_lib.dfw_seg_boundary_workspace_bytes(2, 5, 7, 4), 4)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def _valid_counts(B=2, H=5, W=7, d=2, nlabels=3):
@@ -267,6 +272,9 @@ def test_every_refusal_of_seg_boundary_counts_comes_from_the_host(hip_lib):
     a, keep = _valid_counts()
     a.counts = a.pred + 1                                                  # overlap before alignment
     assert hip_lib.dfw_seg_boundary_counts(C.byref(a), None) == DFW_EINVAL
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_boundary_counts(C.byref(a), None), _valid_counts,
+                       {k: (2 * 5 * 7, 1) for k in ("pred", "pdist", "gt", "gdist")}, dict(counts=(2 * 2 * 4 * 8, 8)))
 
 
 # ------------------------------------------------------------------------------------------------ metrics and the limit

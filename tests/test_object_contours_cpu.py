@@ -14,6 +14,7 @@ import pytest
 import components_ref as cr
 import contours_cases as cc
 import contours_ref as ct
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -257,6 +258,11 @@ def test_every_refusal_comes_from_the_host_before_any_launch(hip_lib):
     a.verts, a.ws_bytes = a.ids, 0
     assert hip_lib.dfw_seg_contours(C.byref(a), None) == DFW_EWORKSPACE
     assert all(not r.any() for raws in kept for r in raws)           # nothing was written by any of these
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_contours(C.byref(a), None), lambda: _valid(hip_lib), dict(ids=(4 * 2 * 5 * 7, 4)),
+                       dict(verts=(2 * 8 * 8, 8), rings=(2 * 2 * 16, 16), ring_off=(2 * 5 * 4, 4), n=(2 * 16, 16),
+                            ws=(hip_lib.dfw_seg_contours_workspace_bytes(2, 5, 7, 4, 8), 16)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def test_ops_pass_the_allocation_scan():

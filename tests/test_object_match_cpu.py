@@ -13,6 +13,7 @@ import pytest
 
 import components_ref as cr
 import match_ref as mr
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -281,6 +282,13 @@ def test_every_refusal_comes_from_the_host_before_any_launch(hip_lib):
     a.n, a.ws_bytes = a.pids, 0
     assert hip_lib.dfw_seg_match(C.byref(a), None) == DFW_EWORKSPACE
     assert all(not v.any() for keep in kept for v in keep.values())  # nothing was written by any of these
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_match(C.byref(a), None), lambda: _valid(hip_lib),
+                       {k: (v, 1 if k == "skip" else 4) for k, v in sizes.items()},
+                       dict(pairs=(2 * 5 * 12, 4), pair_off=(2 * 6 * 4, 4), area=(2 * 9 * 4, 4), match=(2 * 4 * 12, 4),
+                            gmatch=(2 * 3 * 4, 4), pq=(2 * 3 * 32, 8), n=(2 * 16, 4),
+                            ws=(hip_lib.dfw_seg_match_workspace_bytes(2, 5, 7, 4, 3, 6, 5), 4)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def test_ops_pass_the_allocation_scan():

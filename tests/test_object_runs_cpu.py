@@ -12,6 +12,7 @@ import pytest
 
 import components_ref as cr
 import rle_ref as rr
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -214,6 +215,11 @@ def test_every_refusal_comes_from_the_host_before_any_launch(hip_lib):
     a.H, a.ws_bytes = 70000, 0
     assert hip_lib.dfw_seg_rle(C.byref(a), None) == DFW_ERANGE
     assert all(not v.any() for keep in kept for v in keep.values())  # nothing was written by any of these
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_rle(C.byref(a), None), lambda: _valid(hip_lib), dict(ids=(4 * 2 * 5 * 7, 4)),
+                       dict(runs=(2 * 6 * 8, 4), run_off=(2 * 5 * 4, 4), nruns=(2 * 8, 4),
+                            ws=(hip_lib.dfw_seg_rle_workspace_bytes(2, 5, 7, 4, 6, 1), 4)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def test_ops_pass_the_allocation_scan():

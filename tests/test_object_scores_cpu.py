@@ -14,6 +14,7 @@ import pytest
 import torch
 
 import scores_ref as sr
+from seg_args_cases import check_overlap_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DFW_EINVAL, DFW_ESHAPE, DFW_ERANGE, DFW_EWORKSPACE = -1, -2, -3, -4
@@ -200,6 +201,12 @@ def test_every_refusal_comes_from_the_host_before_any_launch(hip_lib):
     assert hip_lib.dfw_seg_scores(C.byref(a), None) == DFW_EINVAL
     for keep in kept:                                                # nothing was written by any of these
         assert not keep["scores"].any() and not keep["ws"].any() and not keep["ids"].any()
+    # the buffer rule of the object stages: every output and the workspace against every input and each other
+    # (planes_host is host memory and no part of it)
+    check_overlap_rule(lambda a: hip_lib.dfw_seg_scores(C.byref(a), None), lambda: _valid(hip_lib),
+                       dict(ids=(4 * 2 * 5 * 7, 4), labels=(2 * 5 * 7, 1), seg_u8=(6 * 3 * 5 * 7, 1), planes=(2 * 4 * 4, 4)),
+                       dict(scores=(2 * 4 * 32, 8), ws=(hip_lib.dfw_seg_scores_workspace_bytes(2, 4), 4)))
+    assert hip_lib.dfw_version() >= 122
 
 
 def test_ops_pass_the_allocation_scan():
