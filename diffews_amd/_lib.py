@@ -129,7 +129,8 @@ class SegRleArgs(C.Structure):
 
 class SegContoursArgs(C.Structure):
     _fields_ = [("ids", _vp), ("verts", _vp), ("rings", _vp), ("ring_off", _vp), ("n", _vp), ("ws", _vp), ("ws_bytes", _sz),
-                ("B", _i32), ("H", _i32), ("W", _i32), ("cap", _i32), ("max_edges", _i32), ("connectivity", _i32)]
+                ("B", _i32), ("H", _i32), ("W", _i32), ("cap", _i32), ("max_edges", _i32), ("connectivity", _i32),
+                ("simp_verts", _vp), ("simp_rings", _vp), ("simp_n", _vp), ("tol4", _i32)]
 
 
 class SegMatchArgs(C.Structure):
@@ -166,7 +167,8 @@ class SegSortRounds(C.Structure):
 
 class SegContoursTrips(C.Structure):
     _fields_ = [("blocks", _i32), ("block_scan", _i32), ("doubling", _i32), ("ring_blocks", _i32), ("ring_scan", _i32),
-                ("passes", _i32), ("table_scan", _i32), ("offsets_scan", _i32), ("corners_scan", _i32), ("launches", _i32)]
+                ("passes", _i32), ("table_scan", _i32), ("offsets_scan", _i32), ("corners_scan", _i32), ("launches", _i32),
+                ("simplify_launches", _i32)]
 
 
 class InputImageItem(C.Structure):
@@ -358,6 +360,7 @@ SYMBOLS = {
     "dfw_seg_contours_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_contours_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "dfw_seg_contours_rounds": (_i32, [_i32] * 5 + [C.POINTER(SegContoursTrips)]),
+    "dfw_seg_contours_simplify_block": (_i32, [C.POINTER(_i32)]),
     "dfw_seg_rle": (_i32, [C.POINTER(SegRleArgs), _vp]),
     "dfw_seg_rle_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "dfw_seg_rle_block": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),

@@ -69,6 +69,9 @@
 //
 // Termination: no thread waits for another thread or workgroup; every loop has a trip count fixed by the arguments, every
 // cross-workgroup prefix is a scan in a launch of its own.  Any grid is correct at any residency.
+//
+// The optional last stage, the SIMPLIFIED RINGS (three more launches when simp_verts / simp_rings / simp_n are given), is
+// described in front of its kernels below; its loops are bounded by the ring's length and not by the arguments alone.
 #include "seg_args.h"
 #include "seg_sort.h"
 
@@ -337,6 +340,256 @@ __global__ __launch_bounds__(256) void ct_verts_kernel(const i32x4* state, const
     *(i32x2*)(verts + 2 * (r0 + at)) = i32x2{x + (s == 1 || s == 2), y + (s >= 2)};
 }
 
+// ------------------------------------------------------------------------------------------------ simplified rings
+// The optional last stage (simp_verts / simp_rings / simp_n / tol4 of the arguments; include/diffews_hip.h holds the
+// definition): Douglas-Peucker on every ring in its level-synchronous form, all integers, three launches behind
+// ct_verts_kernel and none when the stage is off:
+//
+//   sp_keep_kernel    one workgroup per ring row (grid-stride over the rings the image has).  Anchors 0 and f, then
+//                     rounds: every active corner puts the packed key of its measure into the winner slot of its
+//                     chain's left anchor with a 64-bit integer max (order-free; sp_slot_max folds a wave first), barrier,
+//                     every active corner reads its chain's winner and is kept, dropped or narrows its chain, barrier
+//                     with the workgroup-wide "any active", the kept winners clear the slot they won, barrier.  Corner i
+//                     belongs to thread i % 256 in every loop, so a, b and the status are private to a thread; only the
+//                     slots are shared.  A ring of at most kSpLds corners keeps coordinates, state and slots in LDS, a
+//                     longer one in the workspace (the slots through device-scope atomics only).  Then rule 3, and the
+//                     exclusive prefix of the keep flags inside the ring (block_scan, 256 corners a trip):
+//                     pos [corner row] = its rank among the ring's kept corners or -1, kcount [ring row] = corners kept
+//   sp_scan_kernel    kcount in place -> every ring's first', and the corners kept of the image: block_scan, 1024 rings
+//                     a trip, over the rings the image has
+//   sp_write_kernel   one workgroup per ring row: simp_rings' row, the kept corners at first' + pos, and simp_n
+//
+// The rounds end: a round leaves every live chain finished or with one more kept corner, at most count - 2 rounds.  The
+// exit test is the barrier's own result, uniform over the workgroup.  The state lives in what was `state` and `lead`,
+// 48 bytes per edge, dead since ct_verts_kernel: slot [E] x 8 | a, b, status, pos [E] | kcount [Q] | kept [2] per image.
+
+constexpr int kSpLds = 1024;    // corners of a ring up to which its state lives in LDS
+constexpr int kSpGrid = 8192;   // workgroups per image at the most; the rows beyond are reached by the stride
+
+using u64 = unsigned long long;
+
+enum { kSpActive = 0, kSpKept = 1, kSpDropped = 2, kSpWon = 3 };
+
+// line mode (pa != pb): |cross| of (pb - pa, p - pa), twice the triangle's area; point mode: the squared distance to pa
+__device__ __forceinline__ u64 sp_measure(i32x2 pa, i32x2 pb, i32x2 p) {
+  const long long ux = pb.x - pa.x, uy = pb.y - pa.y, vx = p.x - pa.x, vy = p.y - pa.y;
+  if (ux == 0 && uy == 0) return (u64)(vx * vx + vy * vy);
+  const long long cr = ux * vy - uy * vx;
+  return (u64)(cr < 0 ? -cr : cr);
+}
+
+// 16 m^2 > tol4^2 L, or 16 m > tol4^2 in point mode: below 2^64 by the bounds of the header
+__device__ __forceinline__ bool sp_keeps(i32x2 pa, i32x2 pb, u64 m, u64 tol2) {
+  const long long ux = pb.x - pa.x, uy = pb.y - pa.y;
+  if (ux == 0 && uy == 0) return 16 * m > tol2;
+  return 16 * m * m > tol2 * (u64)(ux * ux + uy * uy);
+}
+
+template <bool LDS>
+__device__ __forceinline__ u64 sp_slot_load(u64* p) {
+  if (LDS) return *p;
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // written by atomics: never from a stale line
+}
+template <bool LDS>
+__device__ __forceinline__ void sp_slot_clear(u64* p) {
+  if (LDS) *p = 0;
+  else __hip_atomic_store(p, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// key into slot [a] by an integer max, for the lanes that are `on`.  A wave's lanes hold consecutive corners, so early on
+// all of them belong to one or two chains and would queue at one address: the lanes that share the first pending lane's
+// chain fold their keys with shuffles and that lane alone goes to memory, twice over; whoever is left (many small chains)
+// goes by itself.  A maximum does not depend on how it is grouped.  Every lane of the wave calls it.
+__device__ __forceinline__ void sp_slot_max(u64* slot, bool on, int a, u64 key) {
+  const int lane = threadIdx.x & 63;
+  bool pending = on;
+  for (int it = 0; it < 2; ++it) {
+    const unsigned long long act = __ballot(pending);
+    if (act == 0) return;                               // the whole wave
+    const int lead = __ffsll((long long)act) - 1;
+    const int la = __shfl(a, lead, 64);
+    const bool same = pending && a == la;
+    if (__popcll(__ballot(same)) < 8) break;            // the whole wave: small chains from here on
+    u64 v = same ? key : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (u64)__shfl_xor(v, o, 64));
+    if (lane == lead) atomicMax(&slot[la], v);
+    pending = pending && !same;
+  }
+  if (pending) atomicMax(&slot[a], key);
+}
+
+// The largest key of the workgroup; red is one LDS word.  Two barriers in front of the read, none behind it: the caller
+// puts one between this and the next use of red.
+__device__ __forceinline__ u64 sp_block_max(u64 v, u64* red) {
+  if (threadIdx.x == 0) *red = 0;
+  __syncthreads();
+  atomicMax(red, v);
+  __syncthreads();
+  return *red;
+}
+
+// One ring of c >= 4 corners P[0..c); slot, sa, sb, sst are [c], in LDS or in the workspace; pos [c] and *kcount are the
+// workspace's.  Every thread of the workgroup calls it.
+template <bool LDS>
+__device__ __forceinline__ void sp_ring(const i32x2* P, int c, u64* slot, int* sa, int* sb, int* sst, int32_t* pos,
+                                        int32_t* kcount, u64 tol2, u64* red, int* wsum) {
+  const int tid = threadIdx.x;
+  const i32x2 p0 = P[0];
+  u64 best = 0;
+  for (int i = tid; i < c; i += 256) {
+    sp_slot_clear<LDS>(&slot[i]);
+    best = max(best, sp_measure(p0, p0, P[i]) << 31 | (u64)(0x7fffffff - i));
+  }
+  int f = 0x7fffffff - (int)(sp_block_max(best, red) & 0x7fffffff);            // the barriers also publish the slots
+  if ((unsigned)f >= (unsigned)c) f = 0;                                        // never: a key carries a rank below c
+  const i32x2 pf = P[f];
+  for (int i = tid; i < c; i += 256) {
+    const bool anchor = i == 0 || i == f;
+    sst[i] = anchor ? kSpKept : kSpActive;
+    sa[i] = i < f ? 0 : f;
+    sb[i] = i < f ? f : c;
+  }
+  // every round every active corner is settled or its chain (a, b) narrows around it: fewer than c rounds, whatever
+  // the slots hold
+  for (int round = 0; round < c; ++round) {
+    for (int base = 0; base < c; base += 256) {          // the same trips for every lane: sp_slot_max shuffles
+      const int i = base + tid;
+      const bool on = i < c && sst[i] == kSpActive;
+      int a = -1;
+      u64 key = 0;
+      if (on) {
+        a = sa[i];
+        const int b = sb[i], s = 2 * i - (a + b);
+        key = sp_measure(P[a], P[b == c ? 0 : b], P[i]) << 31 | (u64)(0x7fffffff - (2 * (s < 0 ? -s : s) + (s > 0)));
+      }
+      sp_slot_max(slot, on, a, key);
+    }
+    __syncthreads();
+    int any = 0;
+    for (int i = tid; i < c; i += 256) {
+      if (sst[i] != kSpActive) continue;
+      const int a = sa[i], b = sb[i];
+      const u64 k = sp_slot_load<LDS>(&slot[a]);
+      const int t = 0x7fffffff - (int)(k & 0x7fffffff), d = t >> 1, w = (a + b + ((t & 1) ? d : -d)) >> 1;
+      if (w <= a || w >= b || !sp_keeps(P[a], P[b == c ? 0 : b], k >> 31, tol2)) sst[i] = kSpDropped;   // w is interior
+      else if (i == w) sst[i] = kSpWon;                 // sa[i] still names the slot it won
+      else if (i < w) sb[i] = w, any = 1;
+      else sa[i] = w, any = 1;
+    }
+    const int more = __syncthreads_or(any);           // every slot of this round has been read
+    for (int i = tid; i < c; i += 256)
+      if (sst[i] == kSpWon) {
+        sp_slot_clear<LDS>(&slot[sa[i]]);
+        sst[i] = kSpKept;
+      }
+    if (!more) break;
+    __syncthreads();
+  }
+  int mine = 0;
+  for (int i = tid; i < c; i += 256) mine += sst[i] == kSpKept;
+  int kept;
+  block_scan(mine, wsum, &kept);
+  if (kept == 2) {                                      // rule 3, the whole workgroup: a ring keeps three corners
+    best = 0;
+    for (int i = tid; i < c; i += 256)
+      if (i != 0 && i != f) best = max(best, sp_measure(p0, pf, P[i]) << 31 | (u64)(0x7fffffff - i));
+    const int g = 0x7fffffff - (int)(sp_block_max(best, red) & 0x7fffffff);
+    if ((unsigned)g < (unsigned)c && (g & 255) == tid) sst[g] = kSpKept;
+  }
+  int carry = 0;
+  for (int i0 = 0; i0 < c; i0 += 256) {
+    const int i = i0 + tid;
+    const int on = i < c && sst[i] == kSpKept;
+    int total;
+    const int ex = block_scan(on, wsum, &total);
+    if (i < c) pos[i] = on ? carry + ex : -1;
+    carry += total;
+  }
+  if (tid == 0) *kcount = carry;
+}
+
+__global__ __launch_bounds__(256) void sp_keep_kernel(const int32_t* verts, const int32_t* rings, const int32_t* n,
+                                                      u64* slot, int32_t* sa, int32_t* sb, int32_t* sst, int32_t* pos,
+                                                      int32_t* kcount, int E, int tol4) {
+  __shared__ __attribute__((aligned(16))) i32x2 lp[kSpLds];
+  __shared__ __attribute__((aligned(16))) u64 lslot[kSpLds];
+  __shared__ __attribute__((aligned(16))) int la[kSpLds];
+  __shared__ __attribute__((aligned(16))) int lb[kSpLds];
+  __shared__ __attribute__((aligned(16))) int ls[kSpLds];
+  __shared__ __attribute__((aligned(16))) u64 red[2];
+  __shared__ __attribute__((aligned(16))) int wsum[4];
+  const int b = blockIdx.y, Q = E / 4, nr = min(n[4 * b + 2], Q);
+  const size_t r0 = (size_t)b * E, q0 = (size_t)b * Q;
+  const u64 tol2 = (u64)tol4 * (u64)tol4;
+  for (int r = blockIdx.x; r < nr; r += gridDim.x) {    // r and nr are the workgroup's: every barrier below is met by all
+    const i32x4 ring = *(const i32x4*)(rings + 4 * (q0 + r));
+    const int first = ring.y, c = ring.z;
+    if (first < 0 || c < 4 || (long long)first + c > E) {   // never: a ring's corners are rows of verts
+      if (threadIdx.x == 0) kcount[q0 + r] = 0;
+      continue;
+    }
+    const i32x2* P = (const i32x2*)verts + r0 + first;
+    if (c <= kSpLds) {
+      for (int i = threadIdx.x; i < c; i += 256) lp[i] = P[i];
+      __syncthreads();
+      sp_ring<true>(lp, c, lslot, la, lb, ls, pos + r0 + first, kcount + q0 + r, tol2, red, wsum);
+    } else {
+      sp_ring<false>(P, c, slot + r0 + first, sa + r0 + first, sb + r0 + first, sst + r0 + first, pos + r0 + first,
+                     kcount + q0 + r, tol2, red, wsum);
+    }
+    __syncthreads();                                    // the next ring of this workgroup takes the same LDS
+  }
+}
+
+// kcount [rings of the image] -> its exclusive prefix in place, every ring's first', and kept [2 b .. 2 b + 1] = the corners
+// kept of image b.  One workgroup per image, 1024 rows a trip, as seg_scan_kernel -- but over the rings the image has and
+// not over the E / 4 rows it may have: at most ceil(E / 4096) trips.
+__global__ __launch_bounds__(256) void sp_scan_kernel(const int32_t* n, int32_t* kcount, int32_t* kept, int E) {
+  __shared__ __attribute__((aligned(16))) int wsum[4];
+  const int b = blockIdx.x, Q = E / 4, nr = min(n[4 * b + 2], Q);
+  int32_t* a = kcount + (size_t)b * Q;
+  int carry = 0;
+  for (int r0 = 0; r0 < nr; r0 += 1024) {
+    const int r = r0 + 4 * threadIdx.x;
+    int v[4], total;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = r + j < nr ? a[r + j] : 0;
+    int ex = carry + block_scan(v[0] + v[1] + v[2] + v[3], wsum, &total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (r + j < nr) a[r + j] = ex;
+      ex += v[j];
+    }
+    carry += total;
+  }
+  if (threadIdx.x == 0) kept[2 * b] = kept[2 * b + 1] = carry;
+}
+
+// kfirst = kcount after its scan; kept [2 b + 1] = the corners kept of image b
+__global__ __launch_bounds__(256) void sp_write_kernel(const int32_t* verts, const int32_t* rings, const int32_t* n,
+                                                       const int32_t* pos, const int32_t* kfirst, const int32_t* kept,
+                                                       int32_t* simp_verts, int32_t* simp_rings, int32_t* simp_n, int E) {
+  const int b = blockIdx.y, Q = E / 4;
+  const i32x4 nn = *(const i32x4*)(n + 4 * b);
+  const int nr = min(nn.z, Q), total = kept[2 * b + 1];
+  const size_t r0 = (size_t)b * E, q0 = (size_t)b * Q;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    *(i32x4*)(simp_n + 4 * b) = nn.w ? i32x4{nn.y, total, nr, 1} : i32x4{0, 0, 0, 0};
+  for (int r = blockIdx.x; r < nr; r += gridDim.x) {
+    const i32x4 ring = *(const i32x4*)(rings + 4 * (q0 + r));
+    const int first = ring.y, c = ring.z, f2 = kfirst[q0 + r];
+    if (first < 0 || c < 4 || (long long)first + c > E) continue;   // never, as in sp_keep_kernel
+    if (threadIdx.x == 0)
+      *(i32x4*)(simp_rings + 4 * (q0 + r)) = i32x4{ring.x, f2, (r + 1 < nr ? kfirst[q0 + r + 1] : total) - f2, ring.w};
+    for (int i = threadIdx.x; i < c; i += 256) {
+      const int p = pos[r0 + first + i];
+      if (p >= 0 && (unsigned)(f2 + p) < (unsigned)E)   // always: the kept corners are corners
+        *(i32x2*)(simp_verts + 2 * (r0 + f2 + p)) = *(const i32x2*)(verts + 2 * (r0 + first + i));
+    }
+  }
+}
+
 inline int ct_blocks(long long HW) { return (int)((HW + kSegPix - 1) / kSegPix); }
 inline int ct_ring_blocks(long long E) { return (int)((E + kCtEdge - 1) / kCtEdge); }
 inline int ct_doubling(long long E) {
@@ -347,6 +600,8 @@ inline int ct_doubling(long long E) {
 
 struct ct_layout {
   size_t state[2], lead[2], key, eid, corner, succ, pre, blk, rblk, cnt, ncorner, rkey[2], rlead[2], rcount, tab, words;
+  // the simplification's state, inside state and lead (12 words per edge, dead by then)
+  size_t sp_slot, sp_a, sp_b, sp_st, sp_pos, sp_kcount, sp_kept;
   int nblk, nrblk, passes, rounds;
 };
 
@@ -388,6 +643,10 @@ static ct_layout ct_plan(long long B, long long HW, long long cap, long long E) 
   l.rcount = w, w += (size_t)B * Q;
   l.tab = w, w += (size_t)B * seg_table_words(Q);
   l.words = w;
+  // 2 + 4 words per edge, then Q + 2 per image: 6 E + E / 4 + 2 <= 12 E for every E >= 4
+  l.sp_slot = l.state[0], l.sp_a = l.sp_slot + 2 * BE, l.sp_b = l.sp_a + BE, l.sp_st = l.sp_b + BE, l.sp_pos = l.sp_st + BE;
+  l.sp_kcount = l.sp_pos + BE, l.sp_kept = l.sp_kcount + (size_t)B * Q;
+  static_assert(sizeof(u64) == 8, "a winner slot is two words");
   return l;
 }
 
@@ -407,6 +666,12 @@ extern "C" int dfw_seg_contours_block(int32_t* pixels, int32_t* edges) {
   return 0;
 }
 
+extern "C" int dfw_seg_contours_simplify_block(int32_t* lds_corners) {
+  if (!lds_corners) return DFW_EINVAL;
+  *lds_corners = kSpLds;
+  return 0;
+}
+
 extern "C" int dfw_seg_contours_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_edges,
                                        dfw_seg_contours_trips* out) {
   if (!out) return DFW_EINVAL;
@@ -422,12 +687,16 @@ extern "C" int dfw_seg_contours_rounds(int32_t B, int32_t H, int32_t W, int32_t 
   out->offsets_scan = seg_scan_rounds((long long)cap + 1);
   out->corners_scan = seg_scan_rounds(max_edges / 4);
   out->launches = 14 + 2 * l.rounds + 3 * l.passes;
+  out->simplify_launches = 3;
   return 0;
 }
 
 extern "C" int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t stream) {
   if (!a || !a->ids || !a->verts || !a->rings || !a->ring_off || !a->n || !a->ws) return DFW_EINVAL;
   if (a->connectivity != 4 && a->connectivity != 8) return DFW_EINVAL;
+  const bool simplify = a->simp_verts || a->simp_rings || a->simp_n;
+  if (simplify ? (!a->simp_verts || !a->simp_rings || !a->simp_n || a->tol4 < 0 || a->tol4 > 32768) : a->tol4 != 0)
+    return DFW_EINVAL;
   if (int e = ct_size_error(a->B, a->H, a->W, a->cap, a->max_edges)) return e;
   const size_t need = dfw_seg_contours_workspace_bytes(a->B, a->H, a->W, a->cap, a->max_edges);
   if (a->ws_bytes < need) return DFW_EWORKSPACE;
@@ -436,7 +705,10 @@ extern "C" int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t str
                           seg_out(a->rings, (size_t)a->B * (a->max_edges / 4) * 16, 16),       // rows and records of 16
                           seg_out(a->ring_off, (size_t)a->B * ((size_t)a->cap + 1) * 4, 4),
                           seg_out(a->n, (size_t)a->B * 16, 16),
-                          seg_out(a->ws, need, 16)};
+                          seg_out(a->ws, need, 16),
+                          seg_out(a->simp_verts, (size_t)a->B * a->max_edges * 8, 8),          // absent when the stage is off
+                          seg_out(a->simp_rings, (size_t)a->B * (a->max_edges / 4) * 16, 16),
+                          seg_out(a->simp_n, (size_t)a->B * 16, 16)};
   if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int B = a->B, H = a->H, W = a->W, cap = a->cap, E = a->max_edges, Q = E / 4;
@@ -493,6 +765,18 @@ extern "C" int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t str
   DFW_CHECK_LAUNCH();
   hipLaunchKernelGGL(ct_verts_kernel, gedge, t, 0, st, fin, (const int32_t*)key, (const int32_t*)corner, (const int32_t*)succ,
                      (const int32_t*)cnt, a->verts, W, E);
+  DFW_CHECK_LAUNCH();
+  if (!simplify) return 0;
+  // state and lead are dead from here on
+  int32_t *pos = ws + l.sp_pos, *kcount = ws + l.sp_kcount, *kept = ws + l.sp_kept;
+  const dim3 gsimp(Q < kSpGrid ? Q : kSpGrid, B);
+  hipLaunchKernelGGL(sp_keep_kernel, gsimp, t, 0, st, (const int32_t*)a->verts, (const int32_t*)a->rings, (const int32_t*)a->n,
+                     (u64*)(ws + l.sp_slot), ws + l.sp_a, ws + l.sp_b, ws + l.sp_st, pos, kcount, E, a->tol4);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sp_scan_kernel, dim3(B), t, 0, st, (const int32_t*)a->n, kcount, kept, E);
+  DFW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sp_write_kernel, gsimp, t, 0, st, (const int32_t*)a->verts, (const int32_t*)a->rings, (const int32_t*)a->n,
+                     (const int32_t*)pos, (const int32_t*)kcount, (const int32_t*)kept, a->simp_verts, a->simp_rings, a->simp_n, E);
   DFW_CHECK_LAUNCH();
   return 0;
 }

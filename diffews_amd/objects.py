@@ -410,9 +410,11 @@ class ContourBuffers:
     [B, max_edges / 4, 4], ring_off int32 [B, max_components + 1], n int32 [B, 4] and the workspace (4 bytes a pixel and 64
     a row of max_edges).  max_edges defaults to max(4096, H * W // 8) rounded down to a multiple of 4 -- a choice and not a
     measurement: compact objects have far fewer unit edges than that, a map of single pixels has 4 * H * W and
-    object_contours reports it as not complete, with the number to size for in n[.., 0]."""
+    object_contours reports it as not complete, with the number to size for in n[.., 0].  simplify=True: it also holds
+    simp_verts, simp_rings and simp_n, shaped like verts, rings and n, for object_contours(.., tolerance=); the workspace
+    is the same."""
 
-    def __init__(self, B, H, W, max_components=1024, max_edges=None, device="cuda"):
+    def __init__(self, B, H, W, max_components=1024, max_edges=None, device="cuda", simplify=False):
         self.shape, self.max_components = (int(B), int(H), int(W)), int(max_components)
         self.max_edges = max(4096, int(H) * int(W) // 8) // 4 * 4 if max_edges is None else int(max_edges)
         if self.max_components < 1 or self.max_edges < 4 or self.max_edges % 4:
@@ -427,12 +429,26 @@ class ContourBuffers:
         self.ring_off = torch.empty(B, self.max_components + 1, dtype=i32, device=dev)
         self.n = torch.empty(B, 4, dtype=i32, device=dev)
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.simplify = bool(simplify)
+        self.simp_verts = torch.empty_like(self.verts) if simplify else None
+        self.simp_rings = torch.empty_like(self.rings) if simplify else None
+        self.simp_n = torch.empty_like(self.n) if simplify else None
+
+
+def _tol4(tolerance):
+    """The tolerance in pixels -> quarter pixels, or a ValueError that names the rule; None -> None."""
+    if tolerance is None:
+        return None
+    t = float(tolerance) * 4 if isinstance(tolerance, (int, float)) and not isinstance(tolerance, bool) else -1.0
+    if not 0 <= t <= 32768 or t != int(t):
+        raise ValueError(f"object_contours: tolerance must be a multiple of 0.25 pixels in 0..8192, not {tolerance!r}")
+    return int(t)
 
 
 _CONTOUR_KEYS = ("verts", "rings", "ring_off", "n")
 
 
-def _contours_one(ids, cap, connectivity, max_edges, buffers):
+def _contours_one(ids, cap, connectivity, max_edges, buffers, tol4=None, tolerance=None):
     squeeze = ids.dim() == 2
     ids, = _lift(squeeze, ids)
     if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
@@ -440,16 +456,25 @@ def _contours_one(ids, cap, connectivity, max_edges, buffers):
     ids = ids.contiguous()
     B, H, W = ids.shape
     if buffers is None:
-        buffers = ContourBuffers(B, H, W, cap, max_edges, ids.device)
+        buffers = ContourBuffers(B, H, W, cap, max_edges, ids.device, simplify=tol4 is not None)
+    elif tol4 is not None and not buffers.simplify:
+        raise ValueError("object_contours: a tolerance needs ContourBuffers(.., simplify=True)")
     elif (buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.max_components != cap
           or (max_edges is not None and buffers.max_edges != int(max_edges))):
         raise ValueError(f"buffers were made for {buffers.shape}, {buffers.max_components} objects, {buffers.max_edges} edges "
                          f"on {buffers.device}; the ids are {(B, H, W)} with {cap} objects on {ids.device}")
-    ops.seg_contours(ids, buffers.verts, buffers.rings, buffers.ring_off, buffers.n, buffers.ws, cap, connectivity)
-    return _unlift(squeeze, dict({k: getattr(buffers, k) for k in _CONTOUR_KEYS}, shape=(H, W), connectivity=connectivity))
+    if tol4 is None:
+        ops.seg_contours(ids, buffers.verts, buffers.rings, buffers.ring_off, buffers.n, buffers.ws, cap, connectivity)
+        return _unlift(squeeze, dict({k: getattr(buffers, k) for k in _CONTOUR_KEYS}, shape=(H, W), connectivity=connectivity))
+    ops.seg_contours(ids, buffers.verts, buffers.rings, buffers.ring_off, buffers.n, buffers.ws, cap, connectivity,
+                     buffers.simp_verts, buffers.simp_rings, buffers.simp_n, tol4)
+    c = _unlift(squeeze, dict({k: getattr(buffers, k) for k in _CONTOUR_KEYS}, shape=(H, W), connectivity=connectivity))
+    s = _unlift(squeeze, dict(verts=buffers.simp_verts, rings=buffers.simp_rings, ring_off=buffers.ring_off, n=buffers.simp_n,
+                              shape=(H, W), connectivity=connectivity))
+    return dict(c, simplified=dict(s, tolerance=tolerance))
 
 
-def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_components=None):
+def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_components=None, tolerance=None):
     """The outline of every object of an id map as rings of corner points.  o: a label_objects or fill_holes result -- the
     ids are o["ids"] and the objects outlined are 1..cap, cap = the rows of o["stats"] -- or an int32 device tensor [H, W] /
     [B, H, W] of ids (or a list of [h_i, w_i] maps) together with max_components=.  connectivity: 4 | 8, the one the ids
@@ -472,23 +497,39 @@ def object_contours(o, connectivity=8, max_edges=None, buffers=None, max_compone
     A list is handled with ONE CALL PER ITEM and every value of the result is then a list, as in label_objects; `buffers`
     is then a list of ContourBuffers or None.  buffers: a ContourBuffers of this shape and object count, reused call after
     call (the result aliases it); max_edges: rows per image for fresh buffers (ContourBuffers' default otherwise).  A fixed
-    number of launches per call and no host synchronisation."""
+    number of launches per call and no host synchronisation.
+
+    tolerance: None, or pixels, a multiple of 0.25 in 0..8192.  The result then gains simplified = dict(verts, rings,
+    ring_off, n, shape, connectivity, tolerance), the same rings simplified by Douglas-Peucker in the same call (three more
+    launches; reused buffers must be ContourBuffers(.., simplify=True)) and of the same form as the result itself, so
+    contours_to_host, rings_to_geojson and rings_to_coco take it unchanged: rings = (id, first, count, area) with the area
+    of the ORIGINAL ring, n = (corners in, corners kept, rings, complete), ring_off shared.  Every ring keeps its first
+    corner and at least three; tolerance 0 keeps every corner.  Douglas-Peucker preserves no topology: a simplified ring
+    may touch or cross itself or a neighbour, and the shared border of two objects is simplified once from each side.
+    Without a tolerance the result has exactly the keys above."""
     if connectivity not in (4, 8):
         raise ValueError(f"object_contours: connectivity must be 4 or 8, not {connectivity!r}")
+    tol4 = _tol4(tolerance)
     ids, caps = _ids_caps(o, max_components, "object_contours", "outline")
     if isinstance(ids, (list, tuple)):
-        return _per_item(lambda i, b: _contours_one(ids[i], caps[i], connectivity, max_edges, b), len(ids), (buffers,),
-                         "object_contours: one buffers entry per id map", _CONTOUR_KEYS + ("shape", "connectivity"))
-    return _contours_one(ids, caps, connectivity, max_edges, buffers)
+        keys = _CONTOUR_KEYS + ("shape", "connectivity")
+        r = _per_item(lambda i, b: _contours_one(ids[i], caps[i], connectivity, max_edges, b, tol4, tolerance), len(ids),
+                      (buffers,), "object_contours: one buffers entry per id map", keys + (("simplified",) if tol4 is not None else ()))
+        if tol4 is not None:                                  # a list of dicts -> a dict of lists, like the result itself
+            r["simplified"] = {k: [s[k] for s in r["simplified"]] for k in keys + ("tolerance",)}
+        return r
+    return _contours_one(ids, caps, connectivity, max_edges, buffers, tol4, tolerance)
 
 
 def contours_to_host(c):
     """object_contours' result -> (per image a list over the objects 1..n of lists of (area, int32 numpy [k, 2] of (X, Y)),
     the outer ring first; incomplete) with TWO synchronising copies (per item for a list result): the tables n, ring_off
     and rings first, then verts[:corners] of every image and nothing behind it.  n = the highest object with a ring.
-    incomplete: some image had more edges than max_edges; its list is empty.  A [H, W] result gives one image's list."""
+    incomplete: some image had more edges than max_edges; its list is empty.  A [H, W] result gives one image's list.
+    The simplified form, object_contours(.., tolerance=)["simplified"], is taken the same way: its n holds the kept corners
+    in column 1, and the areas are those of the original rings."""
     if isinstance(c["n"], (list, tuple)):
-        per = [contours_to_host({k: v[i] for k, v in c.items()}) for i in range(len(c["n"]))]
+        per = [contours_to_host({k: v[i] for k, v in c.items() if isinstance(v, (list, tuple))}) for i in range(len(c["n"]))]
         return [p[0] for p in per], any(p[1] for p in per)
     n, ring_off, rings, verts = c["n"], c["ring_off"], c["rings"], c["verts"]
     single = n.dim() == 1
@@ -529,7 +570,8 @@ def rings_to_coco(rings):
 
 
 def rings_to_mask(rings, h, w):
-    """One object's rings [(area, corners [k, 2])] -> numpy bool [h, w].  Every vertical side of a ring adds, for each row
+    """One object's rings [(area, corners [k, 2])] -> numpy bool [h, w], for RECTILINEAR rings only (object_contours'
+    own; a simplified ring has slanted sides, which this ignores).  Every vertical side of a ring adds, for each row
     it spans, -1 at its column when it heads south (the object lies to its west) and +1 when it heads north; the
     cumulative sum along x is 1 inside and 0 outside."""
     acc = np.zeros((h, w + 1), np.int64)

@@ -1188,7 +1188,16 @@ def seg_contours_workspace(B, H, W, cap, max_edges):
     return int(L.lib().dfw_seg_contours_workspace_bytes(int(B), int(H), int(W), int(cap), int(max_edges)))
 
 
-def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8):
+def seg_contours_simplify_block():
+    """The ring length up to which seg_contours' simplification keeps a ring's state in LDS; longer rings keep it in the
+    workspace."""
+    v = C.c_int32()
+    L.check(L.lib().dfw_seg_contours_simplify_block(C.byref(v)), "dfw_seg_contours_simplify_block")
+    return int(v.value)
+
+
+def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8, simp_verts=None, simp_rings=None, simp_n=None,
+                 tol4=0):
     """Outlines of the objects 1..cap of an id map as rings of corner points, on caller-owned buffers only
     (objects.ContourBuffers holds a set): ids int32 [B, H, W], normally seg_components' or seg_holes' (any int32 map is
     accepted; ids outside 1..cap count as 0); connectivity = 4 | 8, the one the ids were made with.  Pixel (x, y) is the
@@ -1200,9 +1209,21 @@ def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8):
     first + count.  An image with more than max_edges edges gets n = (found, 0, 0, 0), a zero ring_off and no row: there
     are no partial results.  Rows behind the kept ones are left as they were.  ws: a uint8 buffer of at least
     seg_contours_workspace(B, H, W, cap, max_edges) bytes, which needs no initialisation.  A number of launches fixed by
-    the arguments, no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    the arguments, no host synchronisation, no memset node: the call can be captured.  Returns None.
+
+    simp_verts, simp_rings, simp_n (all three or none; shaped like verts, rings and n) and tol4, the tolerance in quarter
+    pixels, 0..32768: the same rings simplified by Douglas-Peucker in integers (include/diffews_hip.h holds the
+    definition), three more launches.  simp_rings = (id, first', count', area of the original ring) in the rows of rings,
+    simp_verts the kept corners, simp_n = (corners in, corners kept, rings, complete), (0, 0, 0, 0) for an image that is
+    not complete; ring_off serves both.  Without them the call is what it was."""
     if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
         raise ValueError("seg_contours: ids must be a contiguous int32 device tensor [B, H, W]")
+    simp = (simp_verts, simp_rings, simp_n)
+    if any(t is None for t in simp) != all(t is None for t in simp):
+        raise ValueError("seg_contours: simp_verts, simp_rings and simp_n come together or not at all")
+    tol4 = int(tol4)
+    if not 0 <= tol4 <= 32768 or (simp_n is None and tol4):
+        raise ValueError("seg_contours: tol4 must be 0..32768 quarter pixels, and 0 without the simp_ buffers")
     if connectivity not in (4, 8):
         raise ValueError(f"seg_contours: connectivity must be 4 or 8, not {connectivity!r}")
     B, H, W = ids.shape
@@ -1217,6 +1238,10 @@ def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8):
     a.n = own("n", n, torch.int32, (B, 4))
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
     a.B, a.H, a.W, a.cap, a.max_edges, a.connectivity = B, H, W, cap, max_edges, int(connectivity)
+    if simp_n is not None:
+        a.simp_verts = own("simp_verts", simp_verts, torch.int32, (B, max_edges, 2))
+        a.simp_rings = own("simp_rings", simp_rings, torch.int32, (B, max_edges // 4, 4))
+        a.simp_n, a.tol4 = own("simp_n", simp_n, torch.int32, (B, 4)), tol4
     L.check(L.lib().dfw_seg_contours(C.byref(a), _stream()), "dfw_seg_contours")
 
 

@@ -1020,7 +1020,8 @@ class MarigoldPipelineRGBLatentNoise:
 
     def object_contours(self, o, **kw):
         """The outline of every object of pipe.objects' (or pipe.fill_holes') result as rings of corner points:
-        objects.object_contours(o, **kw) -- connectivity, max_edges, buffers."""
+        objects.object_contours(o, **kw) -- connectivity, max_edges, buffers, and tolerance (pixels) for the simplified
+        rings next to them, result["simplified"]."""
         from .objects import object_contours
         return object_contours(o, **kw)
 

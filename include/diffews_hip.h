@@ -1236,6 +1236,47 @@ int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t 
  * n / ws; connectivity not 4 or 8; B, H, W or cap < 1; max_edges < 4 or not a multiple of 4.  DFW_ERANGE: H, W or B above
  * 65535, 4 * H * W above 2^31 - 1 (the keys), B * max_edges * 2 or B * (cap + 1) above 2^31 - 1.  Then the workspace and
  * the buffers, by the rule above, with alignments of its own: verts 8 bytes, rings, n and ws 16 (rows and records of 16).
+ *
+ * SIMPLIFIED RINGS (version >= 123), an optional last stage of the same call, as approxPolyDP stands behind findContours:
+ * Douglas-Peucker with a tolerance of tol4 quarter pixels on every ring, in integers only, so the result is exact and
+ * depends on no order of execution.  With simp_verts, simp_rings and simp_n null and tol4 = 0 the call is what it was,
+ * launch for launch.  A ring is the count >= 4 corners P[0..c) of one row of rings, in rank order and closed (P[c] means
+ * P[0]).
+ *   1  anchors: f is the corner with the largest squared distance from P[0], the lowest rank on ties.  Corners 0 and f
+ *      are kept; the chains are (0, f) and (f, c)
+ *   2  a chain (a, b) with b - a >= 2: the measure m(i) of an interior corner is, in line mode (P[a] != P[b]),
+ *      |(bx-ax)(py-ay) - (by-ay)(px-ax)| with L = (bx-ax)^2 + (by-ay)^2, and in point mode (P[a] == P[b]: an 8-connected
+ *      ring may visit a vertex twice) its squared distance to P[a].  The winner w has the largest m; on ties the rank
+ *      nearest the middle, the smallest |2i - (a+b)|, then the lower rank.  w is kept iff 16 m^2 > tol4^2 L (line mode) or
+ *      16 m > tol4^2 (point mode), strictly.  If w is kept the chains (a, w) and (w, b) follow, else every interior corner
+ *      is dropped.  The distance is the one to the infinite line through the anchors, as in the original algorithm
+ *   3  if only the two anchors survive, the corner with the largest line-mode measure against P[0]P[f] is kept too, the
+ *      lowest rank on ties: a ring encloses area, so that measure is above zero, every ring keeps at least 3 corners and
+ *      no ring disappears
+ * The middle rule keeps the rounds few: a perfect 45 degree staircase at half a pixel splits in the middle every round
+ * where "lowest rank" would peel one corner a round.  At tol4 = 0 every corner is kept.  Example: [[1,0],[0,1]] with
+ * connectivity 8 is one ring of 8 corners, (0,0) (1,0) (1,1) (2,1) (2,2) (1,2) (1,1) (0,1); at tol4 = 4 the anchors are
+ * ranks 0 and 4, every other corner lies within one pixel of the diagonal, and rule 3 keeps rank 1: ranks 0, 1, 4.
+ * Bounds: 4 H W <= 2^31 - 1 gives |cross| <= 2 H W < 2^30, so 16 m^2 < 2^64; a point-mode m is at most 2 * 65535^2 <
+ * 2^33; tol4 <= 32768 (8192 pixels) and L < 2^33 give tol4^2 L < 2^63: everything fits 64 unsigned bits.  A winner is
+ * one order-free 64-bit maximum of the packed key m << 31 | (2^31 - 1 - (2 |2i - (a+b)| + (2i > a+b))), 33 bits above 31.
+ *   simp_rings  row r = (id, first', count', area) in the rows and the order of rings; area is the ORIGINAL ring's exact
+ *               area, whose sign still tells outer from hole: the simplified polygon's area is not computed
+ *   simp_verts  the kept corners, contiguous per ring in rank order; a ring's first corner is still P[0]
+ *   simp_n      (corners in, corners kept, rings, complete): dfw_seg_contours' readers of columns 1 to 3 take it as it is.
+ *               An image that is not complete gets (0, 0, 0, 0) and no row
+ *   ring_off    is shared with the unsimplified result
+ * Rows behind the kept ones are left as they were.  Douglas-Peucker preserves no topology: a simplified ring may touch or
+ * cross itself or a neighbour, and two objects' shared border is simplified twice, independently.
+ * Three more launches (dfw_seg_contours_trips.simplify_launches), whatever the image: one workgroup of 256 per ring row
+ * runs the level-synchronous form in a bounded loop -- every round each live chain finishes or keeps one more corner, at
+ * most count - 2 rounds, the exit test uniform over the workgroup -- with the state of a ring of at most
+ * dfw_seg_contours_simplify_block() corners in LDS and of a longer one in the workspace; a scan of the corners kept per
+ * ring gives first'; one workgroup per ring row writes.  No memset node, no readback, no atomic decides a position, no
+ * thread waits for another workgroup.  The workspace does not grow: the state lives where the pointer doubling's buffers
+ * lay.  Validated with the null pointers and scalars (DFW_EINVAL, before the sizes): some but not all of the three
+ * pointers; tol4 outside 0..32768; tol4 != 0 with the stage off.  The three outputs are written buffers of the table
+ * above, also against verts, rings and n, which the stage reads.
  */
 typedef struct {
   const int32_t* ids;      /* [B][H][W] contiguous, read only */
@@ -1246,6 +1287,11 @@ typedef struct {
   void* ws;
   size_t ws_bytes;
   int32_t B, H, W, cap, max_edges, connectivity;   /* connectivity 4 | 8: the one the ids were made with */
+  /* the simplified rings (version >= 123, below): all three null and tol4 = 0 -- the stage is off -- or all three given */
+  int32_t* simp_verts;     /* out [B][max_edges][2], 8-byte aligned: the kept corners; rows behind them are left */
+  int32_t* simp_rings;     /* out [B][max_edges / 4][4], 16-byte aligned: (id, first', count', area of the original ring) */
+  int32_t* simp_n;         /* out [B][4], 16-byte aligned: (corners in, corners kept, rings, complete) */
+  int32_t tol4;            /* the tolerance in quarter pixels, 0..32768 */
 } dfw_seg_contours_args;
 int dfw_seg_contours(const dfw_seg_contours_args* a, dfw_stream_t stream);
 /* 0 for arguments dfw_seg_contours answers DFW_EINVAL for; monotone in every argument */
@@ -1267,8 +1313,12 @@ typedef struct {
   int32_t offsets_scan;   /* trips of the scan of ring_off (cap + 1 words) */
   int32_t corners_scan;   /* trips of the scan of the corners per ring (max_edges / 4 words) */
   int32_t launches;       /* 14 + 2 * doubling + 3 * passes */
+  int32_t simplify_launches;   /* 3: the launches behind them when the simplified rings are asked for */
 } dfw_seg_contours_trips;
 int dfw_seg_contours_rounds(int32_t B, int32_t H, int32_t W, int32_t cap, int32_t max_edges, dfw_seg_contours_trips* out);
+/* the ring length up to which the simplification keeps a ring's state in LDS; longer rings keep it in the workspace.
+ * Host only, launches nothing.  DFW_EINVAL for a null pointer */
+int dfw_seg_contours_simplify_block(int32_t* lds_corners);
 
 /* ======================================================================================================
  * Training step (BASELINE configs[4]; train_tools/train_icl_multitask_nocrop_nearest_nshot_v3.py:1374-1396 =
