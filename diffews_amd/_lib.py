@@ -148,12 +148,12 @@ class SegScoresArgs(C.Structure):
 
 class SegBoundaryArgs(C.Structure):
     _fields_ = [("map", _vp), ("dist", _vp), ("band", _vp), ("ws", _vp), ("ws_bytes", _sz), ("elem", _i32), ("B", _i32),
-                ("H", _i32), ("W", _i32), ("dmax", _i32), ("d", _i32)]
+                ("H", _i32), ("W", _i32), ("dmax", _i32), ("d", _i32), ("metric", _i32), ("peaks", _vp), ("cap", _i32)]
 
 
 class SegBoundaryCountsArgs(C.Structure):
     _fields_ = [("pred", _vp), ("pdist", _vp), ("gt", _vp), ("gdist", _vp), ("counts", _vp), ("B", _i32), ("H", _i32),
-                ("W", _i32), ("d", _i32), ("nlabels", _i32)]
+                ("W", _i32), ("d", _i32), ("nlabels", _i32), ("dist_elem", _i32)]
 
 
 class SegComponentsRounds(C.Structure):

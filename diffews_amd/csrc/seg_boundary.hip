@@ -40,11 +40,29 @@
 // g = gt if 1 <= gdist <= d else 0; pred[l]++, gt[g]++, inter[l]++ when l == g, in LDS histograms per workgroup of
 // kBndCountPix positions, flushed by seg_flush_counts (seg_fuse.h) into counts [B][2][nlabels + 1] = (intersections,
 // unions).  Pixels in neither band, the bulk of an image, are counted in a register and reach the histogram once per wave.
-// Two launches: a library kernel zeroes counts (no memset node), then the count.
+// Two launches: a library kernel zeroes counts (no memset node), then the count.  dist_elem = 2: both dist maps are the
+// uint16 squared ones and the rule is 1 <= dist <= d * d (boundary_counts_kernel<uint16_t>).
 //
-// Termination: in dfw_seg_boundary no thread waits for another thread or workgroup and no atomics are used; every loop
-// but the column walk has a trip count fixed at compile time, and the walk ends after at most dmax steps.  The counts use
-// LDS and global integer atomics (order-free) and wait for nothing.  Any grid is correct at any residency.
+// The Euclidean metric (metric = 1): dist is uint16 [B][H][W], 0 where map == 0, else min(D2, (dmax + 1)^2), D2 the smallest
+// dy^2 + dx^2 to a position outside the image or of another value; band holds the value where 1 <= dist <= d^2.  The row
+// pass and the workspace are the same, h is all the state there is:
+//   D2(y, x) = min(min(y + 1, H - y)^2, min over dy of c(dy)),  c(0) = h(y, x)^2,
+//   c(dy) = dy^2 + h(y + dy, x)^2 while map[y + dy][x] == v, c(dy) = dy^2 at the first row where it differs.
+// Every candidate is the squared distance to a real differing position, and for a nearest one (y', x') either the column
+// holds v from y to y', so that h(y', x) reaches a differing position no farther along than x', or the column differs at a
+// nearer row.  A capped h only removes candidates above (dmax + 1)^2.
+//
+//   1' boundary_col2_kernel<T, V, P>  the tile, the V = 4 / V = 1 split and the vector condition of boundary_col_kernel (dist
+//                                 aligned to four uint16), walking while dy^2 < the largest best-so-far.  P: peaks int64
+//                                 [B][cap] of an id map, row k - 1 = max over the pixels of id k of (dist << 32) | (2^32 - 1
+//                                 - (y * W + x)); boundary_zero_kernel clears it first (three launches then) and
+//                                 bnd_peaks_wave reduces it with one atomicMax per piece of equal id of a wave's lanes, none
+//                                 when the row already holds as much.
+//
+// Termination: in dfw_seg_boundary no thread waits for another thread or workgroup and, without peaks, no atomics are
+// used; every loop but the column walk has a trip count fixed at compile time, and the walk ends after at most dmax steps.
+// The peaks and the counts use global (and LDS) integer atomics, order-free, and wait for nothing.  Any grid is correct at
+// any residency.
 #include "seg_args.h"
 #include "seg_fuse.h"
 
@@ -221,14 +239,161 @@ __global__ __launch_bounds__(256) void boundary_col_kernel(const T* map, const u
   }
 }
 
+// V neighbouring squared distances -> uint16
+template <int V> __device__ __forceinline__ void bnd_store16(uint16_t* p, const int (&o)[V]) {
+  if constexpr (V == 1) {
+    p[0] = (uint16_t)o[0];
+  } else {
+    u32x2 w;
+    w[0] = (uint32_t)o[0] | ((uint32_t)o[1] << 16), w[1] = (uint32_t)o[2] | ((uint32_t)o[3] << 16);
+    *(u32x2*)p = w;
+  }
+}
+
+// One piece of the peaks reduction goes out: the row only grows, so a key that a relaxed load already finds there, or a
+// larger one, needs no atomic.
+__device__ __forceinline__ void bnd_peak_out(unsigned long long* row, unsigned long long key) {
+  if (__hip_atomic_load(row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) atomicMax(row, key);
+}
+
+// The peaks of one round of a wave: every lane holds V pixels side by side, id[k] in 1..pcap or 0 (not counted, inactive
+// lanes included) and key[k].  A thread folds its runs of equal id into the run's last pixel; the run at a thread's end
+// (its tail) goes on in the next lane when that lane starts with the same id, through all of that lane when it holds one
+// id only.  A wave64 segmented max-scan over the tails folds every such chain, the chain's last lane sends it out, and the
+// runs that end inside a thread go out by themselves.  All 64 lanes must arrive.
+template <int V>
+__device__ __forceinline__ void bnd_peaks_wave(unsigned long long* rows, const int (&idv)[V], unsigned long long (&key)[V]) {
+  const int lane = threadIdx.x & 63;
+  bool uniform = true;
+#pragma unroll
+  for (int k = 1; k < V; ++k) {
+    if (idv[k] == idv[k - 1]) key[k] = max(key[k], key[k - 1]);
+    else uniform = false;
+  }
+  int lead = 0;                                       // the last pixel of the thread's first run
+#pragma unroll
+  for (int k = V - 1; k > 0; --k)
+    if (idv[k] != idv[k - 1]) lead = k - 1;
+  if (uniform) lead = V - 1;
+  const int tid = idv[V - 1];
+  unsigned long long tkey = key[V - 1];
+  // a first run that is not the whole thread joins the tail of the lane before it
+  int lid = idv[0];
+  unsigned long long lkey = key[0];
+#pragma unroll
+  for (int k = 1; k < V; ++k)
+    if (k == lead) lkey = key[k];
+  const int nlid = __shfl_down(lid, 1, 64), nuni = __shfl_down((int)uniform, 1, 64);
+  const unsigned long long nlkey = __shfl_down(lkey, 1, 64);
+  const int ptid = __shfl_up(tid, 1, 64);
+  const bool absorbed = !uniform && lane > 0 && ptid == lid;          // my first run went into the lane before
+  if (lane < 63 && !nuni && nlid == tid) tkey = max(tkey, nlkey);
+  const bool joins = uniform && lane > 0 && ptid == tid;              // my tail goes on from the lane before
+  int start = joins ? 0 : lane;                                       // the lane where my chain starts: a max-scan
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int s = __shfl_up(start, o, 64);
+    if (lane >= o) start = max(start, s);
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long other = __shfl_up(tkey, o, 64);
+    if (lane - o >= start) tkey = max(tkey, other);
+  }
+  const int njoins = __shfl_down((int)joins, 1, 64);
+  if (tid && (lane == 63 || !njoins)) bnd_peak_out(rows + (tid - 1), tkey);
+  if constexpr (V > 1) {
+#pragma unroll
+    for (int k = 0; k < V - 1; ++k)
+      if (idv[k] != idv[k + 1] && idv[k] && !(absorbed && k == lead)) bnd_peak_out(rows + (idv[k] - 1), key[k]);
+  }
+}
+
+// The Euclidean column pass: boundary_col_kernel's tile and threads, the squared walk.  best starts at min(h, y + 1, H - y,
+// cap)^2; round dy offers dy^2 + h(y +- dy, x)^2 where the column still holds v and dy^2 where it does not, and a pixel
+// whose best is <= dy^2 takes nothing from it or any later round.  dy^2 < far <= min(y + 1, H - y, cap)^2: the rows exist
+// and the walk ends after at most cap - 1 = dmax steps; dy^2 + h^2 <= 254^2 + 255^2.  P: the peaks of an id map, reduced
+// per wave and round; no thread leaves before the last round then.
+template <typename T, int V, bool P>
+__global__ __launch_bounds__(256) void boundary_col2_kernel(const T* map, const uint8_t* hrow, uint16_t* dist, T* band,
+                                                            unsigned long long* peaks, int H, int W, int cap, int d2,
+                                                            int pcap) {
+  constexpr int TX = kBndCols / V, TY = 256 / TX;
+  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+  const int x = blockIdx.x * kBndCols + tx * V;
+  if (!P && x >= W) return;
+  const size_t img = (size_t)blockIdx.z * H * W;
+#pragma unroll
+  for (int r = 0; r < kBndRows / TY; ++r) {
+    const int y = blockIdx.y * kBndRows + r * TY + ty;
+    if (!P && y >= H) return;
+    const bool in = x < W && y < H;
+    const size_t o = img + (size_t)(in ? y : 0) * W + (in ? x : 0);
+    int v[V], best[V];
+    if (in) {
+      bnd_load<T, V>(map + o, v);
+      bnd_load<uint8_t, V>(hrow + o, best);
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k) v[k] = best[k] = 0;
+    }
+    const int edge = min(min(y + 1, H - y), cap);
+    int far = 0;
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const int b = min(best[k], edge);
+      best[k] = v[k] ? b * b : 0;
+      far = max(far, best[k]);
+    }
+    for (int dy = 1; dy * dy < far; ++dy) {
+      const size_t s = (size_t)dy * W;
+      int mu[V], hu[V], md[V], hd[V];
+      bnd_load<T, V>(map + o - s, mu);
+      bnd_load<uint8_t, V>(hrow + o - s, hu);
+      bnd_load<T, V>(map + o + s, md);
+      bnd_load<uint8_t, V>(hrow + o + s, hd);
+      const int dd = dy * dy;
+      far = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const int cu = mu[k] == v[k] ? dd + hu[k] * hu[k] : dd, cd = md[k] == v[k] ? dd + hd[k] * hd[k] : dd;
+        best[k] = min(best[k], min(cu, cd));
+        far = max(far, best[k]);
+      }
+    }
+    if (in) {
+      bnd_store16<V>(dist + o, best);
+      if (band) {
+        int w[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) w[k] = best[k] <= d2 ? v[k] : 0;   // best == 0 only where v == 0
+        bnd_store<T, V>(band + o, w);
+      }
+    }
+    if constexpr (P) {
+      int idv[V];
+      unsigned long long key[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        idv[k] = (unsigned)(v[k] - 1) < (unsigned)pcap ? v[k] : 0;     // v == 0 outside the image
+        key[k] = ((unsigned long long)best[k] << 32) | (0xFFFFFFFFu - (unsigned)(y * W + x + k));
+      }
+      bnd_peaks_wave<V>(peaks + (size_t)blockIdx.z * pcap, idv, key);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void boundary_zero_kernel(unsigned long long* words, int n) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < n) words[e] = 0ull;
 }
 
-__global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pred, const uint8_t* pdist, const uint8_t* gt,
-                                                              const uint8_t* gdist, unsigned long long* counts, int HW,
-                                                              int d, int nlabels) {
+// DT: the dist maps' element, uint8 distances (a pixel lies in the band when 1 <= dist <= lim = d) or uint16 squared
+// distances (lim = d * d)
+template <typename DT>
+__global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pred, const DT* pdist, const uint8_t* gt,
+                                                              const DT* gdist, unsigned long long* counts, int HW, int lim,
+                                                              int nlabels) {
   __shared__ unsigned hist[3 * 256];   // [inter | pred | gt][label byte]
   const int t = threadIdx.x;
   for (int i = t; i < 3 * 256; i += 256) hist[i] = 0u;
@@ -239,7 +404,7 @@ __global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pre
   unsigned none = 0u;                  // kept pixels in neither band: bin 0 of all three
   auto count = [&](int p, int pd, int g, int gd) {
     if (bin(g) < 0) return;
-    const int l = (unsigned)(pd - 1) < (unsigned)d ? p : 0, gg = (unsigned)(gd - 1) < (unsigned)d ? g : 0;
+    const int l = (unsigned)(pd - 1) < (unsigned)lim ? p : 0, gg = (unsigned)(gd - 1) < (unsigned)lim ? g : 0;
     if ((l | gg) == 0) {
       ++none;
       return;
@@ -249,16 +414,25 @@ __global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pre
     if (l == gg) atomicAdd(&hist[l], 1u);
   };
   const int p0 = blockIdx.x * kBndCountPix;
-  if ((HW & 3) == 0 && (((uintptr_t)pred | (uintptr_t)pdist | (uintptr_t)gt | (uintptr_t)gdist) & 3) == 0) {
+  if ((HW & 3) == 0 && (((uintptr_t)pred | (uintptr_t)gt) & 3) == 0 &&
+      (((uintptr_t)pdist | (uintptr_t)gdist) & (4 * sizeof(DT) - 1)) == 0) {
 #pragma unroll
     for (int r = 0; r < kBndCountPix / 1024; ++r) {
       const int q = p0 + 4 * (r * 256 + t);
       if (q < HW) {
-        const uint32_t wp = *(const uint32_t*)(pred + q), wpd = *(const uint32_t*)(pdist + q);
-        const uint32_t wg = *(const uint32_t*)(gt + q), wgd = *(const uint32_t*)(gdist + q);
+        const uint32_t wp = *(const uint32_t*)(pred + q), wg = *(const uint32_t*)(gt + q);
+        if constexpr (sizeof(DT) == 1) {
+          const uint32_t wpd = *(const uint32_t*)(pdist + q), wgd = *(const uint32_t*)(gdist + q);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          count((wp >> (8 * k)) & 255u, (wpd >> (8 * k)) & 255u, (wg >> (8 * k)) & 255u, (wgd >> (8 * k)) & 255u);
+          for (int k = 0; k < 4; ++k)
+            count((wp >> (8 * k)) & 255u, (wpd >> (8 * k)) & 255u, (wg >> (8 * k)) & 255u, (wgd >> (8 * k)) & 255u);
+        } else {
+          const u32x2 wpd = *(const u32x2*)(pdist + q), wgd = *(const u32x2*)(gdist + q);
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            count((wp >> (8 * k)) & 255u, (wpd[k >> 1] >> (16 * (k & 1))) & 65535u, (wg >> (8 * k)) & 255u,
+                  (wgd[k >> 1] >> (16 * (k & 1))) & 65535u);
+        }
       }
     }
   } else {
@@ -280,18 +454,35 @@ __global__ __launch_bounds__(256) void boundary_counts_kernel(const uint8_t* pre
   seg_flush_counts(hist, counts + (size_t)blockIdx.y * 2 * NB, NB);
 }
 
+template <typename T, int V, bool P>
+static void boundary_launch_col2(hipStream_t st, const dfw_seg_boundary_args* a, dim3 grid) {
+  hipLaunchKernelGGL((boundary_col2_kernel<T, V, P>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws,
+                     (uint16_t*)a->dist, (T*)a->band, (unsigned long long*)a->peaks, a->H, a->W, a->dmax + 1,
+                     a->band ? a->d * a->d : 0, a->cap);   // d is looked at with a band only
+}
+
 template <typename T>
 static void boundary_launch(hipStream_t st, const dfw_seg_boundary_args* a, bool vec) {
   const int HW = a->H * a->W, cap = a->dmax + 1;
   hipLaunchKernelGGL(boundary_row_kernel<T>, dim3((HW + kBndPos - 1) / kBndPos, a->B), dim3(256), 0, st, (const T*)a->map,
                      (uint8_t*)a->ws, HW, a->W, cap);
   const dim3 grid((a->W + kBndCols - 1) / kBndCols, (a->H + kBndRows - 1) / kBndRows, a->B);
-  if (vec)
-    hipLaunchKernelGGL((boundary_col_kernel<T, 4>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws, a->dist,
-                       (T*)a->band, a->H, a->W, cap, a->d);
+  if (a->metric == 1) {
+    if constexpr (sizeof(T) == 4) {                   // peaks come with an id map only
+      if (a->peaks) {
+        if (vec) boundary_launch_col2<T, 4, true>(st, a, grid);
+        else boundary_launch_col2<T, 1, true>(st, a, grid);
+        return;
+      }
+    }
+    if (vec) boundary_launch_col2<T, 4, false>(st, a, grid);
+    else boundary_launch_col2<T, 1, false>(st, a, grid);
+  } else if (vec)
+    hipLaunchKernelGGL((boundary_col_kernel<T, 4>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws,
+                       (uint8_t*)a->dist, (T*)a->band, a->H, a->W, cap, a->d);
   else
-    hipLaunchKernelGGL((boundary_col_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws, a->dist,
-                       (T*)a->band, a->H, a->W, cap, a->d);
+    hipLaunchKernelGGL((boundary_col_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)a->map, (const uint8_t*)a->ws,
+                       (uint8_t*)a->dist, (T*)a->band, a->H, a->W, cap, a->d);
 }
 
 }  // namespace dfw
@@ -314,17 +505,26 @@ extern "C" int dfw_seg_boundary(const dfw_seg_boundary_args* a, dfw_stream_t str
   if (a->elem != 1 && a->elem != 4) return DFW_EINVAL;
   if (a->dmax < 1 || a->dmax > 254) return DFW_EINVAL;
   if (a->band && (a->d < 1 || a->d > a->dmax)) return DFW_EINVAL;
+  if (a->metric != 0 && a->metric != 1) return DFW_EINVAL;
+  if (a->peaks && (a->metric == 0 || a->elem != 4 || a->cap < 1)) return DFW_EINVAL;
   if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
+  if (a->peaks && (long long)a->B * a->cap > 0x7fffffffll) return DFW_ERANGE;
   const size_t wsb = dfw_seg_boundary_workspace_bytes(a->B, a->H, a->W, a->elem);
   if (a->ws_bytes < wsb) return DFW_EWORKSPACE;
-  const size_t n = (size_t)a->B * a->H * a->W, el = (size_t)a->elem;
-  const seg_buf bufs[] = {seg_in(a->map, n * el, el), seg_out(a->dist, n), seg_out(a->band, n * el, el),
-                          seg_out(a->ws, wsb, 4)};
+  const size_t n = (size_t)a->B * a->H * a->W, el = (size_t)a->elem, de = a->metric == 1 ? 2 : 1;
+  const size_t rows = a->peaks ? (size_t)a->B * a->cap : 0;
+  const seg_buf bufs[] = {seg_in(a->map, n * el, el), seg_out(a->dist, n * de, de), seg_out(a->band, n * el, el),
+                          seg_out(a->ws, wsb, 4), seg_out(a->peaks, rows * 8, 8)};
   if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
+  if (a->peaks) {
+    hipLaunchKernelGGL(boundary_zero_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st,
+                       (unsigned long long*)a->peaks, (int)rows);
+    DFW_CHECK_LAUNCH();
+  }
   // four pixels a thread in the column pass: whole words of every map, in every row of every image
   const uintptr_t al = 4 * el - 1;
-  const bool vec = a->W % 4 == 0 && (((uintptr_t)a->map | (uintptr_t)a->band) & al) == 0 && ((uintptr_t)a->dist & 3) == 0;
+  const bool vec = a->W % 4 == 0 && (((uintptr_t)a->map | (uintptr_t)a->band) & al) == 0 && ((uintptr_t)a->dist & (4 * de - 1)) == 0;
   if (a->elem == 1) boundary_launch<uint8_t>(st, a, vec);
   else boundary_launch<int32_t>(st, a, vec);
   DFW_CHECK_LAUNCH();
@@ -335,17 +535,23 @@ extern "C" int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, df
   if (!a || !a->pred || !a->pdist || !a->gt || !a->gdist || !a->counts) return DFW_EINVAL;
   if (a->d < 1 || a->d > 254) return DFW_EINVAL;
   if (a->nlabels < 1 || a->nlabels > 254) return DFW_EINVAL;
+  if (a->dist_elem < 0 || a->dist_elem > 2) return DFW_EINVAL;
   if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
-  const size_t n = (size_t)a->B * a->H * a->W, cb = (size_t)a->B * 2 * (a->nlabels + 1) * 8;
-  const seg_buf bufs[] = {seg_in(a->pred, n), seg_in(a->pdist, n), seg_in(a->gt, n), seg_in(a->gdist, n),
+  const size_t n = (size_t)a->B * a->H * a->W, cb = (size_t)a->B * 2 * (a->nlabels + 1) * 8, de = a->dist_elem == 2 ? 2 : 1;
+  const seg_buf bufs[] = {seg_in(a->pred, n), seg_in(a->pdist, n * de, de), seg_in(a->gt, n), seg_in(a->gdist, n * de, de),
                           seg_out(a->counts, cb, 8)};
   if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int HW = a->H * a->W, words = a->B * 2 * (a->nlabels + 1);
   hipLaunchKernelGGL(boundary_zero_kernel, dim3((words + 255) / 256), dim3(256), 0, st, (unsigned long long*)a->counts, words);
   DFW_CHECK_LAUNCH();
-  hipLaunchKernelGGL(boundary_counts_kernel, dim3((HW + kBndCountPix - 1) / kBndCountPix, a->B), dim3(256), 0, st, a->pred,
-                     a->pdist, a->gt, a->gdist, (unsigned long long*)a->counts, HW, a->d, a->nlabels);
+  const dim3 grid((HW + kBndCountPix - 1) / kBndCountPix, a->B);
+  if (de == 2)
+    hipLaunchKernelGGL(boundary_counts_kernel<uint16_t>, grid, dim3(256), 0, st, a->pred, (const uint16_t*)a->pdist, a->gt,
+                       (const uint16_t*)a->gdist, (unsigned long long*)a->counts, HW, a->d * a->d, a->nlabels);
+  else
+    hipLaunchKernelGGL(boundary_counts_kernel<uint8_t>, grid, dim3(256), 0, st, a->pred, (const uint8_t*)a->pdist, a->gt,
+                       (const uint8_t*)a->gdist, (unsigned long long*)a->counts, HW, a->d, a->nlabels);
   DFW_CHECK_LAUNCH();
   return 0;
 }

@@ -5,7 +5,7 @@ Every segmentation route ends in a label map -- `labels` of segment_classes / se
 of the binary routes, `r["native"]["labels"]` / `["pred"]` at the queries' own sizes -- and label_objects turns it into
 "which objects, how many, how big, where" without bringing the map to the host.  Nothing here synchronises except
 objects_to_host, which copies the two small tables (n and stats) once, runs_to_host, contours_to_host, matches_to_host,
-scores_to_host and detections_to_host.
+scores_to_host, detections_to_host and thickness_to_host.
 
 fill_holes is the partner of min_area: the background regions that ONE object encloses, up to max_area pixels, take that
 object's id and label (ops.seg_holes), and the result is again a label_objects result, so every stage below takes it.  A
@@ -37,6 +37,12 @@ metrics.boundary_iou read.  Per-object Boundary IoU needs no stage of its own: t
     m = match_objects((pb["ids"]["band"], o_pred["stats"]), (gb["ids"]["band"], o_gt["stats"]), skip=gt_labels, nlabels=N)
 gives in m["pairs"] the shared band pixels of every (pred, gt) pair, in m["area"] the band areas, and in m["match"] / m["pq"]
 the matching and the panoptic counts at Boundary IoU above `iou`.
+
+object_thickness says how THICK an object is and where its MIDDLE lies: the squared Euclidean distance of every pixel of
+the id map to its own contour (ops.seg_boundary with metric="euclidean", which boundary_bands and object_boundaries take as
+well) and, per object, the largest of them with its first position -- radius and centre of the largest inscribed circle, a
+label point inside the object and the measure a min-thickness rule needs; thickness_to_host brings the table to the host.
+object_cores labels the pixels farther than a radius from the contour again: touching objects of one class fall apart.
 """
 import numpy as np
 import torch
@@ -936,30 +942,42 @@ def detections_to_host(o, s, m):
 # ------------------------------------------------------------------------------------------------ boundary bands
 
 _BOUNDARY_DMAX = 254
+_BOUNDARY_METRICS = ("chessboard", "euclidean")
 
 
 class BoundaryBuffers:
     """Everything one boundary_bands call of a shape writes, allocated once: dist uint8 [B, H, W], band [B, H, W] of the
     map's dtype (torch.uint8 for label maps, torch.int32 for id maps) and the workspace.  dmax is the search radius of the
-    calls that use the buffers without naming one."""
+    calls that use the buffers without naming one.  metric="euclidean": dist is uint16 and holds squared distances;
+    max_components (with it, for int32 id maps): peaks int64 [B, max_components], what object_thickness writes."""
 
-    def __init__(self, B, H, W, dmax, dtype=torch.uint8, device="cuda"):
-        self.shape, self.dmax, self.dtype = (int(B), int(H), int(W)), int(dmax), dtype
+    def __init__(self, B, H, W, dmax, dtype=torch.uint8, device="cuda", metric="chessboard", max_components=None):
+        self.shape, self.dmax, self.dtype, self.metric = (int(B), int(H), int(W)), int(dmax), dtype, metric
         if dtype not in (torch.uint8, torch.int32):
             raise ValueError("BoundaryBuffers: dtype must be torch.uint8 (label maps) or torch.int32 (id maps)")
         if not 1 <= self.dmax <= _BOUNDARY_DMAX:
             raise ValueError(f"BoundaryBuffers: dmax must lie in 1..{_BOUNDARY_DMAX}, got {self.dmax}")
+        if metric not in _BOUNDARY_METRICS:
+            raise ValueError(f"BoundaryBuffers: metric must be one of {_BOUNDARY_METRICS}, got {metric!r}")
+        self.max_components = None if max_components is None else int(max_components)
+        if self.max_components is not None and (metric != "euclidean" or dtype != torch.int32 or self.max_components < 1):
+            raise ValueError("BoundaryBuffers: max_components (>= 1) goes with metric='euclidean' and torch.int32")
         nbytes = ops.seg_boundary_workspace(*self.shape, 1 if dtype == torch.uint8 else 4)
         if nbytes == 0:
             raise ValueError(f"seg_boundary refuses these sizes: {self.shape}")
         dev = torch.device(device)
-        self.dist = torch.empty(self.shape, dtype=torch.uint8, device=dev)
+        self.dist = torch.empty(self.shape, dtype=torch.uint16 if metric == "euclidean" else torch.uint8, device=dev)
         self.device = self.dist.device
         self.band = torch.empty(self.shape, dtype=dtype, device=dev)
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.peaks = None
+        if self.max_components is not None:
+            self.peaks = torch.empty(self.shape[0], self.max_components, dtype=torch.int64, device=dev)
 
 
-def _bands_one(m, d, ratio, dmax, buffers):
+def _bands_one(m, d, ratio, dmax, buffers, metric="chessboard"):
+    if metric not in _BOUNDARY_METRICS:
+        raise ValueError(f"boundary_bands: metric must be one of {_BOUNDARY_METRICS}, got {metric!r}")
     squeeze = m.dim() == 2
     m, = _lift(squeeze, m)
     if m.dim() != 3 or m.dtype not in (torch.uint8, torch.int32) or not m.is_cuda:
@@ -978,15 +996,20 @@ def _bands_one(m, d, ratio, dmax, buffers):
     if d < 1 or dmax < d:
         raise ValueError(f"boundary_bands: the width must lie in 1..dmax, got d = {d}, dmax = {dmax}")
     if buffers is None:
-        buffers = BoundaryBuffers(B, H, W, dmax, m.dtype, m.device)
+        buffers = BoundaryBuffers(B, H, W, dmax, m.dtype, m.device, metric)
     elif buffers.shape != (B, H, W) or buffers.device != m.device or buffers.dtype != m.dtype:
         raise ValueError(f"buffers were made for {buffers.shape} of {buffers.dtype} on {buffers.device}, the map is "
                          f"{(B, H, W)} of {m.dtype} on {m.device}")
-    ops.seg_boundary(m.contiguous(), buffers.dist, buffers.ws, dmax, band=buffers.band, d=d)
-    return _unlift(squeeze, dict(dist=buffers.dist, band=buffers.band, d=d, dmax=dmax))
+    elif buffers.metric != metric:
+        raise ValueError(f"buffers were made for the {buffers.metric} metric, the call asks for {metric}")
+    if metric == "chessboard":
+        ops.seg_boundary(m.contiguous(), buffers.dist, buffers.ws, dmax, band=buffers.band, d=d)
+        return _unlift(squeeze, dict(dist=buffers.dist, band=buffers.band, d=d, dmax=dmax))
+    ops.seg_boundary(m.contiguous(), buffers.dist, buffers.ws, dmax, band=buffers.band, d=d, metric=metric)
+    return _unlift(squeeze, dict(dist2=buffers.dist, band=buffers.band, d=d, dmax=dmax, metric=metric))
 
 
-def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None):
+def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None, metric="chessboard"):
     """Distance to the contour and the boundary band of a label map or an id map.  m: a uint8 or int32 device tensor [H, W]
     or [B, H, W] (0 = background; every other value, 255 and negative ints included, is an object value, compared for
     equality only), or a LIST of [h_i, w_i] maps.  d: the band's width in pixels, by default metrics.boundary_width(H, W,
@@ -999,28 +1022,38 @@ def boundary_bands(m, d=None, ratio=0.02, dmax=None, buffers=None):
     one value exactly mask - eroded of the published mask_to_boundary.  A [H, W] input gives the same without the batch
     axis.  A list is handled with ONE CALL PER ITEM, d comes from each item's own size, and every value of the result is a
     list; buffers is then a list of BoundaryBuffers or None.  buffers: a BoundaryBuffers of this shape and dtype, reused
-    call after call (the result aliases it).  Two launches per call and no host synchronisation."""
+    call after call (the result aliases it).  Two launches per call and no host synchronisation.
+
+    metric="euclidean" measures the true distance: the result is dict(dist2, band, d, dmax, metric) with dist2 uint16, 0 on
+    background, else min(D2, (dmax + 1)^2), D2 the smallest dy^2 + dx^2 to a position outside the image or of another value,
+    and band the value where 1 <= dist2 <= d^2 -- a 45-degree edge is sqrt(2) times farther away than the chessboard
+    distance says.  The buffers are then BoundaryBuffers(..., metric="euclidean")."""
     if isinstance(m, (list, tuple)):
         ds = d if isinstance(d, (list, tuple)) else [d] * len(m)
-        return _per_item(lambda i, di, b: _bands_one(m[i], di, ratio, dmax, b), len(m), (ds, buffers),
-                         "boundary_bands: one d / buffers entry per map", ("dist", "band", "d", "dmax"))
-    return _bands_one(m, d, ratio, dmax, buffers)
+        keys = ("dist", "band", "d", "dmax") if metric == "chessboard" else ("dist2", "band", "d", "dmax", "metric")
+        return _per_item(lambda i, di, b: _bands_one(m[i], di, ratio, dmax, b, metric), len(m), (ds, buffers),
+                         "boundary_bands: one d / buffers entry per map", keys)
+    return _bands_one(m, d, ratio, dmax, buffers, metric)
 
 
-def object_boundaries(o, d=None, ratio=0.02, dmax=None, buffers=None):
+def object_boundaries(o, d=None, ratio=0.02, dmax=None, buffers=None, metric="chessboard"):
     """boundary_bands of both maps of a label_objects result o: its (filtered) labels, whose band feeds boundary_counts,
     and its ids, whose band is an id map that match_objects takes (per-object Boundary IoU, see the module docstring).
     buffers: dict(labels=BoundaryBuffers of uint8, ids=BoundaryBuffers of int32) -- of lists of them for a list result --
-    or None.  Returns dict(labels, ids, d): two boundary_bands results and the width they share (a list for a list)."""
+    or None.  Returns dict(labels, ids, d): two boundary_bands results and the width they share (a list for a list).
+    metric: boundary_bands' -- with "euclidean" both results hold dist2 and name the metric."""
     buffers = buffers or {}
-    lab = boundary_bands(o["labels"], d, ratio, dmax, buffers.get("labels"))
-    ids = boundary_bands(o["ids"], lab["d"], ratio, dmax, buffers.get("ids"))
+    lab = boundary_bands(o["labels"], d, ratio, dmax, buffers.get("labels"), metric)
+    ids = boundary_bands(o["ids"], lab["d"], ratio, dmax, buffers.get("ids"), metric)
     return dict(labels=lab, ids=ids, d=lab["d"])
 
 
 def _bcounts_one(bp, bg, pred, gt, nlabels, d, counts):
     squeeze = pred.dim() == 2
-    pdist, gdist = bp["dist"], bg["dist"]
+    if ("dist2" in bp) != ("dist2" in bg):
+        raise ValueError("boundary_counts: both dist maps must be of one metric")
+    key = "dist2" if "dist2" in bp else "dist"
+    pdist, gdist = bp[key], bg[key]
     if squeeze:
         pred, gt, pdist, gdist = pred[None], (gt[None] if gt.dim() == 2 else gt), pdist[None], gdist[None]
     if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_cuda:
@@ -1054,6 +1087,8 @@ def boundary_counts(bp, bg, pred, gt, nlabels, d=None, counts=None):
     pixel beside an ignore region lies in the band -- the published method has no ignore label, and treating the unknown
     as "other" needs no second rule.
 
+    bp and bg may both be results of metric="euclidean": the band is then 1 <= dist2 <= d^2.
+
     Returns counts int64 [.., 2, nlabels + 1] = (intersections, unions) on the device, the layout of label_objects'
     counts: metrics.boundary_iou(counts) is Boundary IoU per class and its mean.  counts (optional): the buffer to write,
     reused call after call.  Two launches per call and no host synchronisation."""
@@ -1061,8 +1096,113 @@ def boundary_counts(bp, bg, pred, gt, nlabels, d=None, counts=None):
         k = len(pred)
         cs = counts if counts is not None else [None] * k
         ds = d if isinstance(d, (list, tuple)) else [d] * k
-        if not isinstance(gt, (list, tuple)) or len(gt) != k or len(bp["dist"]) != k or len(bg["dist"]) != k or len(cs) != k:
+        if not isinstance(gt, (list, tuple)) or len(gt) != k or len(bp["band"]) != k or len(bg["band"]) != k or len(cs) != k:
             raise ValueError("boundary_counts: one gt, one dist pair and one counts entry per predicted map")
         item = lambda r, i: {key: v[i] for key, v in r.items()}  # noqa: E731
         return [_bcounts_one(item(bp, i), item(bg, i), pred[i], gt[i], nlabels, ds[i], cs[i]) for i in range(k)]
     return _bcounts_one(bp, bg, pred, gt, nlabels, d, counts)
+
+
+# ------------------------------------------------------------------------------------------------ thickness and cores
+
+def _thickness_one(ids, n, cap, dmax, buffers):
+    squeeze = ids.dim() == 2
+    ids, n = _lift(squeeze, ids, n)
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
+        raise ValueError("object_thickness takes the int32 device ids [H, W] or [B, H, W] of a label_objects or fill_holes result")
+    B, H, W = ids.shape
+    if dmax is None:
+        dmax = _BOUNDARY_DMAX if buffers is None else buffers.dmax
+    dmax = int(dmax)
+    if not 1 <= dmax <= _BOUNDARY_DMAX:
+        raise ValueError(f"object_thickness: dmax must lie in 1..{_BOUNDARY_DMAX}, got {dmax}")
+    if buffers is None:
+        buffers = BoundaryBuffers(B, H, W, dmax, torch.int32, ids.device, "euclidean", cap)
+    elif (buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.dtype != torch.int32
+          or buffers.metric != "euclidean" or buffers.max_components != cap):
+        raise ValueError(f"object_thickness: the buffers must be BoundaryBuffers({B}, {H}, {W}, dmax, torch.int32, "
+                         f"metric='euclidean', max_components={cap}) on {ids.device}")
+    ops.seg_boundary(ids.contiguous(), buffers.dist, buffers.ws, dmax, metric="euclidean", peaks=buffers.peaks)
+    return _unlift(squeeze, dict(dist2=buffers.dist, peaks=buffers.peaks, n=n, dmax=dmax, shape=(H, W)))
+
+
+def object_thickness(o, dmax=None, buffers=None):
+    """How THICK every object is and where its MIDDLE lies: the largest inscribed circle of every object of a label_objects
+    or fill_holes result o, from the Euclidean distance of its ids to their own contour (ops.seg_boundary with
+    metric="euclidean" and peaks).  dmax: the largest radius told apart, 1..254, by default 254 (or the buffers'); the
+    column walk costs O(min(distance, dmax)) a pixel.  buffers: BoundaryBuffers(B, H, W, dmax, torch.int32,
+    metric="euclidean", max_components=rows of o's stats), reused call after call, or None; a list of them for a list
+    result, which is handled with one call per item.
+
+    Returns dict(dist2, peaks, n, dmax, shape), everything on the device:
+      dist2   uint16 [.., H, W]: 0 on background, else min(D2, (dmax + 1)^2), D2 the smallest dy^2 + dx^2 to a position
+              outside the image or of another id; (dmax + 1)^2 means "at least dmax + 1"
+      peaks   int64 [.., max_components]: row id - 1 = (r2 << 32) | (0xFFFFFFFF - (y * W + x)), r2 the largest dist2 of the
+              object -- the squared radius of its largest inscribed circle, a circle of radius sqrt(r2) around the centre of
+              pixel (y, x) that reaches no farther than the centre of the nearest foreign pixel -- and (y, x) the first
+              pixel in row-major order that has it: a label point that lies INSIDE the object, which a box centre or a
+              centroid need not.  0 for an id without a pixel
+      n       o's n, which thickness_to_host reads;  shape = (H, W)
+    Three launches per call and no host synchronisation."""
+    if not isinstance(o, dict) or "ids" not in o or "stats" not in o or "n" not in o:
+        raise ValueError("object_thickness takes a label_objects or fill_holes result")
+    ids, caps = _ids_caps(o, None, "object_thickness", "measure")
+    if isinstance(ids, (list, tuple)):
+        return _per_item(lambda i, b: _thickness_one(ids[i], o["n"][i], caps[i], dmax, b), len(ids), (buffers,),
+                         "object_thickness: one buffers entry per item", ("dist2", "peaks", "n", "dmax", "shape"))
+    return _thickness_one(ids, o["n"], caps, dmax, buffers)
+
+
+def thickness_to_host(t):
+    """object_thickness' result -> per image a list of (r2, (y, x), capped) over the objects in id order, with ONE
+    synchronising copy of n and peaks (per item for a list result): r2 the squared radius of the largest inscribed circle,
+    (y, x) its centre, capped True when r2 == (dmax + 1)^2, i.e. the radius is at least dmax + 1.  The list ends at the
+    result's object count or at the table's last row; an id without a pixel gives (0, None, False).  A [H, W] result
+    gives one image's list."""
+    if not isinstance(t, dict) or any(k not in t for k in ("peaks", "n", "dmax", "shape")):
+        raise ValueError("thickness_to_host takes an object_thickness result")
+    if isinstance(t["peaks"], (list, tuple)):
+        return [thickness_to_host({k: v[i] for k, v in t.items()}) for i in range(len(t["peaks"]))]
+    single = t["peaks"].dim() == 1
+    n, peaks = _lift(single, t["n"], t["peaks"])
+    if peaks.dim() != 2 or peaks.dtype != torch.int64 or n.shape[0] != peaks.shape[0]:
+        raise ValueError("thickness_to_host: peaks must be int64 [B, cap] and n must describe the same images")
+    W, full = int(t["shape"][1]), (int(t["dmax"]) + 1) ** 2
+    n, peaks = _to_host([n, peaks])                                   # the one copy
+    out = []
+    for b in range(peaks.shape[0]):
+        rows = []
+        for key in peaks[b, :min(int(n[b, 0]), peaks.shape[1])].tolist():
+            r2, pos = key >> 32, 0xFFFFFFFF - (key & 0xFFFFFFFF)
+            rows.append((r2, divmod(pos, W), r2 == full) if key else (0, None, False))
+        out.append(rows)
+    return out[0] if single else out
+
+
+def _cores_one(o, radius, kw):
+    t = object_thickness(o, dmax=max(radius, 1))
+    d2 = t["dist2"].view(torch.int16).to(torch.int32) & 0xFFFF       # uint16 as integers every torch op takes
+    labels = torch.where(d2 > radius * radius, o["labels"], torch.zeros_like(o["labels"]))
+    return label_objects(labels, **kw)
+
+
+def object_cores(o, radius, **label_objects_kwargs):
+    """How many SEPARATE things an object is: the cores of a label_objects or fill_holes result o, its pixels farther than
+    `radius` (an integer, 0..254) from their object's contour, labelled again -- two blobs that touch over a neck of up to
+    2 * radius pixels fall apart, slivers thinner than that vanish.  A composition with no kernel of its own:
+    object_thickness(o, dmax=radius), o's labels kept where dist2 > radius^2, then label_objects(those labels,
+    **label_objects_kwargs) -- gt, connectivity, min_area, max_components, nlabels.  Returns label_objects' result for
+    the cores (a dict of lists for a list result, one call per item)."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= _BOUNDARY_DMAX:
+        raise ValueError(f"object_cores: radius must be an integer in 0..{_BOUNDARY_DMAX}, got {radius!r}")
+    if "buffers" in label_objects_kwargs:
+        raise ValueError("object_cores allocates its own buffers")
+    if not isinstance(o, dict) or any(k not in o for k in ("ids", "labels", "stats", "n")):
+        raise ValueError("object_cores takes a label_objects or fill_holes result")
+    radius = int(radius)
+    if isinstance(o["ids"], (list, tuple)):
+        kw = label_objects_kwargs
+        gts = kw.get("gt") or [None] * len(o["ids"])
+        per = [_cores_one({k: v[i] for k, v in o.items()}, radius, dict(kw, gt=gts[i])) for i in range(len(o["ids"]))]
+        return {key: [p[key] for p in per] for key in per[0]}
+    return _cores_one(o, radius, label_objects_kwargs)

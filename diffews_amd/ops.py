@@ -1354,27 +1354,49 @@ def seg_boundary_block():
     return r.value, c.value, p.value
 
 
-def seg_boundary(map, dist, ws, dmax, band=None, d=None):
-    """Capped chessboard distance to the contour, on caller-owned buffers only (objects.BoundaryBuffers holds a set): map
+_BOUNDARY_METRICS = {"chessboard": 0, "euclidean": 1}
+
+
+def seg_boundary(map, dist, ws, dmax, band=None, d=None, metric="chessboard", peaks=None, cap=None):
+    """Capped distance to the contour, on caller-owned buffers only (objects.BoundaryBuffers holds a set).  The default
+    metric, "chessboard", is described first; metric="euclidean" (below) writes SQUARED Euclidean distances.  map
     uint8 or int32 [B, H, W], values compared for equality only, 0 = background, every other value (255, values above 255
     and negative ints included) an object value.  Writes dist uint8 [B, H, W]: 0 where map == 0, else min(D, dmax + 1), D
     the smallest max(|dy|, |dx|) to a position outside the image or of another value (1 on the image's edge and next to
     another value); 1 <= dmax <= 254 and dmax + 1 means "deeper than dmax".  band (optional, map's dtype) receives the value
     where 1 <= dist <= d and 0 elsewhere, 1 <= d <= dmax, from the same launch.  ws: a uint8 buffer of at least
     seg_boundary_workspace(B, H, W, map.element_size()) bytes, which needs no initialisation.  Two launches, no host
-    synchronisation, no memset node, no atomics: the call can be captured.  Returns None."""
+    synchronisation, no memset node, no atomics: the call can be captured.  Returns None.
+
+    metric="euclidean": dist is uint16 [B, H, W] and receives 0 where map == 0, else min(D2, (dmax + 1)^2), D2 the smallest
+    dy^2 + dx^2 to a position outside the image or of another value; (dmax + 1)^2 means "at least dmax + 1 away".  band
+    receives the value where 1 <= dist <= d^2.  The workspace is the same.  peaks (optional, int64 [B, cap], int32 id maps
+    only; cap defaults to its second size): row k - 1 receives the maximum over the pixels (y, x) of id k of (dist << 32) |
+    (0xFFFFFFFF - (y * W + x)) -- the squared radius of the object's largest inscribed circle and, among equals, its first
+    centre -- and 0 when id k has no pixel; ids outside 1..cap are not counted.  Two launches, three with peaks (a library
+    kernel zeroes the table, the column pass reduces it with integer atomic maxima: order-free)."""
     if map.dim() != 3 or map.dtype not in (torch.uint8, torch.int32) or not map.is_contiguous() or not map.is_cuda:
         raise ValueError("seg_boundary: map must be a contiguous uint8 or int32 device tensor [B, H, W]")
+    if metric not in _BOUNDARY_METRICS:
+        raise ValueError(f"seg_boundary: metric must be one of {sorted(_BOUNDARY_METRICS)}, got {metric!r}")
     B, H, W = map.shape
     dev = map.device
     own = _owner("seg_boundary", dev)
     a = L.SegBoundaryArgs()
-    a.map, a.dist = map.data_ptr(), own("dist", dist, torch.uint8, (B, H, W))
+    a.metric = _BOUNDARY_METRICS[metric]
+    a.map, a.dist = map.data_ptr(), own("dist", dist, torch.uint16 if a.metric else torch.uint8, (B, H, W))
     a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
     if (band is None) != (d is None):
         raise ValueError("seg_boundary: band and d go together")
     if band is not None:
         a.band, a.d = own("band", band, map.dtype, (B, H, W)), int(d)
+    if peaks is not None:
+        if not a.metric or map.dtype != torch.int32 or peaks.dim() != 2:
+            raise ValueError("seg_boundary: peaks (int64 [B, cap]) go with metric='euclidean' and an int32 id map")
+        a.cap = peaks.shape[1] if cap is None else int(cap)
+        a.peaks = own("peaks", peaks, torch.int64, (B, a.cap))
+    elif cap is not None:
+        raise ValueError("seg_boundary: cap goes with peaks")
     a.elem, a.B, a.H, a.W, a.dmax = map.element_size(), B, H, W, int(dmax)
     L.check(L.lib().dfw_seg_boundary(C.byref(a), _stream()), "dfw_seg_boundary")
 
@@ -1386,7 +1408,10 @@ def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
     predicted[l]++ when l <= nlabels, truth[g]++, intersection[l]++ when l == g.  Writes counts int64 [B, 2, nlabels + 1] =
     (intersections, unions), seg_labels' layout: metrics.boundary_iou(counts) is Boundary IoU per class.  nlabels is the
     buffer's shape.  gdist is the distance of gt as given, so a class pixel beside a 255 region lies in the band.  Two
-    launches, no host synchronisation, no memset node: the call can be captured.  Returns None."""
+    launches, no host synchronisation, no memset node: the call can be captured.  Returns None.
+
+    pdist and gdist may both be the uint16 squared maps of seg_boundary(metric="euclidean"); a pixel then lies in the band
+    when 1 <= dist <= d * d."""
     if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_contiguous() or not pred.is_cuda:
         raise ValueError("seg_boundary_counts: pred must be a contiguous uint8 device tensor [B, H, W]")
     B, H, W = pred.shape
@@ -1395,8 +1420,10 @@ def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
         raise ValueError("seg_boundary_counts: counts must be int64 [B, 2, nlabels + 1]")
     own = _owner("seg_boundary_counts", dev)
     a = L.SegBoundaryCountsArgs()
-    a.pred, a.pdist = pred.data_ptr(), own("pdist", pdist, torch.uint8, (B, H, W))
-    a.gt, a.gdist = own("gt", gt, torch.uint8, (B, H, W)), own("gdist", gdist, torch.uint8, (B, H, W))
+    kind = torch.uint16 if pdist.dtype == torch.uint16 else torch.uint8      # both maps are of pdist's kind
+    a.pred, a.pdist = pred.data_ptr(), own("pdist", pdist, kind, (B, H, W))
+    a.gt, a.gdist = own("gt", gt, torch.uint8, (B, H, W)), own("gdist", gdist, kind, (B, H, W))
     a.counts = own("counts", counts, torch.int64, (B, 2, counts.shape[2]))
     a.B, a.H, a.W, a.d, a.nlabels = B, H, W, int(d), counts.shape[2] - 1
+    a.dist_elem = 2 if kind == torch.uint16 else 0
     L.check(L.lib().dfw_seg_boundary_counts(C.byref(a), _stream()), "dfw_seg_boundary_counts")

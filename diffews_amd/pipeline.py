@@ -1085,10 +1085,22 @@ class MarigoldPipelineRGBLatentNoise:
         return fill_holes(o, **kw)
 
     def object_boundaries(self, o, **kw):
-        """The boundary bands of pipe.objects' result: objects.object_boundaries(o, **kw) -- d, ratio, dmax, buffers.
-        Returns dict(labels, ids, d); the band of the ids goes to pipe.match_objects for per-object Boundary IoU."""
+        """The boundary bands of pipe.objects' result: objects.object_boundaries(o, **kw) -- d, ratio, dmax, buffers,
+        metric.  Returns dict(labels, ids, d); the band of the ids goes to pipe.match_objects for per-object Boundary IoU."""
         from .objects import object_boundaries
         return object_boundaries(o, **kw)
+
+    def object_thickness(self, o, **kw):
+        """The largest inscribed circle of every object of pipe.objects' (or pipe.fill_holes') result:
+        objects.object_thickness(o, **kw) -- dmax, buffers.  Returns dict(dist2, peaks, n, dmax, shape) on the device;
+        objects.thickness_to_host brings radius and centre of every object to the host."""
+        from .objects import object_thickness
+        return object_thickness(o, **kw)
+
+    def object_cores(self, o, radius, **kw):
+        """The cores of the objects of pipe.objects' result, labelled again: objects.object_cores(o, radius, **kw)."""
+        from .objects import object_cores
+        return object_cores(o, radius, **kw)
 
     def boundary_counts(self, result, gt, nlabels, key="labels", **kw):
         """Boundary IoU counts of a route's label map against a ground truth: objects.boundary_bands on

@@ -1144,14 +1144,54 @@ int dfw_seg_scores_block(int32_t* pixels);
  * 4; dmax outside 1..254; d outside 1..dmax when band is given; B, H or W < 1.  DFW_ERANGE: H, W or B above 65535, H * W
  * above 2^30.  Then the workspace and the buffers, by the rule above: map and band are aligned to their element, dist
  * needs no alignment.
+ *
+ * The Euclidean metric and inscribed circles (version >= 124): metric, peaks and cap, appended to the struct.  With all
+ * three zero the call is the one above, launch for launch and byte for byte.  With metric = 1:
+ *
+ *   D2(q), for v = map[q] != 0, is the smallest (y - y')^2 + (x - x')^2 over the integer positions (y', x') that lie
+ *   outside the image or hold a value != v.
+ *   dist is uint16 [B][H][W] (2 * B * H * W bytes, aligned to 2): 0 where map[q] == 0, else min(D2(q), (dmax + 1)^2), at
+ *   most 255^2 = 65 025; the cap means "at least dmax + 1 away".
+ *   band holds map[q] where 1 <= dist[q] <= d^2 and 0 elsewhere.
+ *   peaks (optional; int32 id maps only) is int64 [B][cap]: row k - 1 = the maximum over the pixels q = (y, x) with map[q]
+ *   == k of (dist[q] << 32) | (0xFFFFFFFF - (y * W + x)) -- the largest squared distance of object k, i.e. the squared
+ *   radius of its largest inscribed circle, capped like dist, and among equals the smallest position, its centre -- and 0
+ *   when no pixel holds k.  Values outside 1..cap are not counted.
+ *
+ * map [[7,7,7],[7,7,7],[7,7,7]] with metric = 1, dmax = 2: dist [[1,1,1],[1,4,1],[1,1,1]]; as ids with cap = 7, row 6 of
+ * peaks is (4 << 32) | (0xFFFFFFFF - 4) and the other rows are 0.
+ *
+ * The two-pass form.  h(y, x), which the row pass writes to ws capped at dmax + 1, is the distance along the row to the
+ * nearest position that is outside the row or holds another value.  Then
+ *   D2(y, x) = min(min(y + 1, H - y)^2, min over dy of c(dy)),  c(0) = h(y, x)^2,
+ *   c(dy) = dy^2 + h(y + dy, x)^2 while map[y + dy][x] == v, and c(dy) = dy^2 at the first row where it differs;
+ * nothing beyond that row, or beyond dy^2 >= the best so far, can be smaller.  Sketch of the proof: every candidate is the
+ * squared distance to a real differing position, so the minimum is not below D2; and for a nearest differing position
+ * (y', x') either column x holds v from y to y', and then h(y', x) reaches a differing position of row y' no farther along
+ * than x', or the column differs earlier, at a row that is nearer.  Capping h changes no capped D2: a candidate with h >
+ * dmax + 1 is above (dmax + 1)^2 already.  The workspace is the same one byte a pixel; its query does not change.
+ *
+ * Launches: the row pass and a column pass of its own (the same tile and the same four-pixels-a-thread rule, dist aligned
+ * to four of its elements; every product stays below 2 * 255^2, the walk ends after at most dmax steps), two without
+ * peaks; with peaks a library kernel zeroes the table first (no memset node) and the column pass reduces it, three.  The
+ * reduction issues no atomic per pixel: a thread folds its pixels of equal id, a wave its lanes' maximal pieces of equal
+ * id, and one 64-bit atomic maximum goes out per piece unless the row already holds as much.  A maximum is order-free:
+ * the table depends on no order of execution and on no residency.
+ *
+ * Further refusals, each behind the existing ones of its kind: DFW_EINVAL for metric not 0 or 1, and for peaks with
+ * metric = 0, elem != 4 or cap < 1 (after d); DFW_ERANGE for B * cap above 2^31 - 1 with peaks (after the sizes, before
+ * the workspace).  peaks is an output of the buffer rule, aligned to 8; cap is not looked at without peaks.
  */
 typedef struct {
   const void* map;              /* [B][H][W] of uint8 or int32, contiguous, read only */
-  uint8_t* dist;                /* out [B][H][W] */
+  void* dist;                   /* out [B][H][W] of uint8, or of uint16 when metric = 1 */
   void* band;                   /* out [B][H][W] of map's type, or null */
   void* ws;
   size_t ws_bytes;
   int32_t elem, B, H, W, dmax, d;
+  int32_t metric;               /* 0 chessboard, 1 Euclidean (squared) */
+  void* peaks;                  /* out int64 [B][cap], or null; metric = 1 and elem = 4 only */
+  int32_t cap;
 } dfw_seg_boundary_args;
 int dfw_seg_boundary(const dfw_seg_boundary_args* a, dfw_stream_t stream);
 /* 0 for sizes dfw_seg_boundary refuses (B, H or W < 1 or above 65535, H * W above 2^30, elem not 1 or 4) */
@@ -1169,14 +1209,19 @@ int dfw_seg_boundary_block(int32_t* rows, int32_t* cols, int32_t* positions);
  *
  * Validated in this order.  DFW_EINVAL: null args / pred / pdist / gt / gdist / counts; d outside 1..254; nlabels outside
  * 1..254; B, H or W < 1.  DFW_ERANGE: as dfw_seg_boundary.  Then the buffers, by the rule above; there is no workspace.
+ *
+ * dist_elem (version >= 124, appended): 0 and 1 mean uint8 dist maps as above, byte for byte; 2 means the uint16 squared
+ * maps of metric = 1, both of them, aligned to 2, with the band rule 1 <= dist <= d * d.  Any other value is DFW_EINVAL,
+ * behind nlabels.
  */
 typedef struct {
   const uint8_t* pred;          /* [B][H][W] label bytes, read only */
-  const uint8_t* pdist;         /* [B][H][W] dfw_seg_boundary's dist of pred */
+  const void* pdist;            /* [B][H][W] dfw_seg_boundary's dist of pred, uint8 or uint16 (dist_elem) */
   const uint8_t* gt;            /* [B][H][W] */
-  const uint8_t* gdist;         /* [B][H][W] dist of gt */
+  const void* gdist;            /* [B][H][W] dist of gt, of the same kind */
   int64_t* counts;              /* out [B][2][nlabels + 1] */
   int32_t B, H, W, d, nlabels;
+  int32_t dist_elem;            /* 0 | 1: uint8 distances; 2: uint16 squared distances */
 } dfw_seg_boundary_counts_args;
 int dfw_seg_boundary_counts(const dfw_seg_boundary_counts_args* a, dfw_stream_t stream);
 
