@@ -3,6 +3,15 @@
 Every function launches hand-written gfx950 kernels from libdiffews_hip.so on
 `torch.cuda.current_stream()`; nothing here computes with PyTorch.  Activations are NHWC
 (`[B, H, W, C]` or `[rows, C]`) in the engine storage dtype (bf16 or fp16).
+
+The library checks scalars and the extents it is told; what it cannot know -- a tensor's dtype, layout, extent and
+device -- is refused here, by one checker (`_Args`, shared with ops_bwd.py) and never by `assert`, so `python -O` changes
+nothing.  Every tensor whose address reaches the library goes through it: dtype, layout (contiguous, or a unit last
+stride where a wrapper takes row-strided views) and extent (the last element the kernel addresses through the pointer
+lies inside the tensor).  A refusal is ValueError("<wrapper>: <argument> ..."); only _dt, _f32 and _rowbias keep their
+TypeError.  The device rule comes last, after every shape and dtype refusal and before the stream is asked for: all
+tensors of a call lie on ONE cuda device (workspaces are allocated there), the documented host mirrors (tab_host,
+table_host, planes_host) on the host.  Whether that device is the current one is not checked.
 """
 import ctypes as C
 import os
@@ -36,13 +45,72 @@ def _f32(t, name):
     return t
 
 
-def _rowbias(a, rb):
+class _Args:
+    """The argument checker of one wrapper call: `arg = _Args("wrapper")`, then arg(name, t, ...) per tensor,
+    arg.need(condition, message) per relation between scalars and arg.device() last.  Every refusal is
+    ValueError(f"{wrapper}: {name} ...").  Nothing here allocates."""
+    __slots__ = ("fn", "dev", "first", "off")
+
+    def __init__(self, fn):
+        self.fn, self.dev, self.first, self.off = fn, None, None, None
+
+    def need(self, ok, message, *values):
+        """message.format(*values) is the refusal: formatted only when it is raised (sizes print as tuples)."""
+        if not ok:
+            raise ValueError(f"{self.fn}: " + message.format(*(tuple(v) if isinstance(v, torch.Size) else v for v in values)))
+
+    def __call__(self, name, t, dtype=None, shape=None, dim=None, dense=True, elems=None, extent=None, host=False):
+        """t's address, unless t is refused: `dtype` is one dtype, a tuple of them or None (the storage dtypes, left to
+        _dt); `shape` the exact shape, `dim` the number of dimensions, `elems` the number of elements; dense=False takes
+        any view with a unit last stride instead of a contiguous tensor; `extent` is the number of elements the kernel
+        addresses from t's first one, which t must span.  host=True: a host mirror.  The device is only noted here."""
+        ok = (dtype is None or t.dtype == dtype or (type(dtype) is tuple and t.dtype in dtype)) \
+            and (shape is None or t.shape == shape) and (dim is None or t.dim() == dim) \
+            and (elems is None or t.numel() == elems) and (t.is_contiguous() if dense else t.dim() > 0 and t.stride(-1) == 1)
+        if ok and extent is not None:
+            ok = extent <= (t.numel() if dense else _span(t))
+        if not ok:
+            kinds = " or ".join(str(d) for d in (dtype if type(dtype) is tuple else (dtype or "bfloat16 / float16",)))
+            want = (("shape", shape and tuple(shape)), ("dimensions", dim), ("elements", elems), ("extent", extent))
+            raise ValueError(f"{self.fn}: {name} must be a {'contiguous' if dense else 'unit-last-stride'} {kinds} tensor"
+                             + "".join(f", {k} {v}" for k, v in want if v is not None)
+                             + f"; got {t.dtype} {tuple(t.shape)} with strides {t.stride()}")
+        d = t.device
+        if host:
+            if d.type != "cpu" and self.off is None:
+                self.off = f"the host mirror {name} lies on {d}"
+        elif self.dev is None:
+            self.dev, self.first = d, name
+        elif d != self.dev and self.off is None:
+            self.off = f"{name} lies on {d}, {self.first} on {self.dev}"
+        return t.data_ptr()
+
+    def f32(self, name, t, n):
+        """An optional fp32 vector of at least n elements (_f32 and its TypeError first): its address, None for None."""
+        return None if t is None else self(name, _f32(t, name), torch.float32, extent=n)
+
+    def device(self):
+        """The last refusal of a wrapper: the device rule of the module docstring."""
+        if self.off is None and self.dev is not None and self.dev.type != "cuda":
+            self.off = f"{self.first} lies on {self.dev}"
+        if self.off is not None:
+            raise ValueError(f"{self.fn}: all tensors must be device tensors on one cuda device, host mirrors on the host; "
+                             + self.off)
+
+
+def _span(t):
+    """Elements from t's first to its last one, in memory: what a kernel may address through t's pointer."""
+    return 1 + sum((n - 1) * s for n, s in zip(t.shape, t.stride())) if t.numel() else 0
+
+
+def _rowbias(arg, a, rb, imgs, N):
     """rowbias [imgs, N] fp32, rows may be strided (a column slice of a wider buffer)."""
     if rb is None:
         return
     if rb.dtype != torch.float32 or rb.dim() != 2 or rb.stride(1) != 1:
         raise TypeError("rowbias must be float32 [imgs, N] with unit column stride")
-    a.rowbias, a.ld_rowbias = rb.data_ptr(), rb.stride(0)
+    arg.need(rb.shape[0] >= imgs and rb.shape[1] == N, "rowbias must be [{}, {}], got {}", imgs, N, rb.shape)
+    a.rowbias, a.ld_rowbias = arg("rowbias", rb, torch.float32, dense=False), rb.stride(0)
 
 
 # Optional per-launch timing hook (bench.py roofline leg): when set, every GEMM launch is bracketed
@@ -50,21 +118,21 @@ def _rowbias(a, rb):
 gemm_hook = None
 
 
-def _gemm_call(a):
+def _gemm_call(a, device):
     lib = L.lib()
     if gemm_hook is not None:
         buf = C.create_string_buffer(64)
         L.check(lib.dfw_gemm_kernel_name(C.byref(a), buf, 64), "dfw_gemm_kernel_name")
         _timed(buf.value.decode(), 2.0 * a.M * a.N * a.K * max(1, a.batch),
-               (a.M, a.N, a.K, a.taps, a.stride, a.ups, a.splitk, max(1, a.batch)), lambda: _gemm_launch(lib, a))
+               (a.M, a.N, a.K, a.taps, a.stride, a.ups, a.splitk, max(1, a.batch)), lambda: _gemm_launch(lib, a, device))
         return
-    _gemm_launch(lib, a)
+    _gemm_launch(lib, a, device)
 
 
-def _gemm_launch(lib, a):
+def _gemm_launch(lib, a, device):
     nbytes = lib.dfw_gemm_workspace_bytes(C.byref(a))   # 0 unless the plan uses split-K
     if nbytes:
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device="cuda")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     L.check(lib.dfw_gemm(C.byref(a), _stream()), "dfw_gemm")
     return
@@ -74,21 +142,21 @@ def linear(x, w, bias=None, residual=None, rowbias=None, rows_per_img=0, act=L.A
            out=None, out_f32=False, out_scale=1.0, splitk=None, colscale=None):
     """y[M, N] = epi(x[M, K] @ w[N, K]^T).  x may be a row-strided view ([M, K] with stride (ld, 1)).
     colscale = (n, s): output columns < n (a multiple of 64) are multiplied by s in fp32 before rounding."""
-    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.is_contiguous()
+    arg = _Args("linear")
+    arg("x", x, dim=2, dense=False)
     M, K = x.shape
+    arg("w", w, x.dtype, dim=2)
     N = w.shape[0]
-    assert w.shape[1] == K and w.dtype == x.dtype
+    arg.need(w.shape[1] == K, "w must be [N, {}] for x {}, got {}", K, x.shape, w.shape)
     n_out = N // 2 if geglu else N
     if out is None:
         out = torch.empty(M, n_out, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    assert out.stride(1) == 1 and out.shape == (M, n_out)
     a = L.GemmArgs()
-    a.A, a.W, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    a.bias = _p(_f32(bias, "bias"))
-    _rowbias(a, rowbias)
+    a.A, a.W, a.C = x.data_ptr(), w.data_ptr(), arg("out", out, (x.dtype, torch.float32), (M, n_out), dense=False)
+    a.bias = arg.f32("bias", bias, N)
+    _rowbias(arg, a, rowbias, -(-M // rows_per_img) if rows_per_img else 1, N)
     if residual is not None:
-        assert residual.dtype in (x.dtype, torch.float32) and residual.stride(1) == 1 and residual.shape == (M, N)
-        a.residual, a.ldr = residual.data_ptr(), residual.stride(0)
+        a.residual, a.ldr = arg("residual", residual, (x.dtype, torch.float32), (M, N), dense=False), residual.stride(0)
         a.residual_f32 = int(residual.dtype == torch.float32)   # the fp32 residual stream
     a.a_elems = (M - 1) * x.stride(0) + K
     a.w_elems = w.numel()
@@ -101,15 +169,19 @@ def linear(x, w, bias=None, residual=None, rowbias=None, rows_per_img=0, act=L.A
     a.batch, a.dtype = 1, _dt(x)
     if colscale is not None:
         a.colscale_n, a.colscale = int(colscale[0]), float(colscale[1])
-    _gemm_call(a)
+    arg.device()
+    _gemm_call(a, x.device)
     return out
 
 
 def bmm_nt(x, w, out_f32=False, out_scale=1.0):
     """Batched y[b] = x[b] @ w[b]^T for contiguous x [Bt, M, K], w [Bt, N, K]."""
-    assert x.dim() == 3 and w.dim() == 3 and x.is_contiguous() and w.is_contiguous()
+    arg = _Args("bmm_nt")
+    arg("x", x, dim=3)
     Bt, M, K = x.shape
+    arg("w", w, x.dtype, dim=3)
     N = w.shape[1]
+    arg.need(w.shape[0] == Bt and w.shape[2] == K, "w must be [{}, N, {}], got {}", Bt, K, w.shape)
     out = torch.empty(Bt, M, N, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
     a = L.GemmArgs()
     a.A, a.W, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
@@ -121,7 +193,8 @@ def bmm_nt(x, w, out_f32=False, out_scale=1.0):
     a.splitk, a.batch = 1, Bt
     a.strideA, a.strideW, a.strideC = M * K, N * K, M * N
     a.dtype = _dt(x)
-    _gemm_call(a)
+    arg.device()
+    _gemm_call(a, x.device)
     return out
 
 
@@ -138,13 +211,14 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
     built in rounds 1-3, never beat pass + conv, and is gone: DESIGN.md section 3).
     out_f32: NHWC fp32 output, and `residual` may be fp32 -- the fp32 residual stream (x + branch summed and stored
     in fp32; the conv's operands stay 16-bit)."""
-    assert x.dim() == 4 and x.stride(3) == 1 and x.is_contiguous()
+    arg = _Args("conv3x3")
+    arg("x", x, dim=4)
     B, Hi, Wi, Cin = x.shape
     if gn_in is not None:
         x = groupnorm(x, *gn_in, out_dtype=w.dtype)
-    assert w.shape == (cout, 9 * Cin) and w.dtype == x.dtype and w.is_contiguous()
+    arg("w", w, x.dtype, (cout, 9 * Cin))
     if ups:
-        assert stride == 1 and pad == 1
+        arg.need(stride == 1 and pad == 1, "ups goes with stride 1 and pad 1, got stride {} and pad {}", stride, pad)
         Ho, Wo = 2 * Hi, 2 * Wi
     elif stride == 1:
         Ho, Wo = Hi, Wi
@@ -158,13 +232,12 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
     a = L.GemmArgs()
     a.A, a.W, a.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
     if w_blk is not None:
-        assert w_blk.dtype == w.dtype and w_blk.numel() == w.numel() and w_blk.is_contiguous() and Cin % 32 == 0
-        a.W_blocked = w_blk.data_ptr()
-    a.bias = _p(_f32(bias, "bias"))
-    _rowbias(a, rowbias)
+        arg.need(Cin % 32 == 0, "w_blk needs Cin a multiple of 32, got {}", Cin)
+        a.W_blocked = arg("w_blk", w_blk, w.dtype, elems=w.numel())
+    a.bias = arg.f32("bias", bias, cout)
+    _rowbias(arg, a, rowbias, B, cout)
     if residual is not None:
-        assert residual.dtype in (x.dtype, torch.float32) and residual.is_contiguous() and residual.numel() == M * cout
-        a.residual, a.ldr = residual.data_ptr(), cout
+        a.residual, a.ldr = arg("residual", residual, (x.dtype, torch.float32), elems=M * cout), cout
         a.residual_f32 = int(residual.dtype == torch.float32)
     a.a_elems, a.w_elems = x.numel(), w.numel()
     a.M, a.N, a.K, a.lda, a.ldc = M, cout, 9 * Cin, Cin, cout
@@ -176,6 +249,7 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
     a.splitk = 0 if splitk is None else splitk
     a.batch, a.dtype = 1, _dt(x)
     stats = None
+    arg.device()
     if gn_groups and not out_nchw_f32:
         # fused GroupNorm statistics of the output, when the planned kernel supports them
         a.gn_groups = gn_groups
@@ -184,7 +258,7 @@ def conv3x3(x, w, cout, bias=None, stride=1, pad=1, ups=False, rowbias=None, res
             part = torch.empty(B, chunks, gn_groups, 2, dtype=torch.float32, device=x.device)
             a.gn_partial = part.data_ptr()
             stats = (part, chunks, gn_groups)
-    _gemm_call(a)
+    _gemm_call(a, x.device)
     if stats is not None:
         out._gn_stats = stats   # consumed by groupnorm(out, ...) -- valid while `out` is not modified
     return out
@@ -199,14 +273,19 @@ def _timed(name, flops, shape, call):
     gemm_hook(name, flops, e0, e1, shape)
 
 
-def _fsa_args(q, k, v, out, heads):
+def _fsa_args(arg, q, k, v, out, heads):
     """(FsaArgs with the q / k / v / out fields and the dtype filled, out): q / k / v [B, N, heads*64] views with unit
     channel stride, `out` [B, N, heads*64] with dense rows, allocated when None."""
+    arg("q", q, dim=3, dense=False)
     B, N, Cq = q.shape
-    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    arg.need(Cq == heads * 64, "q must be [B, N, {}] for {} heads, got {}", heads * 64, heads, q.shape)
+    arg("k", k, q.dtype, dim=3, dense=False)
+    arg.need(k.shape[0] == B and k.shape[2] == Cq, "k must be [{}, keys, {}], got {}", B, Cq, k.shape)
+    arg("v", v, q.dtype, k.shape, dense=False)
     if out is None:
         out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
-    assert out.shape == (B, N, Cq) and out.stride(2) == 1 and out.stride(1) == Cq
+    arg("out", out, q.dtype, (B, N, Cq), dense=False)
+    arg.need(out.stride(1) == Cq, "out must have dense rows (stride {}), got strides {}", Cq, out.stride())
     a = L.FsaArgs()
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     a.batch, a.heads, a.n_q, a.n_kv = B, heads, N, k.shape[1]
@@ -216,10 +295,14 @@ def _fsa_args(q, k, v, out, heads):
     return a, out
 
 
-def _fsa_bank(a, k_bank, v_bank, nshot):
-    """The bank fields of an FsaArgs from _fsa_args: k_bank / v_bank [images, Nb, heads*64] views in q's dtype."""
-    assert k_bank.stride(2) == 1 and v_bank.stride(2) == 1
-    assert _DT.get(k_bank.dtype) == a.dtype and v_bank.shape == k_bank.shape
+def _fsa_bank(arg, a, q, k_bank, v_bank, nshot, images, count):
+    """The bank fields of an FsaArgs from _fsa_args: k_bank / v_bank [images, Nb, heads*64] views in q's dtype, `images`
+    of them (None: any number), which `count` words in the refusal."""
+    arg.need(k_bank is not None and v_bank is not None, "a bank launch (nshot > 0) needs k_bank and v_bank")
+    arg("k_bank", k_bank, q.dtype, dim=3, dense=False)
+    arg.need(k_bank.shape[2] == q.shape[2], "k_bank must be [images, Nb, {}], got {}", q.shape[2], k_bank.shape)
+    arg.need(images is None or k_bank.shape[0] == images, "k_bank must hold {} images ({}), got {}", images, count, k_bank.shape[0])
+    arg("v_bank", v_bank, q.dtype, k_bank.shape, dense=False)
     a.k_bank, a.v_bank = k_bank.data_ptr(), v_bank.data_ptr()
     a.n_bank, a.nshot = k_bank.shape[1], nshot
     a.ldkb, a.ldvb, a.kb_bs, a.vb_bs = k_bank.stride(1), v_bank.stride(1), k_bank.stride(0), v_bank.stride(0)
@@ -248,27 +331,32 @@ def fsa_attention(q, k, v, heads, k_bank=None, v_bank=None, nshot=0, scale=None,
     bank_shared: k_bank/v_bank hold ONE support set, [nshot, Nb, heads*64], and every batch entry attends over
     [own ; that set] (a prepared SupportBank read by a batch of queries) -- same kernel, same key order as the bank
     repeated B times."""
+    arg = _Args("fsa_attention")
+    a, out = _fsa_args(arg, q, k, v, out, heads)
     B, N = q.shape[:2]
-    a, out = _fsa_args(q, k, v, out, heads)
     if nshot:
+        arg.need(n_plain == 0 or not (bank_shared or _group), "a shared bank or a stack of sets takes no plain entries, got n_plain {}", n_plain)
+        arg.need(not (bank_shared and _group), "bank_shared does not go with a stack of sets")
+        arg.need(not _group or B % _group == 0, "the batch of {} is not a multiple of the group of {}", B, _group)
         if _shots is not None:      # fsa_attention_ragged: nshot is max(shots)
-            assert n_plain == 0 and not bank_shared and _group and B % _group == 0 and k_bank.shape[0] == sum(_shots)
+            arg.need(_group, "a shot count per set needs a group")
             shots_c = (C.c_int32 * len(_shots))(*_shots)
+            images, count = sum(_shots), "the sum of shots"
         elif _group:      # fsa_attention_sets
-            assert n_plain == 0 and not bank_shared and B % _group == 0 and k_bank.shape[0] == (B // _group) * nshot
+            images, count = (B // _group) * nshot, "nshot for each of the B // group sets"
         elif bank_shared:
-            assert n_plain == 0 and k_bank.shape[0] == nshot
+            images, count = nshot, "nshot, one shared set"
         else:
-            assert k_bank.shape[0] == (B - n_plain) * nshot
-        _fsa_bank(a, k_bank, v_bank, nshot)
+            images, count = (B - n_plain) * nshot, "nshot for each of the B - n_plain entries"
+        _fsa_bank(arg, a, q, k_bank, v_bank, nshot, images, count)
         a.bank_shared = int(bool(bank_shared))
     elif bank_shared:
         raise ValueError("bank_shared needs a bank (nshot > 0)")
     a.scale = scale if scale is not None else 64 ** -0.5
     a.n_plain, a.q_prescaled = n_plain, int(bool(q_prescaled))
     if lse is not None:   # training: per-row log2-sum-exp2 for the backward
-        assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, heads, N)
-        a.lse = lse.data_ptr()
+        a.lse = arg("lse", lse, torch.float32, (B, heads, N))
+    arg.device()
     if _shots is not None:
         call = lambda: _fsa_ragged_call(a, shots_c, len(_shots), _group)
         nbytes = L.lib().dfw_fsa_ragged_workspace_bytes(C.byref(a), shots_c, len(_shots), _group) if key_split else 0
@@ -338,18 +426,16 @@ def fsa_attention_routed(q, k, v, heads, k_bank, v_bank, table, table_host, max_
     [min_shots, max_shots], every set inside the stack).  The launch plan and workspace depend on the shapes, max_shots
     and min_shots only; the key split never exceeds 1 + min_shots.  Per entry the kernel arithmetic, key order and tile
     sequence of fsa_attention on that set's slice with bank_shared=True."""
+    arg = _Args("fsa_attention_routed")
+    a, out = _fsa_args(arg, q, k, v, out, heads)
     B = q.shape[0]
-    for name, t in (("table", table), ("table_host", table_host)):
-        if t.dtype != torch.int32 or tuple(t.shape) != (B, 2) or not t.is_contiguous():
-            raise ValueError(f"fsa_attention_routed: {name} must be a contiguous int32 [{B}, 2] tensor")
-    if not table.is_cuda or table.device != q.device or table_host.device.type != "cpu":
-        raise ValueError("fsa_attention_routed: table lives with q on the device, table_host on the host")
-    a, out = _fsa_args(q, k, v, out, heads)
-    _fsa_bank(a, k_bank, v_bank, int(max_shots))
+    host = C.cast(arg("table_host", table_host, torch.int32, (B, 2), host=True), C.POINTER(C.c_int32))
+    arg("table", table, torch.int32, (B, 2))
+    _fsa_bank(arg, a, q, k_bank, v_bank, int(max_shots), None, None)
     a.scale, a.q_prescaled = 64 ** -0.5, int(bool(q_prescaled))
     nbank, min_shots = int(k_bank.shape[0]), int(min_shots)
+    arg.device()
     nbytes = L.lib().dfw_fsa_routed_workspace_bytes(C.byref(a), nbank, min_shots) if key_split else 0
-    host = C.cast(table_host.data_ptr(), C.POINTER(C.c_int32))
     _fsa_launch(a, q, nbytes, lambda: _fsa_routed_call(a, table.data_ptr(), host, nbank, min_shots),
                 lambda: B * k.shape[1] + int(table_host[:, 1].sum()) * k_bank.shape[1])
     return out
@@ -369,7 +455,10 @@ def zeros(shape, dtype, device="cuda"):
 
 def split_storage(x, dtype):
     """fp32 x -> (hi, lo) in `dtype` with hi + lo = x to ~2^-22 relative (fp16): see linear_stream / conv3x3_stream."""
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 8 == 0
+    arg = _Args("split_storage")
+    arg("x", x, torch.float32)
+    arg.need(x.numel() % 8 == 0, "x must hold a multiple of 8 elements, got {}", x.numel())
+    arg.device()
     hi = torch.empty(x.shape, dtype=dtype, device=x.device)
     lo = torch.empty(x.shape, dtype=dtype, device=x.device)
     L.check(L.lib().dfw_split_f32(x.data_ptr(), hi.data_ptr(), lo.data_ptr(), x.numel(), _DT[dtype], _stream()), "dfw_split_f32")
@@ -419,16 +508,18 @@ def conv3x3_up2x(x, w_folded, cout, bias=None, gn_groups=0):
     w_folded [Cout, 16*Cin] from packing.fold_up2x.  Returns [B, 2Hi, 2Wi, Cout] with `_gn_stats` attached as conv3x3 does,
     or None when the library declines the shape (its name query answers DFW_ESHAPE): the caller then runs
     conv3x3(..., ups=True) on the unfolded weights.  The hook sees the FLOPs executed, 2 M N 4 Cin."""
-    assert x.dim() == 4 and x.is_contiguous()
+    arg = _Args("conv3x3_up2x")
+    arg("x", x, dim=4)
     B, Hi, Wi, Cin = x.shape
-    assert w_folded.shape == (cout, 16 * Cin) and w_folded.dtype == x.dtype and w_folded.is_contiguous()
+    arg("w_folded", w_folded, x.dtype, (cout, 16 * Cin))
     out = torch.empty(B, 2 * Hi, 2 * Wi, cout, dtype=x.dtype, device=x.device)
     a = L.ConvUp2xArgs()
     a.x, a.W, a.y = x.data_ptr(), w_folded.data_ptr(), out.data_ptr()
-    a.bias = _p(_f32(bias, "bias"))
+    a.bias = arg.f32("bias", bias, cout)
     a.x_elems, a.w_elems = x.numel(), w_folded.numel()
     a.B, a.Hi, a.Wi, a.Cin, a.Cout, a.ldx, a.ldy = B, Hi, Wi, Cin, cout, Cin, cout
     a.dtype = _dt(x)
+    arg.device()
     lib = L.lib()
     name = C.create_string_buffer(64)
     rc = lib.dfw_conv_up2x_kernel_name(C.byref(a), name, 64)
@@ -463,24 +554,35 @@ VATTN_QSCALE = 512 ** -0.5 * math.log2(math.e)   # the VAE mid-block attention's
 def vae_attention(q, k, v, out=None):
     """Flash attention of the VAE mid-block: q / k / v [B, N, 512] views (column slices of one fused QKV buffer), ONE head of
     dim 512, q pre-multiplied by VATTN_QSCALE (linear(..., colscale=(512, VATTN_QSCALE))).  The N x N scores stay on chip."""
+    arg = _Args("vae_attention")
+    arg("q", q, dim=3, dense=False)
     B, N, D = q.shape
-    assert D == 512 and k.shape == q.shape and v.shape == q.shape and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    arg.need(D == 512, "q must be [B, N, 512], got {}", q.shape)
+    arg("k", k, q.dtype, q.shape, dense=False)
+    arg("v", v, q.dtype, q.shape, dense=False)
     if out is None:
         out = torch.empty(B, N, D, dtype=q.dtype, device=q.device)
+    arg("out", out, q.dtype, q.shape, dense=False)
     a = L.VattnArgs()
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     a.batch, a.n, a.head_dim, a.q_prescaled = B, N, D, 1
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(1), k.stride(1), v.stride(1), out.stride(1)
     a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     a.dtype = _dt(q)
+    arg.device()
     L.check(L.lib().dfw_vae_attention(C.byref(a), _stream()), "dfw_vae_attention")
     return out
 
 
 def cross_attention(q, k, v, heads, scale=None):
     """q [B, N, heads*64]; k/v [B, L, heads*64] views (short context)."""
+    arg = _Args("cross_attention")
+    arg("q", q, dim=3, dense=False)
     B, N, Cq = q.shape
-    assert Cq == heads * 64 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    arg.need(Cq == heads * 64, "q must be [B, N, {}] for {} heads, got {}", heads * 64, heads, q.shape)
+    arg("k", k, q.dtype, dim=3, dense=False)
+    arg.need(k.shape[0] == B and k.shape[2] == Cq, "k must be [{}, L, {}], got {}", B, Cq, k.shape)
+    arg("v", v, q.dtype, k.shape, dense=False)
     out = torch.empty(B, N, Cq, dtype=q.dtype, device=q.device)
     a = L.XattnArgs()
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
@@ -489,6 +591,7 @@ def cross_attention(q, k, v, heads, scale=None):
     a.q_bs, a.k_bs, a.v_bs, a.o_bs = q.stride(0), k.stride(0), v.stride(0), N * Cq
     a.scale = scale if scale is not None else 64 ** -0.5
     a.dtype = _dt(q)
+    arg.device()
     L.check(L.lib().dfw_cross_attention(C.byref(a), _stream()), "dfw_cross_attention")
     return out
 
@@ -497,7 +600,9 @@ def groupnorm(x, gamma, beta, groups, eps, silu=False, return_stats=False, out_d
     """GroupNorm (+SiLU) over NHWC x [B, H, W, C] (or [B, HW, C]).
     return_stats: also return the (mean, rstd) [B, groups, 2] fp32 the kernel normalised with (training).
     x may be fp32 (the fp32 residual stream): the output is then `out_dtype` (bf16 / fp16, required)."""
-    assert x.is_contiguous()
+    arg = _Args("groupnorm")
+    arg("x", x, (*_DT, torch.float32))
+    arg.need(x.dim() >= 2 and x.numel() > 0, "x must be [B, ..., C] and not empty, got {}", x.shape)
     xf32 = x.dtype == torch.float32
     if xf32 and out_dtype not in _DT:
         raise TypeError("groupnorm of an fp32 tensor needs out_dtype=torch.bfloat16 / torch.float16")
@@ -505,8 +610,10 @@ def groupnorm(x, gamma, beta, groups, eps, silu=False, return_stats=False, out_d
     B, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * Cc)
     a = L.GroupNormArgs()
+    a.gamma, a.beta = arg.f32("gamma", gamma, Cc), arg.f32("beta", beta, Cc)
+    arg.device()
     y = torch.empty(x.shape, dtype=odt, device=x.device)
-    a.x, a.y, a.gamma, a.beta = x.data_ptr(), y.data_ptr(), _p(_f32(gamma, "gamma")), _p(_f32(beta, "beta"))
+    a.x, a.y = x.data_ptr(), y.data_ptr()
     a.B, a.HW, a.C, a.groups, a.ldx, a.ldy = B, HW, Cc, groups, Cc, Cc
     a.eps, a.silu, a.dtype, a.x_f32 = eps, int(silu), _DT[odt], int(xf32)
     st = getattr(x, "_gn_stats", None)
@@ -526,14 +633,17 @@ def groupnorm(x, gamma, beta, groups, eps, silu=False, return_stats=False, out_d
 
 def layernorm(x, gamma, beta, eps=1e-5, out_dtype=None):
     """x may be fp32 (the fp32 residual stream inside a transformer block): the output is then `out_dtype`."""
-    assert x.dim() == 2 and x.stride(1) == 1
+    arg = _Args("layernorm")
+    arg("x", x, (*_DT, torch.float32), dim=2, dense=False)
     xf32 = x.dtype == torch.float32
     if xf32 and out_dtype not in _DT:
         raise TypeError("layernorm of an fp32 tensor needs out_dtype=torch.bfloat16 / torch.float16")
     odt = out_dtype if xf32 else x.dtype
-    y = torch.empty(x.shape, dtype=odt, device=x.device)
     a = L.LayerNormArgs()
-    a.x, a.y, a.gamma, a.beta = x.data_ptr(), y.data_ptr(), _p(_f32(gamma, "gamma")), _p(_f32(beta, "beta"))
+    a.gamma, a.beta = arg.f32("gamma", gamma, x.shape[1]), arg.f32("beta", beta, x.shape[1])
+    arg.device()
+    y = torch.empty(x.shape, dtype=odt, device=x.device)
+    a.x, a.y = x.data_ptr(), y.data_ptr()
     a.rows, a.C, a.ldx, a.ldy, a.eps, a.dtype = x.shape[0], x.shape[1], x.stride(0), y.stride(0), eps, _DT[odt]
     a.x_f32 = int(xf32)
     L.check(L.lib().dfw_layernorm(C.byref(a), _stream()), "dfw_layernorm")
@@ -551,13 +661,15 @@ def conv_small(x, w, bias, cout, taps, dtype, nchw_f32_out=False, in_scale=1.0, 
     tensor is fine: the batch stride travels as y_bstride).  gn_part: the matching [B, chunks, groups, 2]
     slice of a larger partial-sum buffer (several conv_small calls filling one batch)."""
     xs = list(x) if isinstance(x, (list, tuple)) else [x]
-    assert 1 <= len(xs) <= 3
-    for t in xs:
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and t.shape[1:] == xs[0].shape[1:]
+    arg = _Args("conv_small")
+    arg.need(1 <= len(xs) <= 3, "x is one tensor or a list of up to three, got {}", len(xs))
+    for i, t in enumerate(xs):
+        arg(f"x[{i}]", t, torch.float32, dim=4)
+        arg.need(t.shape[1:] == xs[0].shape[1:], "x[{}] must be shaped like x[0] {} behind the batch, got {}", i, xs[0].shape, t.shape)
     x = xs[0]
     _, Cin, H, W = x.shape
     B = sum(t.shape[0] for t in xs)
-    assert w.dtype == torch.float32 and w.is_contiguous() and w.numel() == cout * taps * Cin
+    arg("w", w, torch.float32, elems=cout * taps * Cin)
     a = L.ConvSmallArgs()
     if len(xs) > 1:
         a.x1, a.b0 = xs[1].data_ptr(), xs[0].shape[0]
@@ -566,25 +678,28 @@ def conv_small(x, w, bias, cout, taps, dtype, nchw_f32_out=False, in_scale=1.0, 
             a.x2 = xs[2].data_ptr()
     if nchw_f32_out:
         y = out if out is not None else torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-        assert y.shape == (B, cout, H, W) and y.dtype == torch.float32
-        assert y.stride(3) == 1 and y.stride(2) == W and y.stride(1) == H * W
+        arg("out", y, torch.float32, (B, cout, H, W), dense=False)
+        arg.need(y.stride(2) == W and y.stride(1) == H * W, "out must have contiguous channel planes, got strides {}", y.stride())
         a.y_bstride = y.stride(0) if B > 1 else cout * H * W
     else:   # NHWC: storage dtype, or fp32 (out_f32: the fp32 residual stream starts at conv_in)
         ydt = torch.float32 if out_f32 else dtype
         y = out if out is not None else torch.empty(B, H, W, cout, dtype=ydt, device=x.device)
-        assert y.shape == (B, H, W, cout) and y.dtype == ydt and y.is_contiguous()
-    a.x, a.W, a.bias, a.y = x.data_ptr(), w.data_ptr(), _p(_f32(bias, "bias")), y.data_ptr()
+        arg("out", y, ydt, (B, H, W, cout))
+    a.x, a.W, a.bias, a.y = x.data_ptr(), w.data_ptr(), arg.f32("bias", bias, cout), y.data_ptr()
     a.B, a.Cin, a.H, a.Wd, a.Cout, a.taps, a.ldy = B, Cin, H, W, cout, taps, cout
     a.in_scale, a.out_scale = in_scale, out_scale
     a.out_mode = L.OUT_NCHW_F32 if nchw_f32_out else (L.OUT_F32 if out_f32 else L.OUT_T)
     a.dtype = _DT[dtype]
     stats = None
+    if gn_part is not None:      # its chunk count is the library's to name: compared below, after the query
+        arg("gn_part", gn_part, torch.float32, (B, gn_part.shape[1] if gn_part.dim() == 4 else 0, gn_groups, 2))
+    arg.device()
     if gn_groups and not nchw_f32_out and not out_f32:
         a.gn_groups = gn_groups
         chunks = L.lib().dfw_conv_small_gn_chunks(C.byref(a))
         if chunks > 0:
             part = gn_part if gn_part is not None else torch.empty(B, chunks, gn_groups, 2, dtype=torch.float32, device=x.device)
-            assert part.shape == (B, chunks, gn_groups, 2) and part.is_contiguous() and part.dtype == torch.float32
+            arg.need(part.shape == (B, chunks, gn_groups, 2), "gn_part must be [{}, {}, {}, 2], got {}", B, chunks, gn_groups, part.shape)
             a.gn_partial = part.data_ptr()
             stats = (part, chunks, gn_groups)
     L.check(L.lib().dfw_conv_small(C.byref(a), _stream()), "dfw_conv_small")
@@ -605,15 +720,23 @@ def conv_small_gn_chunks(x_shape, cout, taps, dtype, gn_groups):
 
 def meter_update(counts, class_id, inter_buf, union_buf):
     """AverageMeter.update on device: int64 atomics into the two [2, nclass] buffers (logger.py:35-37)."""
-    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape[1] == 4
-    assert class_id.dtype == torch.int64 and class_id.is_contiguous() and class_id.shape[0] == counts.shape[0]
-    assert inter_buf.dtype == torch.int64 and inter_buf.is_contiguous() and union_buf.is_contiguous()
+    arg = _Args("meter_update")
+    arg("counts", counts, torch.int64, dim=2)
+    arg.need(counts.shape[1] == 4, "counts must be [B, 4], got {}", counts.shape)
+    arg("class_id", class_id, torch.int64, elems=counts.shape[0])
+    arg("inter_buf", inter_buf, torch.int64, dim=2)
+    arg.need(inter_buf.shape[0] == 2, "inter_buf must be [2, nclass], got {}", inter_buf.shape)
+    arg("union_buf", union_buf, torch.int64, inter_buf.shape)
+    arg.device()
     L.check(L.lib().dfw_meter_update(counts.data_ptr(), class_id.data_ptr(), inter_buf.data_ptr(), union_buf.data_ptr(),
                                      counts.shape[0], inter_buf.shape[1], _stream()), "dfw_meter_update")
 
 
 def softmax_rows(x, dtype, scale=1.0):
-    assert x.dtype == torch.float32 and x.is_contiguous()
+    arg = _Args("softmax_rows")
+    arg("x", x, torch.float32)
+    arg.need(x.dim() >= 1 and x.numel() > 0, "x must be [..., L] and not empty, got {}", x.shape)
+    arg.device()
     Lr = x.shape[-1]
     rows = x.numel() // Lr
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
@@ -624,7 +747,9 @@ def softmax_rows(x, dtype, scale=1.0):
 
 def softmax_groups(x, groups, L_, dtype):
     """x [rows, ld] fp32 scores -> [rows, ld] `dtype`: softmax over each group's L entries, padding zeroed."""
-    assert x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    arg = _Args("softmax_groups")
+    arg("x", x, torch.float32, dim=2)
+    arg.device()
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
     L.check(L.lib().dfw_softmax_groups(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], groups, L_,
                                        _DT[dtype], _stream()), "dfw_softmax_groups")
@@ -632,15 +757,23 @@ def softmax_groups(x, groups, L_, dtype):
 
 
 def transpose(x):
-    assert x.dim() == 3 and x.is_contiguous()
+    arg = _Args("transpose")
+    arg("x", x, dim=3)
     Bt, R, Cc = x.shape
+    dt = _dt(x)
+    arg.device()
     y = torch.empty(Bt, Cc, R, dtype=x.dtype, device=x.device)
-    L.check(L.lib().dfw_transpose(x.data_ptr(), y.data_ptr(), Bt, R, Cc, _dt(x), _stream()), "dfw_transpose")
+    L.check(L.lib().dfw_transpose(x.data_ptr(), y.data_ptr(), Bt, R, Cc, dt, _stream()), "dfw_transpose")
     return y
 
 
 def concat_channels(a, b):
-    assert a.is_contiguous() and b.is_contiguous() and a.shape[:-1] == b.shape[:-1] and a.dtype == b.dtype
+    arg = _Args("concat_channels")
+    arg("a", a, (*_DT, torch.float32))
+    arg.need(a.dim() >= 1 and a.numel() > 0, "a must be [..., Ca] and not empty, got {}", a.shape)
+    arg("b", b, a.dtype, dim=a.dim())
+    arg.need(a.shape[:-1] == b.shape[:-1], "b must be shaped like a {} up to the last dimension, got {}", a.shape, b.shape)
+    arg.device()
     Ca, Cb = a.shape[-1], b.shape[-1]
     y = torch.empty(*a.shape[:-1], Ca + Cb, dtype=a.dtype, device=a.device)
     rows = a.numel() // Ca
@@ -658,14 +791,19 @@ def to_storage(x, dtype):
     tensor that already is `dtype`."""
     if x.dtype == dtype:
         return x
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 8 == 0
+    arg = _Args("to_storage")
+    arg("x", x, torch.float32)
+    arg.need(x.numel() % 8 == 0, "x must hold a multiple of 8 elements, got {}", x.numel())
+    arg.device()
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
     L.check(L.lib().dfw_convert_f32(x.data_ptr(), y.data_ptr(), x.numel(), _DT[dtype], _stream()), "dfw_convert_f32")
     return y
 
 
 def timestep_embedding(timesteps, dim, dtype, flip_sin_to_cos=True, freq_shift=0.0):
-    assert timesteps.dtype == torch.float32 and timesteps.is_contiguous() and timesteps.dim() == 1
+    arg = _Args("timestep_embedding")
+    arg("timesteps", timesteps, torch.float32, dim=1)
+    arg.device()
     out = torch.empty(timesteps.shape[0], dim, dtype=dtype, device=timesteps.device)
     L.check(L.lib().dfw_timestep_embedding(timesteps.data_ptr(), out.data_ptr(), timesteps.shape[0], dim,
                                            int(flip_sin_to_cos), float(freq_shift), _DT[dtype], _stream()),
@@ -678,15 +816,21 @@ def seg_postprocess(x, gt=None, r_threshold=0.25, threshold=0.0, batch_max=False
     """x: decoder output [B, 3, H, W] fp32 -> (uint8 [B,3,H,W], counts int64 [B,4] or None).
     r_threshold > 0: dynamic threshold r_threshold * max (per image, or over the batch tensor when
     batch_max -- main_oss.py:131 read literally); else the fixed `threshold` (main_oss.py:134-135)."""
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 3
+    arg = _Args("seg_postprocess")
+    arg("x", x, torch.float32, dim=4)
     B, _, H, W = x.shape
+    arg.need(x.shape[1] == 3, "x must be [B, 3, H, W], got {}", x.shape)
     u8 = u8_out if u8_out is not None else torch.empty(B, 3, H, W, dtype=torch.uint8, device=x.device)
+    arg("u8_out", u8, torch.uint8, (B, 3, H, W))
     if scratch is None:
         scratch = torch.empty(B, dtype=torch.int32, device=x.device)
+    arg("scratch", scratch, torch.int32, extent=B)
     counts = None
     if gt is not None:
-        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, H, W)
+        arg("gt", gt, torch.uint8, (B, H, W))
         counts = counts_out if counts_out is not None else torch.empty(B, 4, dtype=torch.int64, device=x.device)
+        arg("counts_out", counts, torch.int64, (B, 4))
+    arg.device()
     L.check(L.lib().dfw_seg_postprocess_ex(x.data_ptr(), u8.data_ptr(), _p(gt), _p(counts), scratch.data_ptr(),
                                            B, H, W, float(r_threshold), float(threshold), int(bool(batch_max)),
                                            _stream()), "dfw_seg_postprocess")
@@ -700,36 +844,34 @@ def seg_labels(seg_u8, mx, gt=None, r_threshold=0.25, threshold=0.0, batch_max=F
     None): label 0 = no class above its threshold (seg_postprocess' rule per class), else 1 + the foreground class of
     the largest score, lowest class on a tie; with gt (uint8 [B, H, W]: 0..N, 255 and anything above N ignored) the
     per-label intersections (row 0) and unions (row 1)."""
-    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 5 and seg_u8.shape[2] == 3
+    arg = _Args("seg_labels")
+    arg("seg_u8", seg_u8, torch.uint8, dim=5)
     N, B, _, H, W = seg_u8.shape
+    arg.need(seg_u8.shape[2] == 3, "seg_u8 must be [N, B, 3, H, W], got {}", seg_u8.shape)
     if mx is not None:
-        assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == N * B
+        arg("mx", mx, torch.int32, elems=N * B)
     elif r_threshold > 0:
         raise ValueError("the dynamic threshold needs the per-image maxima (mx)")
     labels = labels_out if labels_out is not None else torch.empty(B, H, W, dtype=torch.uint8, device=seg_u8.device)
-    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.shape == (B, H, W)
+    arg("labels_out", labels, torch.uint8, (B, H, W))
     counts = None
     if gt is not None:
-        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, H, W)
+        arg("gt", gt, torch.uint8, (B, H, W))
         counts = counts_out if counts_out is not None else torch.empty(B, 2, N + 1, dtype=torch.int64, device=seg_u8.device)
-        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == (B, 2, N + 1)
+        arg("counts_out", counts, torch.int64, (B, 2, N + 1))
+    arg.device()
     L.check(L.lib().dfw_seg_labels(seg_u8.data_ptr(), _p(mx), _p(gt), labels.data_ptr(), _p(counts), N, B, H, W,
                                    float(r_threshold), float(threshold), int(bool(batch_max)), _stream()),
             "dfw_seg_labels")
     return labels, counts
 
 
-def _check_table(name, tab, tab_host, E_cap, device):
-    """ValueError (in `name`'s name) unless tab / tab_host are seg_labels_cand's table for E_cap entries -- contiguous int32
-    [B + 1 + E_cap], equally long, tab on `device` and tab_host on the host.  Returns B."""
-    for what, t in (("tab", tab), ("tab_host", tab_host)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < E_cap + 2:
-            raise ValueError(f"{name}: {what} must be a contiguous int32 [B + 1 + {E_cap}] tensor")
-    if tab.numel() != tab_host.numel():
-        raise ValueError(f"{name}: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
-    if not tab.is_cuda or tab.device != device or tab_host.device.type != "cpu":
-        raise ValueError(f"{name}: tab lives with seg_u8 on the device, tab_host on the host")
-    return tab.numel() - 1 - E_cap
+def _check_table(arg, tab, tab_host, known):
+    """seg_labels_cand's table through `arg`: tab and its host mirror tab_host are contiguous int32 vectors of one length,
+    offsets + 1 + entries, of which the caller knows one count (`known`: E_cap, or the windows T).  Returns the other."""
+    arg("tab", tab, torch.int32, dim=1, extent=known + 2)
+    arg("tab_host", tab_host, torch.int32, (tab.numel(),), host=True)
+    return tab.numel() - 1 - known
 
 
 def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.25, threshold=0.0, want_area=False,
@@ -745,21 +887,24 @@ def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.2
     score, earliest entry on a tie; counts as seg_labels gives them (gt uint8 [B, H, W]: 0..nlabels, 255 and anything
     above nlabels ignored; a gt label outside the query's candidates is a miss in that label's union); area[e] = (pixels
     where e is foreground on its own, pixels where e won), ignore pixels included."""
-    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    arg = _Args("seg_labels_cand")
+    arg("seg_u8", seg_u8, torch.uint8, dim=4)
     E_cap, _, H, W = seg_u8.shape
-    B, nlabels = _check_table("seg_labels_cand", tab, tab_host, E_cap, seg_u8.device), int(nlabels)
+    arg.need(seg_u8.shape[1] == 3, "seg_u8 must be [E_cap, 3, H, W], got {}", seg_u8.shape)
+    B, nlabels = _check_table(arg, tab, tab_host, E_cap), int(nlabels)
     if mx is not None:
-        assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == E_cap
+        arg("mx", mx, torch.int32, elems=E_cap)
     elif r_threshold > 0:
         raise ValueError("the dynamic threshold needs the per-entry maxima (mx)")
     labels = labels_out if labels_out is not None else torch.empty(B, H, W, dtype=torch.uint8, device=seg_u8.device)
-    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.shape == (B, H, W)
+    arg("labels_out", labels, torch.uint8, (B, H, W))
     counts = None
     if gt is not None:
-        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, H, W)
+        arg("gt", gt, torch.uint8, (B, H, W))
         shape = (B, 2, nlabels + 1)
         counts = counts_out if counts_out is not None else torch.empty(shape, dtype=torch.int64, device=seg_u8.device)
-        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == shape
+        arg("counts_out", counts, torch.int64, shape)
+    arg.device()
     area = torch.empty(E_cap, 2, dtype=torch.int64, device=seg_u8.device) if want_area else None
     host = C.cast(tab_host.data_ptr(), C.POINTER(C.c_int32))
     L.check(L.lib().dfw_seg_labels_cand(seg_u8.data_ptr(), _p(mx), tab.data_ptr(), host, _p(gt), labels.data_ptr(),
@@ -768,15 +913,15 @@ def seg_labels_cand(seg_u8, mx, tab, tab_host, nlabels, gt=None, r_threshold=0.2
     return labels, counts, area
 
 
-def _u8_buf(given, n, dev):
-    """`given` (a caller-owned uint8 buffer of at least n bytes on dev) or a fresh one."""
+def _u8_buf(arg, name, given, n, dev):
+    """`given` (a caller-owned uint8 buffer of at least n bytes, checked through `arg` as `name`) or a fresh one on dev."""
     if given is None:
         return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-    assert given.dtype == torch.uint8 and given.is_contiguous() and given.numel() >= n and given.device == dev
+    arg(name, given, torch.uint8, extent=n)
     return given
 
 
-def _native_setup(a, seg_u8, targets, b, n, want_u8, u8_out, tmp, r_threshold, threshold):
+def _native_setup(arg, a, seg_u8, targets, b, n, want_u8, u8_out, tmp, r_threshold, threshold):
     """What seg_native, seg_labels_native and seg_labels_cand_native share: ValueError unless `targets` were built for these
     b queries and seg_u8's (Hs, Ws); the targets' staged table made safe to read on this stream; and the fields the three
     argument records share by name -- source, item / weight tables, ground truth, thresholds, and the workspace of `n` planes
@@ -788,11 +933,15 @@ def _native_setup(a, seg_u8, targets, b, n, want_u8, u8_out, tmp, r_threshold, t
         raise ValueError(f"targets were built for {targets.b} queries from {targets.src_hw}, the call has {b} and seg_u8 is "
                          f"{tuple(seg_u8.shape)}")
     dev = seg_u8.device
+    arg("targets.dev", targets.dev, torch.uint8, dim=1)
+    u8 = _u8_buf(arg, "u8_out", u8_out, n * targets.u8_bytes, dev) if want_u8 else None
+    tmp = _u8_buf(arg, "tmp", tmp, n * targets.tmp_bytes + (0 if want_u8 else n * targets.u8_bytes), dev)
+    gt, gt_bytes = targets.gt_base
+    if gt is not None:
+        arg("targets.gt_base", gt, torch.uint8, extent=gt_bytes)
+    arg.device()        # the callers have checked their own buffers
     if not torch.cuda.is_current_stream_capturing():
         targets.dev.record_stream(torch.cuda.current_stream())     # staged on the loader's stream, read on this one
-    u8 = _u8_buf(u8_out, n * targets.u8_bytes, dev) if want_u8 else None
-    tmp = _u8_buf(tmp, n * targets.tmp_bytes + (0 if want_u8 else n * targets.u8_bytes), dev)
-    gt, gt_bytes = targets.gt_base
     a.seg_u8, a.B, a.Hs, a.Ws = seg_u8.data_ptr(), b, Hs, Ws
     a.items, a.items_host = targets.dev.data_ptr(), C.addressof(targets.items)
     a.weights, a.weights_bytes = targets.dev.data_ptr(), targets.dev.numel()
@@ -830,11 +979,13 @@ def seg_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_max=False
     (inter0, inter1, union0, union1) or None, mx=int32 [b] resized maxima, sizes=[(h_i, w_i)]); the views of each list
     are backed by one packed buffer.  u8_out / pred_out / tmp: caller-owned uint8 buffers of at least targets.u8_bytes /
     pred_bytes / tmp_bytes (tmp_bytes + u8_bytes without want_u8) instead of fresh ones."""
-    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    arg = _Args("seg_native")
+    arg("seg_u8", seg_u8, torch.uint8, dim=4)
+    arg.need(seg_u8.shape[1] == 3, "seg_u8 must be [b, 3, Hs, Ws], got {}", seg_u8.shape)
     b, dev = seg_u8.shape[0], seg_u8.device
     a = L.SegNativeArgs()
-    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, 1, want_u8, u8_out, tmp, r_threshold, threshold)
-    pred = _u8_buf(pred_out, targets.pred_bytes, dev) if want_pred else None
+    pred = _u8_buf(arg, "pred_out", pred_out, targets.pred_bytes, dev) if want_pred else None
+    u8, tmp, has_gt = _native_setup(arg, a, seg_u8, targets, b, 1, want_u8, u8_out, tmp, r_threshold, threshold)
     counts = torch.empty(b, 4, dtype=torch.int64, device=dev) if has_gt else None
     mx = torch.empty(b, dtype=torch.int32, device=dev)
     if pred is not None:
@@ -861,15 +1012,17 @@ def seg_labels_native(seg_u8, targets, r_threshold=0.25, threshold=0.0, batch_ma
     seg_u8=[uint8 views [N, 3, h_i, w_i]] or None (want_u8), sizes=[(h_i, w_i)]); the views of each list are backed by one
     packed buffer, classes targets.u8_bytes apart.  labels_out / u8_out / tmp: caller-owned uint8 buffers of at least
     targets.pred_bytes / N * u8_bytes / N * tmp_bytes (N * (tmp_bytes + u8_bytes) without want_u8) instead of fresh ones."""
-    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 5 and seg_u8.shape[2] == 3
+    arg = _Args("seg_labels_native")
+    arg("seg_u8", seg_u8, torch.uint8, dim=5)
+    arg.need(seg_u8.shape[2] == 3, "seg_u8 must be [N, b, 3, Hs, Ws], got {}", seg_u8.shape)
     N, b, dev = seg_u8.shape[0], seg_u8.shape[1], seg_u8.device
     a = L.SegLabelsNativeArgs()
-    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, N, want_u8, u8_out, tmp, r_threshold, threshold)
+    labels = _u8_buf(arg, "labels_out", labels_out, targets.pred_bytes, dev)
     if class_ids is not None:
         class_ids = torch.as_tensor(class_ids, dtype=torch.int32).to(dev).contiguous()
         if class_ids.shape != (N,):
             raise ValueError(f"class_ids must hold one id per class ({N}), got {tuple(class_ids.shape)}")
-    labels = _u8_buf(labels_out, targets.pred_bytes, dev)
+    u8, tmp, has_gt = _native_setup(arg, a, seg_u8, targets, b, N, want_u8, u8_out, tmp, r_threshold, threshold)
     counts = torch.empty(b, 2, N + 1, dtype=torch.int64, device=dev) if has_gt else None
     mx = torch.empty(N, b, dtype=torch.int32, device=dev)
     a.N, a.tmp_cls_stride, a.u8_cls_stride = N, targets.tmp_bytes, targets.u8_bytes
@@ -910,16 +1063,17 @@ def seg_labels_cand_native(seg_u8, targets, tab, tab_host, nlabels, r_threshold=
     (cand_native_workspace).  Returns dict(labels=[uint8 views [h_i, w_i]], counts=int64 [b, 2, nlabels+1] or None,
     area=int64 [E_cap, 2] or None (want_area; counted on the resized bytes), mx=int32 [E_cap] resized maxima,
     seg_u8=[uint8 views [K_i, 3, h_i, w_i], K_i the query's entries] or None (want_u8), sizes=[(h_i, w_i)])."""
-    assert seg_u8.dtype == torch.uint8 and seg_u8.is_contiguous() and seg_u8.dim() == 4 and seg_u8.shape[1] == 3
+    arg = _Args("seg_labels_cand_native")
+    arg("seg_u8", seg_u8, torch.uint8, dim=4)
+    arg.need(seg_u8.shape[1] == 3, "seg_u8 must be [E_cap, 3, Hs, Ws], got {}", seg_u8.shape)
     E_cap, dev = seg_u8.shape[0], seg_u8.device
-    b, nlabels = _check_table("seg_labels_cand_native", tab, tab_host, E_cap, dev), int(nlabels)
+    b, nlabels = _check_table(arg, tab, tab_host, E_cap), int(nlabels)
     if class_ids is not None and entry_ids is not None:
         raise ValueError("seg_labels_cand_native: give class_ids (labels = 1 + set index) or entry_ids (local labels), not both")
     off = tab_host[:b + 1].tolist()
     rows = [hi - lo for lo, hi in zip(off, off[1:])]
     K = max(max(rows), 1)                  # cand_native_workspace(targets, K, want_u8) is what _native_setup lays out
     a = L.SegLabelsCandNativeArgs()
-    u8, tmp, has_gt = _native_setup(a, seg_u8, targets, b, K, want_u8, u8_out, tmp, r_threshold, threshold)
 
     def ids(t, n, name):
         if t is None:
@@ -929,7 +1083,8 @@ def seg_labels_cand_native(seg_u8, targets, tab, tab_host, nlabels, r_threshold=
             raise ValueError(f"{name} must hold {n} ids, got {tuple(t.shape)}")
         return t
     class_ids, entry_ids = ids(class_ids, nlabels, "class_ids"), ids(entry_ids, E_cap, "entry_ids")
-    labels = _u8_buf(labels_out, targets.pred_bytes, dev)
+    labels = _u8_buf(arg, "labels_out", labels_out, targets.pred_bytes, dev)
+    u8, tmp, has_gt = _native_setup(arg, a, seg_u8, targets, b, K, want_u8, u8_out, tmp, r_threshold, threshold)
     counts = torch.empty(b, 2, nlabels + 1, dtype=torch.int64, device=dev) if has_gt else None
     area = torch.empty(E_cap, 2, dtype=torch.int64, device=dev) if want_area else None
     mx = torch.empty(E_cap, dtype=torch.int32, device=dev)
@@ -955,14 +1110,16 @@ def tiles_cut(plan, img_u8, lut, first=0, count=None, out=None):
     [count, 3, th, tw], each window bit for bit DeviceImageTransform((th, tw)).image(crop).  One launch; `out`: a
     caller-owned contiguous fp32 [count, 3, th, tw] instead of a fresh one."""
     c, T = _tile_plan(plan)
-    assert img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and tuple(img_u8.shape) == (c.img_h, c.img_w, 3)
-    assert lut.dtype == torch.float32 and lut.is_contiguous() and lut.numel() == 256 and lut.device == img_u8.device
+    arg = _Args("tiles_cut")
+    arg("img_u8", img_u8, torch.uint8, (c.img_h, c.img_w, 3))
+    arg("lut", lut, torch.float32, elems=256)
     if count is None:
         count = T - first
     shape = (count, 3, c.tile_h, c.tile_w)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=img_u8.device)
-    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape and out.device == img_u8.device
+    arg("out", out, torch.float32, shape)
+    arg.device()
     L.check(L.lib().dfw_tiles_cut(C.byref(c), img_u8.data_ptr(), lut.data_ptr(), out.data_ptr(), int(first), int(count),
                                   _stream()), "dfw_tiles_cut")
     return out
@@ -974,16 +1131,17 @@ def tiles_merge(plan, win, out=None, mx=None):
     windows over it in integers, round half up (csrc/tiles.hip); exact and independent of any order; one window is the
     identity.  out.view(N, 1, 3, h, w) and mx are seg_labels' inputs.  Two launches; `out` / `mx`: caller-owned buffers."""
     c, T = _tile_plan(plan)
-    assert win.dtype == torch.uint8 and win.is_contiguous() and win.dim() == 5
+    arg = _Args("tiles_merge")
+    arg("win", win, torch.uint8, dim=5)
     N = win.shape[0]
-    assert tuple(win.shape) == (N, T, 3, c.tile_h, c.tile_w)
+    arg.need(win.shape[1:] == (T, 3, c.tile_h, c.tile_w), "win must be [N, {}, 3, {}, {}], got {}", T, c.tile_h, c.tile_w, win.shape)
     if out is None:
         out = torch.empty(N, 3, c.img_h, c.img_w, dtype=torch.uint8, device=win.device)
     if mx is None:
         mx = torch.empty(N, dtype=torch.int32, device=win.device)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (N, 3, c.img_h, c.img_w)
-    assert mx.dtype == torch.int32 and mx.is_contiguous() and mx.numel() == N
-    assert out.device == win.device and mx.device == win.device
+    arg("out", out, torch.uint8, (N, 3, c.img_h, c.img_w))
+    arg("mx", mx, torch.int32, elems=N)
+    arg.device()
     L.check(L.lib().dfw_tiles_merge(C.byref(c), win.data_ptr(), N, out.data_ptr(), mx.data_ptr(), _stream()),
             "dfw_tiles_merge")
     return out, mx
@@ -1005,49 +1163,30 @@ def tiles_labels_cand(plan, ent, tab, tab_host, N, gt=None, r_threshold=0.25, th
     included).  Two or three launches, no memset node; labels_out / counts_out / mx_out / area_out: caller-owned buffers."""
     c, T = _tile_plan(plan)
     N = int(N)
-    for name, t in (("tab", tab), ("tab_host", tab_host)):
-        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < T + 2:
-            raise ValueError(f"tiles_labels_cand: {name} must be a contiguous int32 [{T} + 1 + E_cap] tensor")
-    if tab.numel() != tab_host.numel():
-        raise ValueError(f"tiles_labels_cand: tab holds {tab.numel()} words, its host mirror {tab_host.numel()}")
-    if not tab.is_cuda or tab_host.device.type != "cpu":
-        raise ValueError("tiles_labels_cand: tab lives on the device, tab_host on the host")
-    E_cap, dev = tab.numel() - T - 1, tab.device
-    if ent is not None:
-        assert ent.dtype == torch.uint8 and ent.is_contiguous() and ent.device == dev
-        if tuple(ent.shape) != (E_cap, 3, c.tile_h, c.tile_w):
-            raise ValueError(f"tiles_labels_cand: ent must be [{E_cap}, 3, {c.tile_h}, {c.tile_w}] for a table of {tab.numel()} "
-                             f"words, got {tuple(ent.shape)}")
+    arg = _Args("tiles_labels_cand")
+    E_cap, dev = _check_table(arg, tab, tab_host, T), tab.device
+    if ent is not None:     # a table of tab.numel() words names E_cap entries
+        arg("ent", ent, torch.uint8, (E_cap, 3, c.tile_h, c.tile_w))
     hw = (c.img_h, c.img_w)
 
-    def buf(given, shape, dtype):
+    def buf(name, given, shape, dtype):
         if given is None:
             return torch.empty(shape, dtype=dtype, device=dev)
-        assert given.dtype == dtype and given.is_contiguous() and tuple(given.shape) == shape and given.device == dev
+        arg(name, given, dtype, shape)
         return given
-    labels = buf(labels_out, hw, torch.uint8)
-    mx = buf(mx_out, (N,), torch.int32)
+    labels = buf("labels_out", labels_out, hw, torch.uint8)
+    mx = buf("mx_out", mx_out, (N,), torch.int32)
     counts = None
     if gt is not None:
-        assert gt.dtype == torch.uint8 and gt.is_contiguous() and tuple(gt.shape) == hw and gt.device == dev
-        counts = buf(counts_out, (2, N + 1), torch.int64)
-    area = buf(area_out, (N, 2), torch.int64) if want_area or area_out is not None else None
+        arg("gt", gt, torch.uint8, hw)
+        counts = buf("counts_out", counts_out, (2, N + 1), torch.int64)
+    area = buf("area_out", area_out, (N, 2), torch.int64) if want_area or area_out is not None else None
+    arg.device()
     host = C.cast(tab_host.data_ptr(), C.POINTER(C.c_int32))
     L.check(L.lib().dfw_tiles_labels_cand(C.byref(c), _p(ent), tab.data_ptr(), host, _p(gt), labels.data_ptr(),
                                           mx.data_ptr(), _p(counts), _p(area), E_cap, N, float(r_threshold),
                                           float(threshold), _stream()), "dfw_tiles_labels_cand")
     return labels, counts, mx, area
-
-
-def _owner(fn, dev):
-    """The check every seg_* wrapper runs on a caller-owned buffer: own(name, t, dtype, shape) returns t's address, or
-    raises the wrapper's ValueError unless t is a contiguous `dtype` tensor of `shape` (None: any) on `dev` -- or on
-    `device`, for the one buffer that lives elsewhere."""
-    def own(name, t, dtype, shape, device=dev):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != device or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"{fn}: {name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
-        return t.data_ptr()
-    return own
 
 
 def seg_components_workspace(B, H, W):
@@ -1067,13 +1206,12 @@ def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, count
     bytes against gt uint8 [B, H, W] (nlabels: the number of classes; a byte above it has no bin).  ws: a uint8 buffer of at
     least seg_components_workspace(B, H, W) bytes, which needs no initialisation.  A fixed number of launches (at most 8),
     no host synchronisation, no memset node: the call can be captured.  Returns None."""
-    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
+    own = _Args("seg_components")
+    own("labels", labels, torch.uint8, dim=3)
     B, H, W = labels.shape
-    dev = labels.device
-    own = _owner("seg_components", dev)
     a = L.SegComponentsArgs()
     a.labels, a.ids, a.n = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W)), own("n", n, torch.int32, (B, 2))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     if filtered is not None:
         a.filtered = own("filtered", filtered, torch.uint8, (B, H, W))
     if stats is not None:
@@ -1089,6 +1227,7 @@ def seg_components(labels, ids, n, ws, filtered=None, stats=None, gt=None, count
         if counts is not None:
             a.counts = own("counts", counts, torch.int64, (B, 2, int(nlabels) + 1))
     a.B, a.H, a.W, a.connectivity, a.min_area = B, H, W, int(connectivity), int(min_area)
+    own.device()
     L.check(L.lib().dfw_seg_components(C.byref(a), _stream()), "dfw_seg_components")
 
 
@@ -1111,15 +1250,14 @@ def seg_holes(labels, ids, ids_out, labels_out, holes, ws, stats=None, stats_out
     nlabels + 1], seg_labels' counts of labels_out against gt uint8 [B, H, W].  No output may share memory with an input.
     ws: a uint8 buffer of at least seg_holes_workspace(B, H, W) bytes, which needs no initialisation.  A fixed number of
     launches (at most 6), no host synchronisation, no memset node: the call can be captured.  Returns None."""
-    assert labels.dtype == torch.uint8 and labels.is_contiguous() and labels.dim() == 3 and labels.is_cuda
+    own = _Args("seg_holes")
+    own("labels", labels, torch.uint8, dim=3)
     B, H, W = labels.shape
-    dev = labels.device
-    own = _owner("seg_holes", dev)
     a = L.SegHolesArgs()
     a.labels, a.ids = labels.data_ptr(), own("ids", ids, torch.int32, (B, H, W))
     a.ids_out, a.labels_out = own("ids_out", ids_out, torch.int32, (B, H, W)), own("labels_out", labels_out, torch.uint8, (B, H, W))
     a.holes = own("holes", holes, torch.int32, (B, 2))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     if (stats is None) != (stats_out is None):
         raise ValueError("seg_holes: stats and stats_out come together")
     if stats is not None:
@@ -1139,6 +1277,7 @@ def seg_holes(labels, ids, ids_out, labels_out, holes, ws, stats=None, stats_out
     if not 0 <= max_area <= 2 ** 31 - 1:
         raise ValueError(f"seg_holes: max_area must lie in 0..2^31 - 1, got {max_area}")
     a.B, a.H, a.W, a.connectivity, a.max_area = B, H, W, int(connectivity), max_area
+    own.device()
     L.check(L.lib().dfw_seg_holes(C.byref(a), _stream()), "dfw_seg_holes")
 
 
@@ -1166,19 +1305,18 @@ def seg_rle(ids, runs, run_off, nruns, ws, cap, order="column"):
     run_off[k-1] .. run_off[k].  ws: a uint8 buffer of at least seg_rle_workspace(B, H, W, cap, max_runs, order) bytes, which
     needs no initialisation.  A number of launches fixed by the arguments, no host synchronisation, no memset node: the call
     can be captured.  Returns None."""
-    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
-        raise ValueError("seg_rle: ids must be a contiguous int32 device tensor [B, H, W]")
+    own = _Args("seg_rle")
+    own("ids", ids, torch.int32, dim=3)
     B, H, W = ids.shape
-    dev, cap = ids.device, int(cap)
-    if runs.dim() != 3:
-        raise ValueError("seg_rle: runs must be int32 [B, max_runs, 2]")
+    cap = int(cap)
+    own.need(runs.dim() == 3, "runs must be int32 [B, max_runs, 2]")
     max_runs = runs.shape[1]
-    own = _owner("seg_rle", dev)
     a = L.SegRleArgs()
     a.ids, a.runs = ids.data_ptr(), own("runs", runs, torch.int32, (B, max_runs, 2))
     a.run_off, a.nruns = own("run_off", run_off, torch.int32, (B, cap + 1)), own("nruns", nruns, torch.int32, (B, 2))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     a.B, a.H, a.W, a.cap, a.max_runs, a.order = B, H, W, cap, max_runs, _rle_order(order)
+    own.device()
     L.check(L.lib().dfw_seg_rle(C.byref(a), _stream()), "dfw_seg_rle")
 
 
@@ -1216,8 +1354,8 @@ def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8, simp_v
     definition), three more launches.  simp_rings = (id, first', count', area of the original ring) in the rows of rings,
     simp_verts the kept corners, simp_n = (corners in, corners kept, rings, complete), (0, 0, 0, 0) for an image that is
     not complete; ring_off serves both.  Without them the call is what it was."""
-    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
-        raise ValueError("seg_contours: ids must be a contiguous int32 device tensor [B, H, W]")
+    own = _Args("seg_contours")
+    own("ids", ids, torch.int32, dim=3)
     simp = (simp_verts, simp_rings, simp_n)
     if any(t is None for t in simp) != all(t is None for t in simp):
         raise ValueError("seg_contours: simp_verts, simp_rings and simp_n come together or not at all")
@@ -1227,21 +1365,21 @@ def seg_contours(ids, verts, rings, ring_off, n, ws, cap, connectivity=8, simp_v
     if connectivity not in (4, 8):
         raise ValueError(f"seg_contours: connectivity must be 4 or 8, not {connectivity!r}")
     B, H, W = ids.shape
-    dev, cap = ids.device, int(cap)
+    cap = int(cap)
     if verts.dim() != 3 or verts.shape[1] < 4 or verts.shape[1] % 4:
         raise ValueError("seg_contours: verts must be int32 [B, max_edges, 2] with max_edges a multiple of 4, at least 4")
     max_edges = verts.shape[1]
-    own = _owner("seg_contours", dev)
     a = L.SegContoursArgs()
     a.ids, a.verts = ids.data_ptr(), own("verts", verts, torch.int32, (B, max_edges, 2))
     a.rings, a.ring_off = own("rings", rings, torch.int32, (B, max_edges // 4, 4)), own("ring_off", ring_off, torch.int32, (B, cap + 1))
     a.n = own("n", n, torch.int32, (B, 4))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     a.B, a.H, a.W, a.cap, a.max_edges, a.connectivity = B, H, W, cap, max_edges, int(connectivity)
     if simp_n is not None:
         a.simp_verts = own("simp_verts", simp_verts, torch.int32, (B, max_edges, 2))
         a.simp_rings = own("simp_rings", simp_rings, torch.int32, (B, max_edges // 4, 4))
         a.simp_n, a.tol4 = own("simp_n", simp_n, torch.int32, (B, 4)), tol4
+    own.device()
     L.check(L.lib().dfw_seg_contours(C.byref(a), _stream()), "dfw_seg_contours")
 
 
@@ -1270,16 +1408,14 @@ def seg_match(pids, gids, pairs, pair_off, area, match, gmatch, pq, n, ws, max_r
     maximal interval of positions with one equal (p, g) other than (0, 0)), is given.  ws: a uint8 buffer of at least
     seg_match_workspace(B, H, W, cap_p, cap_g, max_records, max_pairs) bytes, which needs no initialisation.  A number of
     launches fixed by the arguments, no host synchronisation, no memset node: the call can be captured.  Returns None."""
-    if pids.dim() != 3 or pids.dtype != torch.int32 or not pids.is_contiguous():
-        raise ValueError("seg_match: pids must be a contiguous int32 device tensor [B, H, W]")
+    own = _Args("seg_match")
+    own("pids", pids, torch.int32, dim=3)
     B, H, W = pids.shape
-    dev = pids.device
     if match.dim() != 3 or gmatch.dim() != 2 or pairs.dim() != 3 or pq.dim() != 3:
         raise ValueError("seg_match: match must be int32 [B, cap_p, 3], gmatch int32 [B, cap_g], pairs int32 [B, max_pairs, 3] "
                          "and pq int64 [B, nlabels + 1, 4]")
     cap_p, cap_g, max_pairs, nlabels = match.shape[1], gmatch.shape[1], pairs.shape[1], pq.shape[1] - 1
     num, den = (int(v) for v in iou)
-    own = _owner("seg_match", dev)
     a = L.SegMatchArgs()
     a.pids, a.gids = pids.data_ptr(), own("gids", gids, torch.int32, (B, H, W))
     if pstats is not None:
@@ -1291,11 +1427,10 @@ def seg_match(pids, gids, pairs, pair_off, area, match, gmatch, pq, n, ws, max_r
     a.pairs, a.pair_off = own("pairs", pairs, torch.int32, (B, max_pairs, 3)), own("pair_off", pair_off, torch.int32, (B, cap_p + 2))
     a.area, a.match = own("area", area, torch.int32, (B, cap_p + cap_g + 2)), own("match", match, torch.int32, (B, cap_p, 3))
     a.gmatch, a.pq = own("gmatch", gmatch, torch.int32, (B, cap_g)), own("pq", pq, torch.int64, (B, nlabels + 1, 4))
-    a.n, a.ws, a.ws_bytes = own("n", n, torch.int32, (B, 4)), own("ws", ws, torch.uint8, None), ws.numel()
+    a.n, a.ws, a.ws_bytes = own("n", n, torch.int32, (B, 4)), own("ws", ws, torch.uint8), ws.numel()
     a.B, a.H, a.W, a.capP, a.capG, a.nlabels = B, H, W, cap_p, cap_g, nlabels
     a.max_records, a.max_pairs, a.num, a.den = int(max_records), max_pairs, num, den
-    if not pids.is_cuda:
-        raise ValueError("seg_match: pids and every buffer must be device tensors")
+    own.device()
     L.check(L.lib().dfw_seg_match(C.byref(a), _stream()), "dfw_seg_match")
 
 
@@ -1322,22 +1457,21 @@ def seg_scores(ids, labels, seg_u8, planes, planes_host, scores, ws):
     min, max) of object id in row id - 1, zeros for a row without a counted pixel; cap and nlabels are the buffers' shapes.
     ws: a uint8 buffer of at least seg_scores_workspace(B, cap) bytes, which needs no initialisation.  Three launches, no
     host synchronisation, no memset node: the call can be captured.  Returns None."""
-    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or not ids.is_cuda:
-        raise ValueError("seg_scores: ids must be a contiguous int32 device tensor [B, H, W]")
+    own = _Args("seg_scores")
+    own("ids", ids, torch.int32, dim=3)
     B, H, W = ids.shape
-    dev = ids.device
     if scores.dim() != 3 or planes.dim() != 2 or seg_u8.dim() != 4:
         raise ValueError("seg_scores: scores must be int64 [B, cap, 4], planes int32 [B, nlabels + 1] and seg_u8 uint8 "
                          "[P, 3, H, W]")
     cap, nl1, P = scores.shape[1], planes.shape[1], seg_u8.shape[0]
-    own = _owner("seg_scores", dev)
     a = L.SegScoresArgs()
     a.ids, a.labels = ids.data_ptr(), own("labels", labels, torch.uint8, (B, H, W))
     a.seg_u8, a.planes = own("seg_u8", seg_u8, torch.uint8, (P, 3, H, W)), own("planes", planes, torch.int32, (B, nl1))
-    a.planes_host = own("planes_host", planes_host, torch.int32, (B, nl1), torch.device("cpu"))
+    a.planes_host = own("planes_host", planes_host, torch.int32, (B, nl1), host=True)
     a.scores = own("scores", scores, torch.int64, (B, cap, 4))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     a.B, a.H, a.W, a.cap, a.nlabels, a.P = B, H, W, cap, nl1 - 1, P
+    own.device()
     L.check(L.lib().dfw_seg_scores(C.byref(a), _stream()), "dfw_seg_scores")
 
 
@@ -1375,17 +1509,15 @@ def seg_boundary(map, dist, ws, dmax, band=None, d=None, metric="chessboard", pe
     (0xFFFFFFFF - (y * W + x)) -- the squared radius of the object's largest inscribed circle and, among equals, its first
     centre -- and 0 when id k has no pixel; ids outside 1..cap are not counted.  Two launches, three with peaks (a library
     kernel zeroes the table, the column pass reduces it with integer atomic maxima: order-free)."""
-    if map.dim() != 3 or map.dtype not in (torch.uint8, torch.int32) or not map.is_contiguous() or not map.is_cuda:
-        raise ValueError("seg_boundary: map must be a contiguous uint8 or int32 device tensor [B, H, W]")
+    own = _Args("seg_boundary")
+    own("map", map, (torch.uint8, torch.int32), dim=3)
     if metric not in _BOUNDARY_METRICS:
         raise ValueError(f"seg_boundary: metric must be one of {sorted(_BOUNDARY_METRICS)}, got {metric!r}")
     B, H, W = map.shape
-    dev = map.device
-    own = _owner("seg_boundary", dev)
     a = L.SegBoundaryArgs()
     a.metric = _BOUNDARY_METRICS[metric]
     a.map, a.dist = map.data_ptr(), own("dist", dist, torch.uint16 if a.metric else torch.uint8, (B, H, W))
-    a.ws, a.ws_bytes = own("ws", ws, torch.uint8, None), ws.numel()
+    a.ws, a.ws_bytes = own("ws", ws, torch.uint8), ws.numel()
     if (band is None) != (d is None):
         raise ValueError("seg_boundary: band and d go together")
     if band is not None:
@@ -1398,6 +1530,7 @@ def seg_boundary(map, dist, ws, dmax, band=None, d=None, metric="chessboard", pe
     elif cap is not None:
         raise ValueError("seg_boundary: cap goes with peaks")
     a.elem, a.B, a.H, a.W, a.dmax = map.element_size(), B, H, W, int(dmax)
+    own.device()
     L.check(L.lib().dfw_seg_boundary(C.byref(a), _stream()), "dfw_seg_boundary")
 
 
@@ -1412,13 +1545,11 @@ def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
 
     pdist and gdist may both be the uint16 squared maps of seg_boundary(metric="euclidean"); a pixel then lies in the band
     when 1 <= dist <= d * d."""
-    if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_contiguous() or not pred.is_cuda:
-        raise ValueError("seg_boundary_counts: pred must be a contiguous uint8 device tensor [B, H, W]")
+    own = _Args("seg_boundary_counts")
+    own("pred", pred, torch.uint8, dim=3)
     B, H, W = pred.shape
-    dev = pred.device
     if counts.dim() != 3:
         raise ValueError("seg_boundary_counts: counts must be int64 [B, 2, nlabels + 1]")
-    own = _owner("seg_boundary_counts", dev)
     a = L.SegBoundaryCountsArgs()
     kind = torch.uint16 if pdist.dtype == torch.uint16 else torch.uint8      # both maps are of pdist's kind
     a.pred, a.pdist = pred.data_ptr(), own("pdist", pdist, kind, (B, H, W))
@@ -1426,4 +1557,5 @@ def seg_boundary_counts(pred, pdist, gt, gdist, counts, d):
     a.counts = own("counts", counts, torch.int64, (B, 2, counts.shape[2]))
     a.B, a.H, a.W, a.d, a.nlabels = B, H, W, int(d), counts.shape[2] - 1
     a.dist_elem = 2 if kind == torch.uint16 else 0
+    own.device()
     L.check(L.lib().dfw_seg_boundary_counts(C.byref(a), _stream()), "dfw_seg_boundary_counts")

@@ -48,7 +48,7 @@ def configured(L, cfg):
 @contextlib.contextmanager
 def fsa_names(ops, L, launch=True):
     """Record dfw_fsa_kernel_name of every dfw_fsa_attention call ops makes (and launch it unless launch=False)."""
-    names, orig = [], ops._fsa_call
+    names, orig, device_rule = [], ops._fsa_call, ops._Args.device
 
     def rec(a):
         buf = C.create_string_buffer(96)
@@ -58,10 +58,12 @@ def fsa_names(ops, L, launch=True):
             orig(a)
 
     ops._fsa_call = rec
+    if not launch:
+        ops._Args.device = lambda self: None          # planning on host tensors: nothing is launched
     try:
         yield names
     finally:
-        ops._fsa_call = orig
+        ops._fsa_call, ops._Args.device = orig, device_rule
 
 
 def _strided(B, n, width, pad, dtype, device, g=None, fill=True):

@@ -191,13 +191,14 @@ def test_every_case_plans_its_kernel_and_the_cases_reach_every_instantiation(hip
     lib = L.lib()
     names = []
 
-    def plan_only(a):          # the arguments ops built, planned instead of launched
+    def plan_only(a, device):          # the arguments ops built, planned instead of launched
         buf = C.create_string_buffer(96)
         L.check(lib.dfw_gemm_kernel_name(C.byref(a), buf, 96), "dfw_gemm_kernel_name")
         names.append(buf.value.decode())
 
     monkeypatch.setattr(ops, "_gemm_call", plan_only)
     monkeypatch.setattr(ops_bwd, "_stream", lambda: None)
+    monkeypatch.setattr(ops._Args, "device", lambda self: None)     # planning on host tensors: nothing is launched
     reached, wrong = set(), []
     for case in plans.FWD_CASES:
         names.clear()

@@ -70,7 +70,7 @@ def test_host_validation(hip_lib):
     assert lab(3, mx=None) == DFW_EINVAL            # dynamic threshold needs the maxima
     from diffews_amd import ops
     q = torch.zeros(4, 128, 128, dtype=torch.bfloat16)
-    with pytest.raises(AssertionError):             # ops: the stack holds exactly (B // group) * nshot images
+    with pytest.raises(ValueError, match=r"fsa_attention: k_bank must hold 2 images \(nshot for each of the B // group sets\), got 3"):     # ops: the stack holds exactly (B // group) * nshot images
         ops.fsa_attention_sets(q, q, q, 2, q[:3], q[:3], nshot=1, group=2)
     with pytest.raises(ValueError):
         ops.fsa_attention_sets(q, q, q, 2, q, q, nshot=0, group=2)

@@ -97,7 +97,7 @@ def test_host_validation(hip_lib):
         assert h.dfw_fsa_ragged_workspace_bytes(C.byref(a), sh, nsets, group) == 0, what
     from diffews_amd import ops
     q = torch.zeros(4, 128, 128, dtype=torch.bfloat16)
-    with pytest.raises(AssertionError):             # ops: the stack holds exactly sum(shots) images
+    with pytest.raises(ValueError, match=r"fsa_attention: k_bank must hold 3 images \(the sum of shots\), got 4"):     # ops: the stack holds exactly sum(shots) images
         ops.fsa_attention_ragged(q, q, q, 2, q[:4], q[:4], shots=(1, 2), group=2)
     with pytest.raises(ValueError):
         ops.fsa_attention_ragged(q, q, q, 2, q[:3], q[:3], shots=(3, 0), group=2)

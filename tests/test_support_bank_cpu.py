@@ -61,7 +61,7 @@ def test_shared_bank_argument_validation(hip_lib):
         assert h.dfw_fsa_kernel_name(C.byref(a), buf, 96) == DFW_EINVAL, bad
     a = _fsa_args(L, **dict(ok, bank_shared=1))
     assert "+shared" in _name(L, a)
-    with pytest.raises(AssertionError):        # ops: the bank of a shared launch holds exactly nshot images
+    with pytest.raises(ValueError, match=r"fsa_attention: k_bank must hold 1 images \(nshot, one shared set\), got 3"):     # ops: the bank of a shared launch holds exactly nshot images
         from diffews_amd import ops
         q = torch.zeros(3, 128, 128, dtype=torch.bfloat16)
         ops.fsa_attention(q, q, q, 2, q, q, nshot=1, bank_shared=True)
