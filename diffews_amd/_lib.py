@@ -113,7 +113,8 @@ class SegLabelsCandNativeArgs(C.Structure):
 class SegComponentsArgs(C.Structure):
     _fields_ = [("labels", _vp), ("ids", _vp), ("filtered", _vp), ("n", _vp), ("stats", _vp), ("gt", _vp), ("counts", _vp),
                 ("ws", _vp), ("ws_bytes", _sz), ("B", _i32), ("H", _i32), ("W", _i32), ("connectivity", _i32),
-                ("min_area", _i32), ("cap", _i32), ("nlabels", _i32)]
+                ("min_area", _i32), ("cap", _i32), ("nlabels", _i32), ("keys", _vp), ("map", _vp),
+                ("seeds", _vp), ("nearest", _vp), ("dist", _vp), ("reach", _i32), ("passes", _i32)]
 
 
 class SegHolesArgs(C.Structure):
@@ -352,6 +353,7 @@ SYMBOLS = {
                                      _f32, _vp]),
     "dfw_seg_components": (_i32, [C.POINTER(SegComponentsArgs), _vp]),
     "dfw_seg_components_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dfw_seg_nearest_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dfw_seg_components_tile": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "dfw_seg_components_rounds": (_i32, [_i32, _i32, _i32, _vp, C.POINTER(SegComponentsRounds)]),
     "dfw_seg_holes": (_i32, [C.POINTER(SegHolesArgs), _vp]),

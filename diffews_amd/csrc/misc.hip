@@ -934,7 +934,7 @@ extern "C" int dfw_debug_tile_stamps(void* buf, int32_t tiles, int32_t grid_cap)
 }
 #endif
 
-extern "C" int dfw_version(void) { return 124; }
+extern "C" int dfw_version(void) { return 125; }
 
 extern "C" const char* dfw_error_string(int code) {
   switch (code) {

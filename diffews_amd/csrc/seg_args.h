@@ -50,4 +50,8 @@ inline int seg_check_buffers(const seg_buf (&t)[N]) {
   return 0;
 }
 
+// The launches of dfw_seg_components' nearest-seed stage (seeds non-null), in seg_boundary.hip, whose pair of passes they
+// are.  The entry point has validated a; nothing is checked there.
+int seg_nearest_launch(const dfw_seg_components_args* a, void* stream);
+
 }  // namespace dfw

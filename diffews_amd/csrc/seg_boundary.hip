@@ -59,6 +59,15 @@
 //                                 bnd_peaks_wave reduces it with one atomicMax per piece of equal id of a wave's lanes, none
 //                                 when the row already holds as much.
 //
+// The nearest seed inside the object (seg_nearest_launch, reached through dfw_seg_components with `seeds`; it lives here because
+// it is this file's pair of passes): per pixel of an int32 map the seed with the smallest (dy^2 + dx^2, value) that an L path
+// on the pixel's value reaches, the column first.  A row pass and a column pass of their own, described where they stand
+// below, 2 * passes launches; the workspace holds a value (int32) beside h.
+//
+//   0" seeds_row_kernel           boundary_row_kernel's window and scans, and the same scans over the seed positions
+//   1" seeds_col_kernel<V, LATER> boundary_col2_kernel's tile and V rule; walks each direction while the column holds the
+//                                 value and dy^2 <= the best so far; LATER (passes 2..) keeps what a pixel already holds
+//
 // Termination: in dfw_seg_boundary no thread waits for another thread or workgroup and, without peaks, no atomics are
 // used; every loop but the column walk has a trip count fixed at compile time, and the walk ends after at most dmax steps.
 // The peaks and the counts use global (and LDS) integer atomics, order-free, and wait for nothing.  Any grid is correct at
@@ -383,6 +392,228 @@ __global__ __launch_bounds__(256) void boundary_col2_kernel(const T* map, const 
   }
 }
 
+// ---- the nearest seed inside the object (version 125) ----
+// The workspace of the seeded call: lab int32 [B * H * W] (the seed value the row pass found, 0 for none), rounded up to 16
+// bytes, then h uint8 [B * H * W] (the distance along the row to it, 0..dmax, dmax + 1 for none).
+inline size_t bnd_seed_lab_bytes(size_t n) { return (n * 4 + 15) & ~(size_t)15; }
+
+// The row pass: boundary_row_kernel's window, breaks and scans, plus the same two scans over the positions that hold a
+// seed.  For a position i of the block: the last seed at or before i counts when no break lies behind it (last seed >= last
+// break), the next seed behind i when it lies before the next break -- both inside i's run of equal value.  The nearer one
+// wins, the smaller seed value among two equally near; h = its distance, dmax + 1 (cap) when there is none within dmax.
+// The halo of kBndHalo > dmax positions a side makes both final.  Seeds on background are found like any other and never
+// read: the column pass looks at rows of its own non-zero value only.
+__global__ __launch_bounds__(256) void seeds_row_kernel(const int32_t* map, const int32_t* seeds, int32_t* lab, uint8_t* hrow,
+                                                        int HW, int W, int cap) {
+  __shared__ __attribute__((aligned(16))) int val[kBndWin];
+  __shared__ __attribute__((aligned(16))) int sd[kBndWin];
+  __shared__ __attribute__((aligned(8))) uint8_t hb[kBndPos];
+  __shared__ int wlast[4], wfirst[4], wslast[4], wsfirst[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int p0 = blockIdx.x * kBndPos, w0 = p0 - kBndHalo;
+  const int32_t* mp = map + (size_t)blockIdx.y * HW;
+  const int32_t* sp = seeds + (size_t)blockIdx.y * HW;
+#pragma unroll
+  for (int r = 0; r < (kBndWin / 4 + 255) / 256; ++r) {
+    const int c = r * 256 + t;
+    if (c < kBndWin / 4) {
+      const int q = w0 + 4 * c;
+      i32x4 w, z;
+      if (q >= 0 && q + 4 <= HW && (((uintptr_t)(mp + q) | (uintptr_t)(sp + q)) & 15) == 0) {
+        w = *(const i32x4*)(mp + q);
+        z = *(const i32x4*)(sp + q);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const bool in = q + k >= 0 && q + k < HW;
+          w[k] = in ? mp[q + k] : 0;
+          z[k] = in ? sp[q + k] : 0;
+        }
+      }
+      *(i32x4*)(val + 4 * c) = w;
+      *(i32x4*)(sd + 4 * c) = z;
+    }
+  }
+  __syncthreads();
+  const int i0 = kBndOwn * t, q0 = w0 + i0;
+  int v[kBndOwn + 1];
+  v[0] = t ? val[i0 - 1] : 0;
+#pragma unroll
+  for (int j = 0; j < kBndOwn; ++j) v[j + 1] = val[i0 + j];
+  int x = q0 >= 0 ? q0 % W : 0;
+  int last = -1, first = kBndWin, slast = -1, sfirst = kBndWin, L[kBndOwn], S[kBndOwn];
+  unsigned brk = 0u, sbit = 0u;
+#pragma unroll
+  for (int j = 0; j < kBndOwn; ++j) {
+    const int q = q0 + j;
+    if (q < 0 || q >= HW || x == 0 || v[j + 1] != v[j] || i0 + j == 0) {
+      brk |= 1u << j;
+      last = i0 + j;
+      if (first == kBndWin) first = i0 + j;
+    }
+    if (sd[i0 + j] != 0) {                 // 0 outside the image
+      sbit |= 1u << j;
+      slast = i0 + j;
+      if (sfirst == kBndWin) sfirst = i0 + j;
+    }
+    L[j] = last;
+    S[j] = slast;
+    if (q >= 0 && ++x == W) x = 0;
+  }
+  int ls = last, fs = first, lss = slast, fss = sfirst;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int a = __shfl_up(ls, o, 64), c = __shfl_down(fs, o, 64);
+    const int sa = __shfl_up(lss, o, 64), sc = __shfl_down(fss, o, 64);
+    if (lane >= o) ls = max(ls, a), lss = max(lss, sa);
+    if (lane + o < 64) fs = min(fs, c), fss = min(fss, sc);
+  }
+  if (lane == 63) wlast[wave] = ls, wslast[wave] = lss;
+  if (lane == 0) wfirst[wave] = fs, wsfirst[wave] = fss;
+  int before = __shfl_up(ls, 1, 64), behind = __shfl_down(fs, 1, 64);
+  int sbefore = __shfl_up(lss, 1, 64), sbehind = __shfl_down(fss, 1, 64);
+  if (lane == 0) before = sbefore = -1;
+  if (lane == 63) behind = sbehind = kBndWin;
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (u < wave) before = max(before, wlast[u]), sbefore = max(sbefore, wslast[u]);
+    if (u > wave) behind = min(behind, wfirst[u]), sbehind = min(sbehind, wsfirst[u]);
+  }
+  int nb = behind, ns = sbehind, out[kBndOwn];
+#pragma unroll
+  for (int j = kBndOwn - 1; j >= 0; --j) {
+    const int i = i0 + j;
+    const int lb = max(L[j], before), lsd = max(S[j], sbefore);
+    const int dl = lsd >= lb ? i - lsd : cap, dr = ns < nb ? ns - i : cap;   // lb >= 0: the window's first position is a break
+    int h = min(min(dl, dr), cap), lv = 0;
+    if (h < cap) {
+      if (dl < dr) lv = sd[lsd];
+      else if (dr < dl) lv = sd[ns];
+      else lv = min(sd[lsd], sd[ns]);
+    }
+    out[j] = lv;
+    if (i >= kBndHalo && i < kBndHalo + kBndPos) hb[i - kBndHalo] = (uint8_t)h;
+    if (brk & (1u << j)) nb = i;
+    if (sbit & (1u << j)) ns = i;
+  }
+  __syncthreads();                         // every lookup of sd is done: it now carries the labels out
+#pragma unroll
+  for (int j = 0; j < kBndOwn; ++j) sd[i0 + j] = out[j];
+  __syncthreads();
+  const int p = p0 + 8 * t;
+  uint8_t* hp = hrow + (size_t)blockIdx.y * HW;
+  int32_t* lp = lab + (size_t)blockIdx.y * HW;
+  if (p + 8 <= HW && ((uintptr_t)(hp + p) & 7) == 0) {
+    *(u32x2*)(hp + p) = *(const u32x2*)(hb + 8 * t);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (p + k < HW) hp[p + k] = hb[8 * t + k];
+  }
+  if (p + 8 <= HW && ((uintptr_t)(lp + p) & 15) == 0) {
+    *(i32x4*)(lp + p) = *(const i32x4*)(sd + kBndHalo + 8 * t);
+    *(i32x4*)(lp + p + 4) = *(const i32x4*)(sd + kBndHalo + 8 * t + 4);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (p + k < HW) lp[p + k] = sd[kBndHalo + 8 * t + k];
+  }
+}
+
+// The column pass: boundary_col2_kernel's tile and threads.  A pixel of value v starts from its own row's (h^2, label) and
+// walks dy = 1, 2, ... up and down, each direction while the rows exist and the column holds v; row y +- dy offers (dy^2 +
+// h^2, label) when h <= R and the sum is <= R^2.  The smaller (distance, label) pair wins.  A later row can still tie the
+// best distance with a smaller label (only with h = 0 there), so the walk goes on while dy^2 <= the best so far, not <, and
+// at most R steps; dy^2 + h^2 <= 2 * 254^2.  Labels come from the workspace only, never from `nearest`, which this launch
+// writes: a repeat in place is safe.  LATER (passes 2..): a pixel whose own row distance is 0 holds a value already and keeps
+// it and its dist -- its label is rewritten with itself, its old dist is read back and stored, by the one thread that owns
+// the pixel -- and its walk is skipped.
+template <int V, bool LATER>
+__global__ __launch_bounds__(256) void seeds_col_kernel(const int32_t* map, const int32_t* lab, const uint8_t* hrow,
+                                                        int32_t* nearest, uint16_t* dist, int H, int W, int R) {
+  constexpr int TX = kBndCols / V, TY = 256 / TX;
+  constexpr int kNone = 0x7fffffff;
+  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+  const int x = blockIdx.x * kBndCols + tx * V;
+  if (x >= W) return;                               // V == 4 only with W % 4 == 0: x < W covers x + 3
+  const size_t img = (size_t)blockIdx.z * H * W;
+  const int R2 = R * R, none = (R + 1) * (R + 1);
+#pragma unroll
+  for (int r = 0; r < kBndRows / TY; ++r) {
+    const int y = blockIdx.y * kBndRows + r * TY + ty;
+    if (y >= H) return;
+    const size_t o = img + (size_t)y * W + x;
+    int v[V], h0[V], best[V], bl[V], keep[V];
+    bool up[V], dn[V];
+    bnd_load<int32_t, V>(map + o, v);
+    bnd_load<uint8_t, V>(hrow + o, h0);
+    bnd_load<int32_t, V>(lab + o, bl);
+    if constexpr (LATER) {
+      if constexpr (V == 4) {
+        const u32x2 w = *(const u32x2*)(dist + o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) keep[k] = (int)((w[k >> 1] >> (16 * (k & 1))) & 65535u);
+      } else {
+        keep[0] = dist[o];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const bool walk = v[k] != 0 && !(LATER && h0[k] == 0);
+      best[k] = h0[k] <= R ? h0[k] * h0[k] : kNone;
+      if (best[k] == kNone) bl[k] = 0;
+      up[k] = dn[k] = walk;
+    }
+    for (int dy = 1; dy <= R; ++dy) {
+      const int dd = dy * dy;
+      const bool rowu = y - dy >= 0, rowd = y + dy < H;
+      bool gu = false, gd = false;
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        up[k] = up[k] && rowu && dd <= best[k];
+        dn[k] = dn[k] && rowd && dd <= best[k];
+        gu = gu || up[k];
+        gd = gd || dn[k];
+      }
+      if (!gu && !gd) break;
+      const size_t s = (size_t)dy * W;
+      if (gu) {
+        int m[V], hh[V], ll[V];
+        bnd_load<int32_t, V>(map + o - s, m);
+        bnd_load<uint8_t, V>(hrow + o - s, hh);
+        bnd_load<int32_t, V>(lab + o - s, ll);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          up[k] = up[k] && m[k] == v[k];
+          const int c = dd + hh[k] * hh[k];
+          if (up[k] && hh[k] <= R && c <= R2 && (c < best[k] || (c == best[k] && ll[k] < bl[k]))) best[k] = c, bl[k] = ll[k];
+        }
+      }
+      if (gd) {
+        int m[V], hh[V], ll[V];
+        bnd_load<int32_t, V>(map + o + s, m);
+        bnd_load<uint8_t, V>(hrow + o + s, hh);
+        bnd_load<int32_t, V>(lab + o + s, ll);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          dn[k] = dn[k] && m[k] == v[k];
+          const int c = dd + hh[k] * hh[k];
+          if (dn[k] && hh[k] <= R && c <= R2 && (c < best[k] || (c == best[k] && ll[k] < bl[k]))) best[k] = c, bl[k] = ll[k];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      if (v[k] == 0) best[k] = 0, bl[k] = 0;
+      else if (LATER && h0[k] == 0) best[k] = keep[k];
+      else if (best[k] == kNone) best[k] = none;
+    }
+    bnd_store<int32_t, V>(nearest + o, bl);
+    bnd_store16<V>(dist + o, best);
+  }
+}
+
 __global__ __launch_bounds__(256) void boundary_zero_kernel(unsigned long long* words, int n) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < n) words[e] = 0ull;
@@ -485,6 +716,36 @@ static void boundary_launch(hipStream_t st, const dfw_seg_boundary_args* a, bool
                        (uint8_t*)a->dist, (T*)a->band, a->H, a->W, cap, a->d);
 }
 
+// The launches of the nearest-seed stage of dfw_seg_components (seeds non-null), which has validated everything: 2 * passes,
+// pass k > 1 with seeds := nearest in place.
+int seg_nearest_launch(const dfw_seg_components_args* a, void* stream) {
+  const int HW = a->H * a->W;
+  const size_t n = (size_t)a->B * HW;
+  hipStream_t st = (hipStream_t)stream;
+  // four pixels a thread: whole words of map, nearest, dist and both planes of the workspace, in every row of every image
+  const bool vec = a->W % 4 == 0 && (((uintptr_t)a->map | (uintptr_t)a->nearest | (uintptr_t)a->ws) & 15) == 0 &&
+                   ((uintptr_t)a->dist & 7) == 0;
+  int32_t* lab = (int32_t*)a->ws;
+  uint8_t* h = (uint8_t*)a->ws + bnd_seed_lab_bytes(n);
+  const dim3 rgrid((HW + kBndPos - 1) / kBndPos, a->B);
+  const dim3 grid((a->W + kBndCols - 1) / kBndCols, (a->H + kBndRows - 1) / kBndRows, a->B);
+  uint16_t* dist = (uint16_t*)a->dist;
+  for (int k = 0; k < a->passes; ++k) {
+    hipLaunchKernelGGL(seeds_row_kernel, rgrid, dim3(256), 0, st, a->map, k ? (const int32_t*)a->nearest : a->seeds, lab, h, HW,
+                       a->W, a->reach + 1);
+    DFW_CHECK_LAUNCH();
+    if (k == 0) {
+      if (vec) hipLaunchKernelGGL((seeds_col_kernel<4, false>), grid, dim3(256), 0, st, a->map, lab, h, a->nearest, dist, a->H, a->W, a->reach);
+      else hipLaunchKernelGGL((seeds_col_kernel<1, false>), grid, dim3(256), 0, st, a->map, lab, h, a->nearest, dist, a->H, a->W, a->reach);
+    } else {
+      if (vec) hipLaunchKernelGGL((seeds_col_kernel<4, true>), grid, dim3(256), 0, st, a->map, lab, h, a->nearest, dist, a->H, a->W, a->reach);
+      else hipLaunchKernelGGL((seeds_col_kernel<1, true>), grid, dim3(256), 0, st, a->map, lab, h, a->nearest, dist, a->H, a->W, a->reach);
+    }
+    DFW_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 }  // namespace dfw
 
 using namespace dfw;
@@ -492,6 +753,12 @@ using namespace dfw;
 extern "C" size_t dfw_seg_boundary_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t elem) {
   if ((elem != 1 && elem != 4) || seg_map_size_error(B, H, W)) return 0;
   return ((size_t)B * H * W + 15) & ~(size_t)15;   // h, one byte a pixel
+}
+
+extern "C" size_t dfw_seg_nearest_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+  if (seg_map_size_error(B, H, W)) return 0;
+  const size_t n = (size_t)B * H * W;
+  return bnd_seed_lab_bytes(n) + ((n + 15) & ~(size_t)15);   // lab, four bytes a pixel, and h, one
 }
 
 extern "C" int dfw_seg_boundary_block(int32_t* rows, int32_t* cols, int32_t* positions) {

@@ -27,6 +27,13 @@
 //                            (tile, local component) and field, only for ids <= cap (y0 is the first pixel's row)
 //
 // Launches 1 to 3, the grids' sizing and the argument why every loop ends are seg_unionfind.h's, shared with seg_holes.hip.
+//
+// keys (optional int32 [B][H][W], version 125): launches 1 and 2 are cc_tile_keyed_kernel / cc_merge_keyed_kernel, the same
+// bodies comparing (byte, key) pairs; a pixel is a member by its byte alone, so numbering, filter, stats (the label column
+// is the byte), counts, the launch count and the workspace are unchanged.
+//
+// seeds (version 125): the call is then the nearest-seed stage (validated here, launched by seg_nearest_launch, seg_boundary.hip) on map, seeds, nearest,
+// dist, reach, passes and the workspace of dfw_seg_nearest_workspace_bytes; none of the launches above runs.
 #include "common.h"
 #include "seg_args.h"
 #include "seg_fuse.h"
@@ -52,6 +59,18 @@ __global__ __launch_bounds__(256) void cc_tile_kernel(const uint8_t* labels, int
 __global__ __launch_bounds__(256) void cc_merge_kernel(const uint8_t* labels, int32_t* parent, int H, int W, int ntx, int nty,
                                                        int conn8) {
   cc_merge_body<cc_key_label>(labels, parent, H, W, ntx, nty, conn8);
+}
+
+// ... and on (byte, key) pairs (version 125, `keys`): equal non-zero bytes with equal keys join.  Everything behind the
+// merge reads parent and area only, so launches 3 to 7 are the keyless ones.
+__global__ __launch_bounds__(256) void cc_tile_keyed_kernel(const uint8_t* labels, const int32_t* keys, int32_t* parent,
+                                                            int32_t* area, int H, int W, int conn8) {
+  cc_tile_body<cc_key_label, true>(labels, parent, area, H, W, conn8, keys);
+}
+
+__global__ __launch_bounds__(256) void cc_merge_keyed_kernel(const uint8_t* labels, const int32_t* keys, int32_t* parent, int H,
+                                                             int W, int ntx, int nty, int conn8) {
+  cc_merge_body<cc_key_label, true>(labels, parent, H, W, ntx, nty, conn8, keys);
 }
 
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int32_t* parent, int32_t* area, int HW) {
@@ -319,6 +338,19 @@ extern "C" int dfw_seg_components_rounds(int32_t B, int32_t H, int32_t W, const 
 }
 
 extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream) {
+  if (a && a->seeds) {                                     // the nearest-seed stage: its own fields, its own checks
+    if (!a->map || !a->nearest || !a->dist || !a->ws) return DFW_EINVAL;
+    if (a->reach < 1 || a->reach > 254) return DFW_EINVAL;
+    if (a->passes < 1 || a->passes > 8) return DFW_EINVAL;
+    if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
+    const size_t wsb = dfw_seg_nearest_workspace_bytes(a->B, a->H, a->W);
+    if (a->ws_bytes < wsb) return DFW_EWORKSPACE;
+    const size_t px = (size_t)a->B * a->H * a->W;
+    const seg_buf bufs[] = {seg_in(a->map, px * 4, 4), seg_in(a->seeds, px * 4, 4), seg_out(a->dist, px * 2, 2),
+                            seg_out(a->ws, wsb, 4), seg_out(a->nearest, px * 4, 4)};
+    if (int e = seg_check_buffers(bufs)) return e;
+    return seg_nearest_launch(a, stream);
+  }
   if (!a || !a->labels || !a->ids || !a->n || !a->ws) return DFW_EINVAL;
   if (a->B < 1 || a->H < 1 || a->W < 1) return DFW_EINVAL;
   if (a->connectivity != 4 && a->connectivity != 8) return DFW_EINVAL;
@@ -326,6 +358,7 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
   if (a->stats && a->cap < 1) return DFW_EINVAL;
   if (a->counts && !a->gt) return DFW_EINVAL;
   if (a->gt && (a->nlabels < 1 || a->nlabels > 254)) return DFW_EINVAL;
+  if (a->nearest) return DFW_EINVAL;                       // nearest without seeds
   if (int e = seg_map_size_error(a->B, a->H, a->W)) return e;
   if (a->stats && (long long)a->B * a->cap * 8 > 0x7fffffffll) return DFW_ERANGE;   // seg_zero_launch counts in int
   if (a->ws_bytes < dfw_seg_components_workspace_bytes(a->B, a->H, a->W)) return DFW_EWORKSPACE;
@@ -338,7 +371,8 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
                           seg_out(a->filtered, px),
                           seg_out(a->stats, (size_t)B * a->cap * 32, 4),
                           seg_out(a->counts, (size_t)B * 2 * (a->nlabels + 1) * 8, 8),
-                          seg_out(a->ws, dfw_seg_components_workspace_bytes(B, H, W), 4)};
+                          seg_out(a->ws, dfw_seg_components_workspace_bytes(B, H, W), 4),
+                          seg_in(a->keys, px * 4, 4)};
   if (int e = seg_check_buffers(bufs)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int ntx = (W + kCcTW - 1) / kCcTW, nty = (H + kCcTH - 1) / kCcTH, nblk = (int)cc_blocks(HW);
@@ -349,12 +383,20 @@ extern "C" int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t
   if (int e = seg_zero_launch(st, (uint32_t*)a->stats, a->stats ? B * a->cap * 8 : 0, want_counts ? a->counts : nullptr,
                               want_counts ? B * 2 * (a->nlabels + 1) : 0))
     return e;
-  hipLaunchKernelGGL(cc_tile_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, parent, area, H, W, conn8);
+  if (a->keys)
+    hipLaunchKernelGGL(cc_tile_keyed_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, a->keys, parent, area, H, W,
+                       conn8);
+  else
+    hipLaunchKernelGGL(cc_tile_kernel, dim3(ntx, nty, B), dim3(256), 0, st, a->labels, parent, area, H, W, conn8);
   DFW_CHECK_LAUNCH();
   const long long items = cc_merge_items(H, W);
   if (items > 0) {
-    hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_merge_grid(items), B), dim3(256), 0, st, a->labels, parent, H, W, ntx, nty,
-                       conn8);
+    if (a->keys)
+      hipLaunchKernelGGL(cc_merge_keyed_kernel, dim3(cc_merge_grid(items), B), dim3(256), 0, st, a->labels, a->keys, parent, H,
+                         W, ntx, nty, conn8);
+    else
+      hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_merge_grid(items), B), dim3(256), 0, st, a->labels, parent, H, W, ntx, nty,
+                         conn8);
     DFW_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_flatten_grid(HW), B), dim3(256), 0, st, parent, area, HW);

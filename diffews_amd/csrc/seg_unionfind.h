@@ -12,6 +12,13 @@
 // every other pixel: a pixel is two hops from its root.  area holds the set's pixel count at the root, the tile-local count
 // (> 0) at every other tile-local root and 0 elsewhere.
 //
+// A second plane (template parameter K, seg_components with `keys`): int32 keys [B][H][W], compared for equality only.  Two
+// neighbouring members then join when their bytes AND their keys are equal; membership is still the byte's alone.  The
+// tile pass keeps the keys of its pixels in LDS (8 KB more).  The shortcut "upper diagonals only where the upper pixel
+// differs" holds for the combined comparison as it stands: an upper pixel that is equal in both parts is joined to every
+// diagonal neighbour that is equal to this pixel in both parts, by that neighbour's own left or this pixel's upper union.
+// With K = false nothing of it is compiled: the bodies are the keyless ones.
+//
 // Termination: no thread waits for another thread or workgroup.  Every loop is a find, which reads strictly decreasing
 // indices (it stops at any word that is not smaller than the index it was read at, so even a damaged workspace cannot send
 // it round or outside), or a union's retry, where a failed atomicMin replaces the larger root by a strictly smaller index.
@@ -80,11 +87,13 @@ __device__ __forceinline__ void g_union(int32_t* par, int a, int b) {
 // One workgroup of 256 per kCcTH x kCcTW tile, grid (ntx, nty, B): union-find of the tile in LDS.  Every pixel gets parent
 // = its tile-local root (the tile-local set's smallest index, as a GLOBAL index; -1 for a pixel that is no member) and area
 // = the tile-local set's pixel count at that local root, 0 elsewhere.
-template <class Key>
-__device__ __forceinline__ void cc_tile_body(const uint8_t* labels, int32_t* parent, int32_t* area, int H, int W, int conn8) {
+template <class Key, bool K = false>
+__device__ __forceinline__ void cc_tile_body(const uint8_t* labels, int32_t* parent, int32_t* area, int H, int W, int conn8,
+                                             const int32_t* keys = nullptr) {
   __shared__ uint32_t lab4[kCcWords];
   __shared__ int par[kCcTile];
   __shared__ int cnt[kCcTile];
+  __shared__ __attribute__((aligned(16))) int kk[K ? kCcTile : 4];   // the keys of the tile's pixels, K only
   const uint8_t* lab = (const uint8_t*)lab4;
   const int ty0 = blockIdx.y * kCcTH, tx0 = blockIdx.x * kCcTW;
   const size_t img = (size_t)blockIdx.z * H * W;
@@ -112,10 +121,25 @@ __device__ __forceinline__ void cc_tile_body(const uint8_t* labels, int32_t* par
       par[4 * w + j] = 4 * w + j;
       cnt[4 * w + j] = 0;
     }
+    if constexpr (K) {
+      const int32_t* Q = keys + img;
+      const size_t o = (size_t)y * W + x;
+      if (y < H && x < W && vec && ((uintptr_t)keys & 15) == 0) {
+        *(i32x4*)(kk + 4 * w) = *(const i32x4*)(Q + o);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kk[4 * w + j] = (y < H && x + j < W) ? Q[o + j] : 0;
+      }
+    }
   }
   __syncthreads();
+  // equal in the byte (c, this pixel's, non-zero) and, with keys, in the key
+  auto same = [&](int l, int m, uint8_t c) -> bool {
+    if constexpr (K) return lab[m] == c && kk[m] == kk[l];
+    else return lab[m] == c;
+  };
   // a pixel joins its left and upper neighbour; with 8 neighbours the two upper diagonals only where the upper one is
-  // another byte (else they reach this pixel through it)
+  // another byte, or another key (else they reach this pixel through it)
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int w = threadIdx.x + 256 * k, ly = w >> 4;
@@ -124,13 +148,13 @@ __device__ __forceinline__ void cc_tile_body(const uint8_t* labels, int32_t* par
       const int l = 4 * w + j, lx = l & (kCcTW - 1);
       const uint8_t c = lab[l];
       if (c == 0) continue;
-      if (lx > 0 && lab[l - 1] == c) lds_union(par, l, l - 1);
+      if (lx > 0 && same(l, l - 1, c)) lds_union(par, l, l - 1);
       if (ly > 0) {
-        if (lab[l - kCcTW] == c) {
+        if (same(l, l - kCcTW, c)) {
           lds_union(par, l, l - kCcTW);
         } else if (conn8) {
-          if (lx > 0 && lab[l - kCcTW - 1] == c) lds_union(par, l, l - kCcTW - 1);
-          if (lx < kCcTW - 1 && lab[l - kCcTW + 1] == c) lds_union(par, l, l - kCcTW + 1);
+          if (lx > 0 && same(l, l - kCcTW - 1, c)) lds_union(par, l, l - kCcTW - 1);
+          if (lx < kCcTW - 1 && same(l, l - kCcTW + 1, c)) lds_union(par, l, l - kCcTW + 1);
         }
       }
     }
@@ -187,12 +211,17 @@ __device__ __forceinline__ void cc_tile_body(const uint8_t* labels, int32_t* par
 // One thread per pixel on a tile's left column or top row, grid (cc_merge_grid, B): unions across the border with global
 // atomicMin.  A pair that the pixel before it on the border already joins is skipped.  Items of an image: (ntx - 1) * H
 // pixels on the left column of a tile (not the image's), then (nty - 1) * W on a top row.
-template <class Key>
+template <class Key, bool K = false>
 __device__ __forceinline__ void cc_merge_body(const uint8_t* labels, int32_t* parent, int H, int W, int ntx, int nty,
-                                              int conn8) {
+                                              int conn8, const int32_t* keys = nullptr) {
   const size_t img = (size_t)blockIdx.y * H * W;
   const uint8_t* L = labels + img;
   int32_t* P = parent + img;
+  // pixel m equals pixel a, whose byte la is non-zero, in the byte and, with keys, in the key
+  auto same = [&](int a, int m, uint8_t la) -> bool {
+    if constexpr (K) return Key::byte(L[m]) == la && keys[img + m] == keys[img + a];
+    else return Key::byte(L[m]) == la;
+  };
   const long long nv = (long long)(ntx - 1) * H, total = nv + (long long)(nty - 1) * W;
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
     if (t < nv) {
@@ -200,13 +229,13 @@ __device__ __forceinline__ void cc_merge_body(const uint8_t* labels, int32_t* pa
       const int a = y * W + x;
       const uint8_t la = Key::byte(L[a]);
       if (la == 0) continue;
-      if (Key::byte(L[a - 1]) == la) {
+      if (same(a, a - 1, la)) {
         // the pixel above joins the same two tile-local components
-        const bool dup = (y % kCcTH) != 0 && Key::byte(L[a - W]) == la && Key::byte(L[a - W - 1]) == la;
+        const bool dup = (y % kCcTH) != 0 && same(a, a - W, la) && same(a, a - W - 1, la);
         if (!dup) g_union(P, a, a - 1);
       } else if (conn8) {
-        if (y > 0 && Key::byte(L[a - W - 1]) == la) g_union(P, a, a - W - 1);
-        if (y + 1 < H && Key::byte(L[a + W - 1]) == la) g_union(P, a, a + W - 1);
+        if (y > 0 && same(a, a - W - 1, la)) g_union(P, a, a - W - 1);
+        if (y + 1 < H && same(a, a + W - 1, la)) g_union(P, a, a + W - 1);
       }
     } else {
       const long long u = t - nv;
@@ -214,12 +243,12 @@ __device__ __forceinline__ void cc_merge_body(const uint8_t* labels, int32_t* pa
       const int a = y * W + x, up = a - W;
       const uint8_t la = Key::byte(L[a]);
       if (la == 0) continue;
-      if (Key::byte(L[up]) == la) {
-        const bool dup = (x % kCcTW) != 0 && Key::byte(L[a - 1]) == la && Key::byte(L[up - 1]) == la;
+      if (same(a, up, la)) {
+        const bool dup = (x % kCcTW) != 0 && same(a, a - 1, la) && same(a, up - 1, la);
         if (!dup) g_union(P, a, up);
       } else if (conn8) {
-        if (x > 0 && Key::byte(L[up - 1]) == la) g_union(P, a, up - 1);
-        if (x + 1 < W && Key::byte(L[up + 1]) == la) g_union(P, a, up + 1);
+        if (x > 0 && same(a, up - 1, la)) g_union(P, a, up - 1);
+        if (x + 1 < W && same(a, up + 1, la)) g_union(P, a, up + 1);
       }
     }
   }

@@ -43,11 +43,16 @@ the id map to its own contour (ops.seg_boundary with metric="euclidean", which b
 well) and, per object, the largest of them with its first position -- radius and centre of the largest inscribed circle, a
 label point inside the object and the measure a min-thickness rule needs; thickness_to_host brings the table to the host.
 object_cores labels the pixels farther than a radius from the contour again: touching objects of one class fall apart.
+
+split_objects grows those cores back into full INSTANCES: every object pixel takes the core that an L path inside its
+object reaches first (nearest_seeds, ops_split.seg_nearest), and the object's labels are labelled again with that core as
+a second key (label_objects(..., keys=), ops_split.seg_components_keyed).  The result is a label_objects result -- every
+stage above takes it as it stands -- that also says which object each instance came from.
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, ops_split
 
 
 # ------------------------------------------------------------------------------------------------ what the stages share
@@ -130,9 +135,9 @@ class ComponentBuffers:
     counts = _cached_counts
 
 
-def _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers):
+def _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers, keys=None):
     squeeze = labels.dim() == 2
-    labels, gt = _lift(squeeze, labels, gt)
+    labels, gt, keys = _lift(squeeze, labels, gt, keys)
     if labels.dim() != 3 or labels.dtype != torch.uint8 or not labels.is_cuda:
         raise ValueError("label_objects takes a uint8 device tensor [H, W] or [B, H, W], or a list of [h, w] maps")
     labels = labels.contiguous()
@@ -148,12 +153,19 @@ def _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers):
         if gt.dtype != torch.uint8 or gt.shape != labels.shape:
             raise ValueError("label_objects: gt must be uint8 and shaped like the labels")
         gt, counts = gt.contiguous(), buffers.counts(int(nlabels))
-    ops.seg_components(labels, buffers.ids, buffers.n, buffers.ws, filtered=buffers.labels, stats=buffers.stats, gt=gt,
-                       counts=counts, connectivity=connectivity, min_area=min_area, nlabels=nlabels)
+    if keys is not None:
+        if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int32 or keys.shape != labels.shape:
+            raise ValueError("label_objects: keys must be an int32 tensor shaped like the labels")
+        ops_split.seg_components_keyed(labels, keys.contiguous(), buffers.ids, buffers.n, buffers.ws, filtered=buffers.labels,
+                                       stats=buffers.stats, gt=gt, counts=counts, connectivity=connectivity, min_area=min_area,
+                                       nlabels=nlabels)
+    else:
+        ops.seg_components(labels, buffers.ids, buffers.n, buffers.ws, filtered=buffers.labels, stats=buffers.stats, gt=gt,
+                           counts=counts, connectivity=connectivity, min_area=min_area, nlabels=nlabels)
     return _unlift(squeeze, dict(ids=buffers.ids, labels=buffers.labels, n=buffers.n, stats=buffers.stats, counts=counts))
 
 
-def label_objects(labels, gt=None, connectivity=8, min_area=0, max_components=1024, nlabels=None, buffers=None):
+def label_objects(labels, gt=None, connectivity=8, min_area=0, max_components=1024, nlabels=None, buffers=None, keys=None):
     """Connected components of a label map.  labels: a uint8 device tensor [H, W] or [B, H, W] (0 = background; pixels of
     the same non-zero byte joined over `connectivity` = 4 | 8 neighbours are one object; different bytes never merge), or a
     LIST of [h_i, w_i] maps of different sizes, as the native-size routes return them.  An object with fewer than min_area
@@ -170,12 +182,16 @@ def label_objects(labels, gt=None, connectivity=8, min_area=0, max_components=10
     A [H, W] input gives the same without the batch axis.  A list is handled with ONE CALL PER ITEM -- ragged sizes do not
     share a launch -- and every value of the result is then a list; `gt` is a list too and `buffers` a list of
     ComponentBuffers or None.  buffers: a ComponentBuffers of this shape, reused call after call (the result then aliases
-    it); without it fresh buffers are allocated.  A fixed number of launches per call and no host synchronisation."""
+    it); without it fresh buffers are allocated.  A fixed number of launches per call and no host synchronisation.
+
+    keys (optional): an int32 tensor shaped like the labels (a list for a list), compared for equality only.  Two
+    neighbouring pixels then join only when their keys are equal as well; 0 and negative values are keys like any other,
+    and a pixel is an object pixel by its byte alone.  Everything else is unchanged, stats' label column included."""
     if isinstance(labels, (list, tuple)):
-        return _per_item(lambda i, g, b: _one(labels[i], g, connectivity, min_area, max_components, nlabels, b), len(labels),
-                         (gt, buffers), "label_objects: one gt / buffers entry per label map",
+        return _per_item(lambda i, g, b, k: _one(labels[i], g, connectivity, min_area, max_components, nlabels, b, k),
+                         len(labels), (gt, buffers, keys), "label_objects: one gt / buffers / keys entry per label map",
                          ("ids", "labels", "n", "stats", "counts"))
-    return _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers)
+    return _one(labels, gt, connectivity, min_area, max_components, nlabels, buffers, keys)
 
 
 def objects_to_host(r):
@@ -1206,3 +1222,136 @@ def object_cores(o, radius, **label_objects_kwargs):
         per = [_cores_one({k: v[i] for k, v in o.items()}, radius, dict(kw, gt=gts[i])) for i in range(len(o["ids"]))]
         return {key: [p[key] for p in per] for key in per[0]}
     return _cores_one(o, radius, label_objects_kwargs)
+
+
+# ------------------------------------------------------------------------------------------------ instances
+
+_SPLIT_KEYS = ("ids", "labels", "n", "stats", "counts", "parent", "cores", "nearest")
+
+
+class SplitBuffers:
+    """Everything one split_objects call of a shape writes, allocated once: `thick` (BoundaryBuffers of the Euclidean
+    distance, with peaks), `seeds` (ComponentBuffers of the cores), nearest int32 [B, H, W], dist uint16 [B, H, W] and ws
+    (what nearest_seeds writes, which takes these buffers as well), `out` (ComponentBuffers of the instances) and parent
+    int32 [B, max_components].  max_components: the rows of the stats table of the result that is split, and of both
+    tables made here.  A later call with the same buffers overwrites them."""
+
+    def __init__(self, B, H, W, max_components=1024, device="cuda"):
+        self.shape, self.max_components = (int(B), int(H), int(W)), int(max_components)
+        if self.max_components < 1:
+            raise ValueError("max_components must be at least 1")
+        nbytes = ops_split.seg_nearest_workspace(*self.shape)
+        if nbytes == 0:
+            raise ValueError(f"seg_nearest refuses these sizes: {self.shape}")
+        dev = torch.device(device)
+        self.nearest = torch.empty(self.shape, dtype=torch.int32, device=dev)
+        self.device = self.nearest.device
+        self.dist = torch.empty(self.shape, dtype=torch.uint16, device=dev)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.parent = torch.empty(self.shape[0], self.max_components, dtype=torch.int32, device=dev)
+        self.thick = BoundaryBuffers(B, H, W, _BOUNDARY_DMAX, torch.int32, dev, "euclidean", self.max_components)
+        self.seeds = ComponentBuffers(B, H, W, self.max_components, dev)
+        self.out = ComponentBuffers(B, H, W, self.max_components, dev)
+
+
+def _nearest_one(ids, seeds, reach, passes, buffers):
+    squeeze = ids.dim() == 2
+    ids, seeds = _lift(squeeze, ids, seeds)
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_cuda:
+        raise ValueError("nearest_seeds takes an int32 device map [H, W] or [B, H, W], or a list of [h, w] maps")
+    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.int32 or seeds.shape != ids.shape:
+        raise ValueError("nearest_seeds: seeds must be an int32 tensor shaped like the map")
+    if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or not 1 <= reach <= _BOUNDARY_DMAX:
+        raise ValueError(f"nearest_seeds: reach must be an integer in 1..{_BOUNDARY_DMAX}, got {reach!r}")
+    if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= passes <= 8:
+        raise ValueError(f"nearest_seeds: passes must be an integer in 1..8, got {passes!r}")
+    B, H, W = ids.shape
+    if buffers is None:
+        nearest = torch.empty_like(ids, memory_format=torch.contiguous_format)
+        dist = torch.empty(B, H, W, dtype=torch.uint16, device=ids.device)
+        ws = torch.empty(ops_split.seg_nearest_workspace(B, H, W), dtype=torch.uint8, device=ids.device)
+    elif buffers.shape != (B, H, W) or buffers.device != ids.device:
+        raise ValueError(f"buffers were made for {buffers.shape} on {buffers.device}, the map is {(B, H, W)} on {ids.device}")
+    else:
+        nearest, dist, ws = buffers.nearest, buffers.dist, buffers.ws
+    ops_split.seg_nearest(ids.contiguous(), seeds.contiguous(), nearest, dist, ws, int(reach), int(passes))
+    return _unlift(squeeze, dict(nearest=nearest, dist=dist, reach=int(reach), passes=int(passes), shape=(H, W)))
+
+
+def nearest_seeds(ids, seeds, reach, passes=1, buffers=None):
+    """For every pixel of an id map, the nearest seed that an L path INSIDE its object reaches (ops_split.seg_nearest).
+    ids: an int32 device tensor [H, W] or [B, H, W] (0 = background, values compared for equality only), or a list of
+    [h_i, w_i] maps; seeds: int32, shaped like it, every non-zero value a seed -- any map, not only cores.  A candidate
+    of pixel (y, x) is a seed (y + dy, x + dx) with dy^2 + dx^2 <= reach^2 (reach 1..254) such that column x from row y to
+    row y + dy and then row y + dy from x to x + dx hold the pixel's id; the candidate with the smallest (dy^2 + dx^2, seed
+    value) wins.  passes (1..8) repeats that with the result as seeds: a pixel that holds a value keeps it, the others look
+    again, so each pass carries every label round one more bend.  buffers: a SplitBuffers of this shape, or None.
+
+    Returns dict(nearest, dist, reach, passes, shape) on the device: nearest int32, the winner's value, 0 without a
+    candidate and on background; dist uint16, 0 on a seed and on background, else the winner's dy^2 + dx^2 (in the pass
+    that gave the pixel its value), (reach + 1)^2 without a candidate.  2 * passes launches and no host synchronisation."""
+    if isinstance(ids, (list, tuple)):
+        if not isinstance(seeds, (list, tuple)) or len(seeds) != len(ids):
+            raise ValueError("nearest_seeds: one seed map per id map")
+        return _per_item(lambda i, b: _nearest_one(ids[i], seeds[i], reach, passes, b), len(ids), (buffers,),
+                         "nearest_seeds: one buffers entry per item", ("nearest", "dist", "reach", "passes", "shape"))
+    return _nearest_one(ids, seeds, reach, passes, buffers)
+
+
+def _split_one(o, radius, reach, passes, min_area, connectivity, buffers):
+    squeeze = o["ids"].dim() == 2
+    ids, labels, n, stats = _lift(squeeze, o["ids"], o["labels"], o["n"], o["stats"])
+    if ids.dim() != 3 or ids.dtype != torch.int32 or labels.dtype != torch.uint8 or labels.shape != ids.shape or not ids.is_cuda:
+        raise ValueError("split_objects takes a label_objects or fill_holes result")
+    B, H, W = ids.shape
+    cap = stats.shape[-2]
+    if buffers is not None and (buffers.shape != (B, H, W) or buffers.device != ids.device or buffers.max_components != cap):
+        raise ValueError(f"split_objects: the buffers must be SplitBuffers({B}, {H}, {W}, max_components={cap}) on {ids.device}")
+    o3 = dict(ids=ids, labels=labels, n=n, stats=stats)
+    t = object_thickness(o3, dmax=max(radius, 1), buffers=buffers.thick if buffers else None)
+    d2 = t["dist2"].view(torch.int16).to(torch.int32) & 0xFFFF       # uint16 as integers every torch op takes
+    core = torch.where(d2 > radius * radius, labels, torch.zeros_like(labels))
+    cores = label_objects(core, connectivity=connectivity, max_components=cap, buffers=buffers.seeds if buffers else None)
+    near = nearest_seeds(ids, cores["ids"], reach, passes, buffers)
+    r = label_objects(labels, connectivity=connectivity, min_area=min_area, max_components=cap,
+                      buffers=buffers.out if buffers else None, keys=near["nearest"])
+    # parent: o's id at every instance's first pixel, 0 behind the last instance
+    first = r["stats"][..., 6].to(torch.int64)
+    rows = torch.arange(cap, device=ids.device)[None] < r["n"][:, :1]
+    parent = torch.where(rows, torch.gather(ids.reshape(B, H * W), 1, first), torch.zeros((), dtype=torch.int32, device=ids.device))
+    if buffers is not None:
+        parent = buffers.parent.copy_(parent)
+    return _unlift(squeeze, dict(r, parent=parent, cores=cores["n"], nearest=near["nearest"]))
+
+
+def split_objects(o, radius, reach=None, passes=3, min_area=0, buffers=None, connectivity=8):
+    """Touching objects as separate INSTANCES: the cores of a label_objects or fill_holes result o (object_cores' rule:
+    the pixels with dist2 > radius^2, labelled again) grown back over their objects.  A composition: object_thickness(o,
+    dmax=radius), the cores, nearest_seeds(o's ids, the cores' ids, reach, passes), then label_objects(o's labels,
+    keys=nearest, connectivity, min_area, max_components=rows of o's stats).  radius: an integer in 0..254.  reach: how far
+    a pixel looks for a core, by default min(254, 2 * radius + 2); passes: 3 by default.  Both defaults are choices, not
+    measurements: a pixel within `radius` of a core pixel is always reached in one pass when reach >= radius, the rest of a
+    ragged object takes bends, one per pass.  connectivity: the one o was labelled with (a result does not carry it), used
+    for the cores and for the instances.  buffers: a SplitBuffers of o's shape and rows, or None (a list for a list).
+
+    An object without a core keeps key 0 everywhere and comes out as the one object it was.  Pixels of an object with a
+    core that no pass reaches keep key 0 as well and form instances of their own; min_area removes them like any speck.
+
+    Returns a label_objects result of the instances -- ids, labels, n, stats, counts (None) -- which every stage that takes
+    one takes unchanged, with three more entries:
+      parent   int32 [.., max_components]: row k - 1 = the id in o of instance k (o's id at the instance's first pixel), 0
+               from row min(n, max_components) on
+      cores    the cores' n, int32 [.., 2]
+      nearest  int32 [.., H, W], nearest_seeds' map: the core id every pixel took, 0 for none
+    A list result is handled with one call per item.  No host synchronisation."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= _BOUNDARY_DMAX:
+        raise ValueError(f"split_objects: radius must be an integer in 0..{_BOUNDARY_DMAX}, got {radius!r}")
+    if not isinstance(o, dict) or any(k not in o for k in ("ids", "labels", "stats", "n")):
+        raise ValueError("split_objects takes a label_objects or fill_holes result")
+    radius = int(radius)
+    reach = min(_BOUNDARY_DMAX, 2 * radius + 2) if reach is None else reach
+    if isinstance(o["ids"], (list, tuple)):
+        return _per_item(lambda i, b: _split_one({k: o[k][i] for k in ("ids", "labels", "stats", "n")}, radius, reach, passes,
+                                                 min_area, connectivity, b),
+                         len(o["ids"]), (buffers,), "split_objects: one buffers entry per item", _SPLIT_KEYS)
+    return _split_one(o, radius, reach, passes, min_area, connectivity, buffers)

@@ -1102,6 +1102,13 @@ class MarigoldPipelineRGBLatentNoise:
         from .objects import object_cores
         return object_cores(o, radius, **kw)
 
+    def split_objects(self, o, radius, **kw):
+        """Touching objects of pipe.objects' (or pipe.fill_holes') result as separate instances: objects.split_objects(o,
+        radius, **kw) -- reach, passes, min_area, buffers, connectivity.  Returns a label_objects result, which every later
+        stage takes, with parent, cores and nearest."""
+        from .objects import split_objects
+        return split_objects(o, radius, **kw)
+
     def boundary_counts(self, result, gt, nlabels, key="labels", **kw):
         """Boundary IoU counts of a route's label map against a ground truth: objects.boundary_bands on
         result["native"][key] when the route ran at native size (lists, one call per item), otherwise on result[key],

@@ -824,6 +824,68 @@ int dfw_tiles_labels_cand(const dfw_tile_plan* plan, const uint8_t* ent, const i
  * or 8; min_area < 0; stats with cap < 1; counts without gt; gt with nlabels outside 1..254.  DFW_ERANGE: H or W above
  * 65535, H * W above 2^30, B above 65535 (also B * cap * 8 above 2^31 - 1 with stats).  Then the workspace and the buffers,
  * by the rule above: filtered on labels is one such overlap; gt counts only with counts.
+ *
+ * Components of equal (byte, key) (version >= 125): keys, appended to the struct.  With keys null the call is the one
+ * above, launch for launch and byte for byte.  With keys, int32 [B][H][W], two neighbouring pixels join when their label
+ * bytes are equal and non-zero AND their keys are equal.  Keys are compared for equality only: 0 and negative values are
+ * keys like any other, and a pixel is an object pixel by its byte alone.  Numbering by first pixel, min_area, filtered,
+ * stats (the label column is still the byte), n, counts, the number of launches and the workspace query are unchanged;
+ * launches 1 and 2 (the tile pass, which keeps the keys of its pixels in 8 KB more of LDS, and the border merge) compare
+ * pairs, everything behind them never looks at a label.  With keys all equal the outputs are those of the keyless call.
+ * This is also how an int32 map is labelled at all: labels = (map != 0), keys = map.  keys is an input of the buffer rule,
+ * aligned to 4: it may alias nothing the call writes.
+ *
+ * The nearest seed inside the object (version >= 125): map, seeds, nearest, dist, reach and passes, appended to the struct.
+ * With all of them zero the call is the one above, launch for launch and byte for byte.  With seeds (int32 [B][H][W], any
+ * non-zero value is a seed) the call is ANOTHER STAGE on the same entry point: it reads map (int32 [B][H][W], values
+ * compared for equality only, 0 = background) and seeds, writes nearest, dist and the workspace, and looks at no other
+ * field than B, H, W, ws, ws_bytes, reach (1..254) and passes (1..8) -- labels, ids, n and keys may be null, and none of
+ * the launches above runs.  It stands here and not on dfw_seg_boundary, whose row and column passes it shares (the code is
+ * in csrc/seg_boundary.hip), because that struct's last fields are pinned by its tests and a new launching entry point
+ * needs a case in every launch-guard table.  objects.split_objects runs it and then this call with keys = nearest.  With
+ * R = reach:
+ *
+ *   A CANDIDATE of a pixel p = (y, x) with v = map[p] != 0 is a position q = (y + dy, x + dx) with seeds[q] != 0, dy^2 +
+ *   dx^2 <= R^2 and an L path from p to q that stays on v, the column first and then the row: map[y + t][x] == v for every
+ *   t between 0 and dy, and map[y + dy][x + s] == v for every s between 0 and dx.
+ *   One pass: nearest[p] = seeds[q] of the candidate with the smallest (dy^2 + dx^2, seeds[q]) -- the nearer one, and among
+ *   equally near ones the smaller value as a signed int -- and 0 without a candidate.  dist[p] (uint16) = 0 on a seed
+ *   pixel, else the winner's dy^2 + dx^2, and (R + 1)^2 without a candidate.  Background has nearest 0 and dist 0.
+ *   passes = k repeats the pass k - 1 times with seeds := nearest, in place: a pixel that holds a value keeps it and its
+ *   dist, and its walk is skipped, so every pass carries each label round one more bend and a label never changes.
+ *
+ * map [[5,5,5,5],[5,0,0,5]], seeds [[0,0,0,0],[9,0,0,3]], R = 3.  One pass: nearest [[9,0,0,3],[9,0,0,3]], dist
+ * [[1,16,16,1],[0,0,0,0]] -- (0, 0) goes down one row to the 9; (0, 1) has no seed in its row and its column leaves the
+ * value at once, so it has no candidate.  passes = 2: the second pass's seeds are that result, (0, 1) finds the 9 one to
+ * its left and (0, 2) the 3 one to its right: nearest [[9,9,3,3],[9,0,0,3]], dist [[1,1,1,1],[0,0,0,0]].
+ *
+ * The two-pass form.  The row pass writes, per pixel, h = the distance along the row to the nearest seed inside the
+ * pixel's run of equal value (0 on a seed, R + 1 for none within R) and lab = that seed's value, the smaller of the two
+ * when left and right are equally near.  The column pass starts from (h(y, x)^2, lab(y, x)) and offers, for dy = 1, 2,
+ * ... up and down while the rows exist and map[y + dy][x] == v, the pair (dy^2 + h(y + dy, x)^2, lab(y + dy, x)) when it
+ * is within R^2; the smallest pair wins.  Sketch of the proof: every pair the walk offers belongs to a real candidate --
+ * the walk has stayed on v down column x to row y + dy, and h, lab describe a seed of that row inside the run of (y + dy,
+ * x), which is the row part of an L path.  And no candidate beats it: a candidate (dy, dx) lies in row y + dy, which the
+ * walk reaches because the column holds v that far, inside the run of (y + dy, x); the row pass's seed of that run
+ * position is no farther along than |dx|, and at the same |dx| no larger in value, so it dominates the candidate in both
+ * parts of the key -- a farther seed of the same row only has a larger distance.  A row with dy^2 above the best so far
+ * cannot win; one with dy^2 EQUAL to it still can, by a smaller value straight above or below, so the walk goes on while
+ * dy^2 <= the best so far, at most R steps, with dy^2 + h^2 <= 2 * 254^2.
+ *
+ * Launches: 2 * passes, fixed by the argument -- a row pass of its own (the same window of positions with halo, the breaks'
+ * scans and the same scans over seed positions; dfw_seg_boundary's, see there) and a column pass on the tile and the
+ * four-pixels-a-thread rule of the Euclidean one (W % 4 == 0, map, nearest and ws aligned to 16, dist to 8).  The column pass reads labels from the
+ * workspace only, never from nearest, which it writes: the row pass of pass k + 1 reads nearest after the column pass of
+ * pass k has finished it, which is what makes the repeat in place safe.  No atomics, no memset node, no host readback,
+ * no thread that waits for another; a lexicographic minimum depends on no order of execution.  Nothing is written outside
+ * nearest, dist and ws.  The workspace is dfw_seg_nearest_workspace_bytes(B, H, W), 5 bytes a pixel; the other query and
+ * its value do not change.
+ *
+ * Refusals of the stage, in the house order.  DFW_EINVAL: null map / nearest / dist / ws, reach outside 1..254, passes
+ * outside 1..8, B, H or W < 1; DFW_ERANGE: the sizes, as above; DFW_EWORKSPACE against dfw_seg_nearest_workspace_bytes; then
+ * the buffers: map and seeds are inputs aligned to 4, dist an output aligned to 2, nearest an output aligned to 4 that may
+ * share no byte with map, seeds, dist or ws.  Without seeds, a non-null nearest is DFW_EINVAL (behind nlabels' rule, before
+ * the sizes); map, dist, reach and passes are not looked at.
  */
 typedef struct {
   const uint8_t* labels;   /* [B][H][W] contiguous; 0 = background, any other byte is a class; equal bytes connect */
@@ -836,9 +898,19 @@ typedef struct {
   void* ws;
   size_t ws_bytes;
   int32_t B, H, W, connectivity, min_area, cap, nlabels;   /* connectivity 4 | 8; min_area >= 0 */
+  const int32_t* keys;     /* optional [B][H][W] (version >= 125): neighbours join only when their keys are equal too */
+  const int32_t* map;      /* the nearest-seed stage (seeds non-null): [B][H][W], read only */
+  const int32_t* seeds;    /* [B][H][W] or null; non-null: the call is the nearest-seed stage, see above */
+  int32_t* nearest;        /* out [B][H][W], with seeds only */
+  void* dist;              /* out uint16 [B][H][W], with seeds only */
+  int32_t reach, passes;   /* 1..254 and 1..8, with seeds only */
 } dfw_seg_components_args;
 int dfw_seg_components(const dfw_seg_components_args* a, dfw_stream_t stream);
 size_t dfw_seg_components_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* the workspace of the nearest-seed stage (seeds non-null): 5 bytes a pixel -- the row pass's value (int32 [B * H * W],
+ * rounded up to 16 bytes) and its distance (one byte a pixel, rounded up to 16) -- and 0 for sizes the call refuses;
+ * monotone otherwise */
+size_t dfw_seg_nearest_workspace_bytes(int32_t B, int32_t H, int32_t W);
 /* the tile of the LDS pass (rows, columns): the shapes at which the kernels change path, for tests and docs */
 int dfw_seg_components_tile(int32_t* tile_h, int32_t* tile_w);
 /* How often each loop of dfw_seg_components that carries a value from one round to the next would run for these
